@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- the headline measurement of BASELINE.json: UTF-8 MB/s (+ tokens/s) tokenized on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Workload at EVERY N: BASELINE.json configs[3] (SURVEY.md 8(d) cfg 4) -- one FIXED job of 10 M mixed-length sentences
 = 8 shards x 1.25 M documents (shard s is drawn with seed 100 + s), max_len=256 pad+trunc, bundled vocab.  Rank r of G
@@ -14,13 +14,16 @@ attention_mask) over the whole job: every rank tokenizes each of its shards thro
 of every shard travel to rank 0 by the RCCL gather (CSR form: row lengths + unpadded 16-bit ids), overlapped with the
 next shard's kernels.  `value` = bytes of the whole job x steps / wall time (max over ranks).
 
-After the timed region EVERY rank checks the dense [n, 256] input_ids / attention_mask of each of its shards against
-the committed per-shard digests (tests/golden/g5_hashes.json: cfg4_shard0..7), and rank 0 also expands every PEER's
-gathered block and checks it against that peer's digests; any mismatch exits non-zero on all ranks.
+A plain run does only what the headline needs: it makes the job, warms up, times the steps and prints the line.
+--dump-outputs DIR then writes what the last timed step computed (a seeded sample of every shard's rows and every
+document's token count, float32 / float64 .npy; see dump_outputs), so that two builds can be compared output for output.
 
-At N=1 the line also carries: the roofline run of BASELINE configs[2] (1 M documents, verified against the
-reference's own digests) with its three timings (kernels / device end-to-end incl. PCIe / Python end-to-end), the
-merge-loop-only and OOV-sensitivity figures, configs[1] and configs[4], and the CPU baseline.
+--full adds everything else.  After the timed region EVERY rank checks the dense [n, 256] input_ids / attention_mask
+of each of its shards against the committed per-shard digests (tests/golden/g5_hashes.json: cfg4_shard0..7), and
+rank 0 also expands every PEER's gathered block and checks it against that peer's digests; any mismatch exits
+non-zero on all ranks.  At N=1 the line also carries: the roofline run of BASELINE configs[2] (1 M documents,
+verified against the reference's own digests) with its three timings (kernels / device end-to-end incl. PCIe /
+Python end-to-end), the merge-loop-only and OOV-sensitivity figures, configs[1] and configs[4], and the CPU baseline.
 
 torch is used only for torch.distributed (rendezvous, barrier, max-over-ranks) and torch.cuda.synchronize(); the
 tokenizer itself never touches it.
@@ -127,6 +130,32 @@ def _check_dense(ids, mask, digest, what):
     if bad or int(mask.sum(dtype=np.int64)) != digest["n_tokens"]:
         return "%s: blocks %s differ from tests/golden/g5_hashes.json" % (what, bad[:5])
     return None
+
+
+DUMP_ROWS, DUMP_SEED = 1024, 20261016
+
+
+def dump_outputs(ctx, shards, set_idx, L, out_dir):
+    """--dump-outputs: what the last timed step left in HBM, for a comparison of two builds output for output.  Per shard s:
+    shard<s>_rows.npy (float64 [R]: a fixed, seeded sample of R = 1024 document indices), shard<s>_input_ids.npy and
+    shard<s>_attention_mask.npy (float32 [R, max_len]: those documents' dense rows; ids < 2^24 are exact in float32) and
+    shard<s>_n_tokens.npy (float32: the real-token count of every document, of the first 1.25 M when a shard is larger).
+    At most 7 MB per shard, 56 MB for the job."""
+    os.makedirs(out_dir, exist_ok=True)
+    for sh in shards:
+        st = sh["sets"][set_idx]
+        rng = np.random.default_rng(DUMP_SEED + sh["id"])
+        rows = np.sort(rng.choice(sh["n"], size=min(sh["n"], DUMP_ROWS), replace=False))
+        ids = np.empty((len(rows), L), dtype=np.int32)
+        mask = np.empty((len(rows), L), dtype=np.int32)
+        for k, r in enumerate(rows.tolist()):
+            ctx.d2h(ids[k], st["ids"] + 4 * L * r)
+            ctx.d2h(mask[k], st["mask"] + 4 * L * r)
+        pre = os.path.join(out_dir, "shard%d_" % sh["id"])
+        np.save(pre + "rows.npy", rows.astype(np.float64))
+        np.save(pre + "input_ids.npy", ids.astype(np.float32))
+        np.save(pre + "attention_mask.npy", mask.astype(np.float32))
+        np.save(pre + "n_tokens.npy", sh["n_real"][:SHARD_DOCS].astype(np.float32))
 
 
 # ---- CPU baseline ---------------------------------------------------------------------------------------------------
@@ -309,7 +338,15 @@ def main():
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the N=1 secondary measurements")
     ap.add_argument("--switches", default="", help='(diagnostic) library switches for this run, "key=value,...": gz_debug_set through gz_switches.py')
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: check every shard (and at N > 1 every gathered block) against the committed digests, and "
+                         "at N=1 run the CPU baselines and the secondary measurements (--no-verify, --no-secondary, --no-cpu-baseline "
+                         "leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/*.npy (float32 / float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -327,7 +364,7 @@ def main():
     # ---- CPU baseline (N=1 only): timed first, before the GPU is touched -- its all-cores figure forks worker processes
     cpu = {}
     cfg2 = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         import corpus as _corpus
         t2_, o2_, L2_ = _corpus.config_corpus(3)
         cfg2 = (np.ascontiguousarray(t2_), np.ascontiguousarray(o2_, dtype=np.int64), L2_)
@@ -543,7 +580,8 @@ def main():
         elapsed = float(t.item())
     last_set = (step_no[0] - 1) % len(shards[0]["sets"])
 
-    # ---- after the timed region: verification of EVERY shard on EVERY rank ----------------------------------------------
+    # ---- after the timed region: the token counts; with --full, verification of EVERY shard on EVERY rank ----------------
+    verify_on = args.full and not args.no_verify
     g5 = json.load(open(os.path.join(ROOT, "tests", "golden", "g5_hashes.json")))
     errors, checked = [], []
     tokens_local = 0
@@ -552,7 +590,8 @@ def main():
         st = sh["sets"][last_set]
         nr = np.empty(sh["n"], dtype=np.int32); ctx.d2h(nr, st["nreal"])
         tokens_local += int(nr.sum(dtype=np.int64))
-        if args.no_verify:
+        sh["n_real"] = nr
+        if not verify_on:
             continue
         ids = np.empty((sh["n"], L), dtype=np.int32); ctx.d2h(ids, st["ids"])
         mask = np.empty((sh["n"], L), dtype=np.int32); ctx.d2h(mask, st["mask"])
@@ -574,7 +613,7 @@ def main():
             errors.append(e)
         del ids, mask
     # rank 0: every gathered block (its own and every peer's), expanded on the GPU and checked the same way
-    if gather and rank == 0 and not args.no_verify:
+    if gather and rank == 0 and verify_on:
         d_ci, d_cm = ctx.alloc(4 * n * L), ctx.alloc(4 * n * L)
         for j, r in enumerate(rounds):
             plan = r["plan"]
@@ -602,6 +641,8 @@ def main():
                 checked.append("gathered shard %d (from rank %d)" % (gid, q))
                 del blk, mblk
         ctx.free(d_ci); ctx.free(d_cm)
+    if args.dump_outputs:
+        dump_outputs(ctx, shards, last_set, L, args.dump_outputs)
 
     tot = np.array([sum(sh["in_bytes"] for sh in shards), tokens_local, sum(sh["n"] for sh in shards), len(errors)], dtype=np.float64)
     if dist is not None:
@@ -616,7 +657,7 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         sys.exit(1)
-    verify = None if args.no_verify else (
+    verify = None if not verify_on else (
         "every rank: dense input_ids + attention_mask of each of its shards == %s" % (
             "committed per-shard sha256 digests (tests/golden/g5_hashes.json cfg4_shard*: C oracle over the whole shard, "
             "the reference itself over the first 20 000 documents)" if full_size else "C oracle, whole arrays")
@@ -624,7 +665,7 @@ def main():
 
     # ---- N=1 secondary measurements (untimed for `value`) --------------------------------------------------------------
     sec = {}
-    if world == 1 and rank == 0 and not args.no_secondary:
+    if world == 1 and rank == 0 and args.full and not args.no_secondary:
         # free the job's buffers first (20+ GB); the secondary workloads are small
         for sh in shards:
             for q in [sh["d_text"], sh["d_off"]] + [x for st in sh["sets"] for x in (st["ids"], st["mask"], st["nreal"])]:

@@ -60,7 +60,9 @@ def _worker(rank, world, port, q):
 
 
 def test_gather_rows_world2_gloo():
-    import torch.multiprocessing as mp
+    # the standard library's spawn context: torch is imported by the workers only.  Imported into this process, its bundled HIP
+    # runtime would sit beside the library's in a GPU run of the whole suite, and the library's RCCL would resolve to torch's.
+    import multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -167,7 +169,7 @@ def test_size_exchange_of_the_exchange_step_over_gloo(world, capsys):
     (no pickling; round 4 used all_gather_object): right values at world 2 and 8, and its latency -- printed, and written to
     gpurun_out/size_exchange_world<N>.txt when that directory exists: the number DESIGN.md section 7 sets against one launch's
     kernel time (the exchange is hidden only while the host's part stays under it)."""
-    import torch.multiprocessing as mp
+    import multiprocessing as mp                                  # (not torch's: see test_gather_rows_world2_gloo)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()

@@ -1074,7 +1074,7 @@ def test_bench_multirank_exchange_on_one_gpu_over_gloo(world):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--docs", "160000", "--transport", "gloo", "--device", "0"]
+           "--docs", "160000", "--transport", "gloo", "--device", "0", "--full"]
     r = _run_child(cmd, "bench_gloo_world%d" % world, env=env, timeout=420, cwd=root)
     assert r.returncode == 0, r.report
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -1102,7 +1102,7 @@ def test_bench_exchange_step_over_rccl_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--docs", "160000", "--force-exchange", "--no-secondary"]
+           "--docs", "160000", "--force-exchange", "--no-secondary", "--full"]
     r = _run_child(cmd, "bench_rccl_one_rank", env=env, timeout=420, cwd=root)
     assert r.returncode == 0, r.report
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

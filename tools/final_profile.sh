@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/final_profile.sh <tag>   -- everything profiles/ holds for one build:
 #   kernel stats of a bench.py run (rocprofv3 --kernel-trace --stats), steady-state per-kernel times of the roofline
-#   workload, PMC traffic (separate --pmc passes, no trace domains), the default bench.py line
+#   workload, PMC traffic (separate --pmc passes, no trace domains), the bench.py --full line
 set -o pipefail
 tag=$1
 R=$PWD
@@ -26,6 +26,6 @@ python3 tools/pmc_traffic.py gpurun_out/pmc_fin_${tag}_1 gpurun_out/pmc_fin_${ta
 SEED=100 tools/pmc.sh finS_$tag 1250000 "FETCH_SIZE" "WRITE_SIZE" || exit 1
 python3 tools/pmc_traffic.py gpurun_out/pmc_finS_${tag}_1 gpurun_out/pmc_finS_${tag}_2 $O/pmc_traffic_shard.json "$(python3 -c 'import bench; print(bench.PIPELINE)')" "" "BASELINE configs[3], shard 0: 1.25 M documents (seed 100), 358 MB, max_len 256 (SEED=100 tools/prof_run.py 1250000 2)"
 echo "(3) done" >> $O/progress.txt
-# (4) the default bench line
-timeout -k 10 700 python3 bench.py > $O/bench.json.log 2>$O/bench.err || { tail -5 $O/bench.err; exit 1; }
+# (4) the bench line with every secondary figure (--full)
+timeout -k 10 700 python3 bench.py --full > $O/bench.json.log 2>$O/bench.err || { tail -5 $O/bench.err; exit 1; }
 tail -c 300 $O/bench.json.log

@@ -4,7 +4,7 @@
 #   launch on BASELINE configs[2]; (3) HBM traffic (separate --pmc passes, no trace domains) of configs[2], of one shard of the
 #   headline job, of BASELINE configs[4] and of configs[2] with the whole-word tables off; (4) SQ / TCP / TCC counters of the
 #   pipeline's kernels; (5) kernel stats of configs[4] and of the no-table mode; (6) table load and small-call latencies;
-#   (7) the default bench line.
+#   (7) the bench.py --full line.
 set -o pipefail
 tag=$1
 ROUND=${2:-r06}
@@ -71,7 +71,7 @@ echo "(5)" >> $O/progress.txt
 echo "(6)" >> $O/progress.txt
 # (7) (the traffic files go where bench.py looks for them: this run's line then carries them)
 cp $O/pmc_traffic.json $R/profiles/${ROUND}_pmc_traffic.json; cp $O/pmc_traffic_shard.json $R/profiles/${ROUND}_pmc_traffic_shard.json; cp $O/pmc_traffic_cfg4.json $R/profiles/${ROUND}_pmc_traffic_cfg4.json
-( cd $R && timeout -k 10 900 python3 bench.py > $O/bench.json.log 2> $O/bench.err ) || { tail -5 $O/bench.err; exit 1; }
+( cd $R && timeout -k 10 900 python3 bench.py --full > $O/bench.json.log 2> $O/bench.err ) || { tail -5 $O/bench.err; exit 1; }
 tail -c 400 $O/bench.json.log
 find $O -name "*counter_collection.csv" -delete
 find $O -name "*agent_info.csv" -delete
