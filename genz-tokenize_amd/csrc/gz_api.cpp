@@ -15,6 +15,7 @@
 #include <vector>
 #include <unordered_map>
 #include <algorithm>
+#include <memory>
 
 namespace {
 
@@ -173,6 +174,8 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
+    DBuf w_bm[24];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring call (gz_bm25.inc)
+    std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
 namespace {
@@ -939,6 +942,207 @@ static int install_word_tables(gz_ctx* c, const WordImages& W)
 }
 
 
+// ---- BM25 index (gz_bm25.inc) ------------------------------------------------------------------------------------------
+struct gz_bm25 {
+    gz_ctx* c = nullptr;
+    int64_t n_docs = 0, n_words = 0, n_terms = 0, n_ent = 0, off0 = 0;
+    unsigned long long hmask = 0, pmask = 0, tmask = 0;
+    // the index: a copy of the text (the terms' bytes), fieldLens, signatures, doc-major (term, count) entries, the (document, term)
+    // pair table, the term table, the terms' byte ranges and df
+    DBuf text, dl, sig, eoff, ent, ptab, ttab, tstart, tlen, df;
+    ~gz_bm25() { for (DBuf* b : {&text, &dl, &sig, &eoff, &ent, &ptab, &ttab, &tstart, &tlen, &df}) release(*b); }
+};
+
+namespace {
+enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW_HASH, BMW_REP, BMW_SLOT, BMW_LIST0, BMW_LIST1, BMW_DTAB,
+       BMW_FLAG, BMW_SCAN, BMW_TERM, BMW_DFS, BMW_QTEXT, BMW_QOFF, BMW_QRES, BMW_QTERM, BMW_QIDF, BMW_SCORES };
+
+// Every error return of an index build drains the context's stream before the buffers the call owns (the index under
+// construction) are freed: declared AFTER the index, destroyed before it.
+struct BmDrain { gz_ctx* c; ~BmDrain() { hipStreamSynchronize(c->stream); } };
+
+// a device buffer of the BM25 paths: an allocation site of the inject_bad_alloc switch
+int bm_alloc(gz_ctx* c, DBuf& b, size_t bytes)
+{
+    alloc_site(c);
+    return ensure(c, b, bytes ? bytes : 16);
+}
+
+uint64_t bm_pow2(uint64_t x)
+{
+    uint64_t p = 16;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+// every word needs a byte and, unless it ends its document, a separator: words <= (bytes + documents) / 2, which keeps word indices,
+// term ids and entry offsets in 31 bits
+int bm_limits(gz_ctx* c, int64_t text_bytes, int64_t n_docs)
+{
+    if (text_bytes + n_docs >= ((int64_t)1 << 32))
+        return fail(c, GZ_E_LIMIT, "BM25 index: %lld bytes + %lld documents; the index takes fewer than 2^32", (long long)text_bytes, (long long)n_docs);
+    return GZ_OK;
+}
+
+int bm_scan(gz_ctx* c, const uint32_t* in, int64_t n, uint32_t* out)
+{
+    gz_launch_bm25_scan(in, n, out, (uint32_t*)c->w_bm[BMW_BSUM].p, c->stream);
+    return GZ_OK;
+}
+
+int bm_read_u32(gz_ctx* c, const uint32_t* src, int64_t& v)
+{
+    uint32_t x = 0;
+    int rc = copy_out_small(c, &x, src, 4, c->stream);
+    v = x;
+    return rc;
+}
+
+// The build after the text is in ix->text: off_dev = the documents' absolute offsets (device), text_bytes = bytes from off[0].
+// Four host round trips: the word count, each de-duplication round's leftovers (one round unless hashes collide), the term count
+// and the entry count size the next buffers.
+int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text_bytes)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t N = ix->n_docs;
+    int rc;
+    GzBm25Args A{};
+    A.tb = (const uint8_t*)ix->text.p - ix->off0;
+    A.off = off_dev; A.n_docs = N; A.lo = ix->off0; A.hi = ix->off0 + text_bytes;
+    const int bits = c->opt.bm25_hash_bits;
+    ix->hmask = A.hmask = bits > 0 ? (1ull << bits) - 1ull : ~0ull >> 1;
+    const int64_t wmax = (text_bytes + N) / 2 + 1;
+    if ((rc = bm_alloc(c, ix->dl, (size_t)N * 4)) || (rc = bm_alloc(c, ix->sig, (size_t)N * 32)) || (rc = bm_alloc(c, ix->eoff, (size_t)(N + 1) * 4)) ||
+        (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(N + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
+        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((N > wmax ? N : wmax) / 4096 + 2) * 4)))
+        return rc;
+    A.ctl = (uint32_t*)w[BMW_CTL].p; A.wcnt = (uint32_t*)ix->dl.p; A.woff = (uint32_t*)w[BMW_WOFF].p;
+    A.sig = (unsigned long long*)ix->sig.p; A.eoff = (uint32_t*)ix->eoff.p;
+    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    if (N) HIPCHK(c, hipMemsetAsync(A.sig, 0, (size_t)N * 32, s));
+    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.wcnt, N, A.woff))) return rc;
+    int64_t bad = 0, W = 0;
+    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + N, W))) return rc;
+    if (bad) return fail(c, GZ_E_INVALID, "BM25 index: document offsets decrease or leave the %lld bytes of text", (long long)text_bytes);
+    ix->n_words = A.n_words = W;
+
+    // ---- words, their hashes, the de-duplication rounds
+    const size_t w1 = (size_t)W + 1;
+    const uint64_t slots = bm_pow2((uint64_t)W + (uint64_t)W / 3 + 16);           // load <= 3/4 in the de-duplication and pair tables
+    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) || (rc = bm_alloc(c, w[BMW_DTAB], slots * 16)) ||
+        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) || (rc = bm_alloc(c, w[BMW_TERM], w1 * 4)) ||
+        (rc = bm_alloc(c, ix->ptab, slots * 16)))
+        return rc;
+    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
+    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
+    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = slots - 1;
+    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p; A.term = (uint32_t*)w[BMW_TERM].p;
+    A.ptab = (GzBm25Slot*)ix->ptab.p; A.pmask = ix->pmask = slots - 1;
+    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
+    // each round settles at least the word that wins each slot, so the rounds end; with the whole hash there is one
+    const uint32_t* list = nullptr;
+    for (int64_t n = W, k = 0; n > 0; ++k) {
+        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
+        HIPCHK(c, hipMemsetAsync(A.dtab, 0, slots * 16, s));
+        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
+        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, n, nullptr, s);
+        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, n, next, s);
+        if ((rc = bm_read_u32(c, A.ctl, n))) return rc;
+        list = next;
+    }
+
+    // ---- term ids, term table, pairs, df, signatures, entries
+    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
+    int64_t T = 0;
+    if ((rc = bm_read_u32(c, A.scan + W, T))) return rc;
+    ix->n_terms = T;
+    const uint64_t tslots = bm_pow2(2 * (uint64_t)T + 16);
+    if ((rc = bm_alloc(c, ix->tstart, (size_t)T * 8)) || (rc = bm_alloc(c, ix->tlen, (size_t)T * 4)) || (rc = bm_alloc(c, ix->df, (size_t)T * 4)) ||
+        (rc = bm_alloc(c, ix->ttab, tslots * 16)) || (rc = bm_alloc(c, w[BMW_DFS], (size_t)T * 4 * GZ_BM25_DF_SHARDS)))
+        return rc;
+    A.n_terms = T; A.dfs = (uint32_t*)w[BMW_DFS].p;
+    A.tstart = (int64_t*)ix->tstart.p; A.tlen = (uint32_t*)ix->tlen.p; A.df = (uint32_t*)ix->df.p;
+    A.ttab = (GzBm25Slot*)ix->ttab.p; A.tmask = ix->tmask = tslots - 1;
+    HIPCHK(c, hipMemsetAsync(A.ttab, 0, tslots * 16, s));
+    HIPCHK(c, hipMemsetAsync(A.ptab, 0, slots * 16, s));
+    if (T) HIPCHK(c, hipMemsetAsync(A.dfs, 0, (size_t)T * 4 * GZ_BM25_DF_SHARDS, s));
+    gz_launch_bm25(GZ_BM25_TERM, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_PAIR_INS, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_PAIR_FIRST, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_DF, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
+    int64_t E = 0;
+    if ((rc = bm_read_u32(c, A.scan + W, E))) return rc;
+    ix->n_ent = E;
+    if ((rc = bm_alloc(c, ix->ent, (size_t)E * 8))) return rc;
+    A.ent = (uint2*)ix->ent.p;
+    gz_launch_bm25(GZ_BM25_ENT, A, nullptr, 0, nullptr, s);
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+int bm_adopt(gz_ctx* c, std::unique_ptr<gz_bm25>& ix, gz_bm25** out)
+{
+    alloc_site(c);
+    c->bm25_live.push_back(ix.get());
+    *out = ix.release();
+    return GZ_OK;
+}
+
+// the query arrays of a scoring call -> the kernel; out_dev null: into the context's workspace and back to out_host
+int bm25_score_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
+                      double* out_dev, double* out_host)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t nw = qoff[nq] - qoff[0], N = ix->n_docs;
+    int rc;
+    if ((rc = bm_alloc(c, w[BMW_QTERM], (size_t)nw * 4)) || (rc = bm_alloc(c, w[BMW_QIDF], (size_t)nw * 8)) ||
+        (rc = bm_alloc(c, w[BMW_QOFF], (size_t)(nq + 1) * 8)))
+        return rc;
+    if (!out_dev && (rc = bm_alloc(c, w[BMW_SCORES], (size_t)(nq * N) * 8))) return rc;
+    if (nw && ((rc = copy_in(c, w[BMW_QTERM].p, terms + qoff[0], (size_t)nw * 4, s)) || (rc = copy_in(c, w[BMW_QIDF].p, idf + qoff[0], (size_t)nw * 8, s))))
+        return rc;
+    if ((rc = copy_in(c, w[BMW_QOFF].p, qoff, (size_t)(nq + 1) * 8, s))) return rc;
+    GzBm25Score S{};
+    S.dl = (const uint32_t*)ix->dl.p; S.sig = (const unsigned long long*)ix->sig.p; S.eoff = (const uint32_t*)ix->eoff.p;
+    S.ent = (const uint2*)ix->ent.p; S.ptab = (const GzBm25Slot*)ix->ptab.p; S.pmask = ix->pmask; S.n_docs = N;
+    S.qterm = (const int32_t*)w[BMW_QTERM].p - qoff[0]; S.qidf = (const double*)w[BMW_QIDF].p - qoff[0];
+    S.qoff = (const int64_t*)w[BMW_QOFF].p; S.n_q = nq;
+    S.kp1 = P[0]; S.k1 = P[1]; S.omb = P[2]; S.b = P[3]; S.avg = P[4]; S.delta = P[5]; S.plus = plus ? 1 : 0;
+    S.out = out_dev ? out_dev : (double*)w[BMW_SCORES].p;
+    gz_launch_bm25_score(S, s);
+    HIPCHK(c, hipGetLastError());
+    if (out_dev) return GZ_OK;
+    HostPool pool(pool_threads(c, (size_t)(nq * N) * 8));
+    return copy_out(c, out_host, S.out, (size_t)(nq * N) * 8, s, &pool);
+}
+
+int bm25_score_args(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, const void* out)
+{
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!qoff || nq < 0 || !P || (!out && nq > 0 && ix->n_docs > 0)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (ix->n_docs > 0 && nq > ((int64_t)1 << 59) / ix->n_docs) return fail(c, GZ_E_LIMIT, "scores[%lld, %lld] too large", (long long)nq, (long long)ix->n_docs);
+    const int64_t nw = qoff[nq] - qoff[0];
+    if (nw < 0 || (nw > 0 && (!terms || !idf))) return fail(c, GZ_E_INVALID, "bad query offsets");
+    for (int64_t q = 0; q < nq; ++q) if (qoff[q + 1] < qoff[q]) return fail(c, GZ_E_INVALID, "query offsets must not decrease");
+    for (int64_t j = qoff[0]; j < qoff[nq]; ++j)
+        if (terms[j] < -1 || terms[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "term id %d out of range", terms[j]);
+    return GZ_OK;
+}
+}  // namespace
+
+
 // =================================================================================================================
 extern "C" {
 
@@ -1004,6 +1208,9 @@ try {
     // every stream of the context drained BEFORE any event or stream goes (an event destroyed under a stream that still waits for it,
     // a stream destroyed under its last copy: nothing here should depend on how the runtime treats those)
     for (hipStream_t q : {c->stream, c->stream2, c->side, c->xstream, c->s_in, c->s_out}) if (q) hipStreamSynchronize(q);
+    for (gz_bm25* ix : c->bm25_live) delete ix;
+    c->bm25_live.clear();
+    for (DBuf& b : c->w_bm) release(b);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
@@ -2453,5 +2660,130 @@ try {
     c->xring_n = 0;
     return GZ_OK;
 } GZ_CATCH(c)
+
+
+// ---- BM25 / BM25Plus ------------------------------------------------------------------------------------------------------
+int gz_bm25_build(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, gz_bm25** out)
+try {
+    if (!c || !out || !text_off || n_docs < 0) return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    *out = nullptr;
+    const int64_t nbytes = text_off[n_docs] - text_off[0];
+    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
+    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = bm_limits(c, nbytes, n_docs))) return rc;
+    alloc_site(c);
+    std::unique_ptr<gz_bm25> ix(new gz_bm25());
+    BmDrain drain{c};
+    ix->c = c; ix->n_docs = n_docs; ix->off0 = text_off[0];
+    if ((rc = bm_alloc(c, ix->text, (size_t)nbytes + 16)) || (rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
+    if (nbytes && (rc = copy_in(c, ix->text.p, text + text_off[0], (size_t)nbytes, c->stream))) return rc;
+    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
+    if ((rc = bm25_build_core(c, ix.get(), (const int64_t*)c->w_bm[BMW_OFF].p, nbytes))) return rc;
+    return bm_adopt(c, ix, out);
+} GZ_CATCH(c)
+
+int gz_bm25_build_device(gz_ctx* c, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes, gz_bm25** out)
+try {
+    if (!c || !out || !text_off_dev || n_docs < 0 || text_bytes < 0 || (text_bytes > 0 && !text_dev))
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = bm_limits(c, text_bytes, n_docs))) return rc;
+    alloc_site(c);
+    std::unique_ptr<gz_bm25> ix(new gz_bm25());
+    BmDrain drain{c};
+    int64_t off0 = 0;
+    if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
+    if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+    ix->c = c; ix->n_docs = n_docs; ix->off0 = off0;
+    if ((rc = bm_alloc(c, ix->text, (size_t)text_bytes + 16))) return rc;
+    if (text_bytes) HIPCHK(c, hipMemcpyAsync(ix->text.p, text_dev + off0, (size_t)text_bytes, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = bm25_build_core(c, ix.get(), text_off_dev, text_bytes))) return rc;
+    return bm_adopt(c, ix, out);
+} GZ_CATCH(c)
+
+int gz_bm25_info(gz_bm25* ix, int64_t* n_docs, int64_t* n_terms, int64_t* n_words)
+try {
+    if (!ix) return GZ_E_INVALID;
+    if (n_docs) *n_docs = ix->n_docs;
+    if (n_terms) *n_terms = ix->n_terms;
+    if (n_words) *n_words = ix->n_words;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_field_lengths(gz_bm25* ix, int32_t* out)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!out && ix->n_docs > 0) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return copy_out(c, out, ix->dl.p, (size_t)ix->n_docs * 4, c->stream);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_lookup(gz_bm25* ix, const uint8_t* words, const int64_t* word_off, int64_t n, int32_t* term_out, int32_t* df_out)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!word_off || n < 0 || (n > 0 && (!term_out || !df_out))) return fail(c, GZ_E_INVALID, "bad arguments");
+    const int64_t nbytes = word_off[n] - word_off[0];
+    if (nbytes < 0 || (nbytes > 0 && !words)) return fail(c, GZ_E_INVALID, "bad word offsets");
+    for (int64_t i = 0; i < n; ++i) if (word_off[i + 1] < word_off[i]) return fail(c, GZ_E_INVALID, "word offsets must not decrease");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return GZ_OK;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = bm_alloc(c, w[BMW_QTEXT], (size_t)nbytes + 16)) || (rc = bm_alloc(c, w[BMW_QOFF], (size_t)(n + 1) * 8)) ||
+        (rc = bm_alloc(c, w[BMW_QRES], (size_t)n * 8)))
+        return rc;
+    if (nbytes && (rc = copy_in(c, w[BMW_QTEXT].p, words + word_off[0], (size_t)nbytes, s))) return rc;
+    if ((rc = copy_in(c, w[BMW_QOFF].p, word_off, (size_t)(n + 1) * 8, s))) return rc;
+    GzBm25Look L{};
+    L.tb = (const uint8_t*)ix->text.p - ix->off0; L.tstart = (const int64_t*)ix->tstart.p; L.tlen = (const uint32_t*)ix->tlen.p;
+    L.df = (const uint32_t*)ix->df.p; L.ttab = (const GzBm25Slot*)ix->ttab.p; L.tmask = ix->tmask; L.hmask = ix->hmask;
+    L.qtext = (const uint8_t*)w[BMW_QTEXT].p - word_off[0]; L.qoff = (const int64_t*)w[BMW_QOFF].p; L.n = n;
+    L.term_out = (int32_t*)w[BMW_QRES].p; L.df_out = L.term_out + n;
+    gz_launch_bm25_lookup(L, s);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = copy_out(c, term_out, L.term_out, (size_t)n * 4, s)) || (rc = copy_out(c, df_out, L.df_out, (size_t)n * 4, s))) return rc;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_score(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                  int32_t plus, double* scores)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, scores);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_score_locked(ix, terms, idf, query_off, n_queries, params, plus, nullptr, scores);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_score_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                         const double params[6], int32_t plus, double* scores_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, scores_dev);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_score_locked(ix, terms, idf, query_off, n_queries, params, plus, scores_dev, nullptr);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+void gz_bm25_destroy(gz_bm25* ix)
+try {
+    if (!ix) return;
+    gz_ctx* c = ix->c;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);                             // (a scoring call into device memory may still read the index)
+    auto& v = c->bm25_live;
+    v.erase(std::remove(v.begin(), v.end(), ix), v.end());
+    delete ix;
+} GZ_CATCH_VOID
 
 }  // extern "C"

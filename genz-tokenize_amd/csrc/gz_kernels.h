@@ -149,3 +149,57 @@ void gz_launch_pp_pack(const uint8_t* in, const int64_t* in_off, const int64_t* 
 // written), four documents per wave, and out_off as 64-bit offsets
 void gz_launch_pp_tail(const uint8_t* slots, const int64_t* in_off, uint32_t* len32, int64_t n_docs, uint8_t* out, int64_t capacity, int64_t* out_off,
                        unsigned long long* lb, uint32_t* ctl, uint32_t epoch, hipStream_t s);
+
+// BM25 / BM25Plus index and scoring (gz_bm25.inc; genz_tokenize/ranking.py of the reference)
+struct GzBm25Slot { unsigned long long key; uint32_t a, b; };     // open-addressing slot, key 0: empty
+struct GzBm25Args {
+    const uint8_t* tb;                  // document d = tb[off[d] .. off[d+1]) (absolute offsets)
+    const int64_t* off;
+    int64_t n_docs, n_words;
+    int64_t lo, hi;                     // the offsets must lie in [lo, hi] (else ctl[1] is raised and the document counts as empty)
+    uint32_t* ctl;                      // [0] words left for the next de-duplication round, [1] bad offsets
+    uint32_t* wcnt;                     // [n_docs] words per document (fieldLens)
+    uint32_t* woff;                     // [n_docs + 1] index of each document's first word
+    int64_t* wstart; int64_t* wend;     // [n_words] absolute byte range of every word
+    uint32_t* wdoc;                     // [n_words] its document
+    unsigned long long* whash;          // [n_words] table key of its bytes
+    unsigned long long hmask;           // hash bits kept (switch bm25_hash_bits)
+    uint32_t* rep;                      // [n_words] representative: the first word in the corpus with the same bytes
+    uint32_t* wslot;                    // [n_words] its slot in the de-duplication table, later in the pair table
+    GzBm25Slot* dtab; unsigned long long dmask;      // de-duplication table: key = hash, a = ~(smallest word index)
+    uint32_t* flag; uint32_t* scan;     // [n_words + 1] flags and their exclusive scan
+    uint32_t* term;                     // [n_words] term id
+    int64_t* tstart; uint32_t* tlen;    // [n_terms] bytes of every term (its representative's)
+    GzBm25Slot* ttab; unsigned long long tmask;      // term table: key = hash, a = term id (one slot per term)
+    GzBm25Slot* ptab; unsigned long long pmask;      // pair table: key = (doc << 32 | term) + 1, a = count, b = ~(first word index)
+    uint32_t* df;                       // [n_terms]
+    uint32_t* dfs;                      // [GZ_BM25_DF_SHARDS * n_terms] df counted per document mod GZ_BM25_DF_SHARDS (zeroed by the caller)
+    int64_t n_terms;
+    unsigned long long* sig;            // [n_docs * 4] 256-bit term signature per document
+    uint2* ent;                         // [n_ent] (term, count), doc-major, first-occurrence order inside a document
+    uint32_t* eoff;                     // [n_docs + 1] each document's first entry
+};
+enum { GZ_BM25_COUNT, GZ_BM25_WORDS, GZ_BM25_HASH, GZ_BM25_DEDUP_INS, GZ_BM25_DEDUP_RES, GZ_BM25_FIRST, GZ_BM25_TERM, GZ_BM25_PAIR_INS,
+       GZ_BM25_PAIR_FIRST, GZ_BM25_DF, GZ_BM25_ENT };
+constexpr int GZ_BM25_DF_SHARDS = 16;
+struct GzBm25Look {
+    const uint8_t* tb; const int64_t* tstart; const uint32_t* tlen; const uint32_t* df;
+    const GzBm25Slot* ttab; unsigned long long tmask, hmask;
+    const uint8_t* qtext; const int64_t* qoff; int64_t n;        // query word i = qtext[qoff[i] .. qoff[i+1])
+    int32_t* term_out; int32_t* df_out;
+};
+struct GzBm25Score {
+    const uint32_t* dl; const unsigned long long* sig; const uint32_t* eoff; const uint2* ent;
+    const GzBm25Slot* ptab; unsigned long long pmask;
+    int64_t n_docs;
+    const int32_t* qterm; const double* qidf; const int64_t* qoff; int64_t n_q;   // query q = words qoff[q] .. qoff[q+1] (absolute)
+    double kp1, k1, omb, b, avg, delta;                            // k1 + 1, k1, 1 - b, b, avgFieldLen, delta (host-computed)
+    int32_t plus;                                                  // 1: BM25Plus
+    double* out;                                                   // [n_q, n_docs]
+};
+// step: GZ_BM25_*; list / n / next: the de-duplication round's words (list null: all), the next round's list
+void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t n, uint32_t* next, hipStream_t s);
+// exclusive scan of u32: out[n + 1] (out[n] = total), bsum: (n + 4095) / 4096 + 1 words of workspace
+void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s);
+void gz_launch_bm25_lookup(const GzBm25Look& L, hipStream_t s);
+void gz_launch_bm25_score(const GzBm25Score& S, hipStream_t s);

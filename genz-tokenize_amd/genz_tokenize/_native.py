@@ -30,6 +30,8 @@ SYMBOLS = [
     "gz_preprocess_batch_device", "gz_block_create", "gz_block_release", "gz_block_dlpack", "gz_dlpack_capsule_destructor", "gz_exchange_select", "gz_encode_emit_block", "gz_block_total", "gz_comm_unique_id", "gz_comm_init", "gz_gather_rows", "gz_exchange_timing_history", "gz_compact_rows", "gz_expand_rows", "gz_compact_rows16", "gz_expand_rows16", "gz_compact_block", "gz_expand_block",
     "gz_host_tables_create", "gz_host_tables_destroy", "gz_host_tables_array", "gz_host_tables_vocab_entry",
     "gz_host_tables_merge_entry", "gz_host_tables_symbol", "gz_limit", "gz_debug_set",
+    "gz_bm25_build", "gz_bm25_build_device", "gz_bm25_info", "gz_bm25_field_lengths", "gz_bm25_lookup", "gz_bm25_score",
+    "gz_bm25_score_device", "gz_bm25_destroy",
 ]
 
 _lib = None
@@ -109,12 +111,21 @@ def load_library():
     L.gz_host_tables_vocab_entry.argtypes = [vp, i64, P(vp), P(i32), P(i32)]
     L.gz_host_tables_merge_entry.argtypes = [vp, i64, P(vp), P(i32), P(i32), P(i32)]
     L.gz_host_tables_symbol.argtypes = [vp, i32, P(vp), P(i32)]
+    if hasattr(L, "gz_bm25_build"):
+        L.gz_bm25_build.argtypes = [vp, vp, vp, i64, P(vp)]
+        L.gz_bm25_build_device.argtypes = [vp, vp, vp, i64, i64, P(vp)]
+        L.gz_bm25_info.argtypes = [vp, P(i64), P(i64), P(i64)]
+        L.gz_bm25_field_lengths.argtypes = [vp, vp]
+        L.gz_bm25_lookup.argtypes = [vp, vp, vp, i64, vp, vp]
+        L.gz_bm25_score.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp]
+        L.gz_bm25_score_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp]
+        L.gz_bm25_destroy.argtypes = [vp]; L.gz_bm25_destroy.restype = None
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
-                        "gz_dlpack_capsule_destructor", "gz_limit"):
+                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -446,6 +457,66 @@ class Context:
                                                         n_docs, text_bytes, C.c_void_p(d_out) if d_out else None, capacity,
                                                         C.c_void_p(d_out_off), C.byref(total)))
         return total.value
+
+    # ---- BM25 index (ranking.py) ----------------------------------------------------------------------------
+    def bm25_build(self, text: np.ndarray, text_off: np.ndarray) -> int:
+        """packed UTF-8 + int64 offsets -> a gz_bm25 handle (int), owned by this context."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        h = C.c_void_p()
+        self._check(self.lib.gz_bm25_build(self.handle, _ptr(text) if len(text) else None, _ptr(text_off), len(text_off) - 1, C.byref(h)))
+        return h.value
+
+    def bm25_build_device(self, d_text, d_off, n_docs: int, text_bytes: int) -> int:
+        h = C.c_void_p()
+        self._check(self.lib.gz_bm25_build_device(self.handle, C.c_void_p(d_text) if d_text else None, C.c_void_p(d_off), n_docs, text_bytes,
+                                                  C.byref(h)))
+        return h.value
+
+    def bm25_destroy(self, index: int):
+        if index and self.handle.value:                  # (a closed context has freed its indexes already)
+            self.lib.gz_bm25_destroy(C.c_void_p(index))
+
+    def bm25_info(self, index: int):
+        """(documents, distinct terms, words)"""
+        n, t, w = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.gz_bm25_info(C.c_void_p(index), C.byref(n), C.byref(t), C.byref(w)))
+        return n.value, t.value, w.value
+
+    def bm25_field_lengths(self, index: int) -> np.ndarray:
+        n = self.bm25_info(index)[0]
+        out = np.empty(max(n, 1), dtype=np.int32)
+        self._check(self.lib.gz_bm25_field_lengths(C.c_void_p(index), _ptr(out)))
+        return out[:n]
+
+    def bm25_lookup(self, index: int, words: np.ndarray, word_off: np.ndarray):
+        """packed query words -> (term ids int32, -1 when absent; df int32)"""
+        words = np.ascontiguousarray(words, dtype=np.uint8)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        n = len(word_off) - 1
+        term = np.empty(max(n, 1), dtype=np.int32)
+        df = np.empty(max(n, 1), dtype=np.int32)
+        self._check(self.lib.gz_bm25_lookup(C.c_void_p(index), _ptr(words) if len(words) else None, _ptr(word_off), n, _ptr(term), _ptr(df)))
+        return term[:n], df[:n]
+
+    def bm25_score(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool,
+                   d_out: int | None = None):
+        """scores [Q, N] float64 (host), or enqueued into d_out (device pointer; sync() waits) when it is given."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        idf = np.ascontiguousarray(idf, dtype=np.float64)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        P = np.ascontiguousarray(params, dtype=np.float64)
+        assert P.shape == (6,)
+        nq = len(query_off) - 1
+        args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
+                1 if plus else 0]
+        if d_out is not None:
+            self._check(self.lib.gz_bm25_score_device(*args, C.c_void_p(d_out)))
+            return None
+        n = self.bm25_info(index)[0]
+        out = np.empty((nq, n), dtype=np.float64)
+        self._check(self.lib.gz_bm25_score(*args, _ptr(out) if out.size else None))
+        return out
 
     def exchange_select(self, back: int):
         """Exchange operations issued from now on belong to the encode call `back` calls before the latest one."""

@@ -1,0 +1,129 @@
+"""Drop-in for genz_tokenize/ranking.py: BM25 and BM25Plus with the index built and the scores computed on the GPU.
+
+Same attributes, methods and results as the reference, to the bit: `b`, `k1`, `delta`, `num_doc`, `fieldLens`, `avgFieldLen`,
+`cal_idf`, `get_score`.  The constructor packs the documents and builds a device index (csrc/gz_bm25.inc): words by str.split(),
+term ids by exact bytes, document frequencies, per-document term counts.  Scoring is one launch for a whole batch of queries
+(`get_scores`, the form meant for real work); `get_score` is a batch of one.  There is no CPU fallback.
+
+What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
+reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
+differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
+first-occurrence order) are built on the host on first access only: they are not on the hot path.
+
+Deviation: documents and queries must be `str` (TypeError otherwise); the reference takes anything with `.split()`.
+"""
+import weakref
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _native
+from ._packing import pack as _pack
+
+_ctx: Optional[_native.Context] = None
+
+
+def _context() -> _native.Context:
+    global _ctx
+    if _ctx is None:
+        _ctx = _native.Context()
+    return _ctx
+
+
+def _strings(items, what: str) -> list:
+    items = list(items)
+    for x in items:
+        if not isinstance(x, str):
+            raise TypeError("%s must be str, not %s" % (what, type(x).__name__))
+    return items
+
+
+class BM25:
+    def __init__(self, documents: List, b: float = 0.75, k1: float = 1.2, ctx: Optional[_native.Context] = None) -> None:
+        self.b = b
+        self.k1 = k1
+        self._texts = _strings(documents, "documents")
+        self._ctx = ctx or _context()
+        buf, off = _pack(self._texts)
+        self._index = self._ctx.bm25_build(buf, off)
+        # (the finalizer holds the context: the index is freed before it)
+        self._finalizer = weakref.finalize(self, self._ctx.bm25_destroy, self._index)
+        self.num_doc = len(self._texts)
+        lens = self._ctx.bm25_field_lengths(self._index)
+        self.fieldLens = lens.tolist()
+        self.avgFieldLen = np.mean(lens)                         # ranking.py:27 (nan and a RuntimeWarning for no documents)
+        self._idf = {}
+        self._documents = None
+        self._freq = None
+
+    # ---- the reference's per-document lists, built lazily on the host -------------------------------------------------
+    @property
+    def documents(self):
+        """document.split() of every document (ranking.py:17-18)."""
+        if self._documents is None:
+            self._documents = [t.split() for t in self._texts]
+        return self._documents
+
+    @property
+    def frequency_word_in_doc(self):
+        """{word: count} per document, in first-occurrence order (ranking.py:22-26)."""
+        if self._freq is None:
+            out = []
+            for words in self.documents:
+                f = {}
+                for w in words:
+                    f[w] = f.get(w, 0) + 1
+                out.append(f)
+            self._freq = out
+        return self._freq
+
+    # ---- scoring ----------------------------------------------------------------------------------------------------
+    def _params(self):
+        delta = getattr(self, "delta", 0.0)
+        return [float(self.k1 + 1), float(self.k1), float(1 - self.b), float(self.b), float(self.avgFieldLen), float(delta)]
+
+    def _idf_of(self, q: str, df: int):
+        v = self._idf.get(q)
+        if v is None:
+            v = self._idf[q] = np.log(1+(self.num_doc-df+0.5)/(df+0.5))          # ranking.py:31, a scalar np.log
+        return v
+
+    def _lookup(self, words: Sequence[str]):
+        buf, off = _pack(list(words))
+        return self._ctx.bm25_lookup(self._index, buf, off)
+
+    def cal_idf(self, q: str) -> float:
+        if not isinstance(q, str):
+            raise TypeError("q must be str, not %s" % type(q).__name__)
+        _, df = self._lookup([q])
+        return self._idf_of(q, int(df[0]))
+
+    def get_scores(self, queries: Sequence[str]) -> np.ndarray:
+        """float64 [len(queries), num_doc]: row q is get_score(queries[q]) (0.0 for a query without words)."""
+        split = [q.split() for q in _strings(queries, "queries")]
+        qoff = np.zeros(len(split) + 1, dtype=np.int64)
+        if split:
+            np.cumsum([len(w) for w in split], out=qoff[1:])
+        words = [w for ws in split for w in ws]
+        terms, df = self._lookup(words) if words else (np.zeros(0, np.int32), np.zeros(0, np.int32))
+        idf = np.array([self._idf_of(w, int(d)) for w, d in zip(words, df.tolist())], dtype=np.float64)
+        if not split or self.num_doc == 0:
+            return np.zeros((len(split), self.num_doc), dtype=np.float64)
+        plus = isinstance(self, BM25Plus)
+        return self._ctx.bm25_score(self._index, terms, idf, qoff, self._params(), plus)
+
+    def get_score(self, query: str) -> List:
+        if not isinstance(query, str):
+            raise TypeError("query must be str, not %s" % type(query).__name__)
+        if self.num_doc == 0:
+            return []
+        if not query.split():
+            return [0] * self.num_doc                           # ranking.py:37-38: the int 0 of an empty sum
+        return list(self.get_scores([query])[0])                 # np.float64 items, like the reference's
+
+
+class BM25Plus(BM25):
+    def __init__(self, documents: List, b: float = 0.75, k1: float = 1.2, delta: float = 1.0,
+                 ctx: Optional[_native.Context] = None) -> None:
+        super().__init__(documents, b, k1, ctx)
+        self.delta = delta

@@ -241,6 +241,7 @@ int64_t gz_limit(int which);
  *                              into the caller's arrays on the host; 0: the dense rows cross
  *   host_hints (0..3; 0)       fresh output arrays of a large host call: bit 0 MADV_HUGEPAGE on them, bit 1 MADV_POPULATE_WRITE per piece
  *   inject_bad_alloc (>= 0; 0) test hook: the k-th allocation site reached from now on throws std::bad_alloc (the call answers GZ_E_NOMEM)
+ *   bm25_hash_bits (0..62; 0)  BM25 index builds keep only the low k bits of every word's hash (0: all of it)
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -362,6 +363,39 @@ int  gz_compact_block(gz_ctx *ctx, const int32_t *rows_dev, const int32_t *n_rea
                       int32_t bits, int32_t *block_dev, int64_t *total_host);
 int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_t n_rows, int32_t row_len, int64_t total_entries,
                      int32_t *ids_dev, int32_t *mask_dev);
+
+/* ---- BM25 / BM25Plus ranking (genz_tokenize/ranking.py of the reference, numpy only) ---------------------------------
+ * An index over packed documents: str.split() words (maximal runs of code points that are not among the 29 of str.isspace();
+ * terms are compared by their exact UTF-8 bytes), fieldLens, document frequencies and per-document term counts, built on the
+ * GPU and owned by the context it was built on (destroy every index before its context; gz_destroy frees what is left).
+ *   gz_bm25_build          host text / offsets (document d = text[text_off[d] .. text_off[d+1]))
+ *   gz_bm25_build_device   the same resident in HBM (offsets ABSOLUTE from the base pointer, text_bytes = text_off_dev[n_docs] -
+ *                          text_off_dev[0]); a document outside those bytes is refused with GZ_E_INVALID.  The index keeps a copy
+ *                          of the text: the caller's buffers may go once the call has returned.
+ *   gz_bm25_info           documents, distinct terms, words (all documents)
+ *   gz_bm25_field_lengths  fieldLens (ranking.py:21): words of every document, out[n_docs]
+ *   gz_bm25_lookup         query words (packed like documents, host buffers) -> term id (-1 when no document has it) and df
+ *                          (documents that contain it, ranking.py:29-31)
+ *   gz_bm25_score          scores[n_queries * n_docs] (row q = query q) into host memory: query q = the term ids
+ *                          terms[query_off[q] .. query_off[q+1]) (-1 allowed), in order, with the caller's idf of every word
+ *                          (the reference computes idf with a scalar np.log on the host, ranking.py:31).
+ *                          params = { k1 + 1, k1, 1 - b, b, avgFieldLen, delta } as the caller computes them; plus = 0 BM25
+ *                          (ranking.py:33-45), 1 BM25Plus (:52-63).  Every score is the reference's IEEE double to the bit.
+ *   gz_bm25_score_device   the same into scores_dev (HBM): enqueued on the context's stream, gz_sync waits for it
+ * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
+ * resolved by comparing bytes, so results do not change). */
+typedef struct gz_bm25 gz_bm25;
+int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
+int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
+                          gz_bm25 **out);
+int  gz_bm25_info(gz_bm25 *index, int64_t *n_docs, int64_t *n_terms, int64_t *n_words);
+int  gz_bm25_field_lengths(gz_bm25 *index, int32_t *out);
+int  gz_bm25_lookup(gz_bm25 *index, const uint8_t *words, const int64_t *word_off, int64_t n_words, int32_t *term_out, int32_t *df_out);
+int  gz_bm25_score(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                   const double params[6], int32_t plus, double *scores);
+int  gz_bm25_score_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                          const double params[6], int32_t plus, double *scores_dev);
+void gz_bm25_destroy(gz_bm25 *index);
 
 #ifdef __cplusplus
 }

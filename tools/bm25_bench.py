@@ -1,0 +1,117 @@
+"""BM25 index / scoring timings on the configs[2] corpus (genz_tokenize.ranking, csrc/gz_bm25.inc).
+
+    python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--out profiles/bm25_bench.json]
+
+Host clock around call + synchronisation, after a warm-up call, median of --reps:
+  build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
+  score_q{1,64,256}_ms scoring Q queries of 8 words into device memory (gz_bm25_score_device + gz_sync)
+  ctor_ms              the Python constructor BM25(list of str): packing, host -> device, build, fieldLens, avgFieldLen
+  restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
+                       its postings built beforehand (not timed)
+Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "genz-tokenize_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+import corpus  # noqa: E402
+from genz_tokenize import _native  # noqa: E402
+from genz_tokenize._packing import pack  # noqa: E402
+from genz_tokenize.ranking import BM25  # noqa: E402
+
+
+def median_ms(fn, reps):
+    fn()                                                             # warm
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), [round(t, 3) for t in ts]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--docs", type=int, default=1_000_000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--restate-docs", type=int, default=100_000)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
+    n, nbytes = len(o) - 1, int(o[-1])
+    ctx = _native.Context()
+    res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
+
+    d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
+    ctx.h2d(d_text, t)
+    ctx.h2d(d_off, o)
+
+    ts = []
+    for k in range(a.reps + 1):                                      # (the first build is the warm-up)
+        t0 = time.perf_counter()
+        ix = ctx.bm25_build_device(d_text, d_off, n, nbytes)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        if k < a.reps:
+            ctx.bm25_destroy(ix)
+    res["build_device_ms"], res["build_device_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
+    res["terms"], res["words"] = ctx.bm25_info(ix)[1:]
+    lens = ctx.bm25_field_lengths(ix)
+    avg = float(np.mean(lens))
+    raw = t.tobytes()
+    vocab = sorted({w for i in range(2000) for w in raw[o[i]:o[i + 1]].decode("utf-8").split()})
+    rng = np.random.default_rng(1)
+    queries = [" ".join(vocab[int(k)] for k in rng.integers(len(vocab), size=8)) for _ in range(256)]
+    words = [w for q in queries for w in q.split()]
+    wb, wo = pack(words)
+    terms, df = ctx.bm25_lookup(ix, wb, wo)
+    idf = np.array([np.log(1+(n-int(d)+0.5)/(int(d)+0.5)) for d in df])
+    params = [2.2, 1.2, 0.25, 0.75, avg, 0.0]
+    d_out = ctx.alloc(256 * n * 8)
+    for q in (1, 64, 256):
+        qoff = np.arange(q + 1, dtype=np.int64) * 8
+
+        def score():
+            ctx.bm25_score(ix, terms[:8 * q], idf[:8 * q], qoff, params, False, d_out=d_out)
+            ctx.sync()
+        res["score_q%d_ms" % q], res["score_q%d_all_ms" % q] = median_ms(score, a.reps)
+    res["score_q256_write_GBps"] = round(256 * n * 8 / res["score_q256_ms"] / 1e6, 1)
+    ctx.free(d_out)
+    ctx.bm25_destroy(ix)
+    ctx.free(d_text)
+    ctx.free(d_off)
+
+    docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n)]
+    holder = []
+    res["ctor_ms"], res["ctor_all_ms"] = median_ms(lambda: (holder.clear(), holder.append(BM25(docs, ctx=ctx))), a.reps)
+    holder.clear()
+
+    if a.restate_docs:
+        import bm25_restate as R
+        sub = docs[:a.restate_docs]
+        lens_s, freq_s = R.stats(sub)
+        post = R.Postings(freq_s)
+        avg_s = R.avg_field_len(lens_s)
+
+        def restate():
+            for q in queries[:64]:
+                w = q.split()
+                R.scores(lens_s, post, avg_s, w, [R.idf(len(sub), post.df(x)) for x in w], 0.75, 1.2)
+        res["restate_docs"] = len(sub)
+        res["restate_q64_ms"], _ = median_ms(restate, 1)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
