@@ -174,7 +174,7 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
-    DBuf w_bm[24];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring call (gz_bm25.inc)
+    DBuf w_bm[32];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
@@ -955,7 +955,8 @@ struct gz_bm25 {
 
 namespace {
 enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW_HASH, BMW_REP, BMW_SLOT, BMW_LIST0, BMW_LIST1, BMW_DTAB,
-       BMW_FLAG, BMW_SCAN, BMW_TERM, BMW_DFS, BMW_QTEXT, BMW_QOFF, BMW_QRES, BMW_QTERM, BMW_QIDF, BMW_SCORES };
+       BMW_FLAG, BMW_SCAN, BMW_TERM, BMW_DFS, BMW_QTEXT, BMW_QOFF, BMW_QRES, BMW_QTERM, BMW_QIDF, BMW_SCORES,
+       BMW_CKEY0, BMW_CIDX0, BMW_CKEY1, BMW_CIDX1, BMW_TOUT };
 
 // Every error return of an index build drains the context's stream before the buffers the call owns (the index under
 // construction) are freed: declared AFTER the index, destroyed before it.
@@ -1096,6 +1097,31 @@ int bm_adopt(gz_ctx* c, std::unique_ptr<gz_bm25>& ix, gz_bm25** out)
     return GZ_OK;
 }
 
+// the query arrays of a scoring / top-k call -> the context's workspace, and the scoring kernel's arguments for all of them
+// (S.out unset)
+int bm25_query_in(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
+                  GzBm25Score& S)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    const int64_t nw = qoff[nq] - qoff[0];
+    int rc;
+    if ((rc = bm_alloc(c, w[BMW_QTERM], (size_t)nw * 4)) || (rc = bm_alloc(c, w[BMW_QIDF], (size_t)nw * 8)) ||
+        (rc = bm_alloc(c, w[BMW_QOFF], (size_t)(nq + 1) * 8)))
+        return rc;
+    if (nw && ((rc = copy_in(c, w[BMW_QTERM].p, terms + qoff[0], (size_t)nw * 4, s)) || (rc = copy_in(c, w[BMW_QIDF].p, idf + qoff[0], (size_t)nw * 8, s))))
+        return rc;
+    if ((rc = copy_in(c, w[BMW_QOFF].p, qoff, (size_t)(nq + 1) * 8, s))) return rc;
+    S = GzBm25Score{};
+    S.dl = (const uint32_t*)ix->dl.p; S.sig = (const unsigned long long*)ix->sig.p; S.eoff = (const uint32_t*)ix->eoff.p;
+    S.ent = (const uint2*)ix->ent.p; S.ptab = (const GzBm25Slot*)ix->ptab.p; S.pmask = ix->pmask; S.n_docs = ix->n_docs;
+    S.qterm = (const int32_t*)w[BMW_QTERM].p - qoff[0]; S.qidf = (const double*)w[BMW_QIDF].p - qoff[0];
+    S.qoff = (const int64_t*)w[BMW_QOFF].p; S.n_q = nq;
+    S.kp1 = P[0]; S.k1 = P[1]; S.omb = P[2]; S.b = P[3]; S.avg = P[4]; S.delta = P[5]; S.plus = plus ? 1 : 0;
+    return GZ_OK;
+}
+
 // the query arrays of a scoring call -> the kernel; out_dev null: into the context's workspace and back to out_host
 int bm25_score_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
                       double* out_dev, double* out_host)
@@ -1104,21 +1130,11 @@ int bm25_score_locked(gz_bm25* ix, const int32_t* terms, const double* idf, cons
     DBuf* w = c->w_bm;
     hipStream_t s = c->stream;
     HIPCHK(c, hipSetDevice(c->device));
-    const int64_t nw = qoff[nq] - qoff[0], N = ix->n_docs;
-    int rc;
-    if ((rc = bm_alloc(c, w[BMW_QTERM], (size_t)nw * 4)) || (rc = bm_alloc(c, w[BMW_QIDF], (size_t)nw * 8)) ||
-        (rc = bm_alloc(c, w[BMW_QOFF], (size_t)(nq + 1) * 8)))
-        return rc;
+    const int64_t N = ix->n_docs;
+    GzBm25Score S;
+    int rc = bm25_query_in(ix, terms, idf, qoff, nq, P, plus, S);
+    if (rc) return rc;
     if (!out_dev && (rc = bm_alloc(c, w[BMW_SCORES], (size_t)(nq * N) * 8))) return rc;
-    if (nw && ((rc = copy_in(c, w[BMW_QTERM].p, terms + qoff[0], (size_t)nw * 4, s)) || (rc = copy_in(c, w[BMW_QIDF].p, idf + qoff[0], (size_t)nw * 8, s))))
-        return rc;
-    if ((rc = copy_in(c, w[BMW_QOFF].p, qoff, (size_t)(nq + 1) * 8, s))) return rc;
-    GzBm25Score S{};
-    S.dl = (const uint32_t*)ix->dl.p; S.sig = (const unsigned long long*)ix->sig.p; S.eoff = (const uint32_t*)ix->eoff.p;
-    S.ent = (const uint2*)ix->ent.p; S.ptab = (const GzBm25Slot*)ix->ptab.p; S.pmask = ix->pmask; S.n_docs = N;
-    S.qterm = (const int32_t*)w[BMW_QTERM].p - qoff[0]; S.qidf = (const double*)w[BMW_QIDF].p - qoff[0];
-    S.qoff = (const int64_t*)w[BMW_QOFF].p; S.n_q = nq;
-    S.kp1 = P[0]; S.k1 = P[1]; S.omb = P[2]; S.b = P[3]; S.avg = P[4]; S.delta = P[5]; S.plus = plus ? 1 : 0;
     S.out = out_dev ? out_dev : (double*)w[BMW_SCORES].p;
     gz_launch_bm25_score(S, s);
     HIPCHK(c, hipGetLastError());
@@ -1138,6 +1154,74 @@ int bm25_score_args(gz_bm25* ix, const int32_t* terms, const double* idf, const 
     for (int64_t q = 0; q < nq; ++q) if (qoff[q + 1] < qoff[q]) return fail(c, GZ_E_INVALID, "query offsets must not decrease");
     for (int64_t j = qoff[0]; j < qoff[nq]; ++j)
         if (terms[j] < -1 || terms[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "term id %d out of range", terms[j]);
+    return GZ_OK;
+}
+
+static_assert(GZ_TOPK_SORT == GZ_BM25_TOPK_MAX, "the last selection level sorts GZ_BM25_TOPK_MAX winners in LDS");
+
+// k (>= 1) -> k' = min(k, documents), refused above GZ_BM25_TOPK_MAX
+int bm25_topk_k(gz_bm25* ix, int64_t k, int64_t& kk)
+{
+    if (k < 1) return fail(ix->c, GZ_E_INVALID, "k = %lld; top-k takes k >= 1", (long long)k);
+    kk = k < ix->n_docs ? k : ix->n_docs;
+    if (kk > GZ_BM25_TOPK_MAX) return fail(ix->c, GZ_E_LIMIT, "k = %lld over %lld documents; top-k takes at most %d", (long long)k,
+                                            (long long)ix->n_docs, GZ_BM25_TOPK_MAX);
+    return GZ_OK;
+}
+
+// documents per workgroup of the first selection level: bm25_topk_tile when it is set, else enough tiles for ~2048 workgroups over
+// the chunk's rows (8 per CU), at least 4 k' (each tile keeps k' candidates) and 256, at most GZ_TOPK_TILE_MAX
+int64_t bm25_topk_tile(const gz_ctx* c, int64_t rows, int64_t N, int64_t kk)
+{
+    int64_t t = c->opt.bm25_topk_tile;
+    if (t <= 0) {
+        const int64_t per_row = (2048 + rows - 1) / rows;
+        t = std::max<int64_t>((N + per_row - 1) / per_row, std::max<int64_t>(256, 4 * kk));
+        t = std::min<int64_t>(t, GZ_TOPK_TILE_MAX);
+    }
+    return std::max<int64_t>(t, (N + ((int64_t)1 << 30) - 1) >> 30);        // (tiles of a row fit a grid dimension)
+}
+
+// Score rows, a chunk of queries at a time, into the context's workspace (at most bm25_topk_chunk doubles, one row at least), and
+// the selection levels over them; ids / scores into doc_dev / score_dev, or into host memory after every chunk (doc_dev null)
+int bm25_topk_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
+                     int64_t kk, int64_t* doc_dev, double* score_dev, int64_t* doc_host, double* score_host)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t N = ix->n_docs;
+    if (nq == 0 || N == 0) return GZ_OK;
+    const int64_t rmax = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>((int64_t)c->opt.bm25_topk_chunk / N, 1), 65535), nq);
+    const int64_t tile = bm25_topk_tile(c, rmax, N, kk);
+    int64_t m1, m2;
+    gz_topk_sizes(N, tile, kk, m1, m2);
+    GzBm25Score S;
+    int rc = bm25_query_in(ix, terms, idf, qoff, nq, P, plus, S);
+    if (rc) return rc;
+    if ((rc = bm_alloc(c, w[BMW_SCORES], (size_t)(rmax * N) * 8)) || (rc = bm_alloc(c, w[BMW_CKEY0], (size_t)(rmax * m1) * 8)) ||
+        (rc = bm_alloc(c, w[BMW_CIDX0], (size_t)(rmax * m1) * 4)) || (rc = bm_alloc(c, w[BMW_CKEY1], (size_t)(rmax * m2) * 8)) ||
+        (rc = bm_alloc(c, w[BMW_CIDX1], (size_t)(rmax * m2) * 4)) || (!doc_dev && (rc = bm_alloc(c, w[BMW_TOUT], (size_t)(rmax * kk) * 16))))
+        return rc;
+    GzTopk T{};
+    T.scores = (const double*)w[BMW_SCORES].p; T.n_docs = N; T.k = kk; T.tile = tile;
+    T.ckey[0] = (unsigned long long*)w[BMW_CKEY0].p; T.cidx[0] = (uint32_t*)w[BMW_CIDX0].p;
+    T.ckey[1] = (unsigned long long*)w[BMW_CKEY1].p; T.cidx[1] = (uint32_t*)w[BMW_CIDX1].p;
+    const int64_t* qoff_dev = S.qoff;
+    for (int64_t q0 = 0; q0 < nq; q0 += rmax) {
+        const int64_t rows = std::min(rmax, nq - q0);
+        S.qoff = qoff_dev + q0; S.n_q = rows; S.out = (double*)w[BMW_SCORES].p;
+        gz_launch_bm25_score(S, s);
+        T.rows = rows;
+        T.doc_out = doc_dev ? doc_dev + q0 * kk : (int64_t*)w[BMW_TOUT].p;
+        T.score_out = doc_dev ? score_dev + q0 * kk : (double*)w[BMW_TOUT].p + rmax * kk;
+        gz_launch_topk(T, s);
+        HIPCHK(c, hipGetLastError());
+        if (!doc_dev && ((rc = copy_out(c, doc_host + q0 * kk, T.doc_out, (size_t)(rows * kk) * 8, s)) ||
+                         (rc = copy_out(c, score_host + q0 * kk, T.score_out, (size_t)(rows * kk) * 8, s))))
+            return rc;
+    }
     return GZ_OK;
 }
 }  // namespace
@@ -2772,6 +2856,26 @@ try {
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_score_locked(ix, terms, idf, query_off, n_queries, params, plus, scores_dev, nullptr);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_topk(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                 int32_t plus, int64_t k, int64_t* doc_out, double* score_out)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out && score_out ? doc_out : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk))) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_topk_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, nullptr, nullptr, doc_out, score_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_topk_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                        const double params[6], int32_t plus, int64_t k, int64_t* doc_out_dev, double* score_out_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out_dev && score_out_dev ? doc_out_dev : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk))) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_topk_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, doc_out_dev, score_out_dev, nullptr, nullptr);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 void gz_bm25_destroy(gz_bm25* ix)

@@ -83,6 +83,8 @@ struct GzOptions {
     int32_t inject_bad_alloc = 0;     // test hook: k > 0 makes the k-th allocation site reached from now on throw std::bad_alloc (counts down to 0)
     int32_t bm25_hash_bits = 0;       // BM25 index build: k > 0 keeps only the low k bits of every word's 64-bit hash (forced collisions: results
                                       // must not change); 0 the whole hash
+    int32_t bm25_topk_chunk = 1 << 27; // BM25 top-k: doubles of score rows in the context's workspace at a time (one row at least; 2^27 = 1 GiB)
+    int32_t bm25_topk_tile = 0;       // BM25 top-k: documents per workgroup of the first selection level (0: chosen per call from Q, N, k)
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

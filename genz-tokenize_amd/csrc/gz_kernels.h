@@ -203,3 +203,26 @@ void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t
 void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s);
 void gz_launch_bm25_lookup(const GzBm25Look& L, hipStream_t s);
 void gz_launch_bm25_score(const GzBm25Score& S, hipStream_t s);
+
+// BM25 top-k (gz_topk.inc): selection over score rows in HBM, level after level until one tile per row is left
+constexpr int GZ_TOPK_TILE_MAX = 4096;    // elements per workgroup of a selection level (16 per thread, in registers)
+constexpr int GZ_TOPK_SORT = 1024;        // == GZ_BM25_TOPK_MAX of the public header: the last level's sort in LDS
+struct GzTopk {
+    const double* scores;                 // [rows, n_docs] the score rows
+    int64_t n_docs, rows, k;              // k = min(k, n_docs) <= GZ_TOPK_SORT
+    int64_t tile;                         // documents per workgroup of the first level (1 .. GZ_TOPK_TILE_MAX)
+    unsigned long long* ckey[2];          // candidates between levels (ping-pong): [rows, m1] and [rows, m2] of gz_topk_sizes
+    uint32_t* cidx[2];
+    int64_t* doc_out; double* score_out;  // [rows, k]
+};
+// candidates per row that a level over m elements in tiles of `tile` keeps
+inline int64_t gz_topk_level(int64_t m, int64_t tile, int64_t k) { return (m + tile - 1) / tile * (k < tile ? k : tile); }
+// candidates per row of the first level's output (m1) and of the second's (m2); 0 where that level is the last
+inline void gz_topk_sizes(int64_t n_docs, int64_t tile, int64_t k, int64_t& m1, int64_t& m2)
+{
+    m1 = m2 = 0;
+    if ((n_docs + tile - 1) / tile <= 1) return;
+    m1 = gz_topk_level(n_docs, tile, k);
+    if ((m1 + GZ_TOPK_TILE_MAX - 1) / GZ_TOPK_TILE_MAX > 1) m2 = gz_topk_level(m1, GZ_TOPK_TILE_MAX, k);
+}
+void gz_launch_topk(const GzTopk& T, hipStream_t s);

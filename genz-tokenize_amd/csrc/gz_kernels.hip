@@ -691,6 +691,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_decode.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
+#include "gz_topk.inc"
 
 // =================================================================================================================
 // launchers

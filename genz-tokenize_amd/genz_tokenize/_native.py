@@ -31,7 +31,7 @@ SYMBOLS = [
     "gz_host_tables_create", "gz_host_tables_destroy", "gz_host_tables_array", "gz_host_tables_vocab_entry",
     "gz_host_tables_merge_entry", "gz_host_tables_symbol", "gz_limit", "gz_debug_set",
     "gz_bm25_build", "gz_bm25_build_device", "gz_bm25_info", "gz_bm25_field_lengths", "gz_bm25_lookup", "gz_bm25_score",
-    "gz_bm25_score_device", "gz_bm25_destroy",
+    "gz_bm25_score_device", "gz_bm25_destroy", "gz_bm25_topk", "gz_bm25_topk_device",
 ]
 
 _lib = None
@@ -120,6 +120,9 @@ def load_library():
         L.gz_bm25_score.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp]
         L.gz_bm25_score_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp]
         L.gz_bm25_destroy.argtypes = [vp]; L.gz_bm25_destroy.restype = None
+    if hasattr(L, "gz_bm25_topk"):
+        L.gz_bm25_topk.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp]
+        L.gz_bm25_topk_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -517,6 +520,27 @@ class Context:
         out = np.empty((nq, n), dtype=np.float64)
         self._check(self.lib.gz_bm25_score(*args, _ptr(out) if out.size else None))
         return out
+
+    def bm25_topk(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool, k: int,
+                  d_ids: int | None = None, d_scores: int | None = None):
+        """(ids int64 [Q, k'], scores float64 [Q, k']) with k' = min(k, documents): the best documents of every query (host), or
+        enqueued into d_ids / d_scores (device pointers; sync() waits) when they are given."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        idf = np.ascontiguousarray(idf, dtype=np.float64)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        P = np.ascontiguousarray(params, dtype=np.float64)
+        assert P.shape == (6,)
+        nq = len(query_off) - 1
+        args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
+                1 if plus else 0, int(k)]
+        if d_ids is not None or d_scores is not None:
+            self._check(self.lib.gz_bm25_topk_device(*args, C.c_void_p(d_ids), C.c_void_p(d_scores)))
+            return None
+        kk = max(0, min(int(k), self.bm25_info(index)[0]))
+        ids = np.empty((nq, kk), dtype=np.int64)
+        scores = np.empty((nq, kk), dtype=np.float64)
+        self._check(self.lib.gz_bm25_topk(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None))
+        return ids, scores
 
     def exchange_select(self, back: int):
         """Exchange operations issued from now on belong to the encode call `back` calls before the latest one."""

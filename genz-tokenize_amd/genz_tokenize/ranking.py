@@ -5,6 +5,10 @@ Same attributes, methods and results as the reference, to the bit: `b`, `k1`, `d
 term ids by exact bytes, document frequencies, per-document term counts.  Scoring is one launch for a whole batch of queries
 (`get_scores`, the form meant for real work); `get_score` is a batch of one.  There is no CPU fallback.
 
+Retrieval: `top_k(queries, k)` returns the ids and scores of every query's k best documents and `get_top_n(query, documents, n)`
+those documents (rank_bm25's form).  The score rows are computed and searched on the GPU (csrc/gz_topk.inc): only [Q, k] ids and
+scores come back.  The order is total: higher scores first, ties to the lower document index, NaN last.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -12,6 +16,7 @@ first-occurrence order) are built on the host on first access only: they are not
 
 Deviation: documents and queries must be `str` (TypeError otherwise); the reference takes anything with `.split()`.
 """
+import numbers
 import weakref
 from typing import List, Optional, Sequence
 
@@ -98,8 +103,8 @@ class BM25:
         _, df = self._lookup([q])
         return self._idf_of(q, int(df[0]))
 
-    def get_scores(self, queries: Sequence[str]) -> np.ndarray:
-        """float64 [len(queries), num_doc]: row q is get_score(queries[q]) (0.0 for a query without words)."""
+    def _queries(self, queries: Sequence[str]):
+        """str.split() of every query -> (query count, term ids, host idf of every word, int64 query offsets)."""
         split = [q.split() for q in _strings(queries, "queries")]
         qoff = np.zeros(len(split) + 1, dtype=np.int64)
         if split:
@@ -107,10 +112,41 @@ class BM25:
         words = [w for ws in split for w in ws]
         terms, df = self._lookup(words) if words else (np.zeros(0, np.int32), np.zeros(0, np.int32))
         idf = np.array([self._idf_of(w, int(d)) for w, d in zip(words, df.tolist())], dtype=np.float64)
-        if not split or self.num_doc == 0:
-            return np.zeros((len(split), self.num_doc), dtype=np.float64)
+        return len(split), terms, idf, qoff
+
+    def get_scores(self, queries: Sequence[str]) -> np.ndarray:
+        """float64 [len(queries), num_doc]: row q is get_score(queries[q]) (0.0 for a query without words)."""
+        nq, terms, idf, qoff = self._queries(queries)
+        if not nq or self.num_doc == 0:
+            return np.zeros((nq, self.num_doc), dtype=np.float64)
         plus = isinstance(self, BM25Plus)
         return self._ctx.bm25_score(self._index, terms, idf, qoff, self._params(), plus)
+
+    def top_k(self, queries: Sequence[str], k: int):
+        """(ids int64 [len(queries), k'], scores float64 [len(queries), k']), k' = min(k, num_doc): row q holds the k' best documents
+        of queries[q], np.argsort(-get_scores(queries)[q], kind="stable")[:k'] and their scores (original bits).  Higher scores first,
+        +0.0 and -0.0 tie, NaN below every number, ties to the lower document index.  Selected on the GPU: the score rows never
+        leave device memory.  k' above 1024 raises _native.GzError (GZ_E_LIMIT)."""
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise TypeError("k must be int, not %s" % type(k).__name__)
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1, not %d" % k)
+        nq, terms, idf, qoff = self._queries(queries)
+        plus = isinstance(self, BM25Plus)
+        return self._ctx.bm25_topk(self._index, terms, idf, qoff, self._params(), plus, k)
+
+    def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
+        """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].
+        documents defaults to the strings the index was built from; any sequence of num_doc objects may stand in for them."""
+        if not isinstance(query, str):
+            raise TypeError("query must be str, not %s" % type(query).__name__)
+        if documents is None:
+            documents = self._texts
+        elif len(documents) != self.num_doc:
+            raise ValueError("documents has %d items; the index has %d documents" % (len(documents), self.num_doc))
+        ids, _ = self.top_k([query], n)
+        return [documents[i] for i in ids[0].tolist()]
 
     def get_score(self, query: str) -> List:
         if not isinstance(query, str):

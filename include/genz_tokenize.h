@@ -242,6 +242,9 @@ int64_t gz_limit(int which);
  *   host_hints (0..3; 0)       fresh output arrays of a large host call: bit 0 MADV_HUGEPAGE on them, bit 1 MADV_POPULATE_WRITE per piece
  *   inject_bad_alloc (>= 0; 0) test hook: the k-th allocation site reached from now on throws std::bad_alloc (the call answers GZ_E_NOMEM)
  *   bm25_hash_bits (0..62; 0)  BM25 index builds keep only the low k bits of every word's hash (0: all of it)
+ *   bm25_topk_chunk (1..2^30; 2^27)  BM25 top-k: doubles of score rows held in the context's workspace at a time (queries are
+ *                              scored a chunk at a time, one row at least)
+ *   bm25_topk_tile (0..4096; 0)  BM25 top-k: documents per workgroup of the first selection level (0: chosen per call)
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -382,8 +385,16 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          params = { k1 + 1, k1, 1 - b, b, avgFieldLen, delta } as the caller computes them; plus = 0 BM25
  *                          (ranking.py:33-45), 1 BM25Plus (:52-63).  Every score is the reference's IEEE double to the bit.
  *   gz_bm25_score_device   the same into scores_dev (HBM): enqueued on the context's stream, gz_sync waits for it
+ *   gz_bm25_topk           the k' = min(k, n_docs) best documents of every query, row-major [n_queries, k'] into doc_out (int64)
+ *                          and score_out: with S the scores of gz_bm25_score, row q is np.argsort(-S[q], kind="stable")[:k'] and
+ *                          S[q] at those ids, original bits.  Higher scores first, +0.0 and -0.0 tie, every NaN below every number,
+ *                          ties to the lower document index.  Query arguments as gz_bm25_score.  k < 1: GZ_E_INVALID; k' above
+ *                          GZ_BM25_TOPK_MAX: GZ_E_LIMIT.  Nothing outside the [n_queries, k'] outputs is written.  The scores stay
+ *                          in HBM (a chunk of queries at a time, switch bm25_topk_chunk); only ids and scores cross to the host.
+ *   gz_bm25_topk_device    the same into doc_out_dev / score_out_dev (HBM): enqueued on the context's stream, gz_sync waits for it
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
+#define GZ_BM25_TOPK_MAX 1024
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
@@ -395,6 +406,10 @@ int  gz_bm25_score(gz_bm25 *index, const int32_t *terms, const double *idf, cons
                    const double params[6], int32_t plus, double *scores);
 int  gz_bm25_score_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
                           const double params[6], int32_t plus, double *scores_dev);
+int  gz_bm25_topk(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                  const double params[6], int32_t plus, int64_t k, int64_t *doc_out, double *score_out);
+int  gz_bm25_topk_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                         const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev);
 void gz_bm25_destroy(gz_bm25 *index);
 
 #ifdef __cplusplus

@@ -5,7 +5,13 @@
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
   score_q{1,64,256}_ms scoring Q queries of 8 words into device memory (gz_bm25_score_device + gz_sync)
+  topk_q{1,64,256}_k{10,1000}_ms  the k best documents of Q queries into device memory (gz_bm25_topk_device + gz_sync): scoring,
+                       a chunk of queries at a time, and the selection levels
   ctor_ms              the Python constructor BM25(list of str): packing, host -> device, build, fieldLens, avgFieldLen
+  topk_host_q256_k100_ms           BM25.top_k(256 queries, 100): ids and scores [256, 100] in host memory
+  get_scores_host_q256_ms          BM25.get_scores(256 queries): the float64 [256, N] matrix in host memory
+  get_scores_argpartition_q256_k100_ms  the same followed by np.argpartition and a sort of the 100 per row (what a caller does
+                       without top_k; --host-reps reps)
   restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
                        its postings built beforehand (not timed)
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
@@ -43,6 +49,7 @@ def main():
     ap.add_argument("--docs", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--restate-docs", type=int, default=100_000)
+    ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
@@ -84,6 +91,18 @@ def main():
         res["score_q%d_ms" % q], res["score_q%d_all_ms" % q] = median_ms(score, a.reps)
     res["score_q256_write_GBps"] = round(256 * n * 8 / res["score_q256_ms"] / 1e6, 1)
     ctx.free(d_out)
+    d_ids, d_sc = ctx.alloc(256 * 1000 * 8), ctx.alloc(256 * 1000 * 8)
+    for q in (1, 64, 256):
+        qoff = np.arange(q + 1, dtype=np.int64) * 8
+        for k in (10, 1000):
+            def topk():
+                ctx.bm25_topk(ix, terms[:8 * q], idf[:8 * q], qoff, params, False, k, d_ids=d_ids, d_scores=d_sc)
+                ctx.sync()
+            res["topk_q%d_k%d_ms" % (q, k)], res["topk_q%d_k%d_all_ms" % (q, k)] = median_ms(topk, a.reps)
+    for k in (10, 1000):
+        res["topk_q256_k%d_over_score_pct" % k] = round(100 * (res["topk_q256_k%d_ms" % k] / res["score_q256_ms"] - 1), 1)
+    ctx.free(d_ids)
+    ctx.free(d_sc)
     ctx.bm25_destroy(ix)
     ctx.free(d_text)
     ctx.free(d_off)
@@ -91,7 +110,25 @@ def main():
     docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n)]
     holder = []
     res["ctor_ms"], res["ctor_all_ms"] = median_ms(lambda: (holder.clear(), holder.append(BM25(docs, ctx=ctx))), a.reps)
+    m = holder[0]
     holder.clear()
+
+    def host_topk():
+        return m.top_k(queries, 100)
+
+    def host_scores():
+        return m.get_scores(queries)
+
+    def host_argpartition():
+        S = m.get_scores(queries)
+        part = np.argpartition(-S, 99, axis=1)[:, :100]
+        v = np.take_along_axis(S, part, 1)
+        order = np.argsort(-v, axis=1, kind="stable")
+        return np.take_along_axis(part, order, 1)
+    res["topk_host_q256_k100_ms"], res["topk_host_q256_k100_all_ms"] = median_ms(host_topk, a.reps)
+    res["get_scores_host_q256_ms"], res["get_scores_host_q256_all_ms"] = median_ms(host_scores, a.reps)
+    res["get_scores_argpartition_q256_k100_ms"], res["get_scores_argpartition_q256_k100_all_ms"] = median_ms(host_argpartition, a.host_reps)
+    del m
 
     if a.restate_docs:
         import bm25_restate as R
