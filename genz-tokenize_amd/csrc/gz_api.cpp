@@ -946,6 +946,7 @@ static int install_word_tables(gz_ctx* c, const WordImages& W)
 struct gz_bm25 {
     gz_ctx* c = nullptr;
     int64_t n_docs = 0, n_words = 0, n_terms = 0, n_ent = 0, off0 = 0;
+    int64_t text_bytes = 0;              // bytes of `text` in use: an append (gz_bm25_append) puts its batch behind them
     unsigned long long hmask = 0, pmask = 0, tmask = 0;
     // the index: a copy of the text (the terms' bytes), fieldLens, signatures, doc-major (term, count) entries, the (document, term)
     // pair table, the term table, the terms' byte ranges and df
@@ -1011,6 +1012,7 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     GzBm25Args A{};
     A.tb = (const uint8_t*)ix->text.p - ix->off0;
     A.off = off_dev; A.n_docs = N; A.lo = ix->off0; A.hi = ix->off0 + text_bytes;
+    ix->text_bytes = text_bytes;
     const int bits = c->opt.bm25_hash_bits;
     ix->hmask = A.hmask = bits > 0 ? (1ull << bits) - 1ull : ~0ull >> 1;
     const int64_t wmax = (text_bytes + N) / 2 + 1;
@@ -1086,6 +1088,157 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     gz_launch_bm25(GZ_BM25_ENT, A, nullptr, 0, nullptr, s);
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+// ---- append (gz_bm25_append) ---------------------------------------------------------------------------------------------------
+// The index's buffers have a capacity (DBuf::cap) and grow geometrically.  A buffer that must grow is STAGED: a larger one is
+// allocated, the live bytes are copied (a table is re-hashed) into it, and the live buffer stays as it is until commit() swaps
+// the two -- after the last allocation of the call.  The stage is declared BEFORE the call's BmDrain: whatever it still holds
+// (the fresh buffers of a failed call, the old ones of a successful one) is freed after the stream has drained.
+struct BmStage {
+    static constexpr int MAX = 12;
+    DBuf* live[MAX] = {};
+    DBuf fresh[MAX];
+    int n = 0;
+    ~BmStage() { for (int i = 0; i < n; ++i) release(fresh[i]); }
+    void commit() { for (int i = 0; i < n; ++i) std::swap(*live[i], fresh[i]); }
+};
+
+// `need` bytes behind *p, the first `keep` of them the live buffer's: the live buffer itself when it has the room, else a staged
+// copy of at least twice its capacity.  renew: always a staged buffer, of `need` bytes, nothing copied (a table to re-hash into).
+int bm_reserve(gz_ctx* c, BmStage& st, DBuf& live, size_t keep, size_t need, void** p, bool renew = false)
+{
+    alloc_site(c);
+    if (!renew && live.p && need <= live.cap) { *p = live.p; return GZ_OK; }
+    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 append: stage overflow");
+    DBuf& f = st.fresh[st.n];
+    int rc = ensure(c, f, renew ? need : std::max(need, 2 * live.cap));
+    if (rc) return rc;
+    st.live[st.n++] = &live;
+    if (keep && !renew) HIPCHK(c, hipMemcpyAsync(f.p, live.p, keep, hipMemcpyDeviceToDevice, c->stream));
+    *p = f.p;
+    return GZ_OK;
+}
+
+// n documents behind the index's own.  text_host / text_dev (one of them): the batch's first byte; off_dev: its n + 1 offsets in
+// device memory, absolute from a base under which the first byte is batch_off0; add: its bytes.
+// Phase A computes the batch's words and new terms beside the live index (tails beyond the counts, workspace, staged copies);
+// phase B makes every remaining allocation; only then phase C commits the staged buffers and writes the term table, the pair
+// table, df, the signatures and the entries.  A return before phase C leaves the index answering as before.  The word count, the
+// unknown-word count, the collision rounds, the new-term count and the entry count are host round trips, as in the build.
+int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_host, const uint8_t* text_dev, const int64_t* off_dev,
+                     int64_t batch_off0, int64_t n, int64_t add)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t N0 = ix->n_docs, T0 = ix->n_terms, E0 = ix->n_ent, used = ix->text_bytes;
+    int rc;
+    // ---- phase A: text, word boundaries, known terms, de-duplication of the rest
+    void* p_text = nullptr; void* p_dl = nullptr;
+    const int64_t wmax = (add + n) / 2 + 1;
+    if ((rc = bm_reserve(c, st, ix->text, (size_t)used, (size_t)(used + add) + 16, &p_text)) ||
+        (rc = bm_reserve(c, st, ix->dl, (size_t)N0 * 4, (size_t)(N0 + n) * 4, &p_dl)) ||
+        (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(n + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
+        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((n > wmax ? n : wmax) / 4096 + 2) * 4)))
+        return rc;
+    if (add && text_host && (rc = copy_in(c, (uint8_t*)p_text + used, text_host, (size_t)add, s))) return rc;
+    if (add && text_dev) HIPCHK(c, hipMemcpyAsync((uint8_t*)p_text + used, text_dev, (size_t)add, hipMemcpyDeviceToDevice, s));
+    GzBm25Args A{};
+    A.tb = (const uint8_t*)p_text - ix->off0;
+    A.off = off_dev; A.n_docs = n; A.lo = ix->off0 + used; A.hi = A.lo + add; A.obase = A.lo - batch_off0;
+    A.hmask = ix->hmask;                                     // (the index's own: the switch's value of today does not enter)
+    A.doc_base = (uint32_t)N0; A.term_base = (uint32_t)T0; A.ent_base = (uint32_t)E0;
+    A.ctl = (uint32_t*)w[BMW_CTL].p; A.wcnt = (uint32_t*)p_dl + N0; A.woff = (uint32_t*)w[BMW_WOFF].p;
+    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.wcnt, n, A.woff))) return rc;
+    int64_t bad = 0, W = 0;
+    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + n, W))) return rc;
+    if (bad) return fail(c, GZ_E_INVALID, "BM25 append: document offsets decrease or leave the %lld bytes of text", (long long)add);
+    A.n_words = W;
+    const size_t w1 = (size_t)W + 1;
+    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) || (rc = bm_alloc(c, w[BMW_TERM], w1 * 4)))
+        return rc;
+    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
+    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
+    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p; A.term = (uint32_t*)w[BMW_TERM].p;
+    A.tstart = (int64_t*)ix->tstart.p; A.tlen = (uint32_t*)ix->tlen.p;          // (read only in this phase)
+    A.ttab = (GzBm25Slot*)ix->ttab.p; A.tmask = ix->tmask;
+    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
+    const uint32_t* list = (const uint32_t*)w[BMW_LIST1].p;
+    gz_launch_bm25(GZ_BM25_KNOWN, A, nullptr, 0, (uint32_t*)w[BMW_LIST1].p, s);
+    int64_t U = 0;
+    if ((rc = bm_read_u32(c, A.ctl, U))) return rc;
+    const uint64_t dslots = bm_pow2((uint64_t)U + (uint64_t)U / 3 + 16);
+    if ((rc = bm_alloc(c, w[BMW_DTAB], dslots * 16))) return rc;
+    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = dslots - 1;
+    for (int64_t m = U, k = 0; m > 0; ++k) {
+        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
+        HIPCHK(c, hipMemsetAsync(A.dtab, 0, dslots * 16, s));
+        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
+        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, m, nullptr, s);
+        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, m, next, s);
+        if ((rc = bm_read_u32(c, A.ctl, m))) return rc;
+        list = next;
+    }
+    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
+    int64_t Tn = 0;
+    if ((rc = bm_read_u32(c, A.scan + W, Tn))) return rc;
+
+    // ---- phase B: room for the new terms, pairs, rows and entries (W bounds the new pairs and entries: their count is known
+    // only once the pair table has been written)
+    const int64_t T1 = T0 + Tn, P1 = E0 + W;
+    void *p_tstart, *p_tlen, *p_df, *p_sig, *p_eoff, *p_ent;
+    if ((rc = bm_reserve(c, st, ix->tstart, (size_t)T0 * 8, (size_t)T1 * 8, &p_tstart)) ||
+        (rc = bm_reserve(c, st, ix->tlen, (size_t)T0 * 4, (size_t)T1 * 4, &p_tlen)) ||
+        (rc = bm_reserve(c, st, ix->df, (size_t)T0 * 4, (size_t)T1 * 4, &p_df)) ||
+        (rc = bm_reserve(c, st, ix->sig, (size_t)N0 * 32, (size_t)(N0 + n) * 32, &p_sig)) ||
+        (rc = bm_reserve(c, st, ix->eoff, (size_t)(N0 + 1) * 4, (size_t)(N0 + n + 1) * 4, &p_eoff)) ||
+        (rc = bm_reserve(c, st, ix->ent, (size_t)E0 * 8, (size_t)P1 * 8, &p_ent)))
+        return rc;
+    uint64_t tslots = ix->tmask + 1, pslots = ix->pmask + 1;
+    void* p_ttab = ix->ttab.p; void* p_ptab = ix->ptab.p;
+    if (2 * (uint64_t)T1 > tslots) {                          // load <= 1/2, as the build leaves it
+        const uint64_t old = tslots;
+        tslots = bm_pow2(4 * (uint64_t)T1 + 16);
+        if ((rc = bm_reserve(c, st, ix->ttab, 0, tslots * 16, &p_ttab, true))) return rc;
+        HIPCHK(c, hipMemsetAsync(p_ttab, 0, tslots * 16, s));
+        gz_launch_bm25_rehash((const GzBm25Slot*)ix->ttab.p, (int64_t)old, (GzBm25Slot*)p_ttab, tslots - 1, s);
+    }
+    if ((uint64_t)P1 + (uint64_t)P1 / 3 + 16 > pslots) {      // load <= 3/4
+        const uint64_t old = pslots;
+        pslots = bm_pow2(2 * ((uint64_t)P1 + (uint64_t)P1 / 3) + 16);
+        if (pslots > (1ull << 32)) pslots = 1ull << 32;       // (slot numbers are 32-bit; P1 < 2^31 still fits at <= 3/4)
+        if ((rc = bm_reserve(c, st, ix->ptab, 0, pslots * 16, &p_ptab, true))) return rc;
+        HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
+        gz_launch_bm25_rehash((const GzBm25Slot*)ix->ptab.p, (int64_t)old, (GzBm25Slot*)p_ptab, pslots - 1, s);
+    }
+    HIPCHK(c, hipGetLastError());
+
+    // ---- phase C: nothing below allocates.  The staged buffers become the index's, then the live structures are written.
+    st.commit();
+    ix->tmask = tslots - 1; ix->pmask = pslots - 1;
+    A.tstart = (int64_t*)p_tstart; A.tlen = (uint32_t*)p_tlen; A.df = (uint32_t*)p_df;
+    A.ttab = (GzBm25Slot*)p_ttab; A.tmask = ix->tmask; A.ptab = (GzBm25Slot*)p_ptab; A.pmask = ix->pmask;
+    A.dfs = A.df; A.n_terms = 0;                              // one df counter per term: the shards of the build collapse onto df itself
+    A.sig = (unsigned long long*)p_sig; A.eoff = (uint32_t*)p_eoff + N0; A.ent = (uint2*)p_ent + E0;
+    if (Tn) HIPCHK(c, hipMemsetAsync(A.df + T0, 0, (size_t)Tn * 4, s));
+    HIPCHK(c, hipMemsetAsync(A.sig + N0 * 4, 0, (size_t)n * 32, s));
+    gz_launch_bm25(GZ_BM25_TERM, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_PAIR_INS, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_PAIR_FIRST, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
+    gz_launch_bm25(GZ_BM25_ENT, A, nullptr, 0, nullptr, s);
+    int64_t E = 0;
+    if ((rc = bm_read_u32(c, A.scan + W, E))) return rc;
+    HIPCHK(c, hipGetLastError());
+    ix->n_docs = N0 + n; ix->n_words += W; ix->n_terms = T1; ix->n_ent = E0 + E; ix->text_bytes = used + add;
     return GZ_OK;
 }
 
@@ -2790,6 +2943,45 @@ try {
     if ((rc = bm25_build_core(c, ix.get(), text_off_dev, text_bytes))) return rc;
     return bm_adopt(c, ix, out);
 } GZ_CATCH(c)
+
+int gz_bm25_append(gz_bm25* ix, const uint8_t* text, const int64_t* text_off, int64_t n_docs)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_docs < 0 || (n_docs > 0 && !text_off)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_docs == 0) return GZ_OK;
+    const int64_t nbytes = text_off[n_docs] - text_off[0];
+    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
+    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = bm_limits(c, ix->text_bytes + nbytes, ix->n_docs + n_docs))) return rc;
+    BmStage st;
+    BmDrain drain{c};
+    if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
+    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
+    return bm25_append_core(c, ix, st, nbytes ? text + text_off[0] : nullptr, nullptr, (const int64_t*)c->w_bm[BMW_OFF].p, text_off[0], n_docs, nbytes);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_append_device(gz_bm25* ix, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_docs < 0 || text_bytes < 0) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_docs == 0) return GZ_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = bm_limits(c, ix->text_bytes + text_bytes, ix->n_docs + n_docs))) return rc;     // (before anything is read)
+    if (!text_off_dev || (text_bytes > 0 && !text_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    BmStage st;
+    BmDrain drain{c};
+    int64_t off0 = 0;
+    if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
+    if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+    return bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
+} GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_info(gz_bm25* ix, int64_t* n_docs, int64_t* n_terms, int64_t* n_words)
 try {

@@ -15,6 +15,9 @@
 //   gz_bm25_pair_*          (document, term) pairs in a second table: count, first occurrence in the document; then df[term] (16
 //                           counters per term, summed by gz_bm25_df_kernel),
 //                           a 256-bit term signature per document and the doc-major (term, count) entries
+//   gz_bm25_known_kernel    an append (gz_bm25_append): the batch's words against the live term table; the unknown ones go through
+//                           the de-duplication as a list, and every kernel above numbers the batch from the bases in GzBm25Args
+//   gz_bm25_rehash_kernel   the term table or the pair table into a larger one, slot by slot (the keys carry the index's own hash mask)
 //   gz_bm25_lookup_kernel   query words (packed) -> term id (-1: absent) and df, bytes compared in full
 //   gz_bm25_score_kernel    scores[Q, N] float64 in the reference's order of operations (ranking.py:33-45, :52-63)
 //
@@ -106,8 +109,8 @@ __device__ uint32_t bm_doc_words(const uint8_t* p, int64_t len, int64_t abs0, ui
 // a document's bytes, or none when its offsets are not inside the text the caller announced (flag raised)
 __device__ __forceinline__ int64_t bm_doc_len(const GzBm25Args& A, int64_t d, int64_t& o, bool raise)
 {
-    o = A.off[d];
-    const int64_t e = A.off[d + 1];
+    o = A.off[d] + A.obase;
+    const int64_t e = A.off[d + 1] + A.obase;
     if (o < A.lo || e < o || e > A.hi) {
         if (raise && lane_id() == 0) atomicOr(&A.ctl[1], 1u);
         return 0;
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_words_kernel(GzBm25Args
     if (d >= A.n_docs) return;
     int64_t o;
     const int64_t len = bm_doc_len(A, d, o, false);
-    (void)bm_doc_words<true>(A.tb + o, len, o, A.woff[d], A.wstart, A.wend, A.wdoc, (uint32_t)d);
+    (void)bm_doc_words<true>(A.tb + o, len, o, A.woff[d], A.wstart, A.wend, A.wdoc, A.doc_base + (uint32_t)d);
 }
 
 // ---- exclusive scan of u32 values: out[i] = in[0] + ... + in[i - 1], out[n] = total (the total must fit 32 bits) ----------
@@ -254,7 +257,8 @@ __global__ __launch_bounds__(256) void gz_bm25_term_kernel(GzBm25Args A)
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= A.n_words) return;
     const uint32_t r = A.rep[w];
-    const uint32_t t = A.scan[r];
+    if (r == GZ_BM25_KNOWN_WORD) return;                  // (an append: gz_bm25_known_kernel wrote its term)
+    const uint32_t t = A.term_base + A.scan[r];
     A.term[w] = t;
     if (r != (uint32_t)w) return;
     A.tstart[t] = A.wstart[w];
@@ -298,7 +302,7 @@ __global__ __launch_bounds__(256) void gz_bm25_ent_kernel(GzBm25Args A)
 {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w < A.n_words && A.flag[w]) A.ent[A.scan[w]] = make_uint2(A.term[w], A.ptab[A.wslot[w]].a);
-    if (w <= A.n_docs) A.eoff[w] = A.scan[A.woff[w]];      // (the launch covers max(words, documents + 1) threads)
+    if (w <= A.n_docs) A.eoff[w] = A.ent_base + A.scan[A.woff[w]];      // (the launch covers max(words, documents + 1) threads)
 }
 
 __global__ __launch_bounds__(256) void gz_bm25_df_kernel(GzBm25Args A)
@@ -308,6 +312,46 @@ __global__ __launch_bounds__(256) void gz_bm25_df_kernel(GzBm25Args A)
     uint32_t n = 0;
     for (int k = 0; k < GZ_BM25_DF_SHARDS; ++k) n += A.dfs[k * A.n_terms + t];
     A.df[t] = n;
+}
+
+// ---- append ---------------------------------------------------------------------------------------------------------------
+// The batch's words against the live term table (gz_bm25_lookup_kernel's probe, the bytes compared in full): a word that is a term
+// already takes its id and stays out of the de-duplication; the others form the first round's list (any order: a round's outcome is
+// a minimum over word indices).
+__global__ __launch_bounds__(256) void gz_bm25_known_kernel(GzBm25Args A, uint32_t* next)
+{
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= A.n_words) return;
+    const int64_t s = A.wstart[w], n = A.wend[w] - s;
+    const unsigned long long key = A.whash[w];
+    unsigned long long slot = bm_mix64(key) & A.tmask;
+    for (;;) {
+        const unsigned long long k = A.ttab[slot].key;
+        if (k == 0ull) break;
+        if (k == key) {
+            const uint32_t t = A.ttab[slot].a;
+            if ((int64_t)A.tlen[t] == n && bm_equal(A.tb + A.tstart[t], A.tb + s, n)) {
+                A.term[w] = t;
+                A.rep[w] = GZ_BM25_KNOWN_WORD;
+                return;
+            }
+        }
+        slot = (slot + 1) & A.tmask;
+    }
+    next[atomicAdd(&A.ctl[0], 1u)] = (uint32_t)w;
+}
+
+// a table moves into a larger one: keys are unique in `from`, so every one claims its own slot; a and b travel with it
+__global__ __launch_bounds__(256) void gz_bm25_rehash_kernel(const GzBm25Slot* from, int64_t n_slots, GzBm25Slot* to, unsigned long long mask)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_slots) return;
+    const GzBm25Slot o = from[i];
+    if (o.key == 0ull) return;
+    unsigned long long s = bm_mix64(o.key) & mask;
+    while (atomicCAS(&to[s].key, 0ull, o.key) != 0ull) s = (s + 1) & mask;
+    to[s].a = o.a;
+    to[s].b = o.b;
 }
 
 // ---- lookup ---------------------------------------------------------------------------------------------------------------
@@ -446,8 +490,14 @@ void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t
         hipLaunchKernelGGL(gz_bm25_ent_kernel, dim3(bm_grid(m, 256)), dim3(256), 0, s, A);
         break;
     }
+    case GZ_BM25_KNOWN: if (A.n_words > 0) hipLaunchKernelGGL(gz_bm25_known_kernel, dim3(bm_grid(A.n_words, 256)), dim3(256), 0, s, A, next); break;
     default: break;
     }
+}
+
+void gz_launch_bm25_rehash(const GzBm25Slot* from, int64_t n_slots, GzBm25Slot* to, unsigned long long mask, hipStream_t s)
+{
+    if (n_slots > 0) hipLaunchKernelGGL(gz_bm25_rehash_kernel, dim3(bm_grid(n_slots, 256)), dim3(256), 0, s, from, n_slots, to, mask);
 }
 
 void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s)

@@ -178,9 +178,16 @@ struct GzBm25Args {
     unsigned long long* sig;            // [n_docs * 4] 256-bit term signature per document
     uint2* ent;                         // [n_ent] (term, count), doc-major, first-occurrence order inside a document
     uint32_t* eoff;                     // [n_docs + 1] each document's first entry
+    // an append (gz_bm25_append): the batch's documents, words and new terms are numbered from 0 in the arrays above, which point at
+    // the tails of the index's own; these bases make the index's numbers of them (all 0 in a build)
+    int64_t obase;                      // added to every off[d]: the batch's text lies behind the index's own
+    uint32_t doc_base;                  // wdoc = doc_base + d
+    uint32_t term_base;                 // term id of a new term = term_base + (representatives before it)
+    uint32_t ent_base;                  // eoff[d] = ent_base + (entries of the batch before d); ent points at entry ent_base
 };
 enum { GZ_BM25_COUNT, GZ_BM25_WORDS, GZ_BM25_HASH, GZ_BM25_DEDUP_INS, GZ_BM25_DEDUP_RES, GZ_BM25_FIRST, GZ_BM25_TERM, GZ_BM25_PAIR_INS,
-       GZ_BM25_PAIR_FIRST, GZ_BM25_DF, GZ_BM25_ENT };
+       GZ_BM25_PAIR_FIRST, GZ_BM25_DF, GZ_BM25_ENT, GZ_BM25_KNOWN };
+constexpr uint32_t GZ_BM25_KNOWN_WORD = 0xFFFFFFFFu;      // rep[] of a batch word that is a term of the index already (an append)
 constexpr int GZ_BM25_DF_SHARDS = 16;
 struct GzBm25Look {
     const uint8_t* tb; const int64_t* tstart; const uint32_t* tlen; const uint32_t* df;
@@ -198,9 +205,12 @@ struct GzBm25Score {
     double* out;                                                   // [n_q, n_docs]
 };
 // step: GZ_BM25_*; list / n / next: the de-duplication round's words (list null: all), the next round's list
+// (GZ_BM25_KNOWN: next = the words that are no term of the index yet, the first round's list)
 void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t n, uint32_t* next, hipStream_t s);
 // exclusive scan of u32: out[n + 1] (out[n] = total), bsum: (n + 4095) / 4096 + 1 words of workspace
 void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s);
+// every used slot of `from` (n_slots of them) enters `to` (cleared by the caller, mask + 1 slots, more than there are keys) with its a and b
+void gz_launch_bm25_rehash(const GzBm25Slot* from, int64_t n_slots, GzBm25Slot* to, unsigned long long mask, hipStream_t s);
 void gz_launch_bm25_lookup(const GzBm25Look& L, hipStream_t s);
 void gz_launch_bm25_score(const GzBm25Score& S, hipStream_t s);
 

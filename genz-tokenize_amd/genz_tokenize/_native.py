@@ -32,6 +32,7 @@ SYMBOLS = [
     "gz_host_tables_merge_entry", "gz_host_tables_symbol", "gz_limit", "gz_debug_set",
     "gz_bm25_build", "gz_bm25_build_device", "gz_bm25_info", "gz_bm25_field_lengths", "gz_bm25_lookup", "gz_bm25_score",
     "gz_bm25_score_device", "gz_bm25_destroy", "gz_bm25_topk", "gz_bm25_topk_device",
+    "gz_bm25_append", "gz_bm25_append_device",
 ]
 
 _lib = None
@@ -123,6 +124,9 @@ def load_library():
     if hasattr(L, "gz_bm25_topk"):
         L.gz_bm25_topk.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp]
         L.gz_bm25_topk_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp]
+    if hasattr(L, "gz_bm25_append"):
+        L.gz_bm25_append.argtypes = [vp, vp, vp, i64]
+        L.gz_bm25_append_device.argtypes = [vp, vp, vp, i64, i64]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -475,6 +479,17 @@ class Context:
         self._check(self.lib.gz_bm25_build_device(self.handle, C.c_void_p(d_text) if d_text else None, C.c_void_p(d_off), n_docs, text_bytes,
                                                   C.byref(h)))
         return h.value
+
+    def bm25_append(self, index: int, text: np.ndarray, text_off: np.ndarray) -> None:
+        """packed UTF-8 + int64 offsets of more documents behind the index's own: afterwards it answers as one built over all of
+        them.  On GzError the index is as it was."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        self._check(self.lib.gz_bm25_append(C.c_void_p(index), _ptr(text) if len(text) else None, _ptr(text_off), len(text_off) - 1))
+
+    def bm25_append_device(self, index: int, d_text, d_off, n_docs: int, text_bytes: int) -> None:
+        self._check(self.lib.gz_bm25_append_device(C.c_void_p(index), C.c_void_p(d_text) if d_text else None,
+                                                   C.c_void_p(d_off) if d_off else None, n_docs, text_bytes))
 
     def bm25_destroy(self, index: int):
         if index and self.handle.value:                  # (a closed context has freed its indexes already)

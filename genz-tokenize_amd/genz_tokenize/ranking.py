@@ -9,6 +9,9 @@ Retrieval: `top_k(queries, k)` returns the ids and scores of every query's k bes
 those documents (rank_bm25's form).  The score rows are computed and searched on the GPU (csrc/gz_topk.inc): only [Q, k] ids and
 scores come back.  The order is total: higher scores first, ties to the lower document index, NaN last.
 
+Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
+one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -60,6 +63,27 @@ class BM25:
         self._idf = {}
         self._documents = None
         self._freq = None
+
+    # ---- growth -----------------------------------------------------------------------------------------------------
+    def add_documents(self, documents: Sequence[str]) -> None:
+        """Append documents: afterwards self equals type(self)(old documents + list(documents), ...) built fresh -- num_doc,
+        fieldLens, avgFieldLen, idf, scores and top-k to the bit.  TypeError (an item that is no str) and _native.GzError leave the
+        object as it was."""
+        more = _strings(documents, "documents")
+        if not more:
+            return
+        buf, off = _pack(more)
+        self._ctx.bm25_append(self._index, buf, off)
+        old = self.num_doc
+        self._texts.extend(more)
+        self.num_doc = len(self._texts)
+        lens = self._ctx.bm25_field_lengths(self._index)
+        self.fieldLens.extend(lens[old:].tolist())
+        self.avgFieldLen = np.mean(lens)                         # (the constructor's expression over all the lengths)
+        self._idf.clear()                                        # N and df changed
+        if self._documents is not None:
+            self._documents.extend(t.split() for t in more)
+        self._freq = None                                        # (rebuilt on the next access)
 
     # ---- the reference's per-document lists, built lazily on the host -------------------------------------------------
     @property

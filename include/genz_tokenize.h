@@ -392,6 +392,17 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          GZ_BM25_TOPK_MAX: GZ_E_LIMIT.  Nothing outside the [n_queries, k'] outputs is written.  The scores stay
  *                          in HBM (a chunk of queries at a time, switch bm25_topk_chunk); only ids and scores cross to the host.
  *   gz_bm25_topk_device    the same into doc_out_dev / score_out_dev (HBM): enqueued on the context's stream, gz_sync waits for it
+ *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
+ *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
+ *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
+ *                          only its unknown words are de-duplicated, and the per-document arrays grow at their tails; the index's
+ *                          buffers have a capacity and grow geometrically, so the work is proportional to the batch unless a
+ *                          buffer grows.  n_docs == 0: GZ_OK, nothing changes.  On any error (GZ_E_NOMEM, GZ_E_INVALID for
+ *                          offsets that decrease or leave the text, GZ_E_LIMIT when all bytes + all documents would reach 2^32)
+ *                          the index answers as before the call.  The index keeps the hash mask it was built with.
+ *   gz_bm25_append_device  the same for a batch resident in HBM (offsets ABSOLUTE from the base pointer, text_bytes =
+ *                          text_off_dev[n_docs] - text_off_dev[0], as gz_bm25_build_device); GZ_E_LIMIT is answered before
+ *                          anything is read
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
@@ -410,6 +421,8 @@ int  gz_bm25_topk(gz_bm25 *index, const int32_t *terms, const double *idf, const
                   const double params[6], int32_t plus, int64_t k, int64_t *doc_out, double *score_out);
 int  gz_bm25_topk_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
                          const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev);
+int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
+int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 void gz_bm25_destroy(gz_bm25 *index);
 
 #ifdef __cplusplus

@@ -12,6 +12,15 @@ Host clock around call + synchronisation, after a warm-up call, median of --reps
   get_scores_host_q256_ms          BM25.get_scores(256 queries): the float64 [256, N] matrix in host memory
   get_scores_argpartition_q256_k100_ms  the same followed by np.argpartition and a sort of the 100 per row (what a caller does
                        without top_k; --host-reps reps)
+Append (gz_bm25_append_device / BM25.add_documents; --append documents behind the --docs of the corpus, 0 skips these rows):
+  append_device_ms     the batch, text and offsets already in HBM, behind an index of --docs documents whose buffers have the room:
+                       --docs - --append documents are built, the batch before ours is appended (every buffer that grows doubles),
+                       then ours is timed
+  append_device_grow_ms  the same batch as the FIRST append to a freshly built index: its tail buffers (text, dl, signatures, eoff,
+                       entries, term ranges, df) are full, so all of them grow; append_grow_tables says whether the two tables did
+  append_python_ms     BM25.add_documents(list of --append str) on a model of --docs documents (first append: buffers grow)
+  rebuild_device_ms    gz_bm25_build_device over the --docs + --append documents: what a caller paid before
+  incremental_build_ms an index of --docs documents made by --docs / --append appends to an empty one (device text)
   restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
                        its postings built beforehand (not timed)
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
@@ -44,6 +53,81 @@ def median_ms(fn, reps):
     return float(np.median(ts)), [round(t, 3) for t in ts]
 
 
+def append_rows(ctx, res, n, batch, reps):
+    """the append rows of the docstring: the corpus is n + batch documents"""
+    t, o, _ = corpus.config_corpus(2, n_docs=n + batch)
+    nbytes = int(o[-1])
+    d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + batch + 1))
+    ctx.h2d(d_text, t)
+    ctx.h2d(d_off, o)
+    # the batch's offsets are absolute in d_text: the entry point takes them from any base
+    d_boff = d_off + 8 * n
+    bbytes = int(o[-1] - o[n])
+    d_poff = d_off + 8 * (n - batch)                                 # the batch before it
+    pbytes = int(o[n] - o[n - batch])
+    res.update(append_docs=batch, append_bytes=bbytes)
+
+    ts = []
+    for k in range(reps + 1):
+        t0 = time.perf_counter()
+        ix = ctx.bm25_build_device(d_text, d_off, n + batch, nbytes)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        ctx.bm25_destroy(ix)
+    res["rebuild_device_ms"], res["rebuild_device_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
+
+    grow, room = [], []
+    for k in range(reps + 1):
+        # growth: the first append to a fresh index of n documents
+        ix = ctx.bm25_build_device(d_text, d_off, n, int(o[n]))
+        t0 = time.perf_counter()
+        ctx.bm25_append_device(ix, d_text, d_boff, batch, bbytes)
+        grow.append((time.perf_counter() - t0) * 1e3)
+        assert ctx.bm25_info(ix)[0] == n + batch
+        ctx.bm25_destroy(ix)
+        # capacity present: n - batch documents built, the batch before ours appended (every buffer doubles), then ours
+        ix = ctx.bm25_build_device(d_text, d_off, n - batch, int(o[n - batch]))
+        ctx.bm25_append_device(ix, d_text, d_poff, batch, pbytes)
+        t0 = time.perf_counter()
+        ctx.bm25_append_device(ix, d_text, d_boff, batch, bbytes)
+        room.append((time.perf_counter() - t0) * 1e3)
+        info = ctx.bm25_info(ix)
+        ctx.bm25_destroy(ix)
+    res["append_device_ms"], res["append_device_all_ms"] = float(np.median(room[1:])), [round(x, 3) for x in room[1:]]
+    res["append_device_grow_ms"], res["append_device_grow_all_ms"] = float(np.median(grow[1:])), [round(x, 3) for x in grow[1:]]
+    res["append_over_rebuild"] = round(res["append_device_ms"] / res["rebuild_device_ms"], 3)
+    res["append_terms"], res["append_words"] = info[1:]
+
+    # the whole index by appends of `batch` to an empty one
+    e_off = ctx.alloc(8)
+    ctx.h2d(e_off, np.zeros(1, np.int64))
+    ts = []
+    for k in range(min(reps, 3)):
+        t0 = time.perf_counter()
+        ix = ctx.bm25_build_device(None, e_off, 0, 0)
+        for i in range(0, n, batch):
+            m = min(batch, n - i)
+            ctx.bm25_append_device(ix, d_text, d_off + 8 * i, m, int(o[i + m] - o[i]))
+        ts.append((time.perf_counter() - t0) * 1e3)
+        assert ctx.bm25_info(ix)[0] == n
+        ctx.bm25_destroy(ix)
+    res["incremental_build_ms"], res["incremental_build_all_ms"] = float(np.median(ts)), [round(x, 3) for x in ts]
+    res["incremental_appends"] = (n + batch - 1) // batch
+    for d in (e_off, d_text, d_off):
+        ctx.free(d)
+
+    raw = t.tobytes()
+    docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n + batch)]
+    old, more = docs[:n], docs[n:]
+    ts = []
+    for k in range(min(reps, 3) + 1):
+        m = BM25(old, ctx=ctx)
+        t0 = time.perf_counter()
+        m.add_documents(more)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        del m
+    res["append_python_ms"], res["append_python_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -51,11 +135,18 @@ def main():
     ap.add_argument("--restate-docs", type=int, default=100_000)
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", type=int, default=10_000, help="documents of the append rows (0: skip them)")
+    ap.add_argument("--append-only", action="store_true", help="only the append rows (a trace of their kernels)")
     a = ap.parse_args()
     t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
     res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
+    if a.append:
+        append_rows(ctx, res, n, a.append, a.reps)
+    if a.append_only:
+        print(json.dumps(res))
+        return
 
     d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
     ctx.h2d(d_text, t)
