@@ -946,6 +946,7 @@ static int install_word_tables(gz_ctx* c, const WordImages& W)
 struct gz_bm25 {
     gz_ctx* c = nullptr;
     int64_t n_docs = 0, n_words = 0, n_terms = 0, n_ent = 0, off0 = 0;
+    int64_t n_live = 0;                  // terms with df > 0: a removal (gz_bm25_remove) leaves dead terms in the table, n_terms counts them too
     int64_t text_bytes = 0;              // bytes of `text` in use: an append (gz_bm25_append) puts its batch behind them
     unsigned long long hmask = 0, pmask = 0, tmask = 0;
     // the index: a copy of the text (the terms' bytes), fieldLens, signatures, doc-major (term, count) entries, the (document, term)
@@ -1064,7 +1065,7 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
     int64_t T = 0;
     if ((rc = bm_read_u32(c, A.scan + W, T))) return rc;
-    ix->n_terms = T;
+    ix->n_terms = ix->n_live = T;
     const uint64_t tslots = bm_pow2(2 * (uint64_t)T + 16);
     if ((rc = bm_alloc(c, ix->tstart, (size_t)T * 8)) || (rc = bm_alloc(c, ix->tlen, (size_t)T * 4)) || (rc = bm_alloc(c, ix->df, (size_t)T * 4)) ||
         (rc = bm_alloc(c, ix->ttab, tslots * 16)) || (rc = bm_alloc(c, w[BMW_DFS], (size_t)T * 4 * GZ_BM25_DF_SHARDS)))
@@ -1235,10 +1236,85 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     gz_launch_bm25(GZ_BM25_PAIR_FIRST, A, nullptr, 0, nullptr, s);
     if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
     gz_launch_bm25(GZ_BM25_ENT, A, nullptr, 0, nullptr, s);
-    int64_t E = 0;
-    if ((rc = bm_read_u32(c, A.scan + W, E))) return rc;
+    int64_t E = 0, revived = 0;
+    if ((rc = bm_read_u32(c, A.scan + W, E)) || (rc = bm_read_u32(c, A.ctl + 2, revived))) return rc;
     HIPCHK(c, hipGetLastError());
     ix->n_docs = N0 + n; ix->n_words += W; ix->n_terms = T1; ix->n_ent = E0 + E; ix->text_bytes = used + add;
+    ix->n_live += Tn + revived;                               // (dead terms of a removal that the batch brought back)
+    return GZ_OK;
+}
+
+// ---- remove (gz_bm25_remove) ---------------------------------------------------------------------------------------------------
+// a staged buffer of the live one's capacity (a later append finds the same room), the first `keep` bytes copied
+int bm_stage(gz_ctx* c, BmStage& st, DBuf& live, size_t keep, size_t need, void** p)
+{
+    alloc_site(c);
+    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 remove: stage overflow");
+    DBuf& f = st.fresh[st.n];
+    int rc = ensure(c, f, std::max(need ? need : 16, live.cap > 256 ? live.cap - 256 : 0));    // (ensure adds the 256 again)
+    if (rc) return rc;
+    st.live[st.n++] = &live;
+    if (keep) HIPCHK(c, hipMemcpyAsync(f.p, live.p, keep, hipMemcpyDeviceToDevice, c->stream));
+    *p = f.p;
+    return GZ_OK;
+}
+
+// The documents ids_dev[0 .. n_ids) leave the index.  Phase A marks them and scans the marks and the kept entry counts (workspace
+// only); phase B makes every allocation: staged fieldLens, signatures, eoff, entries, pair table and a copy of df; then the
+// kernels compact the live arrays into the staged ones, fill the pair table and take the removed documents off the copy of df --
+// the live index is only read.  Phase C, after the last round trip, swaps the buffers in.  A return before it leaves the index
+// answering as before.  The text copy, the term table and the terms' byte ranges stay: a term without documents is a dead entry
+// (df 0) that a later append may bring back.
+int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev, int64_t n_ids)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t N = ix->n_docs, T = ix->n_terms;
+    int rc;
+    // ---- phase A
+    const size_t n1 = (size_t)N + 1;
+    if ((rc = bm_alloc(c, w[BMW_FLAG], n1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], n1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], n1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_WOFF], n1 * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) || (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(N / 4096 + 2) * 4)))
+        return rc;
+    GzBm25Rm R{};
+    R.ids = ids_dev; R.n_ids = n_ids; R.n_docs = N;
+    R.ctl = (uint32_t*)w[BMW_CTL].p; R.gone = (uint32_t*)w[BMW_FLAG].p; R.before = (uint32_t*)w[BMW_SCAN].p;
+    R.kcnt = (uint32_t*)w[BMW_SLOT].p; R.neoff = (uint32_t*)w[BMW_WOFF].p;
+    R.dl = (const uint32_t*)ix->dl.p; R.sig = (const unsigned long long*)ix->sig.p; R.eoff = (const uint32_t*)ix->eoff.p;
+    R.ent = (const uint2*)ix->ent.p;
+    HIPCHK(c, hipMemsetAsync(R.ctl, 0, 64, s));
+    HIPCHK(c, hipMemsetAsync(R.gone, 0, n1 * 4, s));
+    gz_launch_bm25_remove(GZ_BM25_RM_MARK, R, s);
+    int64_t bad = 0;
+    if ((rc = bm_read_u32(c, R.ctl + 1, bad))) return rc;
+    if (bad) return fail(c, GZ_E_INVALID, "BM25 remove: a document id outside [0, %lld)", (long long)N);
+    gz_launch_bm25_remove(GZ_BM25_RM_COUNT, R, s);
+    if ((rc = bm_scan(c, R.gone, N, R.before)) || (rc = bm_scan(c, R.kcnt, N, R.neoff))) return rc;
+    int64_t n_gone = 0, E1 = 0;
+    if ((rc = bm_read_u32(c, R.before + N, n_gone)) || (rc = bm_read_u32(c, R.neoff + N, E1))) return rc;
+    if (n_gone == 0) return GZ_OK;
+    const int64_t N1 = N - n_gone;
+
+    // ---- phase B: every allocation of the call
+    const uint64_t pslots = ix->pmask + 1;
+    void *p_dl, *p_sig, *p_eoff, *p_ent, *p_ptab, *p_df;
+    if ((rc = bm_stage(c, st, ix->dl, 0, (size_t)N1 * 4, &p_dl)) || (rc = bm_stage(c, st, ix->sig, 0, (size_t)N1 * 32, &p_sig)) ||
+        (rc = bm_stage(c, st, ix->eoff, 0, (size_t)(N1 + 1) * 4, &p_eoff)) || (rc = bm_stage(c, st, ix->ent, 0, (size_t)E1 * 8, &p_ent)) ||
+        (rc = bm_stage(c, st, ix->ptab, 0, pslots * 16, &p_ptab)) || (rc = bm_stage(c, st, ix->df, (size_t)T * 4, (size_t)T * 4, &p_df)))
+        return rc;
+    R.dl2 = (uint32_t*)p_dl; R.sig2 = (unsigned long long*)p_sig; R.eoff2 = (uint32_t*)p_eoff; R.ent2 = (uint2*)p_ent;
+    R.ptab2 = (GzBm25Slot*)p_ptab; R.pmask2 = ix->pmask; R.df2 = (uint32_t*)p_df;
+    HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
+    gz_launch_bm25_remove(GZ_BM25_RM_DOCS, R, s);
+    gz_launch_bm25_remove(GZ_BM25_RM_ENT, R, s);
+    uint32_t out[4] = {};                                     // ctl[2 .. 5]: dead terms, -, words of the removed documents (64 bits)
+    if ((rc = copy_out_small(c, out, R.ctl + 2, 16, s))) return rc;
+    HIPCHK(c, hipGetLastError());
+
+    // ---- phase C: nothing below can fail
+    st.commit();
+    ix->n_docs = N1; ix->n_ent = E1; ix->n_live -= (int64_t)out[0];
+    ix->n_words -= (int64_t)((uint64_t)out[2] | (uint64_t)out[3] << 32);
     return GZ_OK;
 }
 
@@ -2983,11 +3059,40 @@ try {
     return bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
+int gz_bm25_remove(gz_bm25* ix, const int64_t* doc_ids, int64_t n_ids)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_ids < 0 || (n_ids > 0 && !doc_ids)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_ids == 0) return GZ_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    BmStage st;
+    BmDrain drain{c};
+    if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)n_ids * 8))) return rc;
+    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, doc_ids, (size_t)n_ids * 8, c->stream))) return rc;
+    return bm25_remove_core(c, ix, st, (const int64_t*)c->w_bm[BMW_OFF].p, n_ids);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_remove_device(gz_bm25* ix, const int64_t* doc_ids_dev, int64_t n_ids)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_ids < 0 || (n_ids > 0 && !doc_ids_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_ids == 0) return GZ_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    BmStage st;
+    BmDrain drain{c};
+    return bm25_remove_core(c, ix, st, doc_ids_dev, n_ids);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
 int gz_bm25_info(gz_bm25* ix, int64_t* n_docs, int64_t* n_terms, int64_t* n_words)
 try {
     if (!ix) return GZ_E_INVALID;
     if (n_docs) *n_docs = ix->n_docs;
-    if (n_terms) *n_terms = ix->n_terms;
+    if (n_terms) *n_terms = ix->n_live;
     if (n_words) *n_words = ix->n_words;
     return GZ_OK;
 } GZ_CATCH(ix ? ix->c : nullptr)

@@ -18,11 +18,16 @@
 //   gz_bm25_known_kernel    an append (gz_bm25_append): the batch's words against the live term table; the unknown ones go through
 //                           the de-duplication as a list, and every kernel above numbers the batch from the bases in GzBm25Args
 //   gz_bm25_rehash_kernel   the term table or the pair table into a larger one, slot by slot (the keys carry the index's own hash mask)
+//   gz_bm25_rm_*            a removal (gz_bm25_remove): mark the documents, scan the marks (new id = old id - removed before it) and
+//                           the kept documents' entry counts, then compact fieldLens, signatures and entries OUT OF PLACE into staged
+//                           buffers, fill a fresh pair table from the compacted entries and take the removed documents' entries off
+//                           a staged copy of df.  The live index is only read.
 //   gz_bm25_lookup_kernel   query words (packed) -> term id (-1: absent) and df, bytes compared in full
 //   gz_bm25_score_kernel    scores[Q, N] float64 in the reference's order of operations (ranking.py:33-45, :52-63)
 //
 // Vector stores and vector atomics only.  Results never depend on the order in which atomics land: counts and df are sums,
-// representatives and first occurrences are minima, signatures are ORs, term ids come out of a scan.
+// representatives and first occurrences are minima, signatures are ORs, term ids come out of a scan; of the decrements that
+// take a term's df to 0 exactly one sees the 1, whatever their order.
 
 namespace {
 
@@ -294,7 +299,10 @@ __global__ __launch_bounds__(256) void gz_bm25_pair_first_kernel(GzBm25Args A)
     A.flag[w] = first ? 1u : 0u;
     if (!first) return;
     const uint32_t t = A.term[w], bit = bm_sig_bit(t);
-    atomicAdd(&A.dfs[(int64_t)(A.wdoc[w] & (GZ_BM25_DF_SHARDS - 1)) * A.n_terms + t], 1u);     // (16 counters per term: frequent terms)
+    const uint32_t had = atomicAdd(&A.dfs[(int64_t)(A.wdoc[w] & (GZ_BM25_DF_SHARDS - 1)) * A.n_terms + t], 1u);     // (16 counters per term: frequent terms)
+    // an append (one counter per term, df itself): a term older than the batch whose df was 0 -- every document that had it was
+    // removed -- is live again; exactly one increment starts from 0
+    if (had == 0u && t < A.term_base) atomicAdd(&A.ctl[2], 1u);
     atomicOr(&A.sig[(int64_t)A.wdoc[w] * 4 + (bit >> 6)], 1ull << (bit & 63u));
 }
 
@@ -354,6 +362,66 @@ __global__ __launch_bounds__(256) void gz_bm25_rehash_kernel(const GzBm25Slot* f
     to[s].b = o.b;
 }
 
+// ---- remove ---------------------------------------------------------------------------------------------------------------
+// Every kernel here reads the live index and writes workspace or staged buffers only (gz_bm25_remove swaps them in afterwards).
+// gone[] is cleared by the caller.  An id listed twice stores the same 1 twice: the scan counts the document once.
+__global__ __launch_bounds__(256) void gz_bm25_rm_mark_kernel(GzBm25Rm R)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= R.n_ids) return;
+    const int64_t id = R.ids[i];
+    if (id < 0 || id >= R.n_docs) atomicOr(&R.ctl[1], 1u);
+    else R.gone[id] = 1u;
+}
+
+// entries each document keeps (none when it goes)
+__global__ __launch_bounds__(256) void gz_bm25_rm_count_kernel(GzBm25Rm R)
+{
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d >= R.n_docs) return;
+    R.kcnt[d] = R.gone[d] ? 0u : R.eoff[d + 1] - R.eoff[d];
+}
+
+// per kept document: fieldLen, signature and first entry under its new id; thread n_docs closes the new eoff
+__global__ __launch_bounds__(256) void gz_bm25_rm_docs_kernel(GzBm25Rm R)
+{
+    const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (d > R.n_docs) return;
+    const int64_t nd = d - (int64_t)R.before[d];
+    if (d == R.n_docs) { R.eoff2[nd] = R.neoff[d]; return; }
+    if (R.gone[d]) return;
+    R.dl2[nd] = R.dl[d];
+    for (int k = 0; k < 4; ++k) R.sig2[nd * 4 + k] = R.sig[d * 4 + k];
+    R.eoff2[nd] = R.neoff[d];
+}
+
+// A wave per document (one may hold 100 000 entries).  Kept: its entries move to their new place and enter the fresh pair table
+// under the new document id (keys are unique, every one claims its own slot; only `a` is read after a build or an append).
+// Removed: each entry takes 1 off the staged df of its term; the decrement that sees 1 makes the term a dead one.
+__global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_rm_ent_kernel(GzBm25Rm R)
+{
+    const int64_t d = (int64_t)blockIdx.x * BM_WPB + (int64_t)(threadIdx.x / WAVE);
+    if (d >= R.n_docs) return;
+    const int lane = lane_id();
+    const uint32_t e0 = R.eoff[d], e1 = R.eoff[d + 1];
+    if (R.gone[d]) {
+        for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += WAVE)
+            if (atomicSub(&R.df2[R.ent[e].x], 1u) == 1u) atomicAdd(&R.ctl[2], 1u);
+        if (lane == 0) atomicAdd((unsigned long long*)(R.ctl + 4), (unsigned long long)R.dl[d]);
+        return;
+    }
+    const unsigned long long pkey = (unsigned long long)(d - (int64_t)R.before[d]) << 32;
+    const uint32_t o = R.neoff[d];
+    for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += WAVE) {
+        const uint2 en = R.ent[e];
+        R.ent2[o + (e - e0)] = en;
+        const unsigned long long key = (pkey | en.x) + 1ull;
+        unsigned long long s = bm_mix64(key) & R.pmask2;
+        while (atomicCAS(&R.ptab2[s].key, 0ull, key) != 0ull) s = (s + 1) & R.pmask2;     // (a probe: more slots than keys)
+        R.ptab2[s].a = en.y;
+    }
+}
+
 // ---- lookup ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gz_bm25_lookup_kernel(GzBm25Look L)
 {
@@ -372,8 +440,10 @@ __global__ __launch_bounds__(256) void gz_bm25_lookup_kernel(GzBm25Look L)
         }
         slot = (slot + 1) & L.tmask;
     }
+    const uint32_t df = found >= 0 ? L.df[found] : 0u;
+    if (df == 0u) found = -1;                                 // (a term whose last document was removed: in the table, in no document)
     L.term_out[i] = found;
-    L.df_out[i] = found >= 0 ? (int32_t)L.df[found] : 0;
+    L.df_out[i] = (int32_t)df;
 }
 
 // ---- scoring: one thread per document, every query of the batch --------------------------------------------------------------
@@ -498,6 +568,17 @@ void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t
 void gz_launch_bm25_rehash(const GzBm25Slot* from, int64_t n_slots, GzBm25Slot* to, unsigned long long mask, hipStream_t s)
 {
     if (n_slots > 0) hipLaunchKernelGGL(gz_bm25_rehash_kernel, dim3(bm_grid(n_slots, 256)), dim3(256), 0, s, from, n_slots, to, mask);
+}
+
+void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s)
+{
+    switch (step) {
+    case GZ_BM25_RM_MARK: if (R.n_ids > 0) hipLaunchKernelGGL(gz_bm25_rm_mark_kernel, dim3(bm_grid(R.n_ids, 256)), dim3(256), 0, s, R); break;
+    case GZ_BM25_RM_COUNT: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_count_kernel, dim3(bm_grid(R.n_docs, 256)), dim3(256), 0, s, R); break;
+    case GZ_BM25_RM_DOCS: hipLaunchKernelGGL(gz_bm25_rm_docs_kernel, dim3(bm_grid(R.n_docs + 1, 256)), dim3(256), 0, s, R); break;
+    case GZ_BM25_RM_ENT: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_ent_kernel, dim3(bm_grid(R.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, R); break;
+    default: break;
+    }
 }
 
 void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s)

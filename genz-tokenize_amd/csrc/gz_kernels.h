@@ -157,7 +157,7 @@ struct GzBm25Args {
     const int64_t* off;
     int64_t n_docs, n_words;
     int64_t lo, hi;                     // the offsets must lie in [lo, hi] (else ctl[1] is raised and the document counts as empty)
-    uint32_t* ctl;                      // [0] words left for the next de-duplication round, [1] bad offsets
+    uint32_t* ctl;                      // [0] words left for the next de-duplication round, [1] bad offsets, [2] an append: dead terms live again
     uint32_t* wcnt;                     // [n_docs] words per document (fieldLens)
     uint32_t* woff;                     // [n_docs + 1] index of each document's first word
     int64_t* wstart; int64_t* wend;     // [n_words] absolute byte range of every word
@@ -204,6 +204,21 @@ struct GzBm25Score {
     int32_t plus;                                                  // 1: BM25Plus
     double* out;                                                   // [n_q, n_docs]
 };
+// a removal (gz_bm25_remove): live arrays are read, the staged ones (...2) written
+struct GzBm25Rm {
+    const int64_t* ids; int64_t n_ids;  // the documents to remove (device memory; any order, duplicates allowed)
+    int64_t n_docs;                     // documents of the index before the removal
+    uint32_t* ctl;                      // [1] an id outside [0, n_docs), [2] terms whose df reached 0, [4..5] (64 bits) words of the removed documents
+    uint32_t* gone;                     // [n_docs] 1: the document goes (cleared by the caller)
+    uint32_t* before;                   // [n_docs + 1] exclusive scan of gone: new id = old id - before[old id]
+    uint32_t* kcnt; uint32_t* neoff;    // [n_docs + 1] entries a document keeps, and their exclusive scan (the new eoff by OLD id)
+    const uint32_t* dl; const unsigned long long* sig; const uint32_t* eoff; const uint2* ent;
+    uint32_t* dl2; unsigned long long* sig2; uint32_t* eoff2; uint2* ent2;
+    GzBm25Slot* ptab2; unsigned long long pmask2;    // the fresh pair table (cleared by the caller)
+    uint32_t* df2;                      // a copy of df: the removed documents' entries are taken off it
+};
+enum { GZ_BM25_RM_MARK, GZ_BM25_RM_COUNT, GZ_BM25_RM_DOCS, GZ_BM25_RM_ENT };
+void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s);
 // step: GZ_BM25_*; list / n / next: the de-duplication round's words (list null: all), the next round's list
 // (GZ_BM25_KNOWN: next = the words that are no term of the index yet, the first round's list)
 void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t n, uint32_t* next, hipStream_t s);

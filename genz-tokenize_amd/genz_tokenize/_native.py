@@ -32,7 +32,7 @@ SYMBOLS = [
     "gz_host_tables_merge_entry", "gz_host_tables_symbol", "gz_limit", "gz_debug_set",
     "gz_bm25_build", "gz_bm25_build_device", "gz_bm25_info", "gz_bm25_field_lengths", "gz_bm25_lookup", "gz_bm25_score",
     "gz_bm25_score_device", "gz_bm25_destroy", "gz_bm25_topk", "gz_bm25_topk_device",
-    "gz_bm25_append", "gz_bm25_append_device",
+    "gz_bm25_append", "gz_bm25_append_device", "gz_bm25_remove", "gz_bm25_remove_device",
 ]
 
 _lib = None
@@ -127,6 +127,9 @@ def load_library():
     if hasattr(L, "gz_bm25_append"):
         L.gz_bm25_append.argtypes = [vp, vp, vp, i64]
         L.gz_bm25_append_device.argtypes = [vp, vp, vp, i64, i64]
+    if hasattr(L, "gz_bm25_remove"):
+        L.gz_bm25_remove.argtypes = [vp, vp, i64]
+        L.gz_bm25_remove_device.argtypes = [vp, vp, i64]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -490,6 +493,15 @@ class Context:
     def bm25_append_device(self, index: int, d_text, d_off, n_docs: int, text_bytes: int) -> None:
         self._check(self.lib.gz_bm25_append_device(C.c_void_p(index), C.c_void_p(d_text) if d_text else None,
                                                    C.c_void_p(d_off) if d_off else None, n_docs, text_bytes))
+
+    def bm25_remove(self, index: int, ids: np.ndarray) -> None:
+        """document ids (int64; any order, duplicates allowed) leave the index: afterwards it answers as one built over the
+        remaining documents, renumbered in their old order.  On GzError the index is as it was."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        self._check(self.lib.gz_bm25_remove(C.c_void_p(index), _ptr(ids) if len(ids) else None, len(ids)))
+
+    def bm25_remove_device(self, index: int, d_ids, n_ids: int) -> None:
+        self._check(self.lib.gz_bm25_remove_device(C.c_void_p(index), C.c_void_p(d_ids) if d_ids else None, n_ids))
 
     def bm25_destroy(self, index: int):
         if index and self.handle.value:                  # (a closed context has freed its indexes already)

@@ -12,6 +12,10 @@ scores come back.  The order is total: higher scores first, ties to the lower do
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
+Deletion: `remove_documents(ids)` takes documents out of the live index on the GPU (gz_bm25_remove): afterwards the object behaves
+exactly like one constructed over the remaining documents, which are renumbered in their old order.  An update is a removal
+followed by an `add_documents`.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -19,6 +23,7 @@ first-occurrence order) are built on the host on first access only: they are not
 
 Deviation: documents and queries must be `str` (TypeError otherwise); the reference takes anything with `.split()`.
 """
+import itertools
 import numbers
 import weakref
 from typing import List, Optional, Sequence
@@ -83,6 +88,36 @@ class BM25:
         self._idf.clear()                                        # N and df changed
         if self._documents is not None:
             self._documents.extend(t.split() for t in more)
+        self._freq = None                                        # (rebuilt on the next access)
+
+    def remove_documents(self, ids) -> None:
+        """Remove the documents with these ids (any iterable of ints; any order, duplicates allowed): afterwards self equals
+        type(self)(remaining documents, ...) built fresh -- num_doc, fieldLens, avgFieldLen, idf, scores and top-k to the bit.  The
+        remaining documents keep their order; new id = old id - the number of removed documents before it.  TypeError (an item
+        that is no int), IndexError (an id outside [0, num_doc)) and _native.GzError leave the object as it was."""
+        gone = set()
+        for i in ids:
+            if isinstance(i, bool) or not isinstance(i, numbers.Integral):
+                raise TypeError("document ids must be int, not %s" % type(i).__name__)
+            gone.add(int(i))
+        for i in gone:
+            if not 0 <= i < self.num_doc:
+                raise IndexError("document id %d is out of range for %d documents" % (i, self.num_doc))
+        if not gone:
+            return
+        ids = np.fromiter(sorted(gone), dtype=np.int64, count=len(gone))
+        self._ctx.bm25_remove(self._index, ids)
+        keep = np.ones(self.num_doc, dtype=bool)
+        keep[ids] = False
+        keep = keep.tolist()
+        self._texts = list(itertools.compress(self._texts, keep))
+        self.num_doc = len(self._texts)
+        lens = self._ctx.bm25_field_lengths(self._index)
+        self.fieldLens = lens.tolist()
+        self.avgFieldLen = np.mean(lens)                         # (nan and a RuntimeWarning when nothing is left, as BM25([]))
+        self._idf.clear()                                        # N and df changed
+        if self._documents is not None:
+            self._documents = list(itertools.compress(self._documents, keep))
         self._freq = None                                        # (rebuilt on the next access)
 
     # ---- the reference's per-document lists, built lazily on the host -------------------------------------------------

@@ -375,7 +375,7 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *   gz_bm25_build_device   the same resident in HBM (offsets ABSOLUTE from the base pointer, text_bytes = text_off_dev[n_docs] -
  *                          text_off_dev[0]); a document outside those bytes is refused with GZ_E_INVALID.  The index keeps a copy
  *                          of the text: the caller's buffers may go once the call has returned.
- *   gz_bm25_info           documents, distinct terms, words (all documents)
+ *   gz_bm25_info           documents, distinct terms (those some document has), words (all documents)
  *   gz_bm25_field_lengths  fieldLens (ranking.py:21): words of every document, out[n_docs]
  *   gz_bm25_lookup         query words (packed like documents, host buffers) -> term id (-1 when no document has it) and df
  *                          (documents that contain it, ranking.py:29-31)
@@ -403,6 +403,18 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *   gz_bm25_append_device  the same for a batch resident in HBM (offsets ABSOLUTE from the base pointer, text_bytes =
  *                          text_off_dev[n_docs] - text_off_dev[0], as gz_bm25_build_device); GZ_E_LIMIT is answered before
  *                          anything is read
+ *   gz_bm25_remove         the documents doc_ids[0 .. n_ids) (host memory; any order, duplicates allowed) leave the index: afterwards
+ *                          it answers every call above exactly as one built over the remaining documents, in their old order, does
+ *                          -- df, fieldLens, counts, scores and top-k to the bit.  Documents are renumbered: new id = old id - the
+ *                          number of removed documents before it.  Term ids may differ from that build's (it numbers terms by first
+ *                          occurrence in what remains); a word no remaining document has is answered -1 with df 0 by
+ *                          gz_bm25_lookup and is not counted by gz_bm25_info, and a later append brings it back.  The work is
+ *                          proportional to the index: fieldLens, signatures and entries are compacted into fresh buffers of the
+ *                          same capacity, the pair table is filled again.  The index's copy of the text is NOT compacted: its
+ *                          device memory is not reclaimed, and the removed bytes still count towards GZ_E_LIMIT of an append.
+ *                          n_ids == 0: GZ_OK, nothing changes.  On any error (GZ_E_INVALID for an id outside [0, n_docs),
+ *                          GZ_E_NOMEM) the index answers as before the call.
+ *   gz_bm25_remove_device  the same for ids resident in HBM
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
@@ -423,6 +435,8 @@ int  gz_bm25_topk_device(gz_bm25 *index, const int32_t *terms, const double *idf
                          const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev);
 int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
+int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);
+int  gz_bm25_remove_device(gz_bm25 *index, const int64_t *doc_ids_dev, int64_t n_ids);
 void gz_bm25_destroy(gz_bm25 *index);
 
 #ifdef __cplusplus

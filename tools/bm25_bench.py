@@ -1,6 +1,6 @@
 """BM25 index / scoring timings on the configs[2] corpus (genz_tokenize.ranking, csrc/gz_bm25.inc).
 
-    python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -21,6 +21,11 @@ Append (gz_bm25_append_device / BM25.add_documents; --append documents behind th
   append_python_ms     BM25.add_documents(list of --append str) on a model of --docs documents (first append: buffers grow)
   rebuild_device_ms    gz_bm25_build_device over the --docs + --append documents: what a caller paid before
   incremental_build_ms an index of --docs documents made by --docs / --append appends to an empty one (device text)
+Remove (gz_bm25_remove_device / BM25.remove_documents; --remove random documents out of the --docs of the corpus, 0 skips these rows):
+  remove_device_ms     the ids already in HBM, out of a freshly built index of --docs documents (the build is not timed)
+  remove_python_ms     BM25.remove_documents(list of the same ids) on a model of --docs documents
+  rebuild_remaining_device_ms  gz_bm25_build_device over the remaining --docs - --remove documents, text and offsets in HBM: what a
+                       caller paid before, timed in the same run
   restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
                        its postings built beforehand (not timed)
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
@@ -128,6 +133,55 @@ def append_rows(ctx, res, n, batch, reps):
     res["append_python_ms"], res["append_python_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
 
 
+def remove_rows(ctx, res, n, k, reps):
+    """the remove rows of the docstring"""
+    t, o, _ = corpus.config_corpus(2, n_docs=n)
+    nbytes = int(o[-1])
+    ids = np.sort(np.random.default_rng(2).choice(n, size=k, replace=False)).astype(np.int64)
+    keep = np.ones(n, bool)
+    keep[ids] = False
+    lens = np.diff(o)
+    # the remaining documents, packed on the host (not timed), for the rebuild
+    r_off = np.zeros(n - k + 1, np.int64)
+    np.cumsum(lens[keep], out=r_off[1:])
+    r_text = t[np.repeat(keep, lens)]
+    assert len(r_text) == int(r_off[-1])
+    d_text, d_off, d_ids = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1)), ctx.alloc(8 * k)
+    d_rtext, d_roff = ctx.alloc(max(len(r_text), 16)), ctx.alloc(8 * (n - k + 1))
+    for d, h in ((d_text, t), (d_off, o), (d_ids, ids), (d_rtext, r_text), (d_roff, r_off)):
+        ctx.h2d(d, h)
+    res.update(remove_docs=k)
+    rm, rb = [], []
+    for _ in range(reps + 1):                                        # (the first of each is the warm-up)
+        ix = ctx.bm25_build_device(d_text, d_off, n, nbytes)
+        t0 = time.perf_counter()
+        ctx.bm25_remove_device(ix, d_ids, k)
+        rm.append((time.perf_counter() - t0) * 1e3)
+        info = ctx.bm25_info(ix)
+        ctx.bm25_destroy(ix)
+        t0 = time.perf_counter()
+        ix = ctx.bm25_build_device(d_rtext, d_roff, n - k, int(r_off[-1]))
+        rb.append((time.perf_counter() - t0) * 1e3)
+        assert ctx.bm25_info(ix) == info                             # documents, live terms and words of the fresh build
+        ctx.bm25_destroy(ix)
+    res["remove_device_ms"], res["remove_device_all_ms"] = float(np.median(rm[1:])), [round(x, 3) for x in rm[1:]]
+    res["rebuild_remaining_device_ms"], res["rebuild_remaining_device_all_ms"] = float(np.median(rb[1:])), [round(x, 3) for x in rb[1:]]
+    res["remove_over_rebuild"] = round(res["remove_device_ms"] / res["rebuild_remaining_device_ms"], 3)
+    for d in (d_text, d_off, d_ids, d_rtext, d_roff):
+        ctx.free(d)
+    raw = t.tobytes()
+    docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n)]
+    id_list = ids.tolist()
+    ts = []
+    for _ in range(min(reps, 3) + 1):
+        m = BM25(docs, ctx=ctx)
+        t0 = time.perf_counter()
+        m.remove_documents(id_list)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        del m
+    res["remove_python_ms"], res["remove_python_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -137,11 +191,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", type=int, default=10_000, help="documents of the append rows (0: skip them)")
     ap.add_argument("--append-only", action="store_true", help="only the append rows (a trace of their kernels)")
+    ap.add_argument("--remove", type=int, default=10_000, help="documents of the remove rows (0: skip them)")
+    ap.add_argument("--remove-only", action="store_true", help="only the remove rows (a trace of their kernels)")
     a = ap.parse_args()
     t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
     res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
+    if a.remove:
+        remove_rows(ctx, res, n, a.remove, a.reps)
+    if a.remove_only:
+        print(json.dumps(res))
+        return
     if a.append:
         append_rows(ctx, res, n, a.append, a.reps)
     if a.append_only:
