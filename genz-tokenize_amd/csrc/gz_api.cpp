@@ -174,7 +174,7 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
-    DBuf w_bm[32];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
+    DBuf w_bm[40];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
@@ -958,7 +958,11 @@ struct gz_bm25 {
 namespace {
 enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW_HASH, BMW_REP, BMW_SLOT, BMW_LIST0, BMW_LIST1, BMW_DTAB,
        BMW_FLAG, BMW_SCAN, BMW_TERM, BMW_DFS, BMW_QTEXT, BMW_QOFF, BMW_QRES, BMW_QTERM, BMW_QIDF, BMW_SCORES,
-       BMW_CKEY0, BMW_CIDX0, BMW_CKEY1, BMW_CIDX1, BMW_TOUT };
+       BMW_CKEY0, BMW_CIDX0, BMW_CKEY1, BMW_CIDX1, BMW_TOUT,
+       BMW_CP_FIRST, BMW_CP_NEWID, BMW_CP_ORDER, BMW_CP_NLEN, BMW_CP_TOFF,          // the canonical numbering (bm25_number)
+       BMW_V_OFF, BMW_V_DF, BMW_V_BYTES,                                            // what gz_bm25_terms hands out
+       BMW_COUNT };
+static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
 // Every error return of an index build drains the context's stream before the buffers the call owns (the index under
 // construction) are freed: declared AFTER the index, destroyed before it.
@@ -1315,6 +1319,104 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
     st.commit();
     ix->n_docs = N1; ix->n_ent = E1; ix->n_live -= (int64_t)out[0];
     ix->n_words -= (int64_t)((uint64_t)out[2] | (uint64_t)out[3] << 32);
+    return GZ_OK;
+}
+
+// ---- compact (gz_bm25_compact) and the vocabulary (gz_bm25_terms) ----------------------------------------------------------------
+// The canonical numbering of the live terms, into the context's workspace: the index is only read.  On return C holds the live
+// arrays and the workspace (newid, order, nlen, toff), C.n_new == ix->n_live is verified and B = the live terms' bytes.  Two host
+// round trips: the number of flags and B.
+int bm25_number(gz_ctx* c, gz_bm25* ix, GzBm25Cp& C, int64_t& B)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t T = ix->n_terms, E = ix->n_ent;
+    int rc;
+    const size_t e1 = (size_t)E + 1, t1 = (size_t)T + 1;
+    if ((rc = bm_alloc(c, w[BMW_CTL], 64)) || (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((E > T ? E : T) / 4096 + 2) * 4)) ||
+        (rc = bm_alloc(c, w[BMW_FLAG], e1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], e1 * 4)) || (rc = bm_alloc(c, w[BMW_CP_FIRST], t1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_CP_NEWID], t1 * 4)) || (rc = bm_alloc(c, w[BMW_CP_ORDER], t1 * 4)) || (rc = bm_alloc(c, w[BMW_CP_NLEN], t1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_CP_TOFF], t1 * 4)))
+        return rc;
+    C = GzBm25Cp{};
+    C.n_docs = ix->n_docs; C.n_ent = E; C.n_terms = T; C.n_new = ix->n_live;
+    C.tb = (const uint8_t*)ix->text.p - ix->off0; C.tstart = (const int64_t*)ix->tstart.p; C.tlen = (const uint32_t*)ix->tlen.p;
+    C.df = (const uint32_t*)ix->df.p; C.ent = (const uint2*)ix->ent.p; C.eoff = (const uint32_t*)ix->eoff.p;
+    C.ctl = (uint32_t*)w[BMW_CTL].p; C.flag = (uint32_t*)w[BMW_FLAG].p; C.scan = (uint32_t*)w[BMW_SCAN].p;
+    C.first = (uint32_t*)w[BMW_CP_FIRST].p; C.newid = (uint32_t*)w[BMW_CP_NEWID].p; C.order = (uint32_t*)w[BMW_CP_ORDER].p;
+    C.nlen = (uint32_t*)w[BMW_CP_NLEN].p; C.toff = (uint32_t*)w[BMW_CP_TOFF].p;
+    HIPCHK(c, hipMemsetAsync(C.ctl, 0, 64, s));
+    HIPCHK(c, hipMemsetAsync(C.first, 0xFF, t1 * 4, s));
+    gz_launch_bm25_compact(GZ_BM25_CP_FIRST, C, s);
+    gz_launch_bm25_compact(GZ_BM25_CP_FLAG, C, s);
+    if ((rc = bm_scan(c, C.flag, E, C.scan))) return rc;
+    int64_t n_new = 0;
+    if ((rc = bm_read_u32(c, C.scan + E, n_new))) return rc;
+    if (n_new != ix->n_live)
+        return fail(c, GZ_E_HIP, "BM25 index: %lld terms have a first entry, %lld are live", (long long)n_new, (long long)ix->n_live);
+    gz_launch_bm25_compact(GZ_BM25_CP_NEWID, C, s);
+    if ((rc = bm_scan(c, C.nlen, n_new, C.toff))) return rc;
+    if ((rc = bm_read_u32(c, C.toff + n_new, B))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+// a staged buffer of exactly the size a build gives it (bm_alloc's), nothing copied
+int bm_stage_exact(gz_ctx* c, BmStage& st, DBuf& live, size_t need, void** p)
+{
+    alloc_site(c);
+    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 compact: stage overflow");
+    DBuf& f = st.fresh[st.n];
+    int rc = ensure(c, f, need ? need : 16);
+    if (rc) return rc;
+    st.live[st.n++] = &live;
+    *p = f.p;
+    return GZ_OK;
+}
+
+// The index becomes the one a fresh build of its current documents gives, term ids included.  Phase A numbers the live terms
+// (workspace only); phase B makes every allocation: all ten buffers staged, each of the size gz_bm25_build gives it for the same
+// counts (the text: the live terms' bytes), so capacities that appends and removals left behind are given back; then the kernels
+// fill the staged buffers from the live index, which is only read.  Phase C, after the last round trip, swaps them in.  A return
+// before it leaves the index answering as before.
+int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = ix->n_docs, E = ix->n_ent;
+    int rc;
+    // ---- phase A
+    GzBm25Cp C;
+    int64_t B = 0;
+    if ((rc = bm25_number(c, ix, C, B))) return rc;
+    const int64_t T1 = C.n_new;
+
+    // ---- phase B: every allocation of the call, sized as bm25_build_core sizes them
+    const uint64_t pslots = bm_pow2((uint64_t)ix->n_words + (uint64_t)ix->n_words / 3 + 16), tslots = bm_pow2(2 * (uint64_t)T1 + 16);
+    void *p_text, *p_dl, *p_sig, *p_eoff, *p_ent, *p_ptab, *p_ttab, *p_tstart, *p_tlen, *p_df;
+    if ((rc = bm_stage_exact(c, st, ix->text, (size_t)B + 16, &p_text)) || (rc = bm_stage_exact(c, st, ix->dl, (size_t)N * 4, &p_dl)) ||
+        (rc = bm_stage_exact(c, st, ix->sig, (size_t)N * 32, &p_sig)) || (rc = bm_stage_exact(c, st, ix->eoff, (size_t)(N + 1) * 4, &p_eoff)) ||
+        (rc = bm_stage_exact(c, st, ix->ent, (size_t)E * 8, &p_ent)) || (rc = bm_stage_exact(c, st, ix->ptab, pslots * 16, &p_ptab)) ||
+        (rc = bm_stage_exact(c, st, ix->ttab, tslots * 16, &p_ttab)) || (rc = bm_stage_exact(c, st, ix->tstart, (size_t)T1 * 8, &p_tstart)) ||
+        (rc = bm_stage_exact(c, st, ix->tlen, (size_t)T1 * 4, &p_tlen)) || (rc = bm_stage_exact(c, st, ix->df, (size_t)T1 * 4, &p_df)))
+        return rc;
+    C.arena = (uint8_t*)p_text; C.tstart2 = (int64_t*)p_tstart; C.tlen2 = (uint32_t*)p_tlen; C.df2 = (uint32_t*)p_df;
+    C.ent2 = (uint2*)p_ent; C.sig2 = (unsigned long long*)p_sig; C.ptab2 = (GzBm25Slot*)p_ptab; C.pmask2 = pslots - 1;
+    HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
+    HIPCHK(c, hipMemsetAsync(p_ttab, 0, tslots * 16, s));
+    if (N) HIPCHK(c, hipMemcpyAsync(p_dl, ix->dl.p, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(p_eoff, ix->eoff.p, (size_t)(N + 1) * 4, hipMemcpyDeviceToDevice, s));
+    gz_launch_bm25_compact(GZ_BM25_CP_GATHER, C, s);
+    gz_launch_bm25_rekey((const GzBm25Slot*)ix->ttab.p, (int64_t)(ix->tmask + 1), C.newid, (GzBm25Slot*)p_ttab, tslots - 1, s);
+    gz_launch_bm25_compact(GZ_BM25_CP_ENT, C, s);
+    int64_t bad = 0;
+    if ((rc = bm_read_u32(c, C.ctl + 1, bad))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, GZ_E_HIP, "BM25 compact: the index's entries, df and term table contradict each other");
+
+    // ---- phase C: nothing below can fail
+    st.commit();
+    ix->n_terms = T1; ix->text_bytes = B; ix->off0 = 0;
+    ix->pmask = pslots - 1; ix->tmask = tslots - 1;
     return GZ_OK;
 }
 
@@ -3086,6 +3188,61 @@ try {
     BmStage st;
     BmDrain drain{c};
     return bm25_remove_core(c, ix, st, doc_ids_dev, n_ids);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_compact(gz_bm25* ix)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    BmStage st;
+    BmDrain drain{c};
+    return bm25_compact_core(c, ix, st);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_terms(gz_bm25* ix, int64_t* term_off, int32_t* df, uint8_t* bytes, int64_t bytes_cap)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if ((!term_off && !bytes) || (bytes && bytes_cap < 0)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    BmDrain drain{c};
+    GzBm25Cp C;
+    int64_t B = 0;
+    int rc;
+    if ((rc = bm25_number(c, ix, C, B))) return rc;
+    const int64_t T1 = C.n_new;
+    if (bytes && bytes_cap < B) return fail(c, GZ_E_CAPACITY, "BM25 terms: %lld bytes, room for %lld", (long long)B, (long long)bytes_cap);
+    if ((rc = bm_alloc(c, w[BMW_V_OFF], (size_t)(T1 + 1) * 8)) || (rc = bm_alloc(c, w[BMW_V_DF], (size_t)T1 * 4)) ||
+        (bytes && (rc = bm_alloc(c, w[BMW_V_BYTES], (size_t)B + 16))))
+        return rc;
+    C.tstart2 = (int64_t*)w[BMW_V_OFF].p; C.close = 1; C.df2 = (uint32_t*)w[BMW_V_DF].p;
+    C.arena = bytes ? (uint8_t*)w[BMW_V_BYTES].p : nullptr;
+    gz_launch_bm25_compact(GZ_BM25_CP_GATHER, C, s);
+    int64_t bad = 0;
+    if ((rc = bm_read_u32(c, C.ctl + 1, bad))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, GZ_E_HIP, "BM25 terms: the index's entries and df contradict each other");
+    if (term_off && (rc = copy_out(c, term_off, C.tstart2, (size_t)(T1 + 1) * 8, s))) return rc;
+    if (df && (rc = copy_out(c, df, C.df2, (size_t)T1 * 4, s))) return rc;
+    if (bytes && (rc = copy_out(c, bytes, C.arena, (size_t)B, s))) return rc;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_footprint(gz_bm25* ix, int64_t out[3])
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!out) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    size_t cap = 0;
+    for (const DBuf* b : {&ix->text, &ix->dl, &ix->sig, &ix->eoff, &ix->ent, &ix->ptab, &ix->ttab, &ix->tstart, &ix->tlen, &ix->df}) cap += b->cap;
+    out[0] = ix->text_bytes; out[1] = ix->n_terms; out[2] = (int64_t)cap;
+    return GZ_OK;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_info(gz_bm25* ix, int64_t* n_docs, int64_t* n_terms, int64_t* n_words)

@@ -22,12 +22,20 @@
 //                           the kept documents' entry counts, then compact fieldLens, signatures and entries OUT OF PLACE into staged
 //                           buffers, fill a fresh pair table from the compacted entries and take the removed documents' entries off
 //                           a staged copy of df.  The live index is only read.
+//   gz_bm25_cp_*            the canonical numbering of the live terms (gz_bm25_compact, gz_bm25_terms): first[term] = its smallest
+//                           entry index, the entries that are their term's first flagged and scanned -> new id = a fresh build's; the
+//                           terms' lengths scanned in new-id order, their bytes gathered into an arena; then (a compaction) entries,
+//                           pair table and signatures again under the new ids and, gz_bm25_rekey_kernel, the term table without its
+//                           dead terms -- all OUT OF PLACE, the live index is only read
 //   gz_bm25_lookup_kernel   query words (packed) -> term id (-1: absent) and df, bytes compared in full
 //   gz_bm25_score_kernel    scores[Q, N] float64 in the reference's order of operations (ranking.py:33-45, :52-63)
 //
 // Vector stores and vector atomics only.  Results never depend on the order in which atomics land: counts and df are sums,
 // representatives and first occurrences are minima, signatures are ORs, term ids come out of a scan; of the decrements that
-// take a term's df to 0 exactly one sees the 1, whatever their order.
+// take a term's df to 0 exactly one sees the 1, whatever their order.  In the compaction: first[] is a minimum; flags, new ids,
+// orders and offsets are plain stores of values that scans of those give; every arena byte, entry and signature word has one
+// writer (signatures are ORed in registers); table slots are claimed by CAS, and which of several equal keys sits first along a
+// probe sequence is the one thing that varies -- no answer reads it (a lookup compares bytes, pair keys are unique).
 
 namespace {
 
@@ -35,6 +43,7 @@ constexpr int BM_WPB = 4;                    // waves (documents) per workgroup 
 constexpr int BM_SCAN_BLOCK = 4096;          // elements per workgroup of the scan (16 rounds of 256)
 constexpr int BM_SC_LDS = 4096;              // (term, count) entries a scoring workgroup stages in LDS (32 KB)
 constexpr int BM_QW_LDS = 512;               // query words a scoring workgroup stages in LDS at a time (8 KB)
+constexpr uint32_t BM_CP_SHORT = 16;         // bytes of a term that its own lane copies (gz_bm25_cp_gather_kernel); longer: the wave
 struct BmQword { int32_t t; uint32_t bit; double idf; };
 
 __device__ __forceinline__ unsigned long long bm_mix64(unsigned long long x)
@@ -422,6 +431,122 @@ __global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_rm_ent_kernel(GzBm25Rm 
     }
 }
 
+// ---- compact / vocabulary ---------------------------------------------------------------------------------------------------
+// The canonical numbering.  Entries are doc-major and in first-occurrence order inside a document (a removal keeps both), so the
+// entry with the smallest index among a term's entries is where a fresh build of the current documents meets the term first:
+// numbering the terms by that entry is that build's numbering.  Every kernel here reads the live index and writes workspace or
+// staged buffers only.  first[] is set to all ones by the caller.
+__global__ __launch_bounds__(256) void gz_bm25_cp_first_kernel(GzBm25Cp C)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= C.n_ent) return;
+    const uint32_t t = C.ent[e].x;
+    if ((int64_t)t >= C.n_terms) { atomicOr(&C.ctl[1], 1u); return; }
+    // a minimum: whatever the order of the atomics (a frequent term has millions of entries: a load first, the atomic only where
+    // it can still lower the value -- a stale load just costs the atomic)
+    if (__hip_atomic_load(&C.first[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)e) atomicMin(&C.first[t], (uint32_t)e);
+}
+
+__global__ __launch_bounds__(256) void gz_bm25_cp_flag_kernel(GzBm25Cp C)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= C.n_ent) return;
+    const uint32_t t = C.ent[e].x;
+    C.flag[e] = (int64_t)t < C.n_terms && C.first[t] == (uint32_t)e ? 1u : 0u;
+}
+
+// new id = flags before the term's first entry; the new order's view of the old terms (order, nlen)
+__global__ __launch_bounds__(256) void gz_bm25_cp_newid_kernel(GzBm25Cp C)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= C.n_terms) return;
+    const uint32_t f = C.first[t];
+    const bool live = f != 0xFFFFFFFFu;
+    if (live != (C.df[t] != 0u)) atomicOr(&C.ctl[1], 1u);
+    if (!live) { C.newid[t] = 0xFFFFFFFFu; return; }
+    const uint32_t n = C.scan[f];                             // (< flags raised <= n_terms: order and nlen hold n_terms + 1)
+    C.newid[t] = n;
+    C.order[n] = (uint32_t)t;
+    C.nlen[n] = C.tlen[t];
+}
+
+// The live terms' bytes into the arena, and their rows under the new ids.  A lane per term, 64 consecutive new ids per wave (their
+// bytes are neighbours in the arena): a term of at most BM_CP_SHORT bytes -- nearly all -- is copied by its lane; the longer ones
+// are then taken one after the other by the whole wave, 64 bytes a step (an 80 000-byte term: 1 250 steps of a wave, and the
+// other waves go on).  Every byte of the arena has exactly one writer.
+__global__ __launch_bounds__(256) void gz_bm25_cp_gather_kernel(GzBm25Cp C)
+{
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = lane_id();
+    int64_t src = 0;
+    uint32_t len = 0, dst = 0;
+    if (n < C.n_new) {
+        const uint32_t o = C.order[n];
+        src = C.tstart[o]; len = C.nlen[n]; dst = C.toff[n];
+        C.tstart2[n] = (int64_t)dst;
+        if (C.tlen2) C.tlen2[n] = len;
+        C.df2[n] = C.df[o];
+    } else if (n == C.n_new && C.close) C.tstart2[n] = (int64_t)C.toff[n];
+    if (!C.arena) return;                                     // (uniform)
+    if (len <= BM_CP_SHORT)
+        for (uint32_t i = 0; i < len; ++i) C.arena[(int64_t)dst + i] = C.tb[src + i];
+    uint64_t m = wballot(len > BM_CP_SHORT);
+    while (m) {                                               // (uniform)
+        const int k = __ffsll((unsigned long long)m) - 1;
+        m &= m - 1;
+        const int64_t s = __shfl(src, k, WAVE), d = (int64_t)(uint32_t)__shfl((int)dst, k, WAVE);
+        const uint32_t l = (uint32_t)__shfl((int)len, k, WAVE);
+        for (uint32_t i = (uint32_t)lane; i < l; i += WAVE) C.arena[d + i] = C.tb[s + i];
+    }
+}
+
+// the term table into a fresh one under the new ids; the keys carry the index's hash mask already (no byte is hashed).  Terms that
+// share a (truncated) key keep a slot each; their order along the probe sequence depends on who lands first, what a lookup
+// answers does not (it compares the bytes).
+__global__ __launch_bounds__(256) void gz_bm25_rekey_kernel(const GzBm25Slot* from, int64_t n_slots, const uint32_t* newid, GzBm25Slot* to,
+                                                            unsigned long long mask)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_slots) return;
+    const GzBm25Slot o = from[i];
+    if (o.key == 0ull) return;
+    const uint32_t t = newid[o.a];
+    if (t == 0xFFFFFFFFu) return;                             // a dead term leaves the table
+    unsigned long long s = bm_mix64(o.key) & mask;
+    while (atomicCAS(&to[s].key, 0ull, o.key) != 0ull) s = (s + 1) & mask;          // (a probe: more slots than keys)
+    to[s].a = t;
+}
+
+// A wave per document, as gz_bm25_rm_ent_kernel: its entries under the new ids at their old places, the pairs into the fresh pair
+// table (unique keys, every one claims its own slot), and the document's signature again from the new ids -- ORed in registers
+// and across the wave, then stored: no atomic touches it.
+__global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_cp_ent_kernel(GzBm25Cp C)
+{
+    const int64_t d = (int64_t)blockIdx.x * BM_WPB + (int64_t)(threadIdx.x / WAVE);
+    if (d >= C.n_docs) return;
+    const int lane = lane_id();
+    const uint32_t e0 = C.eoff[d], e1 = C.eoff[d + 1];
+    const unsigned long long pkey = (unsigned long long)d << 32;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    for (uint32_t e = e0 + (uint32_t)lane; e < e1; e += WAVE) {
+        const uint2 en = C.ent[e];
+        const uint32_t t = (int64_t)en.x < C.n_terms ? C.newid[en.x] : 0xFFFFFFFFu;
+        if (t == 0xFFFFFFFFu) { atomicOr(&C.ctl[1], 1u); continue; }
+        C.ent2[e] = make_uint2(t, en.y);
+        const uint32_t bit = bm_sig_bit(t), w = bit >> 6;
+        const unsigned long long b = 1ull << (bit & 63u);
+        s0 |= w == 0u ? b : 0ull; s1 |= w == 1u ? b : 0ull; s2 |= w == 2u ? b : 0ull; s3 |= w == 3u ? b : 0ull;
+        const unsigned long long key = (pkey | t) + 1ull;
+        unsigned long long s = bm_mix64(key) & C.pmask2;
+        while (atomicCAS(&C.ptab2[s].key, 0ull, key) != 0ull) s = (s + 1) & C.pmask2;     // (a probe: more slots than keys)
+        C.ptab2[s].a = en.y;
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        s0 |= __shfl_xor(s0, o, WAVE); s1 |= __shfl_xor(s1, o, WAVE); s2 |= __shfl_xor(s2, o, WAVE); s3 |= __shfl_xor(s3, o, WAVE);
+    }
+    if (lane < 4) C.sig2[d * 4 + lane] = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? s2 : s3;
+}
+
 // ---- lookup ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gz_bm25_lookup_kernel(GzBm25Look L)
 {
@@ -579,6 +704,23 @@ void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s)
     case GZ_BM25_RM_ENT: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_ent_kernel, dim3(bm_grid(R.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, R); break;
     default: break;
     }
+}
+
+void gz_launch_bm25_compact(int step, const GzBm25Cp& C, hipStream_t s)
+{
+    switch (step) {
+    case GZ_BM25_CP_FIRST: if (C.n_ent > 0) hipLaunchKernelGGL(gz_bm25_cp_first_kernel, dim3(bm_grid(C.n_ent, 256)), dim3(256), 0, s, C); break;
+    case GZ_BM25_CP_FLAG: if (C.n_ent > 0) hipLaunchKernelGGL(gz_bm25_cp_flag_kernel, dim3(bm_grid(C.n_ent, 256)), dim3(256), 0, s, C); break;
+    case GZ_BM25_CP_NEWID: if (C.n_terms > 0) hipLaunchKernelGGL(gz_bm25_cp_newid_kernel, dim3(bm_grid(C.n_terms, 256)), dim3(256), 0, s, C); break;
+    case GZ_BM25_CP_GATHER: hipLaunchKernelGGL(gz_bm25_cp_gather_kernel, dim3(bm_grid(C.n_new + 1, 256)), dim3(256), 0, s, C); break;
+    case GZ_BM25_CP_ENT: if (C.n_docs > 0) hipLaunchKernelGGL(gz_bm25_cp_ent_kernel, dim3(bm_grid(C.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, C); break;
+    default: break;
+    }
+}
+
+void gz_launch_bm25_rekey(const GzBm25Slot* from, int64_t n_slots, const uint32_t* newid, GzBm25Slot* to, unsigned long long mask, hipStream_t s)
+{
+    if (n_slots > 0) hipLaunchKernelGGL(gz_bm25_rekey_kernel, dim3(bm_grid(n_slots, 256)), dim3(256), 0, s, from, n_slots, newid, to, mask);
 }
 
 void gz_launch_bm25_scan(const uint32_t* in, int64_t n, uint32_t* out, uint32_t* bsum, hipStream_t s)

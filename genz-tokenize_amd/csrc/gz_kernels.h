@@ -219,6 +219,32 @@ struct GzBm25Rm {
 };
 enum { GZ_BM25_RM_MARK, GZ_BM25_RM_COUNT, GZ_BM25_RM_DOCS, GZ_BM25_RM_ENT };
 void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s);
+// the canonical numbering of the live terms (order of first occurrence in the current documents: a fresh build's), for a
+// compaction (gz_bm25_compact) and the vocabulary read (gz_bm25_terms): live arrays are read, workspace and the staged /
+// output arrays (...2) written
+struct GzBm25Cp {
+    int64_t n_docs, n_ent, n_terms;     // of the live index; n_terms counts the dead terms too
+    int64_t n_new;                      // live terms = flags raised (the host knows it: n_live)
+    const uint8_t* tb; const int64_t* tstart; const uint32_t* tlen; const uint32_t* df;
+    const uint2* ent; const uint32_t* eoff;
+    uint32_t* ctl;                      // [1] the index contradicts itself (a term id out of range, df > 0 without an entry, ...)
+    uint32_t* first;                    // [n_terms] smallest entry index that holds the term (all ones: none; set by the caller)
+    uint32_t* flag; uint32_t* scan;     // [n_ent + 1] entry e is its term's first, and the exclusive scan
+    uint32_t* newid;                    // [n_terms] new id (all ones: a dead term)
+    uint32_t* order;                    // [n_new] old id of new term n
+    uint32_t* nlen; uint32_t* toff;     // [n_new + 1] bytes of new term n, and their exclusive scan (toff[n_new] = all bytes)
+    uint8_t* arena;                     // [toff[n_new]] the live terms' bytes in new-id order (null: not gathered)
+    int64_t* tstart2;                   // [n_new] = toff; close != 0: [n_new + 1], the total included (offsets of gz_bm25_terms)
+    int32_t close;
+    uint32_t* tlen2; uint32_t* df2;     // [n_new] (tlen2 may be null)
+    uint2* ent2;                        // [n_ent] the entries under the new ids
+    unsigned long long* sig2;           // [n_docs * 4] signatures of the new ids
+    GzBm25Slot* ptab2; unsigned long long pmask2;    // the fresh pair table (cleared by the caller)
+};
+enum { GZ_BM25_CP_FIRST, GZ_BM25_CP_FLAG, GZ_BM25_CP_NEWID, GZ_BM25_CP_GATHER, GZ_BM25_CP_ENT };
+void gz_launch_bm25_compact(int step, const GzBm25Cp& C, hipStream_t s);
+// the term table into a fresh one (cleared by the caller): a = newid[a], slots of dead terms (newid all ones) are dropped
+void gz_launch_bm25_rekey(const GzBm25Slot* from, int64_t n_slots, const uint32_t* newid, GzBm25Slot* to, unsigned long long mask, hipStream_t s);
 // step: GZ_BM25_*; list / n / next: the de-duplication round's words (list null: all), the next round's list
 // (GZ_BM25_KNOWN: next = the words that are no term of the index yet, the first round's list)
 void gz_launch_bm25(int step, const GzBm25Args& A, const uint32_t* list, int64_t n, uint32_t* next, hipStream_t s);

@@ -33,6 +33,7 @@ SYMBOLS = [
     "gz_bm25_build", "gz_bm25_build_device", "gz_bm25_info", "gz_bm25_field_lengths", "gz_bm25_lookup", "gz_bm25_score",
     "gz_bm25_score_device", "gz_bm25_destroy", "gz_bm25_topk", "gz_bm25_topk_device",
     "gz_bm25_append", "gz_bm25_append_device", "gz_bm25_remove", "gz_bm25_remove_device",
+    "gz_bm25_compact", "gz_bm25_terms", "gz_bm25_footprint",
 ]
 
 _lib = None
@@ -130,6 +131,10 @@ def load_library():
     if hasattr(L, "gz_bm25_remove"):
         L.gz_bm25_remove.argtypes = [vp, vp, i64]
         L.gz_bm25_remove_device.argtypes = [vp, vp, i64]
+    if hasattr(L, "gz_bm25_compact"):
+        L.gz_bm25_compact.argtypes = [vp]
+        L.gz_bm25_terms.argtypes = [vp, vp, vp, vp, i64]
+        L.gz_bm25_footprint.argtypes = [vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -502,6 +507,29 @@ class Context:
 
     def bm25_remove_device(self, index: int, d_ids, n_ids: int) -> None:
         self._check(self.lib.gz_bm25_remove_device(C.c_void_p(index), C.c_void_p(d_ids) if d_ids else None, n_ids))
+
+    def bm25_compact(self, index: int) -> None:
+        """the index becomes the one a fresh build of its current documents gives, term ids and buffer sizes included.  On
+        GzError the index is as it was."""
+        self._check(self.lib.gz_bm25_compact(C.c_void_p(index)))
+
+    def bm25_terms(self, index: int):
+        """(term_off int64 [T + 1], bytes uint8 [term_off[T]], df int32 [T]): the live terms in the order of their first
+        occurrence in the current documents.  The index is not modified."""
+        t = self.bm25_info(index)[1]
+        off = np.zeros(t + 1, dtype=np.int64)
+        df = np.empty(max(t, 1), dtype=np.int32)
+        self._check(self.lib.gz_bm25_terms(C.c_void_p(index), _ptr(off), _ptr(df), None, 0))       # sizes first
+        data = np.empty(max(int(off[t]), 1), dtype=np.uint8)
+        if off[t]:
+            self._check(self.lib.gz_bm25_terms(C.c_void_p(index), None, None, _ptr(data), int(off[t])))
+        return off, data[:int(off[t])], df[:t]
+
+    def bm25_footprint(self, index: int):
+        """(text bytes in use, terms held in the term table -- dead ones included, device bytes allocated to the index)"""
+        out = (C.c_int64 * 3)()
+        self._check(self.lib.gz_bm25_footprint(C.c_void_p(index), out))
+        return out[0], out[1], out[2]
 
     def bm25_destroy(self, index: int):
         if index and self.handle.value:                  # (a closed context has freed its indexes already)

@@ -16,6 +16,12 @@ Deletion: `remove_documents(ids)` takes documents out of the live index on the G
 exactly like one constructed over the remaining documents, which are renumbered in their old order.  An update is a removal
 followed by an `add_documents`.
 
+Compaction: a removal leaves the index's copy of the text, its term table (terms no document has any more) and its buffers'
+capacities as they were, and every append adds its whole batch to the text copy.  `compact()` rebuilds text and term table on the
+GPU from the index itself (gz_bm25_compact): afterwards the index is the one a fresh build of the current documents gives -- term
+ids and device memory included -- without any string being packed, tokenised or hashed again.  `footprint()` tells when that is
+worth it, and `vocabulary()` reads the current words and their document frequencies (gz_bm25_terms) in any state of the index.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -119,6 +125,28 @@ class BM25:
         if self._documents is not None:
             self._documents = list(itertools.compress(self._documents, keep))
         self._freq = None                                        # (rebuilt on the next access)
+
+    # ---- upkeep and the vocabulary -----------------------------------------------------------------------------------
+    def compact(self) -> None:
+        """Rebuild text copy and term table on the GPU: afterwards the index equals a fresh build of the current documents, term ids
+        and buffer sizes included.  Nothing observable through this object changes: N and every df stay, so do fieldLens,
+        avgFieldLen and the idf cache.  _native.GzError leaves the index as it was."""
+        self._ctx.bm25_compact(self._index)
+
+    def vocabulary(self):
+        """(words, df): the distinct words of the current documents as a list of str, in the order of their first occurrence, and
+        an int32 array of their document frequencies.  words[i] is the term that has id i once the index is compacted.  The index
+        is not modified."""
+        off, data, df = self._ctx.bm25_terms(self._index)
+        raw = data.tobytes()
+        off = off.tolist()
+        return [raw[off[i]:off[i + 1]].decode("utf-8", "surrogatepass") for i in range(len(off) - 1)], df
+
+    def footprint(self) -> dict:
+        """{"text_bytes": bytes of the index's text copy (what the 2^32 limit of add_documents counts), "table_terms": terms held in
+        the term table, dead ones included, "device_bytes": device memory allocated to the index}"""
+        t, n, d = self._ctx.bm25_footprint(self._index)
+        return {"text_bytes": t, "table_terms": n, "device_bytes": d}
 
     # ---- the reference's per-document lists, built lazily on the host -------------------------------------------------
     @property

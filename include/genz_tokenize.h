@@ -410,11 +410,29 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          occurrence in what remains); a word no remaining document has is answered -1 with df 0 by
  *                          gz_bm25_lookup and is not counted by gz_bm25_info, and a later append brings it back.  The work is
  *                          proportional to the index: fieldLens, signatures and entries are compacted into fresh buffers of the
- *                          same capacity, the pair table is filled again.  The index's copy of the text is NOT compacted: its
- *                          device memory is not reclaimed, and the removed bytes still count towards GZ_E_LIMIT of an append.
+ *                          same capacity, the pair table is filled again.  The index's copy of the text is not touched: its
+ *                          device memory is not reclaimed, and the removed bytes still count towards GZ_E_LIMIT of an append,
+ *                          until gz_bm25_compact.
  *                          n_ids == 0: GZ_OK, nothing changes.  On any error (GZ_E_INVALID for an id outside [0, n_docs),
  *                          GZ_E_NOMEM) the index answers as before the call.
  *   gz_bm25_remove_device  the same for ids resident in HBM
+ *   gz_bm25_compact        the index becomes the one gz_bm25_build gives for its current documents: afterwards it answers every
+ *                          call above exactly as that build does, and now gz_bm25_lookup's term ids are that build's too (terms
+ *                          are numbered by first occurrence in the current documents; dead terms leave the term table).  The text
+ *                          copy shrinks to the live terms' bytes -- the figure GZ_E_LIMIT of an append counts -- and every buffer
+ *                          to the size a build gives it for the same counts: device memory that appends and removals left behind
+ *                          is given back.  Device-only, no text is tokenised or hashed again.  Appends and removals work on the
+ *                          compacted index as before.  On GZ_E_NOMEM the index answers as before the call.
+ *   gz_bm25_terms          the vocabulary, of an index in any state, which is not modified: the T live terms (T = n_terms of
+ *                          gz_bm25_info) in the order of their first occurrence in the current documents -- the order of the ids
+ *                          that gz_bm25_lookup answers once the index is compacted -- as term_off[T + 1] (term i = bytes[term_off[i]
+ *                          .. term_off[i + 1]), term_off[0] = 0) and df[T].  Sizes first: a call with bytes == NULL fills term_off
+ *                          and df (either may be NULL), and B = term_off[T] is the room the bytes need; a second call with
+ *                          bytes != NULL and bytes_cap >= B copies them (and fills term_off / df again where they are not NULL).
+ *                          bytes_cap < B: GZ_E_CAPACITY, nothing written.  term_off and bytes both NULL: GZ_E_INVALID.
+ *   gz_bm25_footprint      host bookkeeping, no device work: out[0] = bytes of the text copy in use (what GZ_E_LIMIT of an append
+ *                          counts), out[1] = terms held in the term table, dead ones included, out[2] = device bytes allocated
+ *                          to the index's ten buffers, capacities included
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
@@ -437,6 +455,9 @@ int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);
 int  gz_bm25_remove_device(gz_bm25 *index, const int64_t *doc_ids_dev, int64_t n_ids);
+int  gz_bm25_compact(gz_bm25 *index);
+int  gz_bm25_terms(gz_bm25 *index, int64_t *term_off, int32_t *df, uint8_t *bytes, int64_t bytes_cap);
+int  gz_bm25_footprint(gz_bm25 *index, int64_t out[3]);
 void gz_bm25_destroy(gz_bm25 *index);
 
 #ifdef __cplusplus

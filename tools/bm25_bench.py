@@ -1,6 +1,6 @@
 """BM25 index / scoring timings on the configs[2] corpus (genz_tokenize.ranking, csrc/gz_bm25.inc).
 
-    python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--compact 10000] [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -26,6 +26,15 @@ Remove (gz_bm25_remove_device / BM25.remove_documents; --remove random documents
   remove_python_ms     BM25.remove_documents(list of the same ids) on a model of --docs documents
   rebuild_remaining_device_ms  gz_bm25_build_device over the remaining --docs - --remove documents, text and offsets in HBM: what a
                        caller paid before, timed in the same run
+Compact (gz_bm25_compact / gz_bm25_terms; --compact random documents are removed from the --docs of the corpus first, 0 skips these
+rows; --compact-only: these rows alone, and with --out they are merged into the file's record instead of replacing it):
+  compact_device_ms    gz_bm25_compact on an index of --docs documents after gz_bm25_remove_device of --compact ids (build and
+                       removal are not timed)
+  terms_device_ms      gz_bm25_terms on the same index before it is compacted: both calls of the sizes-first protocol, the numbering
+                       on the device each time, offsets, df and bytes into host memory
+  rebuild_remaining_device_ms  as in the remove rows, alternating with the two above in the same process (compact_over_rebuild is
+                       taken against THIS run's figure; compact_bar_met: compact_device_ms below it)
+  footprint_before / footprint_after  gz_bm25_footprint (text bytes in use, terms in the table, device bytes) around the compaction
   restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
                        its postings built beforehand (not timed)
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
@@ -182,6 +191,51 @@ def remove_rows(ctx, res, n, k, reps):
     res["remove_python_ms"], res["remove_python_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
 
 
+def compact_rows(ctx, res, n, k, reps):
+    """the compact rows of the docstring"""
+    t, o, _ = corpus.config_corpus(2, n_docs=n)
+    nbytes = int(o[-1])
+    ids = np.sort(np.random.default_rng(2).choice(n, size=k, replace=False)).astype(np.int64)
+    keep = np.ones(n, bool)
+    keep[ids] = False
+    lens = np.diff(o)
+    r_off = np.zeros(n - k + 1, np.int64)
+    np.cumsum(lens[keep], out=r_off[1:])
+    r_text = t[np.repeat(keep, lens)]
+    d_text, d_off, d_ids = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1)), ctx.alloc(8 * k)
+    d_rtext, d_roff = ctx.alloc(max(len(r_text), 16)), ctx.alloc(8 * (n - k + 1))
+    for d, h in ((d_text, t), (d_off, o), (d_ids, ids), (d_rtext, r_text), (d_roff, r_off)):
+        ctx.h2d(d, h)
+    res.update(compact_removed_docs=k)
+    cp, tm, rb = [], [], []
+    for _ in range(reps + 1):                                        # (the first of each is the warm-up)
+        ix = ctx.bm25_build_device(d_text, d_off, n, nbytes)
+        ctx.bm25_remove_device(ix, d_ids, k)
+        before = ctx.bm25_footprint(ix)
+        t0 = time.perf_counter()
+        off, data, df = ctx.bm25_terms(ix)
+        tm.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        ctx.bm25_compact(ix)
+        cp.append((time.perf_counter() - t0) * 1e3)
+        after, info = ctx.bm25_footprint(ix), ctx.bm25_info(ix)
+        assert after[0] == int(off[-1]) == len(data) and after[1] == info[1] == len(df)
+        ctx.bm25_destroy(ix)
+        t0 = time.perf_counter()
+        ix = ctx.bm25_build_device(d_rtext, d_roff, n - k, int(r_off[-1]))
+        rb.append((time.perf_counter() - t0) * 1e3)
+        assert ctx.bm25_info(ix) == info                             # documents, live terms and words of the fresh build
+        ctx.bm25_destroy(ix)
+    res["compact_device_ms"], res["compact_device_all_ms"] = float(np.median(cp[1:])), [round(x, 3) for x in cp[1:]]
+    res["terms_device_ms"], res["terms_device_all_ms"] = float(np.median(tm[1:])), [round(x, 3) for x in tm[1:]]
+    res["rebuild_remaining_device_ms"], res["rebuild_remaining_device_all_ms"] = float(np.median(rb[1:])), [round(x, 3) for x in rb[1:]]
+    res["compact_over_rebuild"] = round(res["compact_device_ms"] / res["rebuild_remaining_device_ms"], 3)
+    res["compact_bar_met"] = bool(res["compact_device_ms"] < res["rebuild_remaining_device_ms"])
+    res["footprint_before"], res["footprint_after"] = list(before), list(after)
+    for d in (d_text, d_off, d_ids, d_rtext, d_roff):
+        ctx.free(d)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -193,16 +247,31 @@ def main():
     ap.add_argument("--append-only", action="store_true", help="only the append rows (a trace of their kernels)")
     ap.add_argument("--remove", type=int, default=10_000, help="documents of the remove rows (0: skip them)")
     ap.add_argument("--remove-only", action="store_true", help="only the remove rows (a trace of their kernels)")
+    ap.add_argument("--compact", type=int, default=10_000, help="documents removed before the compact rows (0: skip them)")
+    ap.add_argument("--compact-only", action="store_true", help="only the compact rows; with --out they are merged into the file")
     a = ap.parse_args()
     t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
     res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
+    if a.compact_only:
+        compact_rows(ctx, res, n, a.compact, a.reps)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith(("compact_", "terms_device", "footprint_"))})
+            old["compact_rows_run"] = dict(docs=n, reps=a.reps, rebuild_remaining_device_ms=res["rebuild_remaining_device_ms"])
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
     if a.remove:
         remove_rows(ctx, res, n, a.remove, a.reps)
     if a.remove_only:
         print(json.dumps(res))
         return
+    if a.compact:
+        compact_rows(ctx, res, n, a.compact, a.reps)                 # (its rebuild_remaining_device_ms is the one recorded)
     if a.append:
         append_rows(ctx, res, n, a.append, a.reps)
     if a.append_only:
