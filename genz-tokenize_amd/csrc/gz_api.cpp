@@ -174,7 +174,7 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
-    DBuf w_bm[40];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
+    DBuf w_bm[56];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
@@ -952,7 +952,11 @@ struct gz_bm25 {
     // the index: a copy of the text (the terms' bytes), fieldLens, signatures, doc-major (term, count) entries, the (document, term)
     // pair table, the term table, the terms' byte ranges and df
     DBuf text, dl, sig, eoff, ent, ptab, ttab, tstart, tlen, df;
-    ~gz_bm25() { for (DBuf* b : {&text, &dl, &sig, &eoff, &ent, &ptab, &ttab, &tstart, &tlen, &df}) release(*b); }
+    // derived from the entries and df by the first search (bm25_postings), dropped by every change of the index: the term-major
+    // postings (gz_search.inc)
+    DBuf poff, pdoc;
+    bool has_post = false;
+    ~gz_bm25() { for (DBuf* b : {&text, &dl, &sig, &eoff, &ent, &ptab, &ttab, &tstart, &tlen, &df, &poff, &pdoc}) release(*b); }
 };
 
 namespace {
@@ -961,6 +965,9 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_CKEY0, BMW_CIDX0, BMW_CKEY1, BMW_CIDX1, BMW_TOUT,
        BMW_CP_FIRST, BMW_CP_NEWID, BMW_CP_ORDER, BMW_CP_NLEN, BMW_CP_TOFF,          // the canonical numbering (bm25_number)
        BMW_V_OFF, BMW_V_DF, BMW_V_BYTES,                                            // what gz_bm25_terms hands out
+       BMW_P_CUR,                                                                   // the postings' cursors (bm25_postings)
+       BMW_S_BM, BMW_S_WROW, BMW_S_WNS, BMW_S_WSOFF, BMW_S_TCNT, BMW_S_TBASE, BMW_S_CNT,     // a search chunk (bm25_search_locked)
+       BMW_S_CAND, BMW_S_CSC, BMW_S_POS, BMW_S_PSC,
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1441,7 +1448,8 @@ int bm25_query_in(gz_bm25* ix, const int32_t* terms, const double* idf, const in
     if ((rc = bm_alloc(c, w[BMW_QTERM], (size_t)nw * 4)) || (rc = bm_alloc(c, w[BMW_QIDF], (size_t)nw * 8)) ||
         (rc = bm_alloc(c, w[BMW_QOFF], (size_t)(nq + 1) * 8)))
         return rc;
-    if (nw && ((rc = copy_in(c, w[BMW_QTERM].p, terms + qoff[0], (size_t)nw * 4, s)) || (rc = copy_in(c, w[BMW_QIDF].p, idf + qoff[0], (size_t)nw * 8, s))))
+    if (nw && ((rc = copy_in(c, w[BMW_QTERM].p, terms + qoff[0], (size_t)nw * 4, s)) ||
+               (idf && (rc = copy_in(c, w[BMW_QIDF].p, idf + qoff[0], (size_t)nw * 8, s)))))       // (a match count has no idf and no P)
         return rc;
     if ((rc = copy_in(c, w[BMW_QOFF].p, qoff, (size_t)(nq + 1) * 8, s))) return rc;
     S = GzBm25Score{};
@@ -1449,7 +1457,8 @@ int bm25_query_in(gz_bm25* ix, const int32_t* terms, const double* idf, const in
     S.ent = (const uint2*)ix->ent.p; S.ptab = (const GzBm25Slot*)ix->ptab.p; S.pmask = ix->pmask; S.n_docs = ix->n_docs;
     S.qterm = (const int32_t*)w[BMW_QTERM].p - qoff[0]; S.qidf = (const double*)w[BMW_QIDF].p - qoff[0];
     S.qoff = (const int64_t*)w[BMW_QOFF].p; S.n_q = nq;
-    S.kp1 = P[0]; S.k1 = P[1]; S.omb = P[2]; S.b = P[3]; S.avg = P[4]; S.delta = P[5]; S.plus = plus ? 1 : 0;
+    if (P) { S.kp1 = P[0]; S.k1 = P[1]; S.omb = P[2]; S.b = P[3]; S.avg = P[4]; S.delta = P[5]; }
+    S.plus = plus ? 1 : 0;
     return GZ_OK;
 }
 
@@ -1552,6 +1561,169 @@ int bm25_topk_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const
         if (!doc_dev && ((rc = copy_out(c, doc_host + q0 * kk, T.doc_out, (size_t)(rows * kk) * 8, s)) ||
                          (rc = copy_out(c, score_host + q0 * kk, T.score_out, (size_t)(rows * kk) * 8, s))))
             return rc;
+    }
+    return GZ_OK;
+}
+
+// ---- search (gz_bm25_search, gz_bm25_match_count; gz_search.inc) -----------------------------------------------------------------
+// the postings leave: the index has changed (or is to equal a fresh build).  After the stream has drained: a search enqueued into
+// device memory may still read them.
+void bm25_drop_postings(gz_bm25* ix)
+{
+    if (!ix->has_post) return;
+    hipStreamSynchronize(ix->c->stream);
+    release(ix->poff);
+    release(ix->pdoc);
+    ix->has_post = false;
+}
+
+// The term-major postings of the index as it is, unless it has them: poff = the scan of df, pdoc filled from the entries.  Both
+// are staged and enter the index after the last round trip: a return before that leaves the index without postings, as it was.
+int bm25_postings(gz_bm25* ix)
+{
+    if (ix->has_post) return GZ_OK;
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    const int64_t T = ix->n_terms, E = ix->n_ent;
+    int rc;
+    BmStage st;
+    BmDrain drain{c};
+    void *p_poff, *p_pdoc;
+    if ((rc = bm_stage_exact(c, st, ix->poff, (size_t)(T + 1) * 4, &p_poff)) || (rc = bm_stage_exact(c, st, ix->pdoc, (size_t)E * 4, &p_pdoc)) ||
+        (rc = bm_alloc(c, w[BMW_P_CUR], (size_t)T * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
+        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(T / 4096 + 2) * 4)))
+        return rc;
+    GzBm25Post P{};
+    P.n_docs = ix->n_docs; P.n_terms = T; P.n_ent = E;
+    P.eoff = (const uint32_t*)ix->eoff.p; P.ent = (const uint2*)ix->ent.p;
+    P.poff = (const uint32_t*)p_poff; P.pdoc = (uint32_t*)p_pdoc; P.cur = (uint32_t*)w[BMW_P_CUR].p; P.ctl = (uint32_t*)w[BMW_CTL].p;
+    HIPCHK(c, hipMemsetAsync(P.ctl, 0, 64, s));
+    if (T) HIPCHK(c, hipMemsetAsync(P.cur, 0, (size_t)T * 4, s));
+    if ((rc = bm_scan(c, (const uint32_t*)ix->df.p, T, (uint32_t*)p_poff))) return rc;
+    gz_launch_bm25_post(P, s);
+    int64_t bad = 0, total = 0;
+    if ((rc = bm_read_u32(c, P.ctl + 1, bad)) || (rc = bm_read_u32(c, P.poff + T, total))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (bad || total != E) return fail(c, GZ_E_HIP, "BM25 postings: the index's entries (%lld) and df (%lld) contradict each other", (long long)E, (long long)total);
+    st.commit();
+    ix->has_post = true;
+    return GZ_OK;
+}
+
+int bm25_match_args(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, const void* out)
+{
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!qoff || nq < 0 || (!out && nq > 0)) return fail(c, GZ_E_INVALID, "bad arguments");
+    const int64_t nw = qoff[nq] - qoff[0];
+    if (nw < 0 || (nw > 0 && !terms)) return fail(c, GZ_E_INVALID, "bad query offsets");
+    for (int64_t q = 0; q < nq; ++q) if (qoff[q + 1] < qoff[q]) return fail(c, GZ_E_INVALID, "query offsets must not decrease");
+    for (int64_t j = qoff[0]; j < qoff[nq]; ++j)
+        if (terms[j] < -1 || terms[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "term id %d out of range", terms[j]);
+    return GZ_OK;
+}
+
+// A chunk of queries at a time (its bitmaps hold at most bm25_search_chunk words, one row at least, at most 65535 rows): mark the
+// documents of every query word's postings in the row's bitmap, count and rank the bits, and read the counts back -- they size
+// what follows.  Then, for runs of rows whose candidate scores (rows x the largest count among them) stay within
+// bm25_search_chunk doubles, one row at least: the candidates in ascending id, their scores, gz_launch_topk over them and the
+// positions mapped back to document ids.  Outputs into doc_dev / score_dev / cnt_dev, or into host memory after every run
+// (doc_dev null).  count_only: nothing behind the counts (idf, P, the document outputs are not read).
+int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
+                       int64_t kk, bool count_only, int64_t* doc_dev, double* score_dev, int64_t* cnt_dev, int64_t* doc_host, double* score_host,
+                       int64_t* cnt_host)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t N = ix->n_docs;
+    if (nq == 0) return GZ_OK;
+    if (N == 0) {
+        if (cnt_dev) HIPCHK(c, hipMemsetAsync(cnt_dev, 0, (size_t)nq * 8, s));
+        if (cnt_host) std::memset(cnt_host, 0, (size_t)nq * 8);
+        return GZ_OK;
+    }
+    int rc;
+    if ((rc = bm25_postings(ix))) return rc;
+    GzBm25Search A{};
+    if ((rc = bm25_query_in(ix, terms, idf, qoff, nq, P, plus, A.S))) return rc;
+    const int64_t chunk = c->opt.bm25_search_chunk;
+    const int64_t W64 = (N + 63) / 64, n_tiles = (W64 + GZ_SEARCH_TILE - 1) / GZ_SEARCH_TILE;
+    const int64_t rmax = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(chunk / W64, 1), 65535), nq);
+    int64_t wmax = 0;                                          // the most query words of a chunk
+    for (int64_t q0 = 0; q0 < nq; q0 += rmax) wmax = std::max(wmax, qoff[std::min(q0 + rmax, nq)] - qoff[q0]);
+    if ((rc = bm_alloc(c, w[BMW_S_BM], (size_t)(rmax * W64) * 8)) || (rc = bm_alloc(c, w[BMW_S_WROW], (size_t)wmax * 4)) ||
+        (rc = bm_alloc(c, w[BMW_S_WNS], (size_t)(wmax + 1) * 4)) || (rc = bm_alloc(c, w[BMW_S_WSOFF], (size_t)(wmax + 1) * 4)) ||
+        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(wmax / 4096 + 2) * 4)) || (rc = bm_alloc(c, w[BMW_S_TCNT], (size_t)(rmax * n_tiles) * 4)) ||
+        (rc = bm_alloc(c, w[BMW_S_TBASE], (size_t)(rmax * n_tiles) * 4)) || (rc = bm_alloc(c, w[BMW_S_CNT], (size_t)rmax * 4)))
+        return rc;
+    alloc_site(c);
+    std::vector<uint32_t> cnt((size_t)rmax);
+    A.poff = (const uint32_t*)ix->poff.p; A.pdoc = (const uint32_t*)ix->pdoc.p;
+    A.n_docs = N; A.n_terms = ix->n_terms; A.n_ent = ix->n_ent;
+    A.qterm = A.S.qterm; A.qidf = A.S.qidf;
+    A.w64 = W64; A.n_tiles = n_tiles; A.bm = (unsigned long long*)w[BMW_S_BM].p;
+    A.wrow = (uint32_t*)w[BMW_S_WROW].p; A.wns = (uint32_t*)w[BMW_S_WNS].p; A.wsoff = (uint32_t*)w[BMW_S_WSOFF].p;
+    A.tcnt = (uint32_t*)w[BMW_S_TCNT].p; A.tbase = (uint32_t*)w[BMW_S_TBASE].p; A.cnt = (uint32_t*)w[BMW_S_CNT].p;
+    const int64_t* qoff_dev = A.S.qoff;
+    for (int64_t q0 = 0; q0 < nq; q0 += rmax) {
+        const int64_t rows = std::min(rmax, nq - q0);
+        A.qoff = qoff_dev + q0; A.rows = rows; A.n_qw = qoff[q0 + rows] - qoff[q0];
+        A.cnt_out = cnt_dev ? cnt_dev + q0 : nullptr;
+        HIPCHK(c, hipMemsetAsync(A.bm, 0, (size_t)(rows * W64) * 8, s));
+        if (A.n_qw > 0) {
+            gz_launch_bm25_search(GZ_BM25_SR_WORDS, A, rows, s);
+            if ((rc = bm_scan(c, A.wns, A.n_qw, A.wsoff))) return rc;
+            gz_launch_bm25_search(GZ_BM25_SR_MARK, A, rows, s);
+        }
+        gz_launch_bm25_search(GZ_BM25_SR_COUNT, A, rows, s);
+        gz_launch_bm25_search(GZ_BM25_SR_ROWS, A, rows, s);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = copy_out_small(c, cnt.data(), A.cnt, (size_t)rows * 4, s))) return rc;
+        if (cnt_host) for (int64_t r = 0; r < rows; ++r) cnt_host[q0 + r] = (int64_t)cnt[(size_t)r];
+        if (count_only) continue;
+        for (int64_t r0 = 0; r0 < rows;) {
+            int64_t M = cnt[(size_t)r0], n = 1;
+            while (r0 + n < rows) {
+                const int64_t M2 = std::max<int64_t>(M, cnt[(size_t)(r0 + n)]);
+                if ((n + 1) * M2 > chunk) break;
+                M = M2;
+                ++n;
+            }
+            const int64_t k2 = std::min(kk, M);
+            A.row0 = r0; A.M = M; A.k2 = k2; A.kk = kk;
+            if (!doc_dev && (rc = bm_alloc(c, w[BMW_TOUT], (size_t)(n * kk) * 16))) return rc;
+            if (M > 0) {
+                const int64_t tile = bm25_topk_tile(c, n, M, k2);
+                int64_t m1, m2;
+                gz_topk_sizes(M, tile, k2, m1, m2);
+                if ((rc = bm_alloc(c, w[BMW_S_CAND], (size_t)(n * M) * 4)) || (rc = bm_alloc(c, w[BMW_S_CSC], (size_t)(n * M) * 8)) ||
+                    (rc = bm_alloc(c, w[BMW_CKEY0], (size_t)(n * m1) * 8)) || (rc = bm_alloc(c, w[BMW_CIDX0], (size_t)(n * m1) * 4)) ||
+                    (rc = bm_alloc(c, w[BMW_CKEY1], (size_t)(n * m2) * 8)) || (rc = bm_alloc(c, w[BMW_CIDX1], (size_t)(n * m2) * 4)) ||
+                    (rc = bm_alloc(c, w[BMW_S_POS], (size_t)(n * k2) * 8)) || (rc = bm_alloc(c, w[BMW_S_PSC], (size_t)(n * k2) * 8)))
+                    return rc;
+                A.cand = (uint32_t*)w[BMW_S_CAND].p; A.csc = (double*)w[BMW_S_CSC].p;
+                A.pos = (const int64_t*)w[BMW_S_POS].p; A.psc = (const double*)w[BMW_S_PSC].p;
+                gz_launch_bm25_search(GZ_BM25_SR_CAND, A, n, s);
+                gz_launch_bm25_search(GZ_BM25_SR_SCORE, A, n, s);
+                GzTopk T{};
+                T.scores = A.csc; T.n_docs = M; T.rows = n; T.k = k2; T.tile = tile;
+                T.ckey[0] = (unsigned long long*)w[BMW_CKEY0].p; T.cidx[0] = (uint32_t*)w[BMW_CIDX0].p;
+                T.ckey[1] = (unsigned long long*)w[BMW_CKEY1].p; T.cidx[1] = (uint32_t*)w[BMW_CIDX1].p;
+                T.doc_out = (int64_t*)w[BMW_S_POS].p; T.score_out = (double*)w[BMW_S_PSC].p;
+                gz_launch_topk(T, s);
+            }
+            A.doc_out = doc_dev ? doc_dev + (q0 + r0) * kk : (int64_t*)w[BMW_TOUT].p;
+            A.score_out = doc_dev ? score_dev + (q0 + r0) * kk : (double*)w[BMW_TOUT].p + n * kk;
+            gz_launch_bm25_search(GZ_BM25_SR_OUT, A, n, s);
+            HIPCHK(c, hipGetLastError());
+            if (!doc_dev && ((rc = copy_out(c, doc_host + (q0 + r0) * kk, A.doc_out, (size_t)(n * kk) * 8, s)) ||
+                             (rc = copy_out(c, score_host + (q0 + r0) * kk, A.score_out, (size_t)(n * kk) * 8, s))))
+                return rc;
+            r0 += n;
+        }
     }
     return GZ_OK;
 }
@@ -3139,7 +3311,9 @@ try {
     BmDrain drain{c};
     if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
     if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
-    return bm25_append_core(c, ix, st, nbytes ? text + text_off[0] : nullptr, nullptr, (const int64_t*)c->w_bm[BMW_OFF].p, text_off[0], n_docs, nbytes);
+    rc = bm25_append_core(c, ix, st, nbytes ? text + text_off[0] : nullptr, nullptr, (const int64_t*)c->w_bm[BMW_OFF].p, text_off[0], n_docs, nbytes);
+    if (!rc) bm25_drop_postings(ix);
+    return rc;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_append_device(gz_bm25* ix, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes)
@@ -3158,7 +3332,9 @@ try {
     int64_t off0 = 0;
     if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
     if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
-    return bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
+    rc = bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
+    if (!rc) bm25_drop_postings(ix);
+    return rc;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_remove(gz_bm25* ix, const int64_t* doc_ids, int64_t n_ids)
@@ -3174,7 +3350,9 @@ try {
     BmDrain drain{c};
     if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)n_ids * 8))) return rc;
     if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, doc_ids, (size_t)n_ids * 8, c->stream))) return rc;
-    return bm25_remove_core(c, ix, st, (const int64_t*)c->w_bm[BMW_OFF].p, n_ids);
+    rc = bm25_remove_core(c, ix, st, (const int64_t*)c->w_bm[BMW_OFF].p, n_ids);
+    if (!rc) bm25_drop_postings(ix);
+    return rc;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_remove_device(gz_bm25* ix, const int64_t* doc_ids_dev, int64_t n_ids)
@@ -3187,7 +3365,9 @@ try {
     HIPCHK(c, hipSetDevice(c->device));
     BmStage st;
     BmDrain drain{c};
-    return bm25_remove_core(c, ix, st, doc_ids_dev, n_ids);
+    const int rc = bm25_remove_core(c, ix, st, doc_ids_dev, n_ids);
+    if (!rc) bm25_drop_postings(ix);
+    return rc;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_compact(gz_bm25* ix)
@@ -3198,7 +3378,9 @@ try {
     HIPCHK(c, hipSetDevice(c->device));
     BmStage st;
     BmDrain drain{c};
-    return bm25_compact_core(c, ix, st);
+    const int rc = bm25_compact_core(c, ix, st);
+    if (!rc) bm25_drop_postings(ix);              // (a fresh build has none: device memory included)
+    return rc;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_terms(gz_bm25* ix, int64_t* term_off, int32_t* df, uint8_t* bytes, int64_t bytes_cap)
@@ -3240,7 +3422,9 @@ try {
     if (!out) return fail(c, GZ_E_INVALID, "bad arguments");
     std::lock_guard<std::mutex> lk(c->mu);
     size_t cap = 0;
-    for (const DBuf* b : {&ix->text, &ix->dl, &ix->sig, &ix->eoff, &ix->ent, &ix->ptab, &ix->ttab, &ix->tstart, &ix->tlen, &ix->df}) cap += b->cap;
+    for (const DBuf* b : {&ix->text, &ix->dl, &ix->sig, &ix->eoff, &ix->ent, &ix->ptab, &ix->ttab, &ix->tstart, &ix->tlen, &ix->df,
+                          &ix->poff, &ix->pdoc})          // (the postings while they exist)
+        cap += b->cap;
     out[0] = ix->text_bytes; out[1] = ix->n_terms; out[2] = (int64_t)cap;
     return GZ_OK;
 } GZ_CATCH(ix ? ix->c : nullptr)
@@ -3330,6 +3514,37 @@ try {
     if (rc || (rc = bm25_topk_k(ix, k, kk))) return rc;
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_topk_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, doc_out_dev, score_out_dev, nullptr, nullptr);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                   int32_t plus, int64_t k, int64_t* doc_out, double* score_out, int64_t* count_out)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out && score_out ? doc_out : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk))) return rc;
+    if (!count_out && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, nullptr, nullptr, nullptr, doc_out, score_out, count_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                          const double params[6], int32_t plus, int64_t k, int64_t* doc_out_dev, double* score_out_dev, int64_t* count_out_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out_dev && score_out_dev ? doc_out_dev : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk))) return rc;
+    if (!count_out_dev && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, doc_out_dev, score_out_dev, count_out_dev, nullptr, nullptr,
+                              nullptr);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_match_count(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, int64_t* count_out)
+try {
+    int rc = bm25_match_args(ix, terms, query_off, n_queries, count_out);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 void gz_bm25_destroy(gz_bm25* ix)

@@ -29,6 +29,7 @@
 //                           dead terms -- all OUT OF PLACE, the live index is only read
 //   gz_bm25_lookup_kernel   query words (packed) -> term id (-1: absent) and df, bytes compared in full
 //   gz_bm25_score_kernel    scores[Q, N] float64 in the reference's order of operations (ranking.py:33-45, :52-63)
+// (gz_search.inc: the term-major postings and the search over them)
 //
 // Vector stores and vector atomics only.  Results never depend on the order in which atomics land: counts and df are sums,
 // representatives and first occurrences are minima, signatures are ORs, term ids come out of a scan; of the decrements that
@@ -36,6 +37,9 @@
 // orders and offsets are plain stores of values that scans of those give; every arena byte, entry and signature word has one
 // writer (signatures are ORed in registers); table slots are claimed by CAS, and which of several equal keys sits first along a
 // probe sequence is the one thing that varies -- no answer reads it (a lookup compares bytes, pair keys are unique).
+// The postings of a search (gz_search.inc) are filled through per-term atomic cursors: the order of the documents inside a term's
+// list varies from run to run, and no answer reads it either -- a list only ever becomes bits of a per-query bitmap (an OR), and
+// counts, candidates (in ascending document id), scores and ranks are functions of the bits.
 
 namespace {
 
@@ -72,6 +76,32 @@ __device__ __forceinline__ double bm_nan(double r, double a, double b)
     const unsigned long long u = a != a ? (unsigned long long)__double_as_longlong(a) | q
                                : b != b ? (unsigned long long)__double_as_longlong(b) | q : 0xFFF8000000000000ull;
     return __longlong_as_double((long long)u);
+}
+// The scoring arithmetic, shared by gz_bm25_score_kernel and gz_bm25_sr_score_kernel (gz_search.inc) so that both give the same
+// bits.  A document's factors: K = k1 * ((1 - b) + b * (dl / avg)) and t0, the term for f = 0.
+__device__ __forceinline__ void bm_doc_factors(const GzBm25Score& S, double dl, double& K, double& t0)
+{
+#pragma clang fp contract(off)
+    const double x = bm_nan(dl / S.avg, dl, S.avg);
+    const double y = bm_nan(S.b * x, S.b, x);
+    const double z = bm_nan(S.omb + y, S.omb, y);
+    K = bm_nan(S.k1 * z, S.k1, z);
+    const double n0 = bm_nan(0.0 * S.kp1, 0.0, S.kp1), d0K = bm_nan(0.0 + K, 0.0, K);
+    t0 = bm_nan(n0 / d0K, n0, d0K);
+}
+// one query word: score + idf * t (BM25Plus: idf * (t + delta)) for the word's count f in the document
+__device__ __forceinline__ double bm_word_score(const GzBm25Score& S, double score, uint32_t f, double K, double t0, double idf)
+{
+#pragma clang fp contract(off)
+    double tf = t0;
+    if (f != 0) {
+        const double fd = (double)f;
+        const double num = bm_nan(fd * S.kp1, fd, S.kp1), den = bm_nan(fd + K, fd, K);
+        tf = bm_nan(num / den, num, den);
+    }
+    const double v = S.plus ? bm_nan(tf + S.delta, tf, S.delta) : tf;
+    const double a = bm_nan(idf * v, idf, v);
+    return bm_nan(score + a, score, a);
 }
 __device__ __forceinline__ bool bm_equal(const uint8_t* a, const uint8_t* b, int64_t n)
 {
@@ -594,13 +624,8 @@ __global__ __launch_bounds__(256) void gz_bm25_score_kernel(GzBm25Score S)
         for (uint32_t k = threadIdx.x; k < e1 - e0; k += 256) L[k] = S.ent[e0 + k];
     const int64_t dc = active ? d : d0;                       // (inactive lanes compute for a real document and write nothing)
     const uint32_t eb = S.eoff[dc] - e0, ne = S.eoff[dc + 1] - S.eoff[dc];
-    const double dl = (double)S.dl[dc];
-    const double x = bm_nan(dl / S.avg, dl, S.avg);
-    const double y = bm_nan(S.b * x, S.b, x);
-    const double z = bm_nan(S.omb + y, S.omb, y);
-    const double K = bm_nan(S.k1 * z, S.k1, z);
-    const double n0 = bm_nan(0.0 * S.kp1, 0.0, S.kp1), d0K = bm_nan(0.0 + K, 0.0, K);
-    const double t0 = bm_nan(n0 / d0K, n0, d0K);
+    double K, t0;
+    bm_doc_factors(S, (double)S.dl[dc], K, t0);
     const unsigned long long sg[4] = {S.sig[dc * 4], S.sig[dc * 4 + 1], S.sig[dc * 4 + 2], S.sig[dc * 4 + 3]};
     const unsigned long long pkey = (unsigned long long)dc << 32;
     // the batch's words, BM_QW_LDS at a time, staged in LDS (term, signature bit, idf); queries end where their offsets say
@@ -645,15 +670,7 @@ __global__ __launch_bounds__(256) void gz_bm25_score_kernel(GzBm25Score S)
                     }
                 }
             }
-            double tf = t0;
-            if (f != 0) {
-                const double fd = (double)f;
-                const double num = bm_nan(fd * S.kp1, fd, S.kp1), den = bm_nan(fd + K, fd, K);
-                tf = bm_nan(num / den, num, den);
-            }
-            const double v = S.plus ? bm_nan(tf + S.delta, tf, S.delta) : tf;
-            const double a = bm_nan(qw.idf * v, qw.idf, v);
-            score = bm_nan(score + a, score, a);
+            score = bm_word_score(S, score, f, K, t0, qw.idf);
         }
     }
     for (; q < S.n_q; ++q) {                                  // the last query, and empty queries at the end

@@ -277,3 +277,41 @@ inline void gz_topk_sizes(int64_t n_docs, int64_t tile, int64_t k, int64_t& m1, 
     if ((m1 + GZ_TOPK_TILE_MAX - 1) / GZ_TOPK_TILE_MAX > 1) m2 = gz_topk_level(m1, GZ_TOPK_TILE_MAX, k);
 }
 void gz_launch_topk(const GzTopk& T, hipStream_t s);
+
+// BM25 search (gz_search.inc): term-major postings, and the matching documents of every query counted, scored and ranked
+constexpr int GZ_SEARCH_TILE = 2048;      // bitmap words per workgroup of the counting / candidate kernels (8 per thread)
+struct GzBm25Post {
+    int64_t n_docs, n_terms, n_ent;
+    const uint32_t* eoff; const uint2* ent;
+    const uint32_t* poff;                 // [n_terms + 1] exclusive scan of df
+    uint32_t* cur;                        // [n_terms] entries of the term placed so far (cleared by the caller)
+    uint32_t* pdoc;                       // [n_ent] the documents of term t at poff[t] .. poff[t + 1], in no particular order
+    uint32_t* ctl;                        // [1] df and the entries contradict each other
+};
+void gz_launch_bm25_post(const GzBm25Post& P, hipStream_t s);
+struct GzBm25Search {
+    GzBm25Score S;                        // the index's arrays and the scoring parameters (its query fields are not read)
+    const uint32_t* poff; const uint32_t* pdoc;
+    int64_t n_docs, n_terms, n_ent;
+    // the chunk: `rows` queries, row r = words qoff[r] .. qoff[r + 1] (absolute indices into qterm / qidf), n_qw words in all
+    const int32_t* qterm; const double* qidf; const int64_t* qoff;
+    int64_t rows, n_qw;
+    int64_t w64;                          // bitmap words per row = ceil(n_docs / 64)
+    unsigned long long* bm;               // [rows, w64] bit d of row r: document d matches query r (cleared by the caller)
+    uint32_t* wrow; uint32_t* wns;        // [n_qw] row of every word, slices of its postings list
+    uint32_t* wsoff;                      // [n_qw + 1] exclusive scan of wns
+    int64_t n_tiles;                      // tiles of a row's bitmap
+    uint32_t* tcnt; uint32_t* tbase;      // [rows, n_tiles] set bits of every tile, and their exclusive scan along the row
+    uint32_t* cnt;                        // [rows] matching documents
+    int64_t* cnt_out;                     // [rows] the same as int64 (may be null)
+    // the rows row0 .. row0 + (rows of the launch) scored together: candidate lists of stride M (the largest of their counts)
+    int64_t row0, M;
+    uint32_t* cand;                       // [., M] the matching documents in ascending id
+    double* csc;                          // [., M] their scores, NaN behind the row's count
+    const int64_t* pos; const double* psc;  // [., k2] the selection's positions into the candidate list and scores
+    int64_t k2, kk;                       // k2 = min(kk, M)
+    int64_t* doc_out; double* score_out;  // [., kk]: -1 / NaN behind the row's count
+};
+enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_BM25_SR_CAND, GZ_BM25_SR_SCORE, GZ_BM25_SR_OUT };
+// rows: of the chunk (WORDS, MARK, COUNT, ROWS), else of the launch (from row0)
+void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStream_t s);

@@ -34,6 +34,7 @@ SYMBOLS = [
     "gz_bm25_score_device", "gz_bm25_destroy", "gz_bm25_topk", "gz_bm25_topk_device",
     "gz_bm25_append", "gz_bm25_append_device", "gz_bm25_remove", "gz_bm25_remove_device",
     "gz_bm25_compact", "gz_bm25_terms", "gz_bm25_footprint",
+    "gz_bm25_search", "gz_bm25_search_device", "gz_bm25_match_count",
 ]
 
 _lib = None
@@ -135,6 +136,10 @@ def load_library():
         L.gz_bm25_compact.argtypes = [vp]
         L.gz_bm25_terms.argtypes = [vp, vp, vp, vp, i64]
         L.gz_bm25_footprint.argtypes = [vp, vp]
+    if hasattr(L, "gz_bm25_search"):
+        L.gz_bm25_search.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, vp]
+        L.gz_bm25_search_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, vp]
+        L.gz_bm25_match_count.argtypes = [vp, vp, vp, i64, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -596,6 +601,38 @@ class Context:
         scores = np.empty((nq, kk), dtype=np.float64)
         self._check(self.lib.gz_bm25_topk(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None))
         return ids, scores
+
+    def bm25_search(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool, k: int,
+                    d_ids: int | None = None, d_scores: int | None = None, d_counts: int | None = None):
+        """(ids int64 [Q, k'], scores float64 [Q, k'], counts int64 [Q]) with k' = min(k, documents): the best MATCHING documents of
+        every query (those that hold at least one of its words) and how many match; positions behind a row's count hold -1 / NaN.
+        With d_ids / d_scores / d_counts (device pointers, all three): enqueued into them, sync() waits."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        idf = np.ascontiguousarray(idf, dtype=np.float64)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        P = np.ascontiguousarray(params, dtype=np.float64)
+        assert P.shape == (6,)
+        nq = len(query_off) - 1
+        args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
+                1 if plus else 0, int(k)]
+        if d_ids is not None or d_scores is not None or d_counts is not None:
+            self._check(self.lib.gz_bm25_search_device(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
+            return None
+        kk = max(0, min(int(k), self.bm25_info(index)[0]))
+        ids = np.empty((nq, kk), dtype=np.int64)
+        scores = np.empty((nq, kk), dtype=np.float64)
+        counts = np.zeros(max(nq, 1), dtype=np.int64)
+        self._check(self.lib.gz_bm25_search(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
+        return ids, scores, counts[:nq]
+
+    def bm25_match_count(self, index: int, terms: np.ndarray, query_off: np.ndarray) -> np.ndarray:
+        """int64 [Q]: the documents that hold at least one word of each query."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        nq = len(query_off) - 1
+        counts = np.zeros(max(nq, 1), dtype=np.int64)
+        self._check(self.lib.gz_bm25_match_count(C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq, _ptr(counts)))
+        return counts[:nq]
 
     def exchange_select(self, back: int):
         """Exchange operations issued from now on belong to the encode call `back` calls before the latest one."""

@@ -9,6 +9,13 @@ Retrieval: `top_k(queries, k)` returns the ids and scores of every query's k bes
 those documents (rank_bm25's form).  The score rows are computed and searched on the GPU (csrc/gz_topk.inc): only [Q, k] ids and
 scores come back.  The order is total: higher scores first, ties to the lower document index, NaN last.
 
+Search: `search(queries, k)` ranks only the documents that MATCH a query -- those that hold at least one of its words -- and
+tells how many match; `count_matches(queries)` only counts.  The matching documents come from term-major postings on the GPU
+(csrc/gz_search.inc), built by the first search and again after the index changes; only they are scored and ranked, so a query of
+rare words does not pay for the whole corpus.  The ranked documents are exactly `top_k`'s order with the other documents left
+out; unlike `top_k`, a row is never filled up with documents that hold none of the query's words (with BM25Plus those have positive
+scores too): unfilled positions hold id -1 and NaN.
+
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
@@ -222,6 +229,32 @@ class BM25:
         nq, terms, idf, qoff = self._queries(queries)
         plus = isinstance(self, BM25Plus)
         return self._ctx.bm25_topk(self._index, terms, idf, qoff, self._params(), plus, k)
+
+    @staticmethod
+    def _k(k) -> int:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+            raise TypeError("k must be int, not %s" % type(k).__name__)
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1, not %d" % k)
+        return k
+
+    def search(self, queries: Sequence[str], k: int):
+        """(ids int64 [len(queries), k'], scores float64 [len(queries), k'], counts int64 [len(queries)]), k' = min(k, num_doc).
+        Document d matches query q when at least one word of q.split() occurs in d.  counts[q] is the number of matching documents
+        (it may exceed k; a repeated query word counts once).  Row q holds the best matching documents in top_k's order:
+        [i for i in np.argsort(-get_scores(queries)[q], kind="stable") if d_i matches][:k'] and their scores (original bits);
+        positions from counts[q] on hold id -1 and NaN (bits 0x7FF8000000000000).  Only the matching documents are scored, on the
+        GPU.  k' above 1024 raises _native.GzError (GZ_E_LIMIT)."""
+        k = self._k(k)
+        nq, terms, idf, qoff = self._queries(queries)
+        plus = isinstance(self, BM25Plus)
+        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k)
+
+    def count_matches(self, queries: Sequence[str]) -> np.ndarray:
+        """int64 [len(queries)]: the documents that hold at least one word of each query; for a query of one word, its df."""
+        _, terms, _, qoff = self._queries(queries)
+        return self._ctx.bm25_match_count(self._index, terms, qoff)
 
     def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
         """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].

@@ -245,6 +245,8 @@ int64_t gz_limit(int which);
  *   bm25_topk_chunk (1..2^30; 2^27)  BM25 top-k: doubles of score rows held in the context's workspace at a time (queries are
  *                              scored a chunk at a time, one row at least)
  *   bm25_topk_tile (0..4096; 0)  BM25 top-k: documents per workgroup of the first selection level (0: chosen per call)
+ *   bm25_search_chunk (1..2^30; 2^27)  BM25 search: doubles of candidate scores held in the context's workspace at a time (queries
+ *                              are marked, scored and ranked a chunk at a time, one row at least; the chunk's bitmap words obey it too)
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -392,6 +394,22 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          GZ_BM25_TOPK_MAX: GZ_E_LIMIT.  Nothing outside the [n_queries, k'] outputs is written.  The scores stay
  *                          in HBM (a chunk of queries at a time, switch bm25_topk_chunk); only ids and scores cross to the host.
  *   gz_bm25_topk_device    the same into doc_out_dev / score_out_dev (HBM): enqueued on the context's stream, gz_sync waits for it
+ *   gz_bm25_search         the matching documents of every query, ranked: document d MATCHES query q when it holds at least one of
+ *                          q's words (term ids >= 0; repeated words count once; this does not depend on params).  count_out[q]
+ *                          (int64) = the matching documents, which may exceed k.  Row q of doc_out / score_out [n_queries, k'],
+ *                          k' = min(k, n_docs): gz_bm25_topk's total order restricted to the matching documents -- with S the
+ *                          scores of gz_bm25_score, [i for i in np.argsort(-S[q], kind="stable") if d_i matches][:k'] and S[q] at
+ *                          those ids, original bits; positions behind count_out[q] hold id -1 and the NaN 0x7FF8000000000000.
+ *                          Query arguments and errors as gz_bm25_topk (k < 1: GZ_E_INVALID; k' above GZ_BM25_TOPK_MAX:
+ *                          GZ_E_LIMIT; GZ_E_NOMEM).  Nothing outside the [n_queries, k'] and [n_queries] outputs is written.
+ *                          The matching documents come from term-major postings, a derived structure the first search or match
+ *                          count builds on the device and later ones reuse; every successful append, removal or compaction
+ *                          drops it and the next search builds it again.  Only the matching documents are scored and ranked (a
+ *                          chunk of queries at a time, switch bm25_search_chunk).  On any error the index answers every call as
+ *                          before, whether or not the postings were built.
+ *   gz_bm25_search_device  the same with the three outputs in HBM: enqueued on the context's stream, gz_sync waits for it (the call
+ *                          itself waits for each chunk's counts, which size its workspace)
+ *   gz_bm25_match_count    count_out[q] of gz_bm25_search alone (host memory); for a query of one word it is the word's df
  *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
@@ -432,7 +450,7 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          bytes_cap < B: GZ_E_CAPACITY, nothing written.  term_off and bytes both NULL: GZ_E_INVALID.
  *   gz_bm25_footprint      host bookkeeping, no device work: out[0] = bytes of the text copy in use (what GZ_E_LIMIT of an append
  *                          counts), out[1] = terms held in the term table, dead ones included, out[2] = device bytes allocated
- *                          to the index's ten buffers, capacities included
+ *                          to the index's ten buffers, capacities included, and to its postings while they exist
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
@@ -451,6 +469,12 @@ int  gz_bm25_topk(gz_bm25 *index, const int32_t *terms, const double *idf, const
                   const double params[6], int32_t plus, int64_t k, int64_t *doc_out, double *score_out);
 int  gz_bm25_topk_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
                          const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev);
+int  gz_bm25_search(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                    const double params[6], int32_t plus, int64_t k, int64_t *doc_out, double *score_out, int64_t *count_out);
+int  gz_bm25_search_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                           const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev,
+                           int64_t *count_out_dev);
+int  gz_bm25_match_count(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int64_t *count_out);
 int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);

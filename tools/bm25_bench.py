@@ -1,12 +1,22 @@
 """BM25 index / scoring timings on the configs[2] corpus (genz_tokenize.ranking, csrc/gz_bm25.inc).
 
     python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--compact 10000] [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --search-only [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
   score_q{1,64,256}_ms scoring Q queries of 8 words into device memory (gz_bm25_score_device + gz_sync)
   topk_q{1,64,256}_k{10,1000}_ms  the k best documents of Q queries into device memory (gz_bm25_topk_device + gz_sync): scoring,
                        a chunk of queries at a time, and the selection levels
+Search (gz_bm25_search_device / gz_bm25_match_count; --search-only: the build, these rows and topk_q*_k10_ms alone, and with --out
+they are merged into the file's record instead of replacing it):
+  postings_build_ms    the first gz_bm25_match_count (one query of one absent word) on a freshly built index: the postings build plus
+                       the marking and counting of that one empty row (the index build is not timed)
+  search_q{1,64,256}_k10_ms        the 10 best MATCHING documents of the same Q queries into device memory, and the match counts
+                       (gz_bm25_search_device + gz_sync), after a warm call that has built the postings
+  search_rare_q{1,64,256}_k10_ms   the same for a second query set: 8 words each with 1 <= df <= N / 1000, drawn with a fixed seed
+  topk_rare_q{1,64,256}_k10_ms     gz_bm25_topk_device over the rare-word queries (top_k's time does not depend on the words)
+  match_fraction / match_fraction_rare   mean(count) / N over the 256 queries of each set
   ctor_ms              the Python constructor BM25(list of str): packing, host -> device, build, fieldLens, avgFieldLen
   topk_host_q256_k100_ms           BM25.top_k(256 queries, 100): ids and scores [256, 100] in host memory
   get_scores_host_q256_ms          BM25.get_scores(256 queries): the float64 [256, N] matrix in host memory
@@ -236,6 +246,51 @@ def compact_rows(ctx, res, n, k, reps):
         ctx.free(d)
 
 
+def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, reps):
+    """the search rows of the docstring; ix is the built index, terms / idf the 256 x 8 words of the tool's own queries"""
+    ts = []
+    qoff1 = np.array([0, 1], np.int64)
+    for _ in range(reps + 1):                                        # (the first is the warm-up)
+        fresh = ctx.bm25_build_device(d_text, d_off, n, nbytes)
+        t0 = time.perf_counter()
+        ctx.bm25_match_count(fresh, np.array([-1], np.int32), qoff1)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        ctx.bm25_destroy(fresh)
+    res["postings_build_ms"], res["postings_build_all_ms"] = float(np.median(ts[1:])), [round(x, 3) for x in ts[1:]]
+    # the rare-word set: 8 words each with 1 <= df <= N / 1000
+    off, data, df = ctx.bm25_terms(ix)
+    rare = np.flatnonzero((df >= 1) & (df <= max(1, n // 1000)))
+    pick = np.random.default_rng(2).choice(rare, size=256 * 8, replace=True)
+    raw = data.tobytes()
+    rb, ro = pack([raw[int(off[i]):int(off[i + 1])].decode("utf-8", "surrogatepass") for i in pick])
+    rterms, rdf = ctx.bm25_lookup(ix, rb, ro)
+    assert (rterms >= 0).all() and np.array_equal(rdf, df[pick])
+    ridf = np.array([np.log(1+(n-int(d)+0.5)/(int(d)+0.5)) for d in rdf])
+    res["rare_df_max"], res["rare_df_mean"] = int(rdf.max()), round(float(rdf.mean()), 1)
+    d_cnt = ctx.alloc(256 * 8)
+    for name, tt, ii in (("", terms, idf), ("rare_", rterms, ridf)):
+        for q in (1, 64, 256):
+            qoff = np.arange(q + 1, dtype=np.int64) * 8
+
+            def search():
+                ctx.bm25_search(ix, tt[:8 * q], ii[:8 * q], qoff, params, False, 10, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt)
+                ctx.sync()
+            key = "search_%sq%d_k10" % (name, q)
+            res[key + "_ms"], res[key + "_all_ms"] = median_ms(search, reps)
+            if name:
+                def topk():
+                    ctx.bm25_topk(ix, tt[:8 * q], ii[:8 * q], qoff, params, False, 10, d_ids=d_ids, d_scores=d_sc)
+                    ctx.sync()
+                res["topk_rare_q%d_k10_ms" % q], res["topk_rare_q%d_k10_all_ms" % q] = median_ms(topk, reps)
+        cnt = np.empty(256, np.int64)
+        ctx.d2h(cnt, d_cnt)
+        res["match_fraction" + ("_rare" if name else "")] = float(cnt.mean() / n)
+    ctx.free(d_cnt)
+    for q in (1, 64, 256):
+        res["search_q%d_k10_over_topk" % q] = round(res["search_q%d_k10_ms" % q] / res["topk_q%d_k10_ms" % q], 3)
+        res["search_rare_q%d_k10_over_topk" % q] = round(res["search_rare_q%d_k10_ms" % q] / res["topk_rare_q%d_k10_ms" % q], 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -249,7 +304,10 @@ def main():
     ap.add_argument("--remove-only", action="store_true", help="only the remove rows (a trace of their kernels)")
     ap.add_argument("--compact", type=int, default=10_000, help="documents removed before the compact rows (0: skip them)")
     ap.add_argument("--compact-only", action="store_true", help="only the compact rows; with --out they are merged into the file")
+    ap.add_argument("--search-only", action="store_true", help="only the build, top-k (k = 10) and search rows; with --out they are merged into the file")
     a = ap.parse_args()
+    if a.search_only:
+        a.remove = a.compact = a.append = 0
     t, o, _ = corpus.config_corpus(2, n_docs=a.docs)
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
@@ -302,31 +360,44 @@ def main():
     terms, df = ctx.bm25_lookup(ix, wb, wo)
     idf = np.array([np.log(1+(n-int(d)+0.5)/(int(d)+0.5)) for d in df])
     params = [2.2, 1.2, 0.25, 0.75, avg, 0.0]
-    d_out = ctx.alloc(256 * n * 8)
-    for q in (1, 64, 256):
+    d_out = ctx.alloc(256 * n * 8) if not a.search_only else None
+    for q in (1, 64, 256) if not a.search_only else ():
         qoff = np.arange(q + 1, dtype=np.int64) * 8
 
         def score():
             ctx.bm25_score(ix, terms[:8 * q], idf[:8 * q], qoff, params, False, d_out=d_out)
             ctx.sync()
         res["score_q%d_ms" % q], res["score_q%d_all_ms" % q] = median_ms(score, a.reps)
-    res["score_q256_write_GBps"] = round(256 * n * 8 / res["score_q256_ms"] / 1e6, 1)
-    ctx.free(d_out)
+    if not a.search_only:
+        res["score_q256_write_GBps"] = round(256 * n * 8 / res["score_q256_ms"] / 1e6, 1)
+        ctx.free(d_out)
     d_ids, d_sc = ctx.alloc(256 * 1000 * 8), ctx.alloc(256 * 1000 * 8)
     for q in (1, 64, 256):
         qoff = np.arange(q + 1, dtype=np.int64) * 8
-        for k in (10, 1000):
+        for k in (10, 1000) if not a.search_only else (10,):
             def topk():
                 ctx.bm25_topk(ix, terms[:8 * q], idf[:8 * q], qoff, params, False, k, d_ids=d_ids, d_scores=d_sc)
                 ctx.sync()
             res["topk_q%d_k%d_ms" % (q, k)], res["topk_q%d_k%d_all_ms" % (q, k)] = median_ms(topk, a.reps)
-    for k in (10, 1000):
+    search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, a.reps)
+    for k in (10, 1000) if not a.search_only else ():
         res["topk_q256_k%d_over_score_pct" % k] = round(100 * (res["topk_q256_k%d_ms" % k] / res["score_q256_ms"] - 1), 1)
     ctx.free(d_ids)
     ctx.free(d_sc)
     ctx.bm25_destroy(ix)
     ctx.free(d_text)
     ctx.free(d_off)
+    if a.search_only:
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith(("search_", "postings_", "match_fraction", "topk_rare_", "rare_df_"))})
+            old["search_rows_run"] = dict(docs=n, reps=a.reps, build_device_ms=res["build_device_ms"],
+                                          **{k: v for k, v in res.items() if k.startswith("topk_q") and k.endswith("_k10_ms")})
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
 
     docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n)]
     holder = []
