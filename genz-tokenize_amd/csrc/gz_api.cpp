@@ -968,6 +968,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_P_CUR,                                                                   // the postings' cursors (bm25_postings)
        BMW_S_BM, BMW_S_WROW, BMW_S_WNS, BMW_S_WSOFF, BMW_S_TCNT, BMW_S_TBASE, BMW_S_CNT,     // a search chunk (bm25_search_locked)
        BMW_S_CAND, BMW_S_CSC, BMW_S_POS, BMW_S_PSC,
+       BMW_S_XTERM, BMW_S_XOFF,                                                     // the excluded terms of a boolean search
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1624,15 +1625,31 @@ int bm25_match_args(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int6
     return GZ_OK;
 }
 
+// what the _bool entry points take on top: the mode, and the excluded terms of every query
+int bm25_bool_args(gz_bm25* ix, int64_t nq, int32_t mode, const int32_t* xterm, const int64_t* xoff)
+{
+    gz_ctx* c = ix->c;
+    if (mode != GZ_BM25_MATCH_ANY && mode != GZ_BM25_MATCH_ALL) return fail(c, GZ_E_INVALID, "match mode %d: GZ_BM25_MATCH_ANY or GZ_BM25_MATCH_ALL", mode);
+    if (!xoff) return GZ_OK;
+    for (int64_t q = 0; q < nq; ++q) if (xoff[q + 1] < xoff[q]) return fail(c, GZ_E_INVALID, "excluded-term offsets must not decrease");
+    if (xoff[nq] > xoff[0] && !xterm) return fail(c, GZ_E_INVALID, "excluded-term offsets without terms");
+    for (int64_t j = xoff[0]; j < xoff[nq]; ++j)
+        if (xterm[j] < -1 || xterm[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "excluded term id %d out of range", xterm[j]);
+    return GZ_OK;
+}
+
 // A chunk of queries at a time (its bitmaps hold at most bm25_search_chunk words, one row at least, at most 65535 rows): mark the
 // documents of every query word's postings in the row's bitmap, count and rank the bits, and read the counts back -- they size
 // what follows.  Then, for runs of rows whose candidate scores (rows x the largest count among them) stay within
 // bm25_search_chunk doubles, one row at least: the candidates in ascending id, their scores, gz_launch_topk over them and the
 // positions mapped back to document ids.  Outputs into doc_dev / score_dev / cnt_dev, or into host memory after every run
 // (doc_dev null).  count_only: nothing behind the counts (idf, P, the document outputs are not read).
+// mode GZ_BM25_MATCH_ALL: only the driver of every row is marked (GZ_BM25_SR_DRIVER) and the filter stage clears the documents
+// that lack a word of the row; xoff (null: none) / xterm: the filter clears the documents that hold an excluded term.  With mode
+// GZ_BM25_MATCH_ANY and no excluded term, neither is launched and nothing more is allocated.
 int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
                        int64_t kk, bool count_only, int64_t* doc_dev, double* score_dev, int64_t* cnt_dev, int64_t* doc_host, double* score_host,
-                       int64_t* cnt_host)
+                       int64_t* cnt_host, int32_t mode = GZ_BM25_MATCH_ANY, const int32_t* xterm = nullptr, const int64_t* xoff = nullptr)
 {
     gz_ctx* c = ix->c;
     DBuf* w = c->w_bm;
@@ -1649,6 +1666,16 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
     if ((rc = bm25_postings(ix))) return rc;
     GzBm25Search A{};
     if ((rc = bm25_query_in(ix, terms, idf, qoff, nq, P, plus, A.S))) return rc;
+    const int64_t nx = xoff ? xoff[nq] - xoff[0] : 0;
+    if (nx > 0) {
+        if ((rc = bm_alloc(c, w[BMW_S_XTERM], (size_t)nx * 4)) || (rc = bm_alloc(c, w[BMW_S_XOFF], (size_t)(nq + 1) * 8)) ||
+            (rc = copy_in(c, w[BMW_S_XTERM].p, xterm + xoff[0], (size_t)nx * 4, s)) ||
+            (rc = copy_in(c, w[BMW_S_XOFF].p, xoff, (size_t)(nq + 1) * 8, s)))
+            return rc;
+        A.xterm = (const int32_t*)w[BMW_S_XTERM].p - xoff[0];
+    }
+    A.mode = mode;
+    const int64_t* xoff_dev = nx > 0 ? (const int64_t*)w[BMW_S_XOFF].p : nullptr;
     const int64_t chunk = c->opt.bm25_search_chunk;
     const int64_t W64 = (N + 63) / 64, n_tiles = (W64 + GZ_SEARCH_TILE - 1) / GZ_SEARCH_TILE;
     const int64_t rmax = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(chunk / W64, 1), 65535), nq);
@@ -1675,8 +1702,11 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
         HIPCHK(c, hipMemsetAsync(A.bm, 0, (size_t)(rows * W64) * 8, s));
         if (A.n_qw > 0) {
             gz_launch_bm25_search(GZ_BM25_SR_WORDS, A, rows, s);
+            if (mode == GZ_BM25_MATCH_ALL) gz_launch_bm25_search(GZ_BM25_SR_DRIVER, A, rows, s);
             if ((rc = bm_scan(c, A.wns, A.n_qw, A.wsoff))) return rc;
             gz_launch_bm25_search(GZ_BM25_SR_MARK, A, rows, s);
+            A.xoff = xoff_dev && xoff[q0 + rows] > xoff[q0] ? xoff_dev + q0 : nullptr;
+            if (mode == GZ_BM25_MATCH_ALL || A.xoff) gz_launch_bm25_search(GZ_BM25_SR_FILTER, A, rows, s);
         }
         gz_launch_bm25_search(GZ_BM25_SR_COUNT, A, rows, s);
         gz_launch_bm25_search(GZ_BM25_SR_ROWS, A, rows, s);
@@ -3545,6 +3575,42 @@ try {
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_bool(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                        int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off, int64_t* doc_out, double* score_out,
+                        int64_t* count_out)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out && score_out ? doc_out : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    if (!count_out && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, nullptr, nullptr, nullptr, doc_out, score_out, count_out,
+                              mode, ex_terms, ex_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_bool_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                               const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off,
+                               int64_t* doc_out_dev, double* score_out_dev, int64_t* count_out_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out_dev && score_out_dev ? doc_out_dev : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    if (!count_out_dev && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, doc_out_dev, score_out_dev, count_out_dev, nullptr, nullptr,
+                              nullptr, mode, ex_terms, ex_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_match_count_bool(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, int32_t mode, const int32_t* ex_terms,
+                             const int64_t* ex_off, int64_t* count_out)
+try {
+    int rc = bm25_match_args(ix, terms, query_off, n_queries, count_out);
+    if (rc || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
+                              mode, ex_terms, ex_off);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 void gz_bm25_destroy(gz_bm25* ix)

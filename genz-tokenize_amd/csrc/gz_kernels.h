@@ -296,6 +296,10 @@ struct GzBm25Search {
     // the chunk: `rows` queries, row r = words qoff[r] .. qoff[r + 1] (absolute indices into qterm / qidf), n_qw words in all
     const int32_t* qterm; const double* qidf; const int64_t* qoff;
     int64_t rows, n_qw;
+    // mode 1 ("all"): a document matches when it holds every word of the row (0: at least one); xoff non-null: and none of the
+    // row's excluded terms xterm[xoff[r]] .. xterm[xoff[r + 1]] (absolute indices; -1 is skipped)
+    int32_t mode;
+    const int32_t* xterm; const int64_t* xoff;
     int64_t w64;                          // bitmap words per row = ceil(n_docs / 64)
     unsigned long long* bm;               // [rows, w64] bit d of row r: document d matches query r (cleared by the caller)
     uint32_t* wrow; uint32_t* wns;        // [n_qw] row of every word, slices of its postings list
@@ -312,6 +316,7 @@ struct GzBm25Search {
     int64_t k2, kk;                       // k2 = min(kk, M)
     int64_t* doc_out; double* score_out;  // [., kk]: -1 / NaN behind the row's count
 };
-enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_BM25_SR_CAND, GZ_BM25_SR_SCORE, GZ_BM25_SR_OUT };
-// rows: of the chunk (WORDS, MARK, COUNT, ROWS), else of the launch (from row0)
+enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_BM25_SR_CAND, GZ_BM25_SR_SCORE, GZ_BM25_SR_OUT,
+       GZ_BM25_SR_DRIVER, GZ_BM25_SR_FILTER };
+// rows: of the chunk (WORDS, DRIVER, MARK, FILTER, COUNT, ROWS), else of the launch (from row0)
 void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStream_t s);

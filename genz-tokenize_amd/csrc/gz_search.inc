@@ -1,5 +1,6 @@
-// gz_search.inc -- BM25 search (gz_bm25_search[_device], gz_bm25_match_count): the documents that hold at least one word of a
-// query, counted, scored and ranked; included by gz_kernels.hip after gz_topk.inc.
+// gz_search.inc -- BM25 search (gz_bm25_search[_device], gz_bm25_match_count and their _bool forms): the documents that match a
+// query, counted, scored and ranked; included by gz_kernels.hip after gz_topk.inc.  A document matches when it holds at least one
+// word of the query (mode "any") or every word of it (mode "all"), and none of the query's excluded words.
 //
 // Postings, a term-major view of the doc-major (term, count) entries: poff[T + 1] = exclusive scan of df over every table term
 // (a dead term's list is empty), pdoc[n_ent] = the documents of every term.
@@ -7,10 +8,18 @@
 // A query chunk (rows = queries, a bitmap of ceil(N / 64) 64-bit words per row, cleared by the caller):
 //   gz_bm25_sr_words_kernel a thread per query word: its row, and the slices (SR_SLICE postings each) its list is cut into
 //                           (term -1: none); the slice counts are scanned (gz_bm25_scan_*)
+//   gz_bm25_sr_driver_kernel (mode "all" only, before the scan) a thread per row: only the row's DRIVER keeps its slices -- the word
+//                           with the shortest postings list, ties to the first; a row with a term -1 keeps none.  Every match
+//                           holds the driver, so its list is a superset of the answer and the filter makes it exact
 //   gz_bm25_sr_mark_kernel  workgroups stride over ALL slices of the chunk (a list of a million documents is hundreds of slices on
 //                           as many workgroups, a list of three is one slice; no workgroup is spent on a slice that does not exist):
 //                           bit d of the row's bitmap is set for every document d of the slice -- a plain load first, the 64-bit
 //                           atomicOr only where the bit is still clear
+//   gz_bm25_sr_filter_kernel (mode "all" or excluded words only) a thread per 64-bit word of a row's bitmap: a zero word costs one
+//                           load; for every set bit d, d's signature and then the pair table (bm_pair_count, the score kernel's
+//                           probe) tell whether d holds a term: the bit goes when a required term is absent (mode "all") or an
+//                           excluded one present.  One owner per word, the marking has finished: a plain 64-bit store, only of a
+//                           word that changed
 //   gz_bm25_sr_count_kernel popcount of every tile (SR_TILE bitmap words) of every row
 //   gz_bm25_sr_rows_kernel  a workgroup per row: exclusive scan of its tiles' counts, count[row] = their sum
 //   gz_bm25_sr_cand_kernel  the set bits of a tile, in ASCENDING document id, into the row's candidate list (stride M = the largest
@@ -151,6 +160,74 @@ __global__ __launch_bounds__(256) void gz_bm25_sr_cand_kernel(GzBm25Search A)
     }
 }
 
+// occurrences of term t (>= 0) in document d: sg = d's four signature words, pkey = d << 32.  The signature bit first, the pair
+// table only where it is set; 0 = d does not hold t (a pair in the table has a count of 1 at least)
+__device__ __forceinline__ uint32_t bm_pair_count(const GzBm25Score& S, const unsigned long long (&sg)[4], unsigned long long pkey, uint32_t t)
+{
+    const uint32_t bit = bm_sig_bit(t);
+    const unsigned long long word = bit < 64 ? sg[0] : bit < 128 ? sg[1] : bit < 192 ? sg[2] : sg[3];
+    if (!((word >> (bit & 63u)) & 1ull)) return 0;
+    const unsigned long long key = (pkey | t) + 1ull;
+    unsigned long long sl = bm_mix64(key) & S.pmask;
+    for (;;) {
+        const unsigned long long kk = S.ptab[sl].key;
+        if (kk == key) return S.ptab[sl].a;
+        if (kk == 0ull) return 0;
+        sl = (sl + 1) & S.pmask;
+    }
+}
+
+__global__ __launch_bounds__(256) void gz_bm25_sr_driver_kernel(GzBm25Search A)
+{
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= A.rows) return;
+    const int64_t j0 = A.qoff[row], j1 = A.qoff[row + 1], base = A.qoff[0];
+    int64_t best = -1;
+    uint32_t len = 0;
+    for (int64_t j = j0; j < j1; ++j) {
+        const int32_t t = A.qterm[j];
+        if (t < 0 || (int64_t)t >= A.n_terms) { best = -1; break; }       // a word no document holds: nothing matches
+        const uint32_t n = A.poff[t + 1] - A.poff[t];
+        if (best < 0 || n < len) { best = j; len = n; }
+    }
+    for (int64_t j = j0; j < j1; ++j)
+        if (j != best) A.wns[j - base] = 0;
+}
+
+__global__ __launch_bounds__(256) void gz_bm25_sr_filter_kernel(GzBm25Search A)
+{
+    const GzBm25Score& S = A.S;
+    const int64_t row = blockIdx.y, w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= A.w64) return;
+    unsigned long long* at = A.bm + row * A.w64 + w;
+    const unsigned long long x0 = *at;
+    if (!x0) return;
+    // (uniform: the workgroup's threads share the row)
+    const int64_t r0 = A.qoff[row], r1 = A.mode == 1 ? A.qoff[row + 1] : r0;
+    const int64_t e0 = A.xoff ? A.xoff[row] : 0, e1 = A.xoff ? A.xoff[row + 1] : 0;
+    unsigned long long x = x0, keep = x0;
+    while (x) {
+        const int b = __ffsll(x) - 1;
+        x &= x - 1;
+        const int64_t d = w * 64 + b;
+        bool ok = d < S.n_docs;
+        if (ok) {
+            const unsigned long long sg[4] = {S.sig[d * 4], S.sig[d * 4 + 1], S.sig[d * 4 + 2], S.sig[d * 4 + 3]};
+            const unsigned long long pkey = (unsigned long long)d << 32;
+            for (int64_t j = r0; ok && j < r1; ++j) {
+                const int32_t t = A.qterm[j];
+                ok = t >= 0 && bm_pair_count(S, sg, pkey, (uint32_t)t) != 0;
+            }
+            for (int64_t j = e0; ok && j < e1; ++j) {
+                const int32_t t = A.xterm[j];
+                if (t >= 0) ok = bm_pair_count(S, sg, pkey, (uint32_t)t) == 0;
+            }
+        }
+        if (!ok) keep &= ~(1ull << b);
+    }
+    if (keep != x0) *at = keep;
+}
+
 __global__ __launch_bounds__(256) void gz_bm25_sr_score_kernel(GzBm25Search A)
 {
     const GzBm25Score& S = A.S;                               // (the index's arrays and the parameters; the query arrays are A's)
@@ -168,21 +245,7 @@ __global__ __launch_bounds__(256) void gz_bm25_sr_score_kernel(GzBm25Search A)
     const int64_t j1 = A.qoff[row + 1];
     for (int64_t j = A.qoff[row]; j < j1; ++j) {              // (uniform: the workgroup's threads share the row)
         const int32_t t = A.qterm[j];
-        uint32_t f = 0;
-        if (t >= 0) {
-            const uint32_t bit = bm_sig_bit((uint32_t)t);
-            const unsigned long long word = bit < 64 ? sg[0] : bit < 128 ? sg[1] : bit < 192 ? sg[2] : sg[3];
-            if ((word >> (bit & 63u)) & 1ull) {
-                const unsigned long long key = (pkey | (uint32_t)t) + 1ull;
-                unsigned long long sl = bm_mix64(key) & S.pmask;
-                for (;;) {
-                    const unsigned long long kk = S.ptab[sl].key;
-                    if (kk == key) { f = S.ptab[sl].a; break; }
-                    if (kk == 0ull) break;
-                    sl = (sl + 1) & S.pmask;
-                }
-            }
-        }
+        const uint32_t f = t >= 0 ? bm_pair_count(S, sg, pkey, (uint32_t)t) : 0u;
         score = bm_word_score(S, score, f, K, t0, A.qidf[j]);
     }
     *out = score;
@@ -222,6 +285,8 @@ void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStr
         if (A.n_qw > 0) hipLaunchKernelGGL(gz_bm25_sr_mark_kernel, dim3((unsigned)(most < 2048 ? most : 2048)), dim3(256), 0, s, A);
         break;
     }
+    case GZ_BM25_SR_DRIVER: if (A.n_qw > 0) hipLaunchKernelGGL(gz_bm25_sr_driver_kernel, dim3(bm_grid(rows, 256)), dim3(256), 0, s, A); break;
+    case GZ_BM25_SR_FILTER: hipLaunchKernelGGL(gz_bm25_sr_filter_kernel, dim3(bm_grid(A.w64, 256), (unsigned)rows), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_COUNT: hipLaunchKernelGGL(gz_bm25_sr_count_kernel, dim3((unsigned)A.n_tiles, (unsigned)rows), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_ROWS: hipLaunchKernelGGL(gz_bm25_sr_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_CAND: if (A.M > 0) hipLaunchKernelGGL(gz_bm25_sr_cand_kernel, dim3((unsigned)A.n_tiles, (unsigned)rows), dim3(256), 0, s, A); break;

@@ -35,6 +35,7 @@ SYMBOLS = [
     "gz_bm25_append", "gz_bm25_append_device", "gz_bm25_remove", "gz_bm25_remove_device",
     "gz_bm25_compact", "gz_bm25_terms", "gz_bm25_footprint",
     "gz_bm25_search", "gz_bm25_search_device", "gz_bm25_match_count",
+    "gz_bm25_search_bool", "gz_bm25_search_bool_device", "gz_bm25_match_count_bool",
 ]
 
 _lib = None
@@ -140,6 +141,10 @@ def load_library():
         L.gz_bm25_search.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, vp]
         L.gz_bm25_search_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, vp, vp, vp]
         L.gz_bm25_match_count.argtypes = [vp, vp, vp, i64, vp]
+    if hasattr(L, "gz_bm25_search_bool"):
+        L.gz_bm25_search_bool.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+        L.gz_bm25_search_bool_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+        L.gz_bm25_match_count_bool.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -603,9 +608,12 @@ class Context:
         return ids, scores
 
     def bm25_search(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool, k: int,
-                    d_ids: int | None = None, d_scores: int | None = None, d_counts: int | None = None):
+                    d_ids: int | None = None, d_scores: int | None = None, d_counts: int | None = None,
+                    mode: int = 0, ex_terms=None, ex_off=None):
         """(ids int64 [Q, k'], scores float64 [Q, k'], counts int64 [Q]) with k' = min(k, documents): the best MATCHING documents of
-        every query (those that hold at least one of its words) and how many match; positions behind a row's count hold -1 / NaN.
+        every query and how many match; positions behind a row's count hold -1 / NaN.  A document matches when it holds at least
+        one of the query's words (mode 0) or every one of them (mode 1), and none of the terms ex_terms[ex_off[q]:ex_off[q + 1]]
+        (ex_off None: no exclusions).  With mode 0 and ex_off None the call is gz_bm25_search[_device], else gz_bm25_search_bool[_device].
         With d_ids / d_scores / d_counts (device pointers, all three): enqueued into them, sync() waits."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         idf = np.ascontiguousarray(idf, dtype=np.float64)
@@ -615,23 +623,46 @@ class Context:
         nq = len(query_off) - 1
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
                 1 if plus else 0, int(k)]
+        plain = mode == 0 and ex_off is None
+        if not plain:
+            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+            args += [int(mode)] + ex
         if d_ids is not None or d_scores is not None or d_counts is not None:
-            self._check(self.lib.gz_bm25_search_device(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
+            fn = self.lib.gz_bm25_search_device if plain else self.lib.gz_bm25_search_bool_device
+            self._check(fn(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
             return None
         kk = max(0, min(int(k), self.bm25_info(index)[0]))
         ids = np.empty((nq, kk), dtype=np.int64)
         scores = np.empty((nq, kk), dtype=np.float64)
         counts = np.zeros(max(nq, 1), dtype=np.int64)
-        self._check(self.lib.gz_bm25_search(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
+        fn = self.lib.gz_bm25_search if plain else self.lib.gz_bm25_search_bool
+        self._check(fn(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
         return ids, scores, counts[:nq]
 
-    def bm25_match_count(self, index: int, terms: np.ndarray, query_off: np.ndarray) -> np.ndarray:
-        """int64 [Q]: the documents that hold at least one word of each query."""
+    @staticmethod
+    def _bm25_exclusions(nq: int, ex_terms, ex_off):
+        """the excluded terms of a boolean search as contiguous arrays (kept alive by the caller) and their two C arguments"""
+        if ex_off is None:
+            return None, None, [None, None]
+        ex_off = np.ascontiguousarray(ex_off, dtype=np.int64)
+        assert ex_off.shape == (nq + 1,)
+        ex_terms = np.ascontiguousarray(ex_terms if ex_terms is not None else [], dtype=np.int32)
+        return ex_terms, ex_off, [_ptr(ex_terms) if len(ex_terms) else None, _ptr(ex_off)]
+
+    def bm25_match_count(self, index: int, terms: np.ndarray, query_off: np.ndarray, mode: int = 0, ex_terms=None,
+                         ex_off=None) -> np.ndarray:
+        """int64 [Q]: the documents that match each query -- counts of bm25_search alone (mode, ex_terms, ex_off as there; with
+        mode 0 and ex_off None the call is gz_bm25_match_count, else gz_bm25_match_count_bool)."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         query_off = np.ascontiguousarray(query_off, dtype=np.int64)
         nq = len(query_off) - 1
         counts = np.zeros(max(nq, 1), dtype=np.int64)
-        self._check(self.lib.gz_bm25_match_count(C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq, _ptr(counts)))
+        args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq]
+        if mode == 0 and ex_off is None:
+            self._check(self.lib.gz_bm25_match_count(*args, _ptr(counts)))
+        else:
+            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+            self._check(self.lib.gz_bm25_match_count_bool(*args, int(mode), *ex, _ptr(counts)))
         return counts[:nq]
 
     def exchange_select(self, back: int):

@@ -16,6 +16,12 @@ rare words does not pay for the whole corpus.  The ranked documents are exactly 
 out; unlike `top_k`, a row is never filled up with documents that hold none of the query's words (with BM25Plus those have positive
 scores too): unfilled positions hold id -1 and NaN.
 
+Boolean search: `search(queries, k, match="all")` keeps only the documents that hold EVERY word of the query, and
+`exclude=[...]` (one string of words per query, with either match) drops the documents that hold any of those words; both also on
+`count_matches`.  The device marks only the postings of each query's rarest word and a filter kernel clears, from those documents,
+the ones that lack a word or hold an excluded one (gz_bm25_search_bool).  Scores, order and padding are those of `search`; excluded
+words never enter a score.  With the defaults the call is the plain search, unchanged.
+
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
@@ -239,22 +245,64 @@ class BM25:
             raise ValueError("k must be >= 1, not %d" % k)
         return k
 
-    def search(self, queries: Sequence[str], k: int):
+    @staticmethod
+    def _match(match) -> int:
+        if not isinstance(match, str):
+            raise TypeError("match must be str, not %s" % type(match).__name__)
+        if match not in ("any", "all"):
+            raise ValueError('match must be "any" or "all", not %r' % match)
+        return 1 if match == "all" else 0
+
+    def _exclusions(self, exclude, nq: int):
+        """str.split() of every exclude[q] -> (term ids, int64 offsets); (None, None) for exclude=None.  A word no document holds
+        has term -1, which the search ignores."""
+        split = [x.split() for x in exclude]
+        xoff = np.zeros(nq + 1, dtype=np.int64)
+        if split:
+            np.cumsum([len(w) for w in split], out=xoff[1:])
+        words = [w for ws in split for w in ws]
+        terms = self._lookup(words)[0] if words else np.zeros(0, np.int32)
+        return terms, xoff
+
+    def _bool_args(self, queries, match, exclude):
+        """validation of search / count_matches, all of it before any native call -> (queries, mode, exclude)"""
+        mode = self._match(match)
+        queries = _strings(queries, "queries")
+        if exclude is not None:
+            exclude = _strings(exclude, "exclude")
+            if len(exclude) != len(queries):
+                raise ValueError("exclude has %d items for %d queries" % (len(exclude), len(queries)))
+        return queries, mode, exclude
+
+    def search(self, queries: Sequence[str], k: int, match: str = "any", exclude: Optional[Sequence[str]] = None):
         """(ids int64 [len(queries), k'], scores float64 [len(queries), k'], counts int64 [len(queries)]), k' = min(k, num_doc).
-        Document d matches query q when at least one word of q.split() occurs in d.  counts[q] is the number of matching documents
+        With R = set(queries[q].split()), X = set(exclude[q].split()) (empty for exclude=None) and W(d) the words of document d:
+        match="any": d matches q iff R & W(d) and not X & W(d); match="all": d matches iff R and R <= W(d) and not X & W(d) (a query
+        without words, or with a word that no document holds, matches nothing).  A word both in R and in X excludes every document
+        that holds it.  Excluded words never enter a score or an idf.  counts[q] is the number of matching documents
         (it may exceed k; a repeated query word counts once).  Row q holds the best matching documents in top_k's order:
         [i for i in np.argsort(-get_scores(queries)[q], kind="stable") if d_i matches][:k'] and their scores (original bits);
         positions from counts[q] on hold id -1 and NaN (bits 0x7FF8000000000000).  Only the matching documents are scored, on the
-        GPU.  k' above 1024 raises _native.GzError (GZ_E_LIMIT)."""
+        GPU; with match="all" only the documents of each query's rarest word are looked at.  k' above 1024 raises
+        _native.GzError (GZ_E_LIMIT).  exclude: None or one str per query (ValueError for another length)."""
         k = self._k(k)
+        queries, mode, exclude = self._bool_args(queries, match, exclude)
         nq, terms, idf, qoff = self._queries(queries)
         plus = isinstance(self, BM25Plus)
-        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k)
+        if mode == 0 and exclude is None:
+            return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k)
+        xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
+        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff)
 
-    def count_matches(self, queries: Sequence[str]) -> np.ndarray:
-        """int64 [len(queries)]: the documents that hold at least one word of each query; for a query of one word, its df."""
-        _, terms, _, qoff = self._queries(queries)
-        return self._ctx.bm25_match_count(self._index, terms, qoff)
+    def count_matches(self, queries: Sequence[str], match: str = "any", exclude: Optional[Sequence[str]] = None) -> np.ndarray:
+        """int64 [len(queries)]: counts of search(queries, k, match, exclude) alone.  With the defaults: the documents that hold at
+        least one word of each query; for a query of one word, its df."""
+        queries, mode, exclude = self._bool_args(queries, match, exclude)
+        nq, terms, _, qoff = self._queries(queries)
+        if mode == 0 and exclude is None:
+            return self._ctx.bm25_match_count(self._index, terms, qoff)
+        xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
+        return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
 
     def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
         """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].

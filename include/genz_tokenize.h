@@ -410,6 +410,25 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *   gz_bm25_search_device  the same with the three outputs in HBM: enqueued on the context's stream, gz_sync waits for it (the call
  *                          itself waits for each chunk's counts, which size its workspace)
  *   gz_bm25_match_count    count_out[q] of gz_bm25_search alone (host memory); for a query of one word it is the word's df
+ *   gz_bm25_search_bool    gz_bm25_search with another notion of a match.  With R = the distinct terms of query q, X = the distinct
+ *                          terms ex_terms[ex_off[q] .. ex_off[q + 1]) (ids as gz_bm25_lookup answers them; -1 is ignored; ex_off
+ *                          NULL: X is empty) and W(d) = the terms of document d:
+ *                            mode GZ_BM25_MATCH_ANY: d matches iff R and W(d) share a term, and X and W(d) share none;
+ *                            mode GZ_BM25_MATCH_ALL: d matches iff R is not empty, every term of R is in W(d), and X and W(d)
+ *                            share none -- a query without words matches nothing, and so does one with a word that no document
+ *                            holds (term -1).
+ *                          A term both in R and in X excludes every document that holds it.  Repeated words count once for
+ *                          matching (and as often as they occur in the scores S).  Excluded terms never enter a score: S, the
+ *                          order, count_out, the rows and their -1 / NaN padding are gz_bm25_search's with this set of matching
+ *                          documents.  GZ_E_INVALID: a mode other than the two, an excluded id outside [-1, n_terms), ex_off
+ *                          (n_queries + 1 offsets into ex_terms) decreasing, a non-empty range with ex_terms NULL; k and every
+ *                          other error as gz_bm25_search.  On any error the index answers every call as before.  In mode ALL only
+ *                          the postings of each query's rarest word are marked; a filter stage then clears, from the marked
+ *                          documents, those that lack a required term or hold an excluded one (signature, then pair table),
+ *                          and everything behind it is gz_bm25_search's.  With mode ANY and no excluded term the work is exactly
+ *                          gz_bm25_search's.
+ *   gz_bm25_search_bool_device  the same with the three outputs in HBM, as gz_bm25_search_device
+ *   gz_bm25_match_count_bool    count_out[q] of gz_bm25_search_bool alone (host memory)
  *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
@@ -454,6 +473,8 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
+#define GZ_BM25_MATCH_ANY 0
+#define GZ_BM25_MATCH_ALL 1
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
@@ -475,6 +496,14 @@ int  gz_bm25_search_device(gz_bm25 *index, const int32_t *terms, const double *i
                            const double params[6], int32_t plus, int64_t k, int64_t *doc_out_dev, double *score_out_dev,
                            int64_t *count_out_dev);
 int  gz_bm25_match_count(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int64_t *count_out);
+int  gz_bm25_search_bool(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                         const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms, const int64_t *ex_off,
+                         int64_t *doc_out, double *score_out, int64_t *count_out);
+int  gz_bm25_search_bool_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                                const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms,
+                                const int64_t *ex_off, int64_t *doc_out_dev, double *score_out_dev, int64_t *count_out_dev);
+int  gz_bm25_match_count_bool(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
+                              const int32_t *ex_terms, const int64_t *ex_off, int64_t *count_out);
 int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);

@@ -17,6 +17,12 @@ they are merged into the file's record instead of replacing it):
   search_rare_q{1,64,256}_k10_ms   the same for a second query set: 8 words each with 1 <= df <= N / 1000, drawn with a fixed seed
   topk_rare_q{1,64,256}_k10_ms     gz_bm25_topk_device over the rare-word queries (top_k's time does not depend on the words)
   match_fraction / match_fraction_rare   mean(count) / N over the 256 queries of each set
+  search_drawn_q{1,64,256}_k10_ms  the same for a third query set, "drawn": 256 queries of 2-4 distinct words, each query's words taken
+                       from one document (fixed seed), mode "any": gz_bm25_search_device, the path of the rows above
+  search_all_drawn_q{1,64,256}_k10_ms  the drawn queries in mode "all" (gz_bm25_search_bool_device, GZ_BM25_MATCH_ALL): every word must
+                       occur.  The two are timed in the same loop, alternating, after a warm call of each; the spread of the "any"
+                       row's own repetitions (search_drawn_*_all_ms) is the margin below which a difference is none
+  match_fraction_drawn / match_fraction_all_drawn   mean(count) / N over the 256 drawn queries, modes "any" and "all"
   ctor_ms              the Python constructor BM25(list of str): packing, host -> device, build, fieldLens, avgFieldLen
   topk_host_q256_k100_ms           BM25.top_k(256 queries, 100): ids and scores [256, 100] in host memory
   get_scores_host_q256_ms          BM25.get_scores(256 queries): the float64 [256, N] matrix in host memory
@@ -246,8 +252,9 @@ def compact_rows(ctx, res, n, k, reps):
         ctx.free(d)
 
 
-def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, reps):
-    """the search rows of the docstring; ix is the built index, terms / idf the 256 x 8 words of the tool's own queries"""
+def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, reps, drawn=None):
+    """the search rows of the docstring; ix is the built index, terms / idf the 256 x 8 words of the tool's own queries, drawn =
+    (terms, idf, offsets) of the 256 drawn queries (None: a library without gz_bm25_search_bool, their rows are left out)"""
     ts = []
     qoff1 = np.array([0, 1], np.int64)
     for _ in range(reps + 1):                                        # (the first is the warm-up)
@@ -285,6 +292,23 @@ def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_id
         cnt = np.empty(256, np.int64)
         ctx.d2h(cnt, d_cnt)
         res["match_fraction" + ("_rare" if name else "")] = float(cnt.mean() / n)
+    for q in (1, 64, 256) if drawn is not None else ():
+        dterms, didf, doff = drawn
+        qoff = doff[:q + 1]
+        ts = {0: [], 1: []}
+        for rep in range(reps + 1):                                  # (the first round is the warm-up of both)
+            for mode in (0, 1):
+                t0 = time.perf_counter()
+                ctx.bm25_search(ix, dterms, didf, qoff, params, False, 10, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt, mode=mode)
+                ctx.sync()
+                if rep:
+                    ts[mode].append((time.perf_counter() - t0) * 1e3)
+                if q == 256 and rep == reps:
+                    cnt = np.empty(256, np.int64)
+                    ctx.d2h(cnt, d_cnt)
+                    res["match_fraction_all_drawn" if mode else "match_fraction_drawn"] = float(cnt.mean() / n)
+        for mode, key in ((0, "search_drawn_q%d_k10" % q), (1, "search_all_drawn_q%d_k10" % q)):
+            res[key + "_ms"], res[key + "_all_ms"] = float(np.median(ts[mode])), [round(x, 3) for x in ts[mode]]
     ctx.free(d_cnt)
     for q in (1, 64, 256):
         res["search_q%d_k10_over_topk" % q] = round(res["search_q%d_k10_ms" % q] / res["topk_q%d_k10_ms" % q], 3)
@@ -379,7 +403,19 @@ def main():
                 ctx.bm25_topk(ix, terms[:8 * q], idf[:8 * q], qoff, params, False, k, d_ids=d_ids, d_scores=d_sc)
                 ctx.sync()
             res["topk_q%d_k%d_ms" % (q, k)], res["topk_q%d_k%d_all_ms" % (q, k)] = median_ms(topk, a.reps)
-    search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, a.reps)
+    drawn = None
+    if hasattr(ctx.lib, "gz_bm25_search_bool_device"):
+        rng = np.random.default_rng(3)
+        dq = []
+        for i in rng.integers(n, size=256):
+            ws = list(dict.fromkeys(raw[o[i]:o[i + 1]].decode("utf-8").split()))
+            dq.append([ws[int(j)] for j in rng.choice(len(ws), min(int(rng.integers(2, 5)), len(ws)), replace=False)])
+        db, do = pack([w for q in dq for w in q])
+        dterms, ddf = ctx.bm25_lookup(ix, db, do)
+        doff = np.zeros(257, np.int64)
+        np.cumsum([len(q) for q in dq], out=doff[1:])
+        drawn = (dterms, np.array([np.log(1+(n-int(d)+0.5)/(int(d)+0.5)) for d in ddf]), doff)
+    search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_ids, d_sc, a.reps, drawn)
     for k in (10, 1000) if not a.search_only else ():
         res["topk_q256_k%d_over_score_pct" % k] = round(100 * (res["topk_q256_k%d_ms" % k] / res["score_q256_ms"] - 1), 1)
     ctx.free(d_ids)
