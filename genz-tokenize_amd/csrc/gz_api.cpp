@@ -956,7 +956,13 @@ struct gz_bm25 {
     // postings (gz_search.inc)
     DBuf poff, pdoc;
     bool has_post = false;
-    ~gz_bm25() { for (DBuf* b : {&text, &dl, &sig, &eoff, &ent, &ptab, &ttab, &tstart, &tlen, &df, &poff, &pdoc}) release(*b); }
+    // a positional index (flags & GZ_BM25_POSITIONS) owns seq: the term id of every word, documents in id order, words in
+    // str.split() order -- n_words of them; every change of the index maintains it.  woff, the exclusive scan of dl (document d =
+    // seq[woff[d] .. woff[d + 1])), is derived like the postings: by the first call that reads positions, dropped by every change
+    int32_t flags = 0;
+    DBuf seq, woff;
+    bool has_woff = false;
+    ~gz_bm25() { for (DBuf* b : {&text, &dl, &sig, &eoff, &ent, &ptab, &ttab, &tstart, &tlen, &df, &poff, &pdoc, &seq, &woff}) release(*b); }
 };
 
 namespace {
@@ -969,6 +975,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_S_BM, BMW_S_WROW, BMW_S_WNS, BMW_S_WSOFF, BMW_S_TCNT, BMW_S_TBASE, BMW_S_CNT,     // a search chunk (bm25_search_locked)
        BMW_S_CAND, BMW_S_CSC, BMW_S_POS, BMW_S_PSC,
        BMW_S_XTERM, BMW_S_XOFF,                                                     // the excluded terms of a boolean search
+       BMW_S_PHTERM, BMW_S_PHOFF,                                                   // the phrase terms of a phrase search
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1021,6 +1028,7 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     hipStream_t s = c->stream;
     DBuf* w = c->w_bm;
     const int64_t N = ix->n_docs;
+    const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
     int rc;
     GzBm25Args A{};
     A.tb = (const uint8_t*)ix->text.p - ix->off0;
@@ -1050,13 +1058,14 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
         (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
         (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) || (rc = bm_alloc(c, w[BMW_DTAB], slots * 16)) ||
-        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) || (rc = bm_alloc(c, w[BMW_TERM], w1 * 4)) ||
-        (rc = bm_alloc(c, ix->ptab, slots * 16)))
+        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) ||
+        (rc = bm_alloc(c, pos ? ix->seq : w[BMW_TERM], pos ? (size_t)W * 4 : w1 * 4)) || (rc = bm_alloc(c, ix->ptab, slots * 16)))
         return rc;
     A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
     A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
     A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = slots - 1;
-    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p; A.term = (uint32_t*)w[BMW_TERM].p;
+    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
+    A.term = (uint32_t*)(pos ? ix->seq : w[BMW_TERM]).p;     // (a positional index owns the words' term ids: they are its seq)
     A.ptab = (GzBm25Slot*)ix->ptab.p; A.pmask = ix->pmask = slots - 1;
     gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
     gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
@@ -1145,7 +1154,8 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
 {
     hipStream_t s = c->stream;
     DBuf* w = c->w_bm;
-    const int64_t N0 = ix->n_docs, T0 = ix->n_terms, E0 = ix->n_ent, used = ix->text_bytes;
+    const int64_t N0 = ix->n_docs, T0 = ix->n_terms, E0 = ix->n_ent, used = ix->text_bytes, W0 = ix->n_words;
+    const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
     int rc;
     // ---- phase A: text, word boundaries, known terms, de-duplication of the rest
     void* p_text = nullptr; void* p_dl = nullptr;
@@ -1174,11 +1184,15 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
         (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
         (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) || (rc = bm_alloc(c, w[BMW_TERM], w1 * 4)))
+        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)))
         return rc;
+    // the batch's term ids: workspace, or -- a positional index -- the tail of seq behind the index's own words
+    void* p_seq = nullptr;
+    if (pos ? (rc = bm_reserve(c, st, ix->seq, (size_t)W0 * 4, (size_t)(W0 + W) * 4, &p_seq)) : (rc = bm_alloc(c, w[BMW_TERM], w1 * 4))) return rc;
     A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
     A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
-    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p; A.term = (uint32_t*)w[BMW_TERM].p;
+    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
+    A.term = pos ? (uint32_t*)p_seq + W0 : (uint32_t*)w[BMW_TERM].p;
     A.tstart = (int64_t*)ix->tstart.p; A.tlen = (uint32_t*)ix->tlen.p;          // (read only in this phase)
     A.ttab = (GzBm25Slot*)ix->ttab.p; A.tmask = ix->tmask;
     gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
@@ -1282,11 +1296,15 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
     hipStream_t s = c->stream;
     DBuf* w = c->w_bm;
     const int64_t N = ix->n_docs, T = ix->n_terms;
+    const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
     int rc;
     // ---- phase A
     const size_t n1 = (size_t)N + 1;
     if ((rc = bm_alloc(c, w[BMW_FLAG], n1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], n1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], n1 * 4)) ||
         (rc = bm_alloc(c, w[BMW_WOFF], n1 * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) || (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(N / 4096 + 2) * 4)))
+        return rc;
+    // (a positional index: the words every document keeps, and the word offsets before and after -- scans of fieldLens)
+    if (pos && ((rc = bm_alloc(c, w[BMW_REP], n1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST0], n1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], n1 * 4))))
         return rc;
     GzBm25Rm R{};
     R.ids = ids_dev; R.n_ids = n_ids; R.n_docs = N;
@@ -1294,6 +1312,10 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
     R.kcnt = (uint32_t*)w[BMW_SLOT].p; R.neoff = (uint32_t*)w[BMW_WOFF].p;
     R.dl = (const uint32_t*)ix->dl.p; R.sig = (const unsigned long long*)ix->sig.p; R.eoff = (const uint32_t*)ix->eoff.p;
     R.ent = (const uint2*)ix->ent.p;
+    if (pos) {
+        R.seq = (const uint32_t*)ix->seq.p; R.n_words = ix->n_words;
+        R.kdl = (uint32_t*)w[BMW_REP].p; R.woff = (uint32_t*)w[BMW_LIST0].p; R.nwoff = (uint32_t*)w[BMW_LIST1].p;
+    }
     HIPCHK(c, hipMemsetAsync(R.ctl, 0, 64, s));
     HIPCHK(c, hipMemsetAsync(R.gone, 0, n1 * 4, s));
     gz_launch_bm25_remove(GZ_BM25_RM_MARK, R, s);
@@ -1302,8 +1324,11 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
     if (bad) return fail(c, GZ_E_INVALID, "BM25 remove: a document id outside [0, %lld)", (long long)N);
     gz_launch_bm25_remove(GZ_BM25_RM_COUNT, R, s);
     if ((rc = bm_scan(c, R.gone, N, R.before)) || (rc = bm_scan(c, R.kcnt, N, R.neoff))) return rc;
-    int64_t n_gone = 0, E1 = 0;
+    if (pos && ((rc = bm_scan(c, R.dl, N, R.woff)) || (rc = bm_scan(c, R.kdl, N, R.nwoff)))) return rc;
+    int64_t n_gone = 0, E1 = 0, Wold = ix->n_words, W1 = 0;
     if ((rc = bm_read_u32(c, R.before + N, n_gone)) || (rc = bm_read_u32(c, R.neoff + N, E1))) return rc;
+    if (pos && ((rc = bm_read_u32(c, R.woff + N, Wold)) || (rc = bm_read_u32(c, R.nwoff + N, W1)))) return rc;
+    if (Wold != ix->n_words) return fail(c, GZ_E_HIP, "BM25 remove: fieldLens sum to %lld words, the index holds %lld", (long long)Wold, (long long)ix->n_words);
     if (n_gone == 0) return GZ_OK;
     const int64_t N1 = N - n_gone;
 
@@ -1314,14 +1339,22 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
         (rc = bm_stage(c, st, ix->eoff, 0, (size_t)(N1 + 1) * 4, &p_eoff)) || (rc = bm_stage(c, st, ix->ent, 0, (size_t)E1 * 8, &p_ent)) ||
         (rc = bm_stage(c, st, ix->ptab, 0, pslots * 16, &p_ptab)) || (rc = bm_stage(c, st, ix->df, (size_t)T * 4, (size_t)T * 4, &p_df)))
         return rc;
+    void* p_seq = nullptr;
+    if (pos && (rc = bm_stage(c, st, ix->seq, 0, (size_t)W1 * 4, &p_seq))) return rc;
+    R.seq2 = (uint32_t*)p_seq;
     R.dl2 = (uint32_t*)p_dl; R.sig2 = (unsigned long long*)p_sig; R.eoff2 = (uint32_t*)p_eoff; R.ent2 = (uint2*)p_ent;
     R.ptab2 = (GzBm25Slot*)p_ptab; R.pmask2 = ix->pmask; R.df2 = (uint32_t*)p_df;
     HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
     gz_launch_bm25_remove(GZ_BM25_RM_DOCS, R, s);
     gz_launch_bm25_remove(GZ_BM25_RM_ENT, R, s);
+    if (pos) gz_launch_bm25_remove(GZ_BM25_RM_SEQ, R, s);
     uint32_t out[4] = {};                                     // ctl[2 .. 5]: dead terms, -, words of the removed documents (64 bits)
     if ((rc = copy_out_small(c, out, R.ctl + 2, 16, s))) return rc;
+    int64_t bad_seq = 0;
+    if (pos && (rc = bm_read_u32(c, R.ctl + 1, bad_seq))) return rc;
     HIPCHK(c, hipGetLastError());
+    if (bad_seq || (pos && ix->n_words - (int64_t)((uint64_t)out[2] | (uint64_t)out[3] << 32) != W1))
+        return fail(c, GZ_E_HIP, "BM25 remove: the index's fieldLens and word sequence contradict each other");
 
     // ---- phase C: nothing below can fail
     st.commit();
@@ -1407,6 +1440,10 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
         (rc = bm_stage_exact(c, st, ix->ttab, tslots * 16, &p_ttab)) || (rc = bm_stage_exact(c, st, ix->tstart, (size_t)T1 * 8, &p_tstart)) ||
         (rc = bm_stage_exact(c, st, ix->tlen, (size_t)T1 * 4, &p_tlen)) || (rc = bm_stage_exact(c, st, ix->df, (size_t)T1 * 4, &p_df)))
         return rc;
+    const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
+    void* p_seq = nullptr;
+    if (pos && (rc = bm_stage_exact(c, st, ix->seq, (size_t)ix->n_words * 4, &p_seq))) return rc;
+    if (pos) { C.seq = (const uint32_t*)ix->seq.p; C.seq2 = (uint32_t*)p_seq; C.n_words = ix->n_words; }
     C.arena = (uint8_t*)p_text; C.tstart2 = (int64_t*)p_tstart; C.tlen2 = (uint32_t*)p_tlen; C.df2 = (uint32_t*)p_df;
     C.ent2 = (uint2*)p_ent; C.sig2 = (unsigned long long*)p_sig; C.ptab2 = (GzBm25Slot*)p_ptab; C.pmask2 = pslots - 1;
     HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
@@ -1416,6 +1453,7 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
     gz_launch_bm25_compact(GZ_BM25_CP_GATHER, C, s);
     gz_launch_bm25_rekey((const GzBm25Slot*)ix->ttab.p, (int64_t)(ix->tmask + 1), C.newid, (GzBm25Slot*)p_ttab, tslots - 1, s);
     gz_launch_bm25_compact(GZ_BM25_CP_ENT, C, s);
+    if (pos) gz_launch_bm25_compact(GZ_BM25_CP_SEQ, C, s);    // (a word whose term has no new id raises the same flag)
     int64_t bad = 0;
     if ((rc = bm_read_u32(c, C.ctl + 1, bad))) return rc;
     HIPCHK(c, hipGetLastError());
@@ -1426,6 +1464,18 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
     ix->n_terms = T1; ix->text_bytes = B; ix->off0 = 0;
     ix->pmask = pslots - 1; ix->tmask = tslots - 1;
     return GZ_OK;
+}
+
+// The last step of a POSITIONAL build.  Such an index never needs the documents' text again, only its terms' bytes, so the build
+// ends in the canonical form a compaction gives: the text copy is the live terms' bytes in first-occurrence order and every
+// buffer has the size its counts ask for.  A fresh positional build and a compacted positional index of the same documents are
+// then the same index, footprint included.  (Term ids and seq are the build's already: the numbering pass is the identity.)
+int bm25_build_finish(gz_ctx* c, gz_bm25* ix)
+{
+    if (!(ix->flags & GZ_BM25_POSITIONS)) return GZ_OK;
+    BmStage st;                                              // (before the drain: what it still holds is freed after the stream has drained)
+    BmDrain drain{c};
+    return bm25_compact_core(c, ix, st);
 }
 
 int bm_adopt(gz_ctx* c, std::unique_ptr<gz_bm25>& ix, gz_bm25** out)
@@ -1499,6 +1549,7 @@ int bm25_score_args(gz_bm25* ix, const int32_t* terms, const double* idf, const 
 }
 
 static_assert(GZ_TOPK_SORT == GZ_BM25_TOPK_MAX, "the last selection level sorts GZ_BM25_TOPK_MAX winners in LDS");
+static_assert(GZ_PHRASE_MAX == GZ_BM25_PHRASE_MAX && GZ_PHRASE_MAX <= 64, "the phrase kernel holds a phrase term per lane");
 
 // k (>= 1) -> k' = min(k, documents), refused above GZ_BM25_TOPK_MAX
 int bm25_topk_k(gz_bm25* ix, int64_t k, int64_t& kk)
@@ -1571,11 +1622,36 @@ int bm25_topk_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const
 // device memory may still read them.
 void bm25_drop_postings(gz_bm25* ix)
 {
-    if (!ix->has_post) return;
+    if (!ix->has_post && !ix->has_woff) return;
     hipStreamSynchronize(ix->c->stream);
     release(ix->poff);
     release(ix->pdoc);
-    ix->has_post = false;
+    release(ix->woff);                            // (a positional index's word offsets: derived from fieldLens in the same way)
+    ix->has_post = ix->has_woff = false;
+}
+
+// The word offsets of a positional index as it is, unless it has them: woff = the scan of fieldLens, staged and entered after the
+// round trip as the postings are.  Its total must be the index's word count: the bound of every read of seq.
+int bm25_word_offsets(gz_bm25* ix)
+{
+    if (ix->has_woff) return GZ_OK;
+    gz_ctx* c = ix->c;
+    const int64_t N = ix->n_docs;
+    int rc;
+    BmStage st;
+    BmDrain drain{c};
+    void* p_woff;
+    if ((rc = bm_stage_exact(c, st, ix->woff, (size_t)(N + 1) * 4, &p_woff)) || (rc = bm_alloc(c, c->w_bm[BMW_BSUM], (size_t)(N / 4096 + 2) * 4)))
+        return rc;
+    if ((rc = bm_scan(c, (const uint32_t*)ix->dl.p, N, (uint32_t*)p_woff))) return rc;
+    int64_t total = 0;
+    if ((rc = bm_read_u32(c, (const uint32_t*)p_woff + N, total))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (total != ix->n_words)
+        return fail(c, GZ_E_HIP, "BM25 positions: fieldLens sum to %lld words, the index holds %lld", (long long)total, (long long)ix->n_words);
+    st.commit();
+    ix->has_woff = true;
+    return GZ_OK;
 }
 
 // The term-major postings of the index as it is, unless it has them: poff = the scan of df, pdoc filled from the entries.  Both
@@ -1638,6 +1714,23 @@ int bm25_bool_args(gz_bm25* ix, int64_t nq, int32_t mode, const int32_t* xterm, 
     return GZ_OK;
 }
 
+// what the _phrase entry points take on top: the phrase terms of every query (phoff null: none)
+int bm25_phrase_args(gz_bm25* ix, int64_t nq, const int32_t* phterm, const int64_t* phoff)
+{
+    gz_ctx* c = ix->c;
+    if (!phoff) return GZ_OK;
+    if (!(ix->flags & GZ_BM25_POSITIONS)) return fail(c, GZ_E_INVALID, "a phrase search needs an index built with GZ_BM25_POSITIONS");
+    for (int64_t q = 0; q < nq; ++q) {
+        if (phoff[q + 1] < phoff[q]) return fail(c, GZ_E_INVALID, "phrase-term offsets must not decrease");
+        if (phoff[q + 1] - phoff[q] > GZ_BM25_PHRASE_MAX)
+            return fail(c, GZ_E_LIMIT, "a phrase of %lld words; a phrase takes at most %d", (long long)(phoff[q + 1] - phoff[q]), GZ_BM25_PHRASE_MAX);
+    }
+    if (phoff[nq] > phoff[0] && !phterm) return fail(c, GZ_E_INVALID, "phrase-term offsets without terms");
+    for (int64_t j = phoff[0]; j < phoff[nq]; ++j)
+        if (phterm[j] < -1 || phterm[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "phrase term id %d out of range", phterm[j]);
+    return GZ_OK;
+}
+
 // A chunk of queries at a time (its bitmaps hold at most bm25_search_chunk words, one row at least, at most 65535 rows): mark the
 // documents of every query word's postings in the row's bitmap, count and rank the bits, and read the counts back -- they size
 // what follows.  Then, for runs of rows whose candidate scores (rows x the largest count among them) stay within
@@ -1647,9 +1740,12 @@ int bm25_bool_args(gz_bm25* ix, int64_t nq, int32_t mode, const int32_t* xterm, 
 // mode GZ_BM25_MATCH_ALL: only the driver of every row is marked (GZ_BM25_SR_DRIVER) and the filter stage clears the documents
 // that lack a word of the row; xoff (null: none) / xterm: the filter clears the documents that hold an excluded term.  With mode
 // GZ_BM25_MATCH_ANY and no excluded term, neither is launched and nothing more is allocated.
+// phoff (null: none) / phterm: the phrase stage (GZ_BM25_SR_PHRASE) then clears, in the rows that have phrase terms, the documents
+// in which they do not stand next to each other; without phrase terms nothing of it is launched, allocated or derived.
 int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
                        int64_t kk, bool count_only, int64_t* doc_dev, double* score_dev, int64_t* cnt_dev, int64_t* doc_host, double* score_host,
-                       int64_t* cnt_host, int32_t mode = GZ_BM25_MATCH_ANY, const int32_t* xterm = nullptr, const int64_t* xoff = nullptr)
+                       int64_t* cnt_host, int32_t mode = GZ_BM25_MATCH_ANY, const int32_t* xterm = nullptr, const int64_t* xoff = nullptr,
+                       const int32_t* phterm = nullptr, const int64_t* phoff = nullptr)
 {
     gz_ctx* c = ix->c;
     DBuf* w = c->w_bm;
@@ -1675,6 +1771,19 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
         A.xterm = (const int32_t*)w[BMW_S_XTERM].p - xoff[0];
     }
     A.mode = mode;
+    const int64_t np = phoff ? phoff[nq] - phoff[0] : 0;
+    if (np > 0) {
+        if ((rc = bm25_word_offsets(ix))) return rc;
+        if ((rc = bm_alloc(c, w[BMW_S_PHTERM], (size_t)np * 4)) || (rc = bm_alloc(c, w[BMW_S_PHOFF], (size_t)(nq + 1) * 8)) ||
+            (rc = bm_alloc(c, w[BMW_CTL], 64)) || (rc = copy_in(c, w[BMW_S_PHTERM].p, phterm + phoff[0], (size_t)np * 4, s)) ||
+            (rc = copy_in(c, w[BMW_S_PHOFF].p, phoff, (size_t)(nq + 1) * 8, s)))
+            return rc;
+        A.phterm = (const int32_t*)w[BMW_S_PHTERM].p - phoff[0];
+        A.seq = (const uint32_t*)ix->seq.p; A.woff = (const uint32_t*)ix->woff.p; A.n_words = ix->n_words;
+        A.ctl = (uint32_t*)w[BMW_CTL].p;
+        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    }
+    const int64_t* phoff_dev = np > 0 ? (const int64_t*)w[BMW_S_PHOFF].p : nullptr;
     const int64_t* xoff_dev = nx > 0 ? (const int64_t*)w[BMW_S_XOFF].p : nullptr;
     const int64_t chunk = c->opt.bm25_search_chunk;
     const int64_t W64 = (N + 63) / 64, n_tiles = (W64 + GZ_SEARCH_TILE - 1) / GZ_SEARCH_TILE;
@@ -1707,11 +1816,18 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
             gz_launch_bm25_search(GZ_BM25_SR_MARK, A, rows, s);
             A.xoff = xoff_dev && xoff[q0 + rows] > xoff[q0] ? xoff_dev + q0 : nullptr;
             if (mode == GZ_BM25_MATCH_ALL || A.xoff) gz_launch_bm25_search(GZ_BM25_SR_FILTER, A, rows, s);
+            A.phoff = phoff_dev && phoff[q0 + rows] > phoff[q0] ? phoff_dev + q0 : nullptr;
+            if (A.phoff) gz_launch_bm25_search(GZ_BM25_SR_PHRASE, A, rows, s);
         }
         gz_launch_bm25_search(GZ_BM25_SR_COUNT, A, rows, s);
         gz_launch_bm25_search(GZ_BM25_SR_ROWS, A, rows, s);
         HIPCHK(c, hipGetLastError());
         if ((rc = copy_out_small(c, cnt.data(), A.cnt, (size_t)rows * 4, s))) return rc;
+        if (np > 0) {
+            int64_t bad = 0;
+            if ((rc = bm_read_u32(c, A.ctl + 1, bad))) return rc;
+            if (bad) return fail(c, GZ_E_HIP, "BM25 phrase search: the index's fieldLens and word sequence contradict each other");
+        }
         if (cnt_host) for (int64_t r = 0; r < rows; ++r) cnt_host[q0 + r] = (int64_t)cnt[(size_t)r];
         if (count_only) continue;
         for (int64_t r0 = 0; r0 < rows;) {
@@ -3281,9 +3397,20 @@ try {
 
 // ---- BM25 / BM25Plus ------------------------------------------------------------------------------------------------------
 int gz_bm25_build(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, gz_bm25** out)
+{
+    return gz_bm25_build_ex(c, text, text_off, n_docs, 0, out);
+}
+
+int gz_bm25_build_device(gz_ctx* c, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes, gz_bm25** out)
+{
+    return gz_bm25_build_device_ex(c, text_dev, text_off_dev, n_docs, text_bytes, 0, out);
+}
+
+int gz_bm25_build_ex(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, int32_t flags, gz_bm25** out)
 try {
     if (!c || !out || !text_off || n_docs < 0) return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
     *out = nullptr;
+    if (flags & ~GZ_BM25_POSITIONS) return fail(c, GZ_E_INVALID, "BM25 build flags 0x%x: only GZ_BM25_POSITIONS is defined", (unsigned)flags);
     const int64_t nbytes = text_off[n_docs] - text_off[0];
     if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
     for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
@@ -3294,19 +3421,21 @@ try {
     alloc_site(c);
     std::unique_ptr<gz_bm25> ix(new gz_bm25());
     BmDrain drain{c};
-    ix->c = c; ix->n_docs = n_docs; ix->off0 = text_off[0];
+    ix->c = c; ix->n_docs = n_docs; ix->off0 = text_off[0]; ix->flags = flags;
     if ((rc = bm_alloc(c, ix->text, (size_t)nbytes + 16)) || (rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
     if (nbytes && (rc = copy_in(c, ix->text.p, text + text_off[0], (size_t)nbytes, c->stream))) return rc;
     if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
-    if ((rc = bm25_build_core(c, ix.get(), (const int64_t*)c->w_bm[BMW_OFF].p, nbytes))) return rc;
+    if ((rc = bm25_build_core(c, ix.get(), (const int64_t*)c->w_bm[BMW_OFF].p, nbytes)) || (rc = bm25_build_finish(c, ix.get()))) return rc;
     return bm_adopt(c, ix, out);
 } GZ_CATCH(c)
 
-int gz_bm25_build_device(gz_ctx* c, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes, gz_bm25** out)
+int gz_bm25_build_device_ex(gz_ctx* c, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes, int32_t flags,
+                            gz_bm25** out)
 try {
     if (!c || !out || !text_off_dev || n_docs < 0 || text_bytes < 0 || (text_bytes > 0 && !text_dev))
         return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
     *out = nullptr;
+    if (flags & ~GZ_BM25_POSITIONS) return fail(c, GZ_E_INVALID, "BM25 build flags 0x%x: only GZ_BM25_POSITIONS is defined", (unsigned)flags);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
@@ -3317,10 +3446,10 @@ try {
     int64_t off0 = 0;
     if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
     if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
-    ix->c = c; ix->n_docs = n_docs; ix->off0 = off0;
+    ix->c = c; ix->n_docs = n_docs; ix->off0 = off0; ix->flags = flags;
     if ((rc = bm_alloc(c, ix->text, (size_t)text_bytes + 16))) return rc;
     if (text_bytes) HIPCHK(c, hipMemcpyAsync(ix->text.p, text_dev + off0, (size_t)text_bytes, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = bm25_build_core(c, ix.get(), text_off_dev, text_bytes))) return rc;
+    if ((rc = bm25_build_core(c, ix.get(), text_off_dev, text_bytes)) || (rc = bm25_build_finish(c, ix.get()))) return rc;
     return bm_adopt(c, ix, out);
 } GZ_CATCH(c)
 
@@ -3453,9 +3582,36 @@ try {
     std::lock_guard<std::mutex> lk(c->mu);
     size_t cap = 0;
     for (const DBuf* b : {&ix->text, &ix->dl, &ix->sig, &ix->eoff, &ix->ent, &ix->ptab, &ix->ttab, &ix->tstart, &ix->tlen, &ix->df,
-                          &ix->poff, &ix->pdoc})          // (the postings while they exist)
+                          &ix->poff, &ix->pdoc,           // (the postings while they exist)
+                          &ix->seq, &ix->woff})           // (a positional index: its words' term ids, and the word offsets while they exist)
         cap += b->cap;
     out[0] = ix->text_bytes; out[1] = ix->n_terms; out[2] = (int64_t)cap;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_flags(gz_bm25* ix, int32_t* flags)
+try {
+    if (!ix) return GZ_E_INVALID;
+    if (!flags) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    *flags = ix->flags;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_sequence(gz_bm25* ix, int32_t* terms_out, int64_t* doc_off_out)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!(ix->flags & GZ_BM25_POSITIONS)) return fail(c, GZ_E_INVALID, "the index was built without GZ_BM25_POSITIONS");
+    if ((!terms_out && ix->n_words > 0) || !doc_off_out) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = bm25_word_offsets(ix))) return rc;
+    const int64_t N = ix->n_docs;
+    std::vector<uint32_t> off((size_t)N + 1);
+    if ((rc = copy_out(c, off.data(), ix->woff.p, (size_t)(N + 1) * 4, c->stream))) return rc;
+    for (int64_t d = 0; d <= N; ++d) doc_off_out[d] = (int64_t)off[(size_t)d];
+    if (ix->n_words > 0 && (rc = copy_out(c, terms_out, ix->seq.p, (size_t)ix->n_words * 4, c->stream))) return rc;
     return GZ_OK;
 } GZ_CATCH(ix ? ix->c : nullptr)
 
@@ -3611,6 +3767,47 @@ try {
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
                               mode, ex_terms, ex_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_phrase(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                          int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off, const int32_t* ph_terms,
+                          const int64_t* ph_off, int64_t* doc_out, double* score_out, int64_t* count_out)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out && score_out ? doc_out : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) ||
+        (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off)))
+        return rc;
+    if (!count_out && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, nullptr, nullptr, nullptr, doc_out, score_out, count_out,
+                              mode, ex_terms, ex_off, ph_terms, ph_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_phrase_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                                 const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off,
+                                 const int32_t* ph_terms, const int64_t* ph_off, int64_t* doc_out_dev, double* score_out_dev,
+                                 int64_t* count_out_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out_dev && score_out_dev ? doc_out_dev : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) ||
+        (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off)))
+        return rc;
+    if (!count_out_dev && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, doc_out_dev, score_out_dev, count_out_dev, nullptr, nullptr,
+                              nullptr, mode, ex_terms, ex_off, ph_terms, ph_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_match_count_phrase(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, int32_t mode,
+                               const int32_t* ex_terms, const int64_t* ex_off, const int32_t* ph_terms, const int64_t* ph_off, int64_t* count_out)
+try {
+    int rc = bm25_match_args(ix, terms, query_off, n_queries, count_out);
+    if (rc || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) || (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off))) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
+                              mode, ex_terms, ex_off, ph_terms, ph_off);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 void gz_bm25_destroy(gz_bm25* ix)

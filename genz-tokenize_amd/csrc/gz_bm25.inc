@@ -21,12 +21,13 @@
 //   gz_bm25_rm_*            a removal (gz_bm25_remove): mark the documents, scan the marks (new id = old id - removed before it) and
 //                           the kept documents' entry counts, then compact fieldLens, signatures and entries OUT OF PLACE into staged
 //                           buffers, fill a fresh pair table from the compacted entries and take the removed documents' entries off
-//                           a staged copy of df.  The live index is only read.
+//                           a staged copy of df.  The live index is only read.  (gz_bm25_rm_seq_kernel: a positional index's words)
 //   gz_bm25_cp_*            the canonical numbering of the live terms (gz_bm25_compact, gz_bm25_terms): first[term] = its smallest
 //                           entry index, the entries that are their term's first flagged and scanned -> new id = a fresh build's; the
 //                           terms' lengths scanned in new-id order, their bytes gathered into an arena; then (a compaction) entries,
 //                           pair table and signatures again under the new ids and, gz_bm25_rekey_kernel, the term table without its
-//                           dead terms -- all OUT OF PLACE, the live index is only read
+//                           dead terms -- all OUT OF PLACE, the live index is only read  (gz_bm25_cp_seq_kernel: a positional
+//                           index's words under the new ids)
 //   gz_bm25_lookup_kernel   query words (packed) -> term id (-1: absent) and df, bytes compared in full
 //   gz_bm25_score_kernel    scores[Q, N] float64 in the reference's order of operations (ranking.py:33-45, :52-63)
 // (gz_search.inc: the term-major postings and the search over them)
@@ -419,6 +420,7 @@ __global__ __launch_bounds__(256) void gz_bm25_rm_count_kernel(GzBm25Rm R)
     const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (d >= R.n_docs) return;
     R.kcnt[d] = R.gone[d] ? 0u : R.eoff[d + 1] - R.eoff[d];
+    if (R.kdl) R.kdl[d] = R.gone[d] ? 0u : R.dl[d];          // (a positional index: the words it keeps)
 }
 
 // per kept document: fieldLen, signature and first entry under its new id; thread n_docs closes the new eoff
@@ -459,6 +461,21 @@ __global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_rm_ent_kernel(GzBm25Rm 
         while (atomicCAS(&R.ptab2[s].key, 0ull, key) != 0ull) s = (s + 1) & R.pmask2;     // (a probe: more slots than keys)
         R.ptab2[s].a = en.y;
     }
+}
+
+// A positional index: a wave per document (one may hold 100 000 words), the kept documents' words to their new places.  The old
+// range must lie inside the n_words words of seq (else the flag: dl and seq contradict each other); the new one is as long, and
+// the scan of the kept lengths ends where seq2 does.
+__global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_rm_seq_kernel(GzBm25Rm R)
+{
+    const int64_t d = (int64_t)blockIdx.x * BM_WPB + (int64_t)(threadIdx.x / WAVE);
+    if (d >= R.n_docs || R.gone[d]) return;
+    const uint32_t w0 = R.woff[d], w1 = R.woff[d + 1], o = R.nwoff[d];
+    if (w1 < w0 || (int64_t)w1 > R.n_words || R.nwoff[d + 1] - o != w1 - w0) {
+        if (lane_id() == 0) atomicOr(&R.ctl[1], 1u);
+        return;
+    }
+    for (uint32_t i = w0 + (uint32_t)lane_id(); i < w1; i += WAVE) R.seq2[o + (i - w0)] = R.seq[i];
 }
 
 // ---- compact / vocabulary ---------------------------------------------------------------------------------------------------
@@ -575,6 +592,17 @@ __global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_cp_ent_kernel(GzBm25Cp 
         s0 |= __shfl_xor(s0, o, WAVE); s1 |= __shfl_xor(s1, o, WAVE); s2 |= __shfl_xor(s2, o, WAVE); s3 |= __shfl_xor(s3, o, WAVE);
     }
     if (lane < 4) C.sig2[d * 4 + lane] = lane == 0 ? s0 : lane == 1 ? s1 : lane == 2 ? s2 : s3;
+}
+
+// A positional index: every word's term id under the new numbering.  A word whose term has no new id contradicts the index.
+__global__ __launch_bounds__(256) void gz_bm25_cp_seq_kernel(GzBm25Cp C)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= C.n_words) return;
+    const uint32_t o = C.seq[i];
+    const uint32_t t = (int64_t)o < C.n_terms ? C.newid[o] : 0xFFFFFFFFu;
+    if (t == 0xFFFFFFFFu) { atomicOr(&C.ctl[1], 1u); return; }
+    C.seq2[i] = t;
 }
 
 // ---- lookup ---------------------------------------------------------------------------------------------------------------
@@ -719,6 +747,7 @@ void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s)
     case GZ_BM25_RM_COUNT: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_count_kernel, dim3(bm_grid(R.n_docs, 256)), dim3(256), 0, s, R); break;
     case GZ_BM25_RM_DOCS: hipLaunchKernelGGL(gz_bm25_rm_docs_kernel, dim3(bm_grid(R.n_docs + 1, 256)), dim3(256), 0, s, R); break;
     case GZ_BM25_RM_ENT: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_ent_kernel, dim3(bm_grid(R.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, R); break;
+    case GZ_BM25_RM_SEQ: if (R.n_docs > 0) hipLaunchKernelGGL(gz_bm25_rm_seq_kernel, dim3(bm_grid(R.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, R); break;
     default: break;
     }
 }
@@ -731,6 +760,7 @@ void gz_launch_bm25_compact(int step, const GzBm25Cp& C, hipStream_t s)
     case GZ_BM25_CP_NEWID: if (C.n_terms > 0) hipLaunchKernelGGL(gz_bm25_cp_newid_kernel, dim3(bm_grid(C.n_terms, 256)), dim3(256), 0, s, C); break;
     case GZ_BM25_CP_GATHER: hipLaunchKernelGGL(gz_bm25_cp_gather_kernel, dim3(bm_grid(C.n_new + 1, 256)), dim3(256), 0, s, C); break;
     case GZ_BM25_CP_ENT: if (C.n_docs > 0) hipLaunchKernelGGL(gz_bm25_cp_ent_kernel, dim3(bm_grid(C.n_docs, BM_WPB)), dim3(WAVE * BM_WPB), 0, s, C); break;
+    case GZ_BM25_CP_SEQ: if (C.n_words > 0) hipLaunchKernelGGL(gz_bm25_cp_seq_kernel, dim3(bm_grid(C.n_words, 256)), dim3(256), 0, s, C); break;
     default: break;
     }
 }

@@ -216,8 +216,13 @@ struct GzBm25Rm {
     uint32_t* dl2; unsigned long long* sig2; uint32_t* eoff2; uint2* ent2;
     GzBm25Slot* ptab2; unsigned long long pmask2;    // the fresh pair table (cleared by the caller)
     uint32_t* df2;                      // a copy of df: the removed documents' entries are taken off it
+    // a positional index (seq non-null): the kept documents' words move to their new places
+    const uint32_t* seq; int64_t n_words;            // [n_words] the term id of every word, doc-major
+    uint32_t* kdl;                      // [n_docs] words a document keeps (none when it goes)
+    uint32_t* woff; uint32_t* nwoff;    // [n_docs + 1] exclusive scans of dl and of kdl: a document's first word, old and new (by OLD id)
+    uint32_t* seq2;                     // [nwoff[n_docs]]
 };
-enum { GZ_BM25_RM_MARK, GZ_BM25_RM_COUNT, GZ_BM25_RM_DOCS, GZ_BM25_RM_ENT };
+enum { GZ_BM25_RM_MARK, GZ_BM25_RM_COUNT, GZ_BM25_RM_DOCS, GZ_BM25_RM_ENT, GZ_BM25_RM_SEQ };
 void gz_launch_bm25_remove(int step, const GzBm25Rm& R, hipStream_t s);
 // the canonical numbering of the live terms (order of first occurrence in the current documents: a fresh build's), for a
 // compaction (gz_bm25_compact) and the vocabulary read (gz_bm25_terms): live arrays are read, workspace and the staged /
@@ -240,8 +245,9 @@ struct GzBm25Cp {
     uint2* ent2;                        // [n_ent] the entries under the new ids
     unsigned long long* sig2;           // [n_docs * 4] signatures of the new ids
     GzBm25Slot* ptab2; unsigned long long pmask2;    // the fresh pair table (cleared by the caller)
+    const uint32_t* seq; uint32_t* seq2; int64_t n_words;      // a positional index: every word's term id, old and under the new ids
 };
-enum { GZ_BM25_CP_FIRST, GZ_BM25_CP_FLAG, GZ_BM25_CP_NEWID, GZ_BM25_CP_GATHER, GZ_BM25_CP_ENT };
+enum { GZ_BM25_CP_FIRST, GZ_BM25_CP_FLAG, GZ_BM25_CP_NEWID, GZ_BM25_CP_GATHER, GZ_BM25_CP_ENT, GZ_BM25_CP_SEQ };
 void gz_launch_bm25_compact(int step, const GzBm25Cp& C, hipStream_t s);
 // the term table into a fresh one (cleared by the caller): a = newid[a], slots of dead terms (newid all ones) are dropped
 void gz_launch_bm25_rekey(const GzBm25Slot* from, int64_t n_slots, const uint32_t* newid, GzBm25Slot* to, unsigned long long mask, hipStream_t s);
@@ -315,8 +321,15 @@ struct GzBm25Search {
     const int64_t* pos; const double* psc;  // [., k2] the selection's positions into the candidate list and scores
     int64_t k2, kk;                       // k2 = min(kk, M)
     int64_t* doc_out; double* score_out;  // [., kk]: -1 / NaN behind the row's count
+    // a phrase search (phoff non-null; a positional index): of the marked documents only those stay in which the terms
+    // phterm[phoff[r]] .. phterm[phoff[r + 1]] (absolute indices; at most GZ_PHRASE_MAX; -1: no document holds it) stand next to each
+    // other in this order; a row without phrase terms is left alone
+    const int32_t* phterm; const int64_t* phoff;
+    const uint32_t* seq; const uint32_t* woff; int64_t n_words;    // document d = seq[woff[d] .. woff[d + 1])
+    uint32_t* ctl;                        // [1] the word offsets contradict n_words
 };
+constexpr int GZ_PHRASE_MAX = 64;         // == GZ_BM25_PHRASE_MAX of the public header: a lane per phrase term
 enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_BM25_SR_CAND, GZ_BM25_SR_SCORE, GZ_BM25_SR_OUT,
-       GZ_BM25_SR_DRIVER, GZ_BM25_SR_FILTER };
-// rows: of the chunk (WORDS, DRIVER, MARK, FILTER, COUNT, ROWS), else of the launch (from row0)
+       GZ_BM25_SR_DRIVER, GZ_BM25_SR_FILTER, GZ_BM25_SR_PHRASE };
+// rows: of the chunk (WORDS, DRIVER, MARK, FILTER, PHRASE, COUNT, ROWS), else of the launch (from row0)
 void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStream_t s);

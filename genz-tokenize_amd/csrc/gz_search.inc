@@ -1,6 +1,7 @@
-// gz_search.inc -- BM25 search (gz_bm25_search[_device], gz_bm25_match_count and their _bool forms): the documents that match a
-// query, counted, scored and ranked; included by gz_kernels.hip after gz_topk.inc.  A document matches when it holds at least one
-// word of the query (mode "any") or every word of it (mode "all"), and none of the query's excluded words.
+// gz_search.inc -- BM25 search (gz_bm25_search[_device], gz_bm25_match_count, their _bool and _phrase forms): the documents that
+// match a query, counted, scored and ranked; included by gz_kernels.hip after gz_topk.inc.  A document matches when it holds at
+// least one word of the query (mode "any") or every word of it (mode "all"), none of the query's excluded words and, where the
+// query has a phrase, the phrase's words next to each other in this order.
 //
 // Postings, a term-major view of the doc-major (term, count) entries: poff[T + 1] = exclusive scan of df over every table term
 // (a dead term's list is empty), pdoc[n_ent] = the documents of every term.
@@ -20,6 +21,15 @@
 //                           probe) tell whether d holds a term: the bit goes when a required term is absent (mode "all") or an
 //                           excluded one present.  One owner per word, the marking has finished: a plain 64-bit store, only of a
 //                           word that changed
+//   gz_bm25_sr_phrase_kernel (a phrase search only, on a positional index: seq = the term id of every word, doc-major, woff = the
+//                           scan of fieldLens) a WAVE per 64-bit word of a row's bitmap: a zero word costs one load, a row
+//                           without a phrase returns at once.  Lane j holds phrase term j (at most 64).  For every set bit d:
+//                           one ballot of bm_pair_count tells whether d holds every phrase term at all; then the wave walks
+//                           seq[woff[d] .. woff[d + 1]) 64 start positions a trip -- a lane compares the ANCHOR's position (the
+//                           phrase term with the shortest postings list, ties to the first) and only on a hit the other terms --
+//                           and leaves the document at the first trip with a match.  Every read lies inside the document's own
+//                           range: a phrase never matches across two documents.  One owner per word, marking and filter have
+//                           finished: a plain 64-bit store, only of a word that changed
 //   gz_bm25_sr_count_kernel popcount of every tile (SR_TILE bitmap words) of every row
 //   gz_bm25_sr_rows_kernel  a workgroup per row: exclusive scan of its tiles' counts, count[row] = their sum
 //   gz_bm25_sr_cand_kernel  the set bits of a tile, in ASCENDING document id, into the row's candidate list (stride M = the largest
@@ -228,6 +238,73 @@ __global__ __launch_bounds__(256) void gz_bm25_sr_filter_kernel(GzBm25Search A)
     if (keep != x0) *at = keep;
 }
 
+__global__ __launch_bounds__(WAVE * BM_WPB) void gz_bm25_sr_phrase_kernel(GzBm25Search A)
+{
+    const GzBm25Score& S = A.S;
+    const int64_t row = blockIdx.y, w = (int64_t)blockIdx.x * BM_WPB + (int64_t)(threadIdx.x / WAVE);
+    if (w >= A.w64) return;
+    // (everything below is uniform in the wave unless it says "lane")
+    const int64_t h0 = A.phoff[row];
+    const int L = (int)(A.phoff[row + 1] - h0);
+    if (L <= 0 || L > GZ_PHRASE_MAX) return;                  // no phrase: the row stays as the marking and the filter left it
+    unsigned long long* at = A.bm + row * A.w64 + w;
+    const unsigned long long xv = *at;                        // (every lane the same address; made a scalar: the bit loop is the wave's)
+    const unsigned long long x0 = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)xv) |
+                                  (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(xv >> 32)) << 32;
+    if (!x0) return;
+    const int lane = lane_id();
+    const bool mine = lane < L;
+    const int32_t tj = mine ? A.phterm[h0 + lane] : 0;        // lane j: phrase term j
+    if (wballot(mine && (tj < 0 || (int64_t)tj >= A.n_terms))) {      // a word no document holds: nothing matches
+        if (lane == 0) *at = 0ull;
+        return;
+    }
+    // the anchor: the smallest (list length, position in the phrase) -- a minimum over the lanes
+    unsigned long long key = mine ? ((unsigned long long)(A.poff[tj + 1] - A.poff[tj]) << 8) | (unsigned long long)lane : ~0ull;
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, WAVE);
+        key = other < key ? other : key;
+    }
+    const int a = (int)(key & 255ull);
+    const uint32_t ta = (uint32_t)__shfl(tj, a, WAVE);
+    unsigned long long x = x0, keep = x0;
+    while (x) {
+        const int b = __ffsll(x) - 1;
+        x &= x - 1;
+        const int64_t d = w * 64 + b;
+        bool ok = d < S.n_docs;
+        if (ok) {                                             // 1. does d hold every phrase term at all?  (lane j asks for term j)
+            const unsigned long long sg[4] = {S.sig[d * 4], S.sig[d * 4 + 1], S.sig[d * 4 + 2], S.sig[d * 4 + 3]};
+            const bool lacks = mine && bm_pair_count(S, sg, (unsigned long long)d << 32, (uint32_t)tj) == 0;
+            ok = wballot(lacks) == 0ull;
+        }
+        if (ok) {                                             // 2. the document's words, 64 start positions a trip
+            const int64_t s0 = A.woff[d], s1 = A.woff[d + 1];
+            if (s1 < s0 || s1 > A.n_words) {
+                if (lane == 0) atomicOr(&A.ctl[1], 1u);
+                ok = false;
+            } else {
+                bool found = false;
+                for (int64_t t = s0; !found && t + L <= s1; t += WAVE) {
+                    const int64_t p = t + lane;               // (lane) a start: the phrase would be seq[p .. p + L), inside the document
+                    bool cand = p + L <= s1 && A.seq[p + a] == ta;
+                    if (wballot(cand)) {
+                        for (int k = 0; k < L; ++k) {
+                            const uint32_t tk = (uint32_t)__shfl(tj, k, WAVE);
+                            if (k != a && cand) cand = A.seq[p + k] == tk;
+                            if (!wballot(cand)) break;
+                        }
+                        found = wballot(cand) != 0ull;
+                    }
+                }
+                ok = found;
+            }
+        }
+        if (!ok) keep &= ~(1ull << b);
+    }
+    if (keep != x0 && lane == 0) *at = keep;
+}
+
 __global__ __launch_bounds__(256) void gz_bm25_sr_score_kernel(GzBm25Search A)
 {
     const GzBm25Score& S = A.S;                               // (the index's arrays and the parameters; the query arrays are A's)
@@ -287,6 +364,9 @@ void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStr
     }
     case GZ_BM25_SR_DRIVER: if (A.n_qw > 0) hipLaunchKernelGGL(gz_bm25_sr_driver_kernel, dim3(bm_grid(rows, 256)), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_FILTER: hipLaunchKernelGGL(gz_bm25_sr_filter_kernel, dim3(bm_grid(A.w64, 256), (unsigned)rows), dim3(256), 0, s, A); break;
+    case GZ_BM25_SR_PHRASE:
+        hipLaunchKernelGGL(gz_bm25_sr_phrase_kernel, dim3(bm_grid(A.w64, BM_WPB), (unsigned)rows), dim3(WAVE * BM_WPB), 0, s, A);
+        break;
     case GZ_BM25_SR_COUNT: hipLaunchKernelGGL(gz_bm25_sr_count_kernel, dim3((unsigned)A.n_tiles, (unsigned)rows), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_ROWS: hipLaunchKernelGGL(gz_bm25_sr_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, A); break;
     case GZ_BM25_SR_CAND: if (A.M > 0) hipLaunchKernelGGL(gz_bm25_sr_cand_kernel, dim3((unsigned)A.n_tiles, (unsigned)rows), dim3(256), 0, s, A); break;

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("GZ_LIBRARY") or os.path.join(_HERE, "libgenz_tokenize
 
 GZ_OK, GZ_E_INVALID, GZ_E_UTF8, GZ_E_HIP, GZ_E_NOTABLES = 0, -1, -2, -3, -4
 GZ_E_CAPACITY, GZ_E_LIMIT, GZ_E_NOMEM, GZ_E_RCCL, GZ_E_NODEVICE = -5, -6, -7, -8, -9
+GZ_BM25_POSITIONS, GZ_BM25_PHRASE_MAX = 1, 64
 GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP_WORDS = 0x1, 0x2, 0x4, 0x100, 0x200, 0x400
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
@@ -36,6 +37,8 @@ SYMBOLS = [
     "gz_bm25_compact", "gz_bm25_terms", "gz_bm25_footprint",
     "gz_bm25_search", "gz_bm25_search_device", "gz_bm25_match_count",
     "gz_bm25_search_bool", "gz_bm25_search_bool_device", "gz_bm25_match_count_bool",
+    "gz_bm25_build_ex", "gz_bm25_build_device_ex", "gz_bm25_flags", "gz_bm25_sequence",
+    "gz_bm25_search_phrase", "gz_bm25_search_phrase_device", "gz_bm25_match_count_phrase",
 ]
 
 _lib = None
@@ -145,6 +148,14 @@ def load_library():
         L.gz_bm25_search_bool.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.gz_bm25_search_bool_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.gz_bm25_match_count_bool.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp]
+    if hasattr(L, "gz_bm25_search_phrase"):
+        L.gz_bm25_build_ex.argtypes = [vp, vp, vp, i64, i32, P(vp)]
+        L.gz_bm25_build_device_ex.argtypes = [vp, vp, vp, i64, i64, i32, P(vp)]
+        L.gz_bm25_flags.argtypes = [vp, P(i32)]
+        L.gz_bm25_sequence.argtypes = [vp, vp, vp]
+        L.gz_bm25_search_phrase.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_bm25_search_phrase_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_bm25_match_count_phrase.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -484,19 +495,42 @@ class Context:
         return total.value
 
     # ---- BM25 index (ranking.py) ----------------------------------------------------------------------------
-    def bm25_build(self, text: np.ndarray, text_off: np.ndarray) -> int:
-        """packed UTF-8 + int64 offsets -> a gz_bm25 handle (int), owned by this context."""
+    def bm25_build(self, text: np.ndarray, text_off: np.ndarray, positions: bool = False) -> int:
+        """packed UTF-8 + int64 offsets -> a gz_bm25 handle (int), owned by this context.  positions: a positional index
+        (gz_bm25_build_ex with GZ_BM25_POSITIONS), which keeps every word's term id for phrase searches; else gz_bm25_build."""
         text = np.ascontiguousarray(text, dtype=np.uint8)
         text_off = np.ascontiguousarray(text_off, dtype=np.int64)
         h = C.c_void_p()
-        self._check(self.lib.gz_bm25_build(self.handle, _ptr(text) if len(text) else None, _ptr(text_off), len(text_off) - 1, C.byref(h)))
+        args = [self.handle, _ptr(text) if len(text) else None, _ptr(text_off), len(text_off) - 1]
+        if positions:
+            self._check(self.lib.gz_bm25_build_ex(*args, GZ_BM25_POSITIONS, C.byref(h)))
+        else:
+            self._check(self.lib.gz_bm25_build(*args, C.byref(h)))
         return h.value
 
-    def bm25_build_device(self, d_text, d_off, n_docs: int, text_bytes: int) -> int:
+    def bm25_build_device(self, d_text, d_off, n_docs: int, text_bytes: int, positions: bool = False) -> int:
         h = C.c_void_p()
-        self._check(self.lib.gz_bm25_build_device(self.handle, C.c_void_p(d_text) if d_text else None, C.c_void_p(d_off), n_docs, text_bytes,
-                                                  C.byref(h)))
+        args = [self.handle, C.c_void_p(d_text) if d_text else None, C.c_void_p(d_off), n_docs, text_bytes]
+        if positions:
+            self._check(self.lib.gz_bm25_build_device_ex(*args, GZ_BM25_POSITIONS, C.byref(h)))
+        else:
+            self._check(self.lib.gz_bm25_build_device(*args, C.byref(h)))
         return h.value
+
+    def bm25_flags(self, index: int) -> int:
+        """the flags the index was built with (GZ_BM25_POSITIONS or 0)"""
+        f = C.c_int32()
+        self._check(self.lib.gz_bm25_flags(C.c_void_p(index), C.byref(f)))
+        return f.value
+
+    def bm25_sequence(self, index: int):
+        """(terms int32 [n_words], offsets int64 [documents + 1]) of a positional index: the term id of every word, documents in id
+        order, words in str.split() order; document d = terms[offsets[d]:offsets[d + 1]].  GzError (GZ_E_INVALID) without positions."""
+        n, _, w = self.bm25_info(index)
+        terms = np.empty(max(w, 1), dtype=np.int32)
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._check(self.lib.gz_bm25_sequence(C.c_void_p(index), _ptr(terms), _ptr(off)))
+        return terms[:w], off
 
     def bm25_append(self, index: int, text: np.ndarray, text_off: np.ndarray) -> None:
         """packed UTF-8 + int64 offsets of more documents behind the index's own: afterwards it answers as one built over all of
@@ -609,11 +643,13 @@ class Context:
 
     def bm25_search(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool, k: int,
                     d_ids: int | None = None, d_scores: int | None = None, d_counts: int | None = None,
-                    mode: int = 0, ex_terms=None, ex_off=None):
+                    mode: int = 0, ex_terms=None, ex_off=None, ph_terms=None, ph_off=None):
         """(ids int64 [Q, k'], scores float64 [Q, k'], counts int64 [Q]) with k' = min(k, documents): the best MATCHING documents of
         every query and how many match; positions behind a row's count hold -1 / NaN.  A document matches when it holds at least
         one of the query's words (mode 0) or every one of them (mode 1), and none of the terms ex_terms[ex_off[q]:ex_off[q + 1]]
         (ex_off None: no exclusions).  With mode 0 and ex_off None the call is gz_bm25_search[_device], else gz_bm25_search_bool[_device].
+        ph_off (None: no phrases) / ph_terms: the terms ph_terms[ph_off[q]:ph_off[q + 1]] must stand next to each other in this order
+        in the document (a positional index only): the call is gz_bm25_search_phrase[_device].
         With d_ids / d_scores / d_counts (device pointers, all three): enqueued into them, sync() waits."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         idf = np.ascontiguousarray(idf, dtype=np.float64)
@@ -623,12 +659,17 @@ class Context:
         nq = len(query_off) - 1
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
                 1 if plus else 0, int(k)]
-        plain = mode == 0 and ex_off is None
+        plain = mode == 0 and ex_off is None and ph_off is None
         if not plain:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
             args += [int(mode)] + ex
+        if ph_off is not None:
+            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
+            args += ph
         if d_ids is not None or d_scores is not None or d_counts is not None:
             fn = self.lib.gz_bm25_search_device if plain else self.lib.gz_bm25_search_bool_device
+            if ph_off is not None:
+                fn = self.lib.gz_bm25_search_phrase_device
             self._check(fn(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
             return None
         kk = max(0, min(int(k), self.bm25_info(index)[0]))
@@ -636,6 +677,8 @@ class Context:
         scores = np.empty((nq, kk), dtype=np.float64)
         counts = np.zeros(max(nq, 1), dtype=np.int64)
         fn = self.lib.gz_bm25_search if plain else self.lib.gz_bm25_search_bool
+        if ph_off is not None:
+            fn = self.lib.gz_bm25_search_phrase
         self._check(fn(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
         return ids, scores, counts[:nq]
 
@@ -650,15 +693,20 @@ class Context:
         return ex_terms, ex_off, [_ptr(ex_terms) if len(ex_terms) else None, _ptr(ex_off)]
 
     def bm25_match_count(self, index: int, terms: np.ndarray, query_off: np.ndarray, mode: int = 0, ex_terms=None,
-                         ex_off=None) -> np.ndarray:
-        """int64 [Q]: the documents that match each query -- counts of bm25_search alone (mode, ex_terms, ex_off as there; with
-        mode 0 and ex_off None the call is gz_bm25_match_count, else gz_bm25_match_count_bool)."""
+                         ex_off=None, ph_terms=None, ph_off=None) -> np.ndarray:
+        """int64 [Q]: the documents that match each query -- counts of bm25_search alone (mode, ex_terms, ex_off, ph_terms, ph_off as
+        there; with mode 0 and ex_off None the call is gz_bm25_match_count, else gz_bm25_match_count_bool; with ph_off
+        gz_bm25_match_count_phrase)."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         query_off = np.ascontiguousarray(query_off, dtype=np.int64)
         nq = len(query_off) - 1
         counts = np.zeros(max(nq, 1), dtype=np.int64)
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq]
-        if mode == 0 and ex_off is None:
+        if ph_off is not None:
+            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
+            self._check(self.lib.gz_bm25_match_count_phrase(*args, int(mode), *ex, *ph, _ptr(counts)))
+        elif mode == 0 and ex_off is None:
             self._check(self.lib.gz_bm25_match_count(*args, _ptr(counts)))
         else:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)

@@ -22,6 +22,17 @@ Boolean search: `search(queries, k, match="all")` keeps only the documents that 
 the ones that lack a word or hold an excluded one (gz_bm25_search_bool).  Scores, order and padding are those of `search`; excluded
 words never enter a score.  With the defaults the call is the plain search, unchanged.
 
+Phrase search: an index built with `positions=True` additionally keeps, on the GPU, the term id of every word of every document
+in order (`seq`, uint32 [all words]; document d is seq[woff[d]:woff[d+1]] with woff the scan of fieldLens, derived on the device
+when first needed; `term_sequences()` reads both back), and `add_documents`, `remove_documents` and `compact` maintain it like
+every other array of the index.  Such an index never needs the documents' text again, so its build ends in the form `compact()`
+gives (the text copy holds the terms' bytes only): a compacted positional index equals a fresh positional build of its documents,
+`footprint()` included.  `search(queries, k, phrase=[...])` (one string per query, with either match and with exclude; also
+on `count_matches`) then keeps only the documents in which the phrase's words stand next to each other in this order:
+`documents[d].split()[i:i+len(P)] == P` for some i.  One more kernel behind the marking and the filter (gz_bm25_sr_phrase_kernel)
+rejects a marked document that lacks a phrase word, else walks its slice of seq.  The phrase is a filter only: its words enter no
+score.  An index built without positions is the same index as before, buffer for buffer, and refuses `phrase=` with ValueError.
+
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
@@ -71,13 +82,15 @@ def _strings(items, what: str) -> list:
 
 
 class BM25:
-    def __init__(self, documents: List, b: float = 0.75, k1: float = 1.2, ctx: Optional[_native.Context] = None) -> None:
+    def __init__(self, documents: List, b: float = 0.75, k1: float = 1.2, ctx: Optional[_native.Context] = None,
+                 positions: bool = False) -> None:
         self.b = b
         self.k1 = k1
         self._texts = _strings(documents, "documents")
         self._ctx = ctx or _context()
+        self._positions = bool(positions)
         buf, off = _pack(self._texts)
-        self._index = self._ctx.bm25_build(buf, off)
+        self._index = self._ctx.bm25_build(buf, off, positions=True) if self._positions else self._ctx.bm25_build(buf, off)
         # (the finalizer holds the context: the index is freed before it)
         self._finalizer = weakref.finalize(self, self._ctx.bm25_destroy, self._index)
         self.num_doc = len(self._texts)
@@ -154,6 +167,15 @@ class BM25:
         raw = data.tobytes()
         off = off.tolist()
         return [raw[off[i]:off[i + 1]].decode("utf-8", "surrogatepass") for i in range(len(off) - 1)], df
+
+    def term_sequences(self):
+        """(terms int32 [all words], offsets int64 [num_doc + 1]) of an index built with positions=True: the term id of every word,
+        documents in id order, words in str.split() order; document d is terms[offsets[d]:offsets[d + 1]].  The ids are those
+        `_lookup` answers; on a compacted (or freshly built) index vocabulary()[0][terms[i]] is the i-th word.  ValueError on an
+        index without positions."""
+        if not getattr(self, "_positions", False):
+            raise ValueError("the index was built without positions=True")
+        return self._ctx.bm25_sequence(self._index)
 
     def footprint(self) -> dict:
         """{"text_bytes": bytes of the index's text copy (what the 2^32 limit of add_documents counts), "table_terms": terms held in
@@ -264,17 +286,24 @@ class BM25:
         terms = self._lookup(words)[0] if words else np.zeros(0, np.int32)
         return terms, xoff
 
-    def _bool_args(self, queries, match, exclude):
-        """validation of search / count_matches, all of it before any native call -> (queries, mode, exclude)"""
+    def _bool_args(self, queries, match, exclude, phrase=None):
+        """validation of search / count_matches, all of it before any native call -> (queries, mode, exclude, phrase)"""
         mode = self._match(match)
         queries = _strings(queries, "queries")
         if exclude is not None:
             exclude = _strings(exclude, "exclude")
             if len(exclude) != len(queries):
                 raise ValueError("exclude has %d items for %d queries" % (len(exclude), len(queries)))
-        return queries, mode, exclude
+        if phrase is not None:
+            phrase = _strings(phrase, "phrase")
+            if len(phrase) != len(queries):
+                raise ValueError("phrase has %d items for %d queries" % (len(phrase), len(queries)))
+            if not getattr(self, "_positions", False):
+                raise ValueError("phrase needs an index built with positions=True")
+        return queries, mode, exclude, phrase
 
-    def search(self, queries: Sequence[str], k: int, match: str = "any", exclude: Optional[Sequence[str]] = None):
+    def search(self, queries: Sequence[str], k: int, match: str = "any", exclude: Optional[Sequence[str]] = None,
+               phrase: Optional[Sequence[str]] = None):
         """(ids int64 [len(queries), k'], scores float64 [len(queries), k'], counts int64 [len(queries)]), k' = min(k, num_doc).
         With R = set(queries[q].split()), X = set(exclude[q].split()) (empty for exclude=None) and W(d) the words of document d:
         match="any": d matches q iff R & W(d) and not X & W(d); match="all": d matches iff R and R <= W(d) and not X & W(d) (a query
@@ -284,25 +313,38 @@ class BM25:
         [i for i in np.argsort(-get_scores(queries)[q], kind="stable") if d_i matches][:k'] and their scores (original bits);
         positions from counts[q] on hold id -1 and NaN (bits 0x7FF8000000000000).  Only the matching documents are scored, on the
         GPU; with match="all" only the documents of each query's rarest word are looked at.  k' above 1024 raises
-        _native.GzError (GZ_E_LIMIT).  exclude: None or one str per query (ValueError for another length)."""
+        _native.GzError (GZ_E_LIMIT).  exclude: None or one str per query (ValueError for another length).
+        phrase: None or one str per query (ValueError for another length, or on an index built without positions=True).  With
+        P = phrase[q].split(), d matches iff it matches as above AND (P is empty or documents[d].split()[i:i+len(P)] == P for some
+        i): a phrase word that no document holds matches nothing, a one-word phrase means "holds this word", a phrase never
+        matches across two documents.  The phrase is a filter only -- its words enter no score and no idf; put them into the
+        query to have them scored.  More than 64 words in a phrase raise _native.GzError (GZ_E_LIMIT)."""
         k = self._k(k)
-        queries, mode, exclude = self._bool_args(queries, match, exclude)
+        queries, mode, exclude, phrase = self._bool_args(queries, match, exclude, phrase)
         nq, terms, idf, qoff = self._queries(queries)
         plus = isinstance(self, BM25Plus)
-        if mode == 0 and exclude is None:
+        if mode == 0 and exclude is None and phrase is None:
             return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k)
         xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
-        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff)
+        if phrase is None:
+            return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff)
+        pterms, poff = self._exclusions(phrase, nq)           # (the same packing: term -1 for a word no document holds)
+        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff,
+                                     ph_terms=pterms, ph_off=poff)
 
-    def count_matches(self, queries: Sequence[str], match: str = "any", exclude: Optional[Sequence[str]] = None) -> np.ndarray:
-        """int64 [len(queries)]: counts of search(queries, k, match, exclude) alone.  With the defaults: the documents that hold at
-        least one word of each query; for a query of one word, its df."""
-        queries, mode, exclude = self._bool_args(queries, match, exclude)
+    def count_matches(self, queries: Sequence[str], match: str = "any", exclude: Optional[Sequence[str]] = None,
+                      phrase: Optional[Sequence[str]] = None) -> np.ndarray:
+        """int64 [len(queries)]: counts of search(queries, k, match, exclude, phrase) alone.  With the defaults: the documents that
+        hold at least one word of each query; for a query of one word, its df."""
+        queries, mode, exclude, phrase = self._bool_args(queries, match, exclude, phrase)
         nq, terms, _, qoff = self._queries(queries)
-        if mode == 0 and exclude is None:
+        if mode == 0 and exclude is None and phrase is None:
             return self._ctx.bm25_match_count(self._index, terms, qoff)
         xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
-        return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
+        if phrase is None:
+            return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
+        pterms, poff = self._exclusions(phrase, nq)
+        return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff, ph_terms=pterms, ph_off=poff)
 
     def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
         """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].
@@ -328,6 +370,6 @@ class BM25:
 
 class BM25Plus(BM25):
     def __init__(self, documents: List, b: float = 0.75, k1: float = 1.2, delta: float = 1.0,
-                 ctx: Optional[_native.Context] = None) -> None:
-        super().__init__(documents, b, k1, ctx)
+                 ctx: Optional[_native.Context] = None, positions: bool = False) -> None:
+        super().__init__(documents, b, k1, ctx, positions)
         self.delta = delta

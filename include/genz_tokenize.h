@@ -377,6 +377,23 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *   gz_bm25_build_device   the same resident in HBM (offsets ABSOLUTE from the base pointer, text_bytes = text_off_dev[n_docs] -
  *                          text_off_dev[0]); a document outside those bytes is refused with GZ_E_INVALID.  The index keeps a copy
  *                          of the text: the caller's buffers may go once the call has returned.
+ *   gz_bm25_build_ex       gz_bm25_build with flags.  0: the same index, buffer for buffer.  GZ_BM25_POSITIONS: a POSITIONAL index,
+ *                          which additionally owns seq, uint32 [n_words]: the term id of every word of every document, documents in
+ *                          id order, words in str.split() order -- what a phrase search reads.  Its word offsets (document d =
+ *                          seq[woff[d] .. woff[d + 1]), the exclusive scan of fieldLens) are derived on the device by the first call
+ *                          that reads positions and dropped by every change, as the postings are.  Every call below maintains seq
+ *                          with the guarantees it gives for the other arrays: gz_bm25_append puts the batch's term ids behind the
+ *                          index's words (the buffer grows geometrically), gz_bm25_remove moves the kept documents' words into a
+ *                          fresh buffer, gz_bm25_compact renumbers them -- after it seq, like everything else, is the fresh
+ *                          positional build's -- and an error leaves the index as it was.  A positional build ends in the form a
+ *                          compaction gives: it never needs the documents' text again, so its text copy holds the terms' bytes only
+ *                          (out[0] of gz_bm25_footprint) and a compacted positional index equals a fresh positional build of its
+ *                          documents in every buffer, gz_bm25_footprint's three numbers included.  Another flag bit: GZ_E_INVALID.
+ *   gz_bm25_build_device_ex  gz_bm25_build_device with the same flags
+ *   gz_bm25_flags          the flags the index was built with
+ *   gz_bm25_sequence       the positional store read back into host memory: terms_out[n_words] = seq (n_words of gz_bm25_info; ids as
+ *                          gz_bm25_lookup answers them) and doc_off_out[n_docs + 1] = the word offsets.  GZ_E_INVALID on an index
+ *                          built without GZ_BM25_POSITIONS.  The index is not modified (the word offsets may be derived).
  *   gz_bm25_info           documents, distinct terms (those some document has), words (all documents)
  *   gz_bm25_field_lengths  fieldLens (ranking.py:21): words of every document, out[n_docs]
  *   gz_bm25_lookup         query words (packed like documents, host buffers) -> term id (-1 when no document has it) and df
@@ -429,6 +446,23 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          gz_bm25_search's.
  *   gz_bm25_search_bool_device  the same with the three outputs in HBM, as gz_bm25_search_device
  *   gz_bm25_match_count_bool    count_out[q] of gz_bm25_search_bool alone (host memory)
+ *   gz_bm25_search_phrase  gz_bm25_search_bool with an exact phrase per query on top.  With P = ph_terms[ph_off[q] .. ph_off[q + 1])
+ *                          (the ex_terms / ex_off conventions: absolute int64 offsets, ids as gz_bm25_lookup answers them, -1 = a
+ *                          word no document holds; ph_off NULL: no phrases, the call is gz_bm25_search_bool) and seq(d) the term
+ *                          ids of document d's words in order: d matches q iff it matches under mode and ex_terms as there AND P
+ *                          is empty or seq(d)[i .. i + len(P)) == P for some i.  So a phrase with a term -1 matches nothing, a
+ *                          phrase of one word means "holds this word", a phrase never matches across two documents, and a phrase
+ *                          with repeated words finds overlapping starts.  The phrase is a filter only: its terms enter no score;
+ *                          S, the order, count_out, the rows and their padding are gz_bm25_search's with this set of matching
+ *                          documents.  Needs an index built with GZ_BM25_POSITIONS (else GZ_E_INVALID, also for empty phrases);
+ *                          GZ_E_INVALID: a phrase id outside [-1, n_terms), ph_off decreasing, a non-empty range with ph_terms
+ *                          NULL; GZ_E_LIMIT: a phrase of more than GZ_BM25_PHRASE_MAX words; every other error as
+ *                          gz_bm25_search_bool.  On any error the index answers every call as before.  One more stage behind the
+ *                          marking and the filter: a wave per 64-bit word of a row's bitmap rejects a marked document that lacks
+ *                          a phrase term (signature, pair table), else walks the document's range of seq, 64 start positions a
+ *                          trip, comparing the phrase's rarest term first; everything behind the bitmap is gz_bm25_search's.
+ *   gz_bm25_search_phrase_device  the same with the three outputs in HBM, as gz_bm25_search_device
+ *   gz_bm25_match_count_phrase    count_out[q] of gz_bm25_search_phrase alone (host memory)
  *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
@@ -469,16 +503,24 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          bytes_cap < B: GZ_E_CAPACITY, nothing written.  term_off and bytes both NULL: GZ_E_INVALID.
  *   gz_bm25_footprint      host bookkeeping, no device work: out[0] = bytes of the text copy in use (what GZ_E_LIMIT of an append
  *                          counts), out[1] = terms held in the term table, dead ones included, out[2] = device bytes allocated
- *                          to the index's ten buffers, capacities included, and to its postings while they exist
+ *                          to the index's ten buffers, capacities included, to its postings while they exist and, for a
+ *                          positional index, to seq and (while they exist) the word offsets
  * Switch bm25_hash_bits (gz_debug_set, read when an index is built): keep only the low k bits of the words' hash (collisions are
  * resolved by comparing bytes, so results do not change). */
 #define GZ_BM25_TOPK_MAX 1024
 #define GZ_BM25_MATCH_ANY 0
 #define GZ_BM25_MATCH_ALL 1
+#define GZ_BM25_POSITIONS 1
+#define GZ_BM25_PHRASE_MAX 64
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
                           gz_bm25 **out);
+int  gz_bm25_build_ex(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, int32_t flags, gz_bm25 **out);
+int  gz_bm25_build_device_ex(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
+                             int32_t flags, gz_bm25 **out);
+int  gz_bm25_flags(gz_bm25 *index, int32_t *flags);
+int  gz_bm25_sequence(gz_bm25 *index, int32_t *terms_out /* n_words */, int64_t *doc_off_out /* n_docs + 1 */);
 int  gz_bm25_info(gz_bm25 *index, int64_t *n_docs, int64_t *n_terms, int64_t *n_words);
 int  gz_bm25_field_lengths(gz_bm25 *index, int32_t *out);
 int  gz_bm25_lookup(gz_bm25 *index, const uint8_t *words, const int64_t *word_off, int64_t n_words, int32_t *term_out, int32_t *df_out);
@@ -504,6 +546,16 @@ int  gz_bm25_search_bool_device(gz_bm25 *index, const int32_t *terms, const doub
                                 const int64_t *ex_off, int64_t *doc_out_dev, double *score_out_dev, int64_t *count_out_dev);
 int  gz_bm25_match_count_bool(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
                               const int32_t *ex_terms, const int64_t *ex_off, int64_t *count_out);
+int  gz_bm25_search_phrase(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                           const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms, const int64_t *ex_off,
+                           const int32_t *ph_terms, const int64_t *ph_off, int64_t *doc_out, double *score_out, int64_t *count_out);
+int  gz_bm25_search_phrase_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                                  const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms,
+                                  const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off, int64_t *doc_out_dev,
+                                  double *score_out_dev, int64_t *count_out_dev);
+int  gz_bm25_match_count_phrase(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
+                                const int32_t *ex_terms, const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off,
+                                int64_t *count_out);
 int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);

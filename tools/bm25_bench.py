@@ -2,6 +2,7 @@
 
     python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--compact 10000] [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --search-only [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --phrase-only [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -53,6 +54,17 @@ rows; --compact-only: these rows alone, and with --out they are merged into the 
   footprint_before / footprint_after  gz_bm25_footprint (text bytes in use, terms in the table, device bytes) around the compaction
   restate_q64_ms       the numpy restatement (tests/bm25_restate.py) scoring 64 queries on the host, on --restate-docs documents,
                        its postings built beforehand (not timed)
+Phrase (gz_bm25_build_device_ex with GZ_BM25_POSITIONS, gz_bm25_search_phrase_device; --phrase-only: these rows alone, and with --out
+they are merged into the file's record instead of replacing it):
+  phrase_build_device_ms / phrase_build_positions_device_ms  gz_bm25_build_device[_ex] without and with positions, alternating in
+                       one loop; phrase_device_bytes / phrase_positions_device_bytes: gz_bm25_footprint's device bytes of each
+  phrase_all_q256_k10_ms   256 queries of two words -- two neighbouring words of one document each (fixed seed) -- in mode "all" without
+                       a phrase (gz_bm25_search_bool_device + gz_sync): what the index could answer before.  A library without the
+                       phrase entry points (an older build through GZ_LIBRARY) gives this row and the plain build alone
+  phrase_search_q256_k10_ms  the same queries in mode "all" with the two words as the phrase (gz_bm25_search_phrase_device), timed
+                       in the same loop, alternating with the row above, after a warm call of each that has derived the word offsets
+  phrase_any_q256_k10_ms   the same with mode "any": every document with one of the two words is marked and goes through the phrase step
+  phrase_match_fraction_all / _phrase / _any_phrase   mean(count) / N over the 256 queries
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
 import argparse
 import json
@@ -315,6 +327,77 @@ def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_id
         res["search_rare_q%d_k10_over_topk" % q] = round(res["search_rare_q%d_k10_ms" % q] / res["topk_rare_q%d_k10_ms" % q], 3)
 
 
+def phrase_rows(ctx, res, t, o, reps):
+    """the phrase rows of the docstring"""
+    n, nbytes = len(o) - 1, int(o[-1])
+    new = hasattr(ctx.lib, "gz_bm25_search_phrase_device")
+    d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
+    ctx.h2d(d_text, t)
+    ctx.h2d(d_off, o)
+    ts = {False: [], True: []}
+    kept = {}
+    for rep in range(reps + 1):                                      # (the first round is the warm-up of both)
+        for pos in (False, True) if new else (False,):
+            t0 = time.perf_counter()
+            ix = ctx.bm25_build_device(d_text, d_off, n, nbytes, positions=True) if pos else ctx.bm25_build_device(d_text, d_off, n, nbytes)
+            if rep:
+                ts[pos].append((time.perf_counter() - t0) * 1e3)
+            if rep == reps:
+                kept[pos] = ix
+            else:
+                ctx.bm25_destroy(ix)
+    res["phrase_build_device_ms"], res["phrase_build_device_all_ms"] = float(np.median(ts[False])), [round(x, 3) for x in ts[False]]
+    res["phrase_device_bytes"] = ctx.bm25_footprint(kept[False])[2]
+    if new:
+        res["phrase_build_positions_device_ms"] = float(np.median(ts[True]))
+        res["phrase_build_positions_device_all_ms"] = [round(x, 3) for x in ts[True]]
+        res["phrase_positions_device_bytes"] = ctx.bm25_footprint(kept[True])[2]
+        ctx.bm25_destroy(kept[False])
+    ix = kept[new]
+    raw = t.tobytes()
+    rng = np.random.default_rng(5)
+    pairs = []
+    while len(pairs) < 256:
+        i = int(rng.integers(n))
+        ws = raw[o[i]:o[i + 1]].decode("utf-8").split()
+        if len(ws) >= 2:
+            j = int(rng.integers(len(ws) - 1))
+            pairs.append(ws[j:j + 2])
+    wb, wo = pack([w for p in pairs for w in p])
+    terms, df = ctx.bm25_lookup(ix, wb, wo)
+    assert (terms >= 0).all()
+    idf = np.array([np.log(1+(n-int(d)+0.5)/(int(d)+0.5)) for d in df])
+    qoff = np.arange(257, dtype=np.int64) * 2
+    lens = ctx.bm25_field_lengths(ix)
+    params = [2.2, 1.2, 0.25, 0.75, float(np.mean(lens)), 0.0]
+    d_ids, d_sc, d_cnt = ctx.alloc(256 * 10 * 8), ctx.alloc(256 * 10 * 8), ctx.alloc(256 * 8)
+    rows = [("phrase_all_q256_k10", 1, False, "phrase_match_fraction_all")]
+    if new:
+        rows += [("phrase_search_q256_k10", 1, True, "phrase_match_fraction_phrase"), ("phrase_any_q256_k10", 0, True, "phrase_match_fraction_any_phrase")]
+    ts = {r[0]: [] for r in rows}
+    for rep in range(reps + 1):                                      # (the first round is the warm-up of all)
+        for key, mode, phrase, frac in rows:
+            kw = dict(ph_terms=terms, ph_off=qoff) if phrase else {}
+            t0 = time.perf_counter()
+            ctx.bm25_search(ix, terms, idf, qoff, params, False, 10, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt, mode=mode, **kw)
+            ctx.sync()
+            if rep:
+                ts[key].append((time.perf_counter() - t0) * 1e3)
+            if rep == reps:
+                cnt = np.empty(256, np.int64)
+                ctx.d2h(cnt, d_cnt)
+                res[frac] = float(cnt.mean() / n)
+                if phrase:
+                    assert (cnt >= 1).all()                          # (every phrase was taken from a document)
+    for key, _, _, _ in rows:
+        res[key + "_ms"], res[key + "_all_ms"] = float(np.median(ts[key])), [round(x, 3) for x in ts[key]]
+    if new:
+        res["phrase_over_all"] = round(res["phrase_search_q256_k10_ms"] / res["phrase_all_q256_k10_ms"], 3)
+    for d in (d_ids, d_sc, d_cnt, d_text, d_off):
+        ctx.free(d)
+    ctx.bm25_destroy(ix)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -329,6 +412,7 @@ def main():
     ap.add_argument("--compact", type=int, default=10_000, help="documents removed before the compact rows (0: skip them)")
     ap.add_argument("--compact-only", action="store_true", help="only the compact rows; with --out they are merged into the file")
     ap.add_argument("--search-only", action="store_true", help="only the build, top-k (k = 10) and search rows; with --out they are merged into the file")
+    ap.add_argument("--phrase-only", action="store_true", help="only the phrase rows; with --out they are merged into the file")
     a = ap.parse_args()
     if a.search_only:
         a.remove = a.compact = a.append = 0
@@ -336,6 +420,16 @@ def main():
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
     res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
+    if a.phrase_only:
+        phrase_rows(ctx, res, t, o, a.reps)
+        print(json.dumps(res))
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith("phrase_")})
+            old["phrase_rows_run"] = dict(docs=n, reps=a.reps)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
     if a.compact_only:
         compact_rows(ctx, res, n, a.compact, a.reps)
         line = json.dumps(res)
