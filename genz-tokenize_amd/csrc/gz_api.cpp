@@ -174,7 +174,7 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
-    DBuf w_bm[56];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
+    DBuf w_bm[64];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
@@ -976,6 +976,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_S_CAND, BMW_S_CSC, BMW_S_POS, BMW_S_PSC,
        BMW_S_XTERM, BMW_S_XOFF,                                                     // the excluded terms of a boolean search
        BMW_S_PHTERM, BMW_S_PHOFF,                                                   // the phrase terms of a phrase search
+       BMW_SN_IDS, BMW_SN_OUT, BMW_SN_CNT, BMW_SN_OFF, BMW_SN_POS, BMW_SN_WORD,     // snippets and occurrences (bm25_snip_*)
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1871,6 +1872,126 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
             r0 += n;
         }
     }
+    return GZ_OK;
+}
+
+// ---- snippets (gz_bm25_snippets, gz_bm25_occurrences; gz_snippet.inc) ------------------------------------------------------------
+// what the snippet entry points check before anything is launched: a positional index, the packed query terms, k
+int bm25_snip_args(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, int64_t k)
+{
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!(ix->flags & GZ_BM25_POSITIONS)) return fail(c, GZ_E_INVALID, "snippets need an index built with GZ_BM25_POSITIONS");
+    int rc = bm25_match_args(ix, terms, qoff, nq, ix);         // (the outputs are checked by the caller)
+    if (rc) return rc;
+    if (k < 0) return fail(c, GZ_E_INVALID, "k = %lld; snippets take k >= 0", (long long)k);
+    if (k > 0 && nq > (((int64_t)1 << 31) - 1) / k) return fail(c, GZ_E_LIMIT, "%lld queries x %lld documents; a call takes fewer than 2^31 pairs", (long long)nq, (long long)k);
+    return GZ_OK;
+}
+
+// the ids of a host form lie in [-1, n_docs) (ids in HBM are not looked at here: the kernels treat a bad one as -1)
+int bm25_snip_ids(gz_bm25* ix, const int64_t* ids, int64_t n)
+{
+    for (int64_t r = 0; r < n; ++r)
+        if (ids[r] < -1 || ids[r] >= ix->n_docs)
+            return fail(ix->c, GZ_E_INVALID, "document id %lld outside [-1, %lld)", (long long)ids[r], (long long)ix->n_docs);
+    return GZ_OK;
+}
+
+// the query arrays into the context's workspace, the word offsets derived if they are not there (nothing else is: no postings),
+// and the kernels' arguments but for ids and outputs
+int bm25_snip_in(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, int64_t k, GzBm25Snip& A)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    int rc;
+    if ((rc = bm25_word_offsets(ix))) return rc;
+    GzBm25Score S;
+    if ((rc = bm25_query_in(ix, terms, nullptr, qoff, nq, nullptr, 0, S)) || (rc = bm_alloc(c, w[BMW_CTL], 64))) return rc;
+    A = GzBm25Snip{};
+    A.seq = (const uint32_t*)ix->seq.p; A.woff = (const uint32_t*)ix->woff.p; A.n_words = ix->n_words; A.n_docs = ix->n_docs;
+    A.qterm = S.qterm; A.qoff = S.qoff;
+    A.n_pairs = nq * k; A.k = k; A.width = 1;
+    A.ctl = (uint32_t*)w[BMW_CTL].p;
+    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, c->stream));
+    return GZ_OK;
+}
+
+int bm25_snip_flag(gz_ctx* c, const GzBm25Snip& A)
+{
+    int64_t bad = 0;
+    int rc = bm_read_u32(c, A.ctl + 1, bad);
+    if (rc) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, GZ_E_HIP, "BM25 snippets: the index's fieldLens and word sequence contradict each other");
+    return GZ_OK;
+}
+
+// ids_dev / start_dev / hits_dev in HBM, or (ids_dev null) ids_host in and start_host / hits_host out through the workspace
+int bm25_snippets_locked(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, int64_t k, int64_t width, const int64_t* ids_dev,
+                         int32_t* start_dev, int32_t* hits_dev, const int64_t* ids_host, int32_t* start_host, int32_t* hits_host)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = nq * k;
+    if (n == 0) return GZ_OK;
+    GzBm25Snip A;
+    int rc = bm25_snip_in(ix, terms, qoff, nq, k, A);
+    if (rc) return rc;
+    A.width = width;
+    if (ids_dev) {
+        A.ids = ids_dev; A.start_out = start_dev; A.hits_out = hits_dev;
+    } else {
+        if ((rc = bm_alloc(c, w[BMW_SN_IDS], (size_t)n * 8)) || (rc = bm_alloc(c, w[BMW_SN_OUT], (size_t)n * 8)) ||
+            (rc = copy_in(c, w[BMW_SN_IDS].p, ids_host, (size_t)n * 8, s)))
+            return rc;
+        A.ids = (const int64_t*)w[BMW_SN_IDS].p; A.start_out = (int32_t*)w[BMW_SN_OUT].p; A.hits_out = A.start_out + n;
+    }
+    gz_launch_bm25_snippet(GZ_BM25_SN_WINDOW, A, s);
+    if ((rc = bm25_snip_flag(c, A))) return rc;
+    if (ids_dev) return GZ_OK;
+    if ((rc = copy_out(c, start_host, A.start_out, (size_t)n * 4, s)) || (rc = copy_out(c, hits_host, A.hits_out, (size_t)n * 4, s))) return rc;
+    return GZ_OK;
+}
+
+int bm25_occurrences_locked(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, const int64_t* ids, int64_t k, int64_t* pair_off,
+                            int32_t* pos_out, int32_t* word_out, int64_t cap)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = nq * k;
+    if (n == 0) { pair_off[0] = 0; return GZ_OK; }
+    GzBm25Snip A;
+    int rc = bm25_snip_in(ix, terms, qoff, nq, k, A);
+    if (rc) return rc;
+    if ((rc = bm_alloc(c, w[BMW_SN_IDS], (size_t)n * 8)) || (rc = bm_alloc(c, w[BMW_SN_CNT], (size_t)n * 4)) ||
+        (rc = bm_alloc(c, w[BMW_SN_OFF], (size_t)(n + 1) * 4)) || (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(n / 4096 + 2) * 4)) ||
+        (rc = copy_in(c, w[BMW_SN_IDS].p, ids, (size_t)n * 8, s)))
+        return rc;
+    A.ids = (const int64_t*)w[BMW_SN_IDS].p; A.cnt = (uint32_t*)w[BMW_SN_CNT].p; A.base = (const uint32_t*)w[BMW_SN_OFF].p;
+    gz_launch_bm25_snippet(GZ_BM25_SN_COUNT, A, s);
+    if ((rc = bm_scan(c, A.cnt, n, (uint32_t*)w[BMW_SN_OFF].p))) return rc;
+    unsigned long long all = 0;                               // the 64-bit sum: the scan's total is only its low half
+    if ((rc = copy_out_small(c, &all, A.ctl + 4, 8, s)) || (rc = bm25_snip_flag(c, A))) return rc;
+    if (all >= (1ull << 32)) return fail(c, GZ_E_LIMIT, "%llu occurrences; a call takes fewer than 2^32", all);
+    const int64_t T = (int64_t)all;
+    if (pos_out && cap < T) return fail(c, GZ_E_CAPACITY, "BM25 occurrences: %lld of them, room for %lld", (long long)T, (long long)cap);
+    alloc_site(c);
+    std::vector<uint32_t> off((size_t)n + 1);
+    if ((rc = copy_out(c, off.data(), A.base, (size_t)(n + 1) * 4, s))) return rc;
+    if ((int64_t)off[(size_t)n] != T) return fail(c, GZ_E_HIP, "BM25 occurrences: the counts sum to %lld, their scan ends at %lld", (long long)T, (long long)off[(size_t)n]);
+    if (pos_out && T > 0) {
+        if ((rc = bm_alloc(c, w[BMW_SN_POS], (size_t)T * 4)) || (rc = bm_alloc(c, w[BMW_SN_WORD], (size_t)T * 4))) return rc;
+        A.pos_out = (int32_t*)w[BMW_SN_POS].p; A.word_out = (int32_t*)w[BMW_SN_WORD].p;
+        gz_launch_bm25_snippet(GZ_BM25_SN_FILL, A, s);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = copy_out(c, pos_out, A.pos_out, (size_t)T * 4, s)) || (rc = copy_out(c, word_out, A.word_out, (size_t)T * 4, s))) return rc;
+    }
+    for (int64_t r = 0; r <= n; ++r) pair_off[r] = (int64_t)off[(size_t)r];
     return GZ_OK;
 }
 }  // namespace
@@ -3808,6 +3929,43 @@ try {
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
                               mode, ex_terms, ex_off, ph_terms, ph_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_snippets(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids, int64_t k, int64_t width,
+                     int32_t* start_out, int32_t* hits_out)
+try {
+    int rc = bm25_snip_args(ix, terms, query_off, n_queries, k);
+    if (rc) return rc;
+    gz_ctx* c = ix->c;
+    if (width < 1) return fail(c, GZ_E_INVALID, "width = %lld; a snippet takes width >= 1", (long long)width);
+    if (n_queries * k > 0 && (!ids || !start_out || !hits_out)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if ((rc = bm25_snip_ids(ix, ids, n_queries * k))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_snippets_locked(ix, terms, query_off, n_queries, k, width, nullptr, nullptr, nullptr, ids, start_out, hits_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_snippets_device(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids_dev, int64_t k,
+                            int64_t width, int32_t* start_out_dev, int32_t* hits_out_dev)
+try {
+    int rc = bm25_snip_args(ix, terms, query_off, n_queries, k);
+    if (rc) return rc;
+    gz_ctx* c = ix->c;
+    if (width < 1) return fail(c, GZ_E_INVALID, "width = %lld; a snippet takes width >= 1", (long long)width);
+    if (n_queries * k > 0 && (!ids_dev || !start_out_dev || !hits_out_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_snippets_locked(ix, terms, query_off, n_queries, k, width, ids_dev, start_out_dev, hits_out_dev, nullptr, nullptr, nullptr);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_occurrences(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids, int64_t k,
+                        int64_t* pair_off_out, int32_t* pos_out, int32_t* word_out, int64_t cap)
+try {
+    int rc = bm25_snip_args(ix, terms, query_off, n_queries, k);
+    if (rc) return rc;
+    gz_ctx* c = ix->c;
+    if (!pair_off_out || (n_queries * k > 0 && !ids) || (pos_out && (!word_out || cap < 0))) return fail(c, GZ_E_INVALID, "bad arguments");
+    if ((rc = bm25_snip_ids(ix, ids, n_queries * k))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_occurrences_locked(ix, terms, query_off, n_queries, ids, k, pair_off_out, pos_out, word_out, cap);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 void gz_bm25_destroy(gz_bm25* ix)

@@ -333,3 +333,19 @@ enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_
        GZ_BM25_SR_DRIVER, GZ_BM25_SR_FILTER, GZ_BM25_SR_PHRASE };
 // rows: of the chunk (WORDS, DRIVER, MARK, FILTER, PHRASE, COUNT, ROWS), else of the launch (from row0)
 void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStream_t s);
+
+// BM25 snippets (gz_snippet.inc): where the query's words stand inside given documents of a positional index.  A pair r is
+// (query r / k, document ids[r]); document d = seq[woff[d] .. woff[d + 1]).  An id outside [0, n_docs) is a pair without words.
+struct GzBm25Snip {
+    const uint32_t* seq; const uint32_t* woff; int64_t n_words, n_docs;
+    const int32_t* qterm; const int64_t* qoff;      // query q = terms qoff[q] .. qoff[q + 1] (absolute indices; -1 matches nothing)
+    const int64_t* ids; int64_t n_pairs, k;
+    int64_t width;                                  // the window (GZ_BM25_SN_WINDOW), >= 1
+    int32_t* start_out; int32_t* hits_out;          // [n_pairs] the smallest start with the most hits, and the hits; -1 / 0 without a document
+    uint32_t* cnt;                                  // [n_pairs] occurrences of every pair (GZ_BM25_SN_COUNT)
+    const uint32_t* base;                           // [n_pairs + 1] their exclusive scan (GZ_BM25_SN_FILL)
+    int32_t* pos_out; int32_t* word_out;            // [base[n_pairs]] position in the document, first place of the word in the query
+    uint32_t* ctl;                                  // [1] the word offsets contradict n_words, [4..5] (64 bits) all occurrences counted
+};
+enum { GZ_BM25_SN_WINDOW, GZ_BM25_SN_COUNT, GZ_BM25_SN_FILL };
+void gz_launch_bm25_snippet(int step, const GzBm25Snip& A, hipStream_t s);

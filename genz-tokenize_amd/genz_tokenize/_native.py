@@ -39,6 +39,7 @@ SYMBOLS = [
     "gz_bm25_search_bool", "gz_bm25_search_bool_device", "gz_bm25_match_count_bool",
     "gz_bm25_build_ex", "gz_bm25_build_device_ex", "gz_bm25_flags", "gz_bm25_sequence",
     "gz_bm25_search_phrase", "gz_bm25_search_phrase_device", "gz_bm25_match_count_phrase",
+    "gz_bm25_snippets", "gz_bm25_snippets_device", "gz_bm25_occurrences",
 ]
 
 _lib = None
@@ -156,6 +157,10 @@ def load_library():
         L.gz_bm25_search_phrase.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]
         L.gz_bm25_search_phrase_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp]
         L.gz_bm25_match_count_phrase.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]
+    if hasattr(L, "gz_bm25_snippets"):
+        L.gz_bm25_snippets.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
+        L.gz_bm25_snippets_device.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
+        L.gz_bm25_occurrences.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -712,6 +717,50 @@ class Context:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
             self._check(self.lib.gz_bm25_match_count_bool(*args, int(mode), *ex, _ptr(counts)))
         return counts[:nq]
+
+    @staticmethod
+    def _bm25_pairs(terms, query_off, ids):
+        """the packed query terms and the [Q, k] ids of a snippet call as contiguous arrays, and their leading C arguments"""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        nq = len(query_off) - 1
+        assert ids.ndim == 2 and ids.shape[0] == nq
+        return terms, query_off, ids, nq, [_ptr(terms) if len(terms) else None, _ptr(query_off), nq, _ptr(ids) if ids.size else None, ids.shape[1]]
+
+    def bm25_snippets(self, index: int, terms: np.ndarray, query_off: np.ndarray, ids: np.ndarray, width: int):
+        """(starts int32 [Q, k], hits int32 [Q, k]) of a positional index: for every pair (query q, document ids[q, j]) the window
+        of `width` words with the most query words in it -- the smallest start among the best, and the count; -1 / 0 for id -1
+        (gz_bm25_snippets)."""
+        terms, query_off, ids, nq, args = self._bm25_pairs(terms, query_off, ids)
+        starts = np.empty(ids.shape, dtype=np.int32)
+        hits = np.empty(ids.shape, dtype=np.int32)
+        self._check(self.lib.gz_bm25_snippets(C.c_void_p(index), *args, int(width), _ptr(starts) if starts.size else None,
+                                              _ptr(hits) if hits.size else None))
+        return starts, hits
+
+    def bm25_snippets_device(self, index: int, terms: np.ndarray, query_off: np.ndarray, d_ids: int, k: int, width: int, d_starts: int,
+                             d_hits: int) -> None:
+        """bm25_snippets with the ids (int64 [Q, k]) and both outputs (int32 [Q, k]) in device memory: what bm25_search wrote into
+        d_ids goes straight in.  An id outside [-1, documents) counts as -1 (gz_bm25_snippets_device)."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        self._check(self.lib.gz_bm25_snippets_device(C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), len(query_off) - 1,
+                                                     C.c_void_p(d_ids), int(k), int(width), C.c_void_p(d_starts), C.c_void_p(d_hits)))
+
+    def bm25_occurrences(self, index: int, terms: np.ndarray, query_off: np.ndarray, ids: np.ndarray):
+        """(positions int32 [T], words int32 [T], offsets int64 [Q * k + 1]) of a positional index: pair r = q * k + j owns
+        [offsets[r], offsets[r + 1]) -- the positions in document ids[q, j] of the words of query q, ascending, and for each the
+        first place of that term in the query (gz_bm25_occurrences: sizes first, then the fill)."""
+        terms, query_off, ids, nq, args = self._bm25_pairs(terms, query_off, ids)
+        off = np.zeros(ids.size + 1, dtype=np.int64)
+        self._check(self.lib.gz_bm25_occurrences(C.c_void_p(index), *args, _ptr(off), None, None, 0))       # sizes first
+        t = int(off[-1])
+        pos = np.empty(max(t, 1), dtype=np.int32)
+        word = np.empty(max(t, 1), dtype=np.int32)
+        if t:
+            self._check(self.lib.gz_bm25_occurrences(C.c_void_p(index), *args, _ptr(off), _ptr(pos), _ptr(word), t))
+        return pos[:t], word[:t], off
 
     def exchange_select(self, back: int):
         """Exchange operations issued from now on belong to the encode call `back` calls before the latest one."""

@@ -33,6 +33,15 @@ on `count_matches`) then keeps only the documents in which the phrase's words st
 rejects a marked document that lacks a phrase word, else walks its slice of seq.  The phrase is a filter only: its words enter no
 score.  An index built without positions is the same index as before, buffer for buffer, and refuses `phrase=` with ValueError.
 
+Snippets: a positional index also tells where INSIDE a document the query's words stand -- the second reader of `seq`, and what
+a result page needs.  `snippets(queries, ids, width)` takes the ids `search` or `top_k` returned ([Q, k]; -1 is the padding) and
+gives, for every (query, document) pair, the window of `width` words that holds the most query words: the smallest start among the
+best windows, and that count.  `occurrences(queries, ids)` lists every position of a query word in those documents, with the word's
+first place in the query, pair after pair.  Both walk the documents' slices of seq on the GPU (csrc/gz_snippet.inc), a wave per
+pair; nothing but the word offsets is derived for them -- no postings -- and the index may be in any state.
+`snippet_texts(queries, ids, width, mark)` joins the windows' words on the host, splitting only the texts of the ids it was given,
+and wraps the query's words in `mark`.  An index built without positions refuses all three with ValueError.
+
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
@@ -345,6 +354,98 @@ class BM25:
             return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
         pterms, poff = self._exclusions(phrase, nq)
         return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff, ph_terms=pterms, ph_off=poff)
+
+    # ---- inside a document: snippets and the positions of the query's words ---------------------------------------------
+    def _snippet_args(self, queries, ids, width=1):
+        """validation of snippets / occurrences / snippet_texts, all of it before any native call -> (queries, ids int64 [Q, k])"""
+        queries = _strings(queries, "queries")
+        if isinstance(width, bool) or not isinstance(width, numbers.Integral):
+            raise TypeError("width must be int, not %s" % type(width).__name__)
+        ids = np.asarray(ids)
+        if ids.dtype == np.bool_ or not np.issubdtype(ids.dtype, np.integer):
+            raise TypeError("ids must be integers, not %s" % ids.dtype)
+        if ids.ndim != 2:
+            raise ValueError("ids must be 2-D [queries, k], not %d-D" % ids.ndim)
+        if ids.shape[0] != len(queries):
+            raise ValueError("ids has %d rows for %d queries" % (ids.shape[0], len(queries)))
+        if int(width) < 1:
+            raise ValueError("width must be >= 1, not %d" % width)
+        if not getattr(self, "_positions", False):
+            raise ValueError("snippets need an index built with positions=True")
+        if ids.size and (int(ids.min()) < -1 or int(ids.max()) >= self.num_doc):
+            raise IndexError("document ids must lie in [-1, %d)" % self.num_doc)
+        return queries, np.ascontiguousarray(ids, dtype=np.int64)
+
+    def _query_terms(self, queries):
+        """str.split() of every query -> (term ids, int64 query offsets): _queries without the idf"""
+        split = [q.split() for q in queries]
+        qoff = np.zeros(len(split) + 1, dtype=np.int64)
+        if split:
+            np.cumsum([len(w) for w in split], out=qoff[1:])
+        words = [w for ws in split for w in ws]
+        return (self._lookup(words)[0] if words else np.zeros(0, np.int32)), qoff
+
+    def snippets(self, queries: Sequence[str], ids, width: int = 32):
+        """(starts int32 [Q, k], hits int32 [Q, k]) for ids [Q, k] (what search / top_k returned; anything np.asarray makes a 2-D
+        integer array of).  With W = documents[d].split(), n = len(W), R = set(queries[q].split()) and h[p] = W[p] in R: over the
+        starts s in range(max(1, n - width + 1)), hits(s) = sum(h[s:s + width]); starts[q, j] is the SMALLEST s with the largest
+        hits(s) for d = ids[q, j], hits[q, j] that count.  A document without words gives (0, 0), n <= width start 0 and all of the
+        document's hits, a query without (known) words hits 0; id -1 gives start -1, hits 0.  Computed on the GPU from the positional
+        store.  TypeError: a query that is no str, ids that are no integers, a width that is no int; ValueError: ids not 2-D or
+        with another row count than queries, width < 1, an index built without positions=True; IndexError: an id outside
+        [-1, num_doc)."""
+        queries, ids = self._snippet_args(queries, ids, width)
+        if ids.size == 0:
+            return np.zeros(ids.shape, dtype=np.int32), np.zeros(ids.shape, dtype=np.int32)
+        terms, qoff = self._query_terms(queries)
+        return self._ctx.bm25_snippets(self._index, terms, qoff, ids, int(width))
+
+    def occurrences(self, queries: Sequence[str], ids):
+        """(positions int32 [T], words int32 [T], offsets int64 [Q * k + 1]) for ids [Q, k]: pair r = q * k + j owns
+        [offsets[r], offsets[r + 1]).  With W and Rl = queries[q].split() as in `snippets`: its positions are the p with W[p] in Rl,
+        ascending, and words holds Rl.index(W[p]) -- the first place of that word in the query.  Id -1 owns nothing.  Computed on
+        the GPU (count, scan, fill).  Errors as `snippets`."""
+        queries, ids = self._snippet_args(queries, ids)
+        if ids.size == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64)
+        terms, qoff = self._query_terms(queries)
+        return self._ctx.bm25_occurrences(self._index, terms, qoff, ids)
+
+    def snippet_texts(self, queries: Sequence[str], ids, width: int = 32, mark=None) -> list:
+        """A list of Q lists of k str: " ".join(W[s:s + width]) of every pair's snippet (`snippets`), "" for id -1.  With
+        mark=(open, close) every word of the window that is an occurrence (`occurrences`) is wrapped: open + word + close.  Only the
+        texts of the given ids are split, each once."""
+        queries, ids = self._snippet_args(queries, ids, width)
+        if mark is not None:
+            mark = tuple(_strings(mark, "mark"))
+            if len(mark) != 2:
+                raise ValueError("mark must be (open, close), not %d items" % len(mark))
+        width = int(width)
+        starts, _ = self.snippets(queries, ids, width)
+        if mark is not None:
+            pos, _, off = self.occurrences(queries, ids)
+            pos, off = pos.tolist(), off.tolist()
+        words = {}
+        out = []
+        k = ids.shape[1]
+        for q, (row, srow) in enumerate(zip(ids.tolist(), starts.tolist())):
+            texts = []
+            for j, (d, s) in enumerate(zip(row, srow)):
+                if d < 0:
+                    texts.append("")
+                    continue
+                W = words.get(d)
+                if W is None:
+                    W = words[d] = self._texts[d].split()
+                win = W[s:s + width]
+                if mark is not None:
+                    r = q * k + j
+                    for p in pos[off[r]:off[r + 1]]:
+                        if s <= p < s + width:
+                            win[p - s] = mark[0] + win[p - s] + mark[1]
+                texts.append(" ".join(win))
+            out.append(texts)
+        return out
 
     def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
         """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].

@@ -463,6 +463,38 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          trip, comparing the phrase's rarest term first; everything behind the bitmap is gz_bm25_search's.
  *   gz_bm25_search_phrase_device  the same with the three outputs in HBM, as gz_bm25_search_device
  *   gz_bm25_match_count_phrase    count_out[q] of gz_bm25_search_phrase alone (host memory)
+ *   gz_bm25_snippets       where the words of a query stand INSIDE given documents: a positional index's second reader.  terms /
+ *                          query_off as gz_bm25_search (a term -1 matches nothing, a repeated term changes nothing; the length of a
+ *                          query has no limit), ids[n_queries * k] (int64, host memory) the documents of every query -- what
+ *                          gz_bm25_search or gz_bm25_topk wrote goes in as it is -- and pair r = q * k + j is (query q, document
+ *                          ids[r]).  With seq(d) the term ids of document d's words in order, n their number and h[p] = 1 where
+ *                          seq(d)[p] is a term of the query: over the starts s in [0, max(1, n - width + 1)), hits(s) = the sum of
+ *                          h[s .. s + width) inside the document; start_out[r] = the SMALLEST s with the largest hits(s),
+ *                          hits_out[r] = that sum (both int32).  A document without words gives (0, 0), n <= width gives start 0
+ *                          and all of the document's hits, a query without terms gives hits 0 and start 0; a window never
+ *                          reaches into the next document.  An id -1 (the padding of gz_bm25_search) gives start -1, hits 0.
+ *                          GZ_E_INVALID: an index without GZ_BM25_POSITIONS, a term outside [-1, n_terms), query_off decreasing,
+ *                          width < 1, k < 0, an id outside [-1, n_docs) (checked before any launch: nothing is written);
+ *                          GZ_E_LIMIT: 2^31 pairs or more; GZ_E_HIP: the index's fieldLens and seq contradict each other.
+ *                          n_queries * k == 0: GZ_OK, nothing written.  Derives the word offsets if the index has none and
+ *                          nothing else: no postings are built.  A wave per pair: the query's terms sit in the lanes, 64 at a
+ *                          time; hits(0) is counted, then the starts are walked 64 a trip -- hits(s) - hits(s - 1) =
+ *                          h[s - 1 + width] - h[s - 1], a wave prefix sum plus a carry, a wave arg-max with ties to the lower
+ *                          start kept across trips only when strictly greater.  The index is not modified.
+ *   gz_bm25_snippets_device  the same with ids, start_out and hits_out in HBM: the doc_out of gz_bm25_search_device goes straight in.
+ *                          The ids are not looked at by the host: an id outside [-1, n_docs) is treated as -1 (start -1, hits 0)
+ *                          and never read through.  The call returns after the kernel has run (its check of the word offsets is
+ *                          read back).
+ *   gz_bm25_occurrences    every place of a query word in the documents of gz_bm25_snippets' pairs (host memory): pair r owns
+ *                          [pair_off_out[r], pair_off_out[r + 1]) of pos_out / word_out (int32), ascending in pos_out -- the
+ *                          positions p with h[p] = 1 -- and word_out = the FIRST place of that term in the query (an index into
+ *                          terms[query_off[q] ..), so a repeated query word is reported under its first place).  An id -1 owns
+ *                          nothing.  Sizes first, as gz_bm25_terms: a call with pos_out == NULL fills pair_off_out[n_queries * k + 1]
+ *                          (pair_off_out[0] = 0) and T = its last entry is the room the two arrays need; a call with pos_out !=
+ *                          NULL and cap >= T fills all three.  cap < T: GZ_E_CAPACITY, nothing written.  GZ_E_LIMIT: 2^32
+ *                          occurrences or more in one call, or 2^31 pairs; every other error as gz_bm25_snippets (no width).  A
+ *                          count kernel (ballot popcounts per pair), the scan of the counts, a fill kernel that writes at the
+ *                          pair's base + the set bits of the ballot below the lane: no atomic decides an order.
  *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
@@ -556,6 +588,12 @@ int  gz_bm25_search_phrase_device(gz_bm25 *index, const int32_t *terms, const do
 int  gz_bm25_match_count_phrase(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
                                 const int32_t *ex_terms, const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off,
                                 int64_t *count_out);
+int  gz_bm25_snippets(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids, int64_t k,
+                      int64_t width, int32_t *start_out, int32_t *hits_out);
+int  gz_bm25_snippets_device(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids_dev,
+                             int64_t k, int64_t width, int32_t *start_out_dev, int32_t *hits_out_dev);
+int  gz_bm25_occurrences(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids, int64_t k,
+                         int64_t *pair_off_out, int32_t *pos_out, int32_t *word_out, int64_t cap);
 int  gz_bm25_append(gz_bm25 *index, const uint8_t *text, const int64_t *text_off, int64_t n_docs);
 int  gz_bm25_append_device(gz_bm25 *index, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes);
 int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);

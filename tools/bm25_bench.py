@@ -3,6 +3,7 @@
     python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--compact 10000] [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --search-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --phrase-only [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --snippet-only [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -65,6 +66,16 @@ they are merged into the file's record instead of replacing it):
                        in the same loop, alternating with the row above, after a warm call of each that has derived the word offsets
   phrase_any_q256_k10_ms   the same with mode "any": every document with one of the two words is marked and goes through the phrase step
   phrase_match_fraction_all / _phrase / _any_phrase   mean(count) / N over the 256 queries
+Snippets (BM25(..., positions=True).snippets / occurrences, gz_bm25_snippets_device; --snippet-only: these rows alone, and with --out
+they are merged into the file's record instead of replacing it).  The model is BM25(list of str, positions=True) over the corpus; the
+256 "drawn" queries (2-4 distinct words of one document each, fixed seed) and ids = search(queries, k)[0] for k = 10 and k = 1000;
+width 32:
+  snippet_device_q256_k{10,1000}_ms   gz_bm25_snippets_device + gz_sync, the ids already in HBM (what gz_bm25_search_device wrote)
+  snippet_python_q256_k{10,1000}_ms   BM25.snippets(queries, ids, 32): terms looked up, ids in, starts and hits [256, k] out
+  occurrences_python_q256_k{10,1000}_ms   BM25.occurrences(queries, ids): both calls of the sizes-first protocol
+  snippet_host_loop_q256_k{10,1000}_ms    the host route they replace: texts[d].split() and the definition's loop over the starts for
+                       every pair, plain Python (one repetition; k = 1000 only when the k = 10 figure scaled to its pairs stays under a minute)
+  snippet_pairs_k* / snippet_pair_words_k* / occurrences_total_k*   pairs with a document, the words of their documents, all occurrences
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
 import argparse
 import json
@@ -398,6 +409,69 @@ def phrase_rows(ctx, res, t, o, reps):
     ctx.bm25_destroy(ix)
 
 
+def snippet_rows(ctx, res, t, o, reps):
+    """the snippet rows of the docstring"""
+    n = len(o) - 1
+    raw = t.tobytes()
+    docs = [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(n)]
+    m = BM25(docs, ctx=ctx, positions=True)
+    rng = np.random.default_rng(3)
+    queries = []
+    for i in rng.integers(n, size=256):
+        ws = list(dict.fromkeys(docs[int(i)].split()))
+        queries.append(" ".join(ws[int(j)] for j in rng.choice(len(ws), min(int(rng.integers(2, 5)), len(ws)), replace=False)))
+    terms, qoff = m._query_terms(queries)
+    width = 32
+
+    def host_loop(ids):
+        out = []
+        for q, row in enumerate(ids.tolist()):
+            R = set(queries[q].split())
+            for d in row:
+                if d < 0:
+                    out.append((-1, 0))
+                    continue
+                W = docs[d].split()
+                h = [1 if x in R else 0 for x in W]
+                best_s, best = 0, -1
+                for s in range(max(1, len(W) - width + 1)):
+                    v = sum(h[s:s + width])
+                    if v > best:
+                        best_s, best = s, v
+                out.append((best_s, best))
+        return out
+
+    for k in (10, 1000):
+        ids = np.ascontiguousarray(m.search(queries, k)[0])
+        kk = ids.shape[1]
+        d_ids, d_s, d_h = ctx.alloc(ids.size * 8), ctx.alloc(ids.size * 4), ctx.alloc(ids.size * 4)
+        ctx.h2d(d_ids, ids)
+
+        def device():
+            ctx.bm25_snippets_device(m._index, terms, qoff, d_ids, kk, width, d_s, d_h)
+            ctx.sync()
+        key = "q256_k%d" % k
+        res["snippet_device_%s_ms" % key], res["snippet_device_%s_all_ms" % key] = median_ms(device, reps)
+        res["snippet_python_%s_ms" % key], res["snippet_python_%s_all_ms" % key] = median_ms(lambda: m.snippets(queries, ids, width), reps)
+        res["occurrences_python_%s_ms" % key], res["occurrences_python_%s_all_ms" % key] = median_ms(lambda: m.occurrences(queries, ids), reps)
+        starts, hits = m.snippets(queries, ids, width)
+        got = np.empty(ids.size, np.int32)
+        ctx.d2h(got, d_s)
+        assert np.array_equal(got.reshape(ids.shape), starts)
+        lens = np.asarray(m.fieldLens, dtype=np.int64)
+        res["snippet_pairs_k%d" % k] = int((ids >= 0).sum())
+        res["snippet_pair_words_k%d" % k] = int(lens[ids[ids >= 0]].sum())
+        res["occurrences_total_k%d" % k] = int(m.occurrences(queries, ids)[2][-1])
+        if k == 10 or res["snippet_host_loop_q256_k10_ms"] * ids.size / 2560.0 < 60e3:
+            t0 = time.perf_counter()
+            want = host_loop(ids)
+            res["snippet_host_loop_%s_ms" % key] = (time.perf_counter() - t0) * 1e3
+            assert want == list(zip(starts.ravel().tolist(), hits.ravel().tolist()))
+        for d in (d_ids, d_s, d_h):
+            ctx.free(d)
+    del m
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -413,6 +487,7 @@ def main():
     ap.add_argument("--compact-only", action="store_true", help="only the compact rows; with --out they are merged into the file")
     ap.add_argument("--search-only", action="store_true", help="only the build, top-k (k = 10) and search rows; with --out they are merged into the file")
     ap.add_argument("--phrase-only", action="store_true", help="only the phrase rows; with --out they are merged into the file")
+    ap.add_argument("--snippet-only", action="store_true", help="only the snippet rows; with --out they are merged into the file")
     a = ap.parse_args()
     if a.search_only:
         a.remove = a.compact = a.append = 0
@@ -427,6 +502,16 @@ def main():
             old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
             old.update({k: v for k, v in res.items() if k.startswith("phrase_")})
             old["phrase_rows_run"] = dict(docs=n, reps=a.reps)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
+    if a.snippet_only:
+        snippet_rows(ctx, res, t, o, a.reps)
+        print(json.dumps(res))
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith(("snippet_", "occurrences_"))})
+            old["snippet_rows_run"] = dict(docs=n, reps=a.reps)
             with open(a.out, "w") as f:
                 f.write(json.dumps(old) + "\n")
         return
