@@ -977,6 +977,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_S_XTERM, BMW_S_XOFF,                                                     // the excluded terms of a boolean search
        BMW_S_PHTERM, BMW_S_PHOFF,                                                   // the phrase terms of a phrase search
        BMW_SN_IDS, BMW_SN_OUT, BMW_SN_CNT, BMW_SN_OFF, BMW_SN_POS, BMW_SN_WORD,     // snippets and occurrences (bm25_snip_*)
+       BMW_S_NRTERM, BMW_S_NROFF, BMW_S_NRWIN,                                      // the near terms and windows of a near search
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1551,6 +1552,7 @@ int bm25_score_args(gz_bm25* ix, const int32_t* terms, const double* idf, const 
 
 static_assert(GZ_TOPK_SORT == GZ_BM25_TOPK_MAX, "the last selection level sorts GZ_BM25_TOPK_MAX winners in LDS");
 static_assert(GZ_PHRASE_MAX == GZ_BM25_PHRASE_MAX && GZ_PHRASE_MAX <= 64, "the phrase kernel holds a phrase term per lane");
+static_assert(GZ_NEAR_MAX == GZ_BM25_NEAR_MAX && GZ_NEAR_MAX <= 64, "the near and cover kernels hold a term of the set per lane");
 
 // k (>= 1) -> k' = min(k, documents), refused above GZ_BM25_TOPK_MAX
 int bm25_topk_k(gz_bm25* ix, int64_t k, int64_t& kk)
@@ -1732,6 +1734,26 @@ int bm25_phrase_args(gz_bm25* ix, int64_t nq, const int32_t* phterm, const int64
     return GZ_OK;
 }
 
+// what the _near entry points take on top: the near terms and the window of every query (nroff null: none)
+int bm25_near_args(gz_bm25* ix, int64_t nq, const int32_t* nrterm, const int64_t* nroff, const int64_t* nrwin)
+{
+    gz_ctx* c = ix->c;
+    if (!nroff) return GZ_OK;
+    if (!(ix->flags & GZ_BM25_POSITIONS)) return fail(c, GZ_E_INVALID, "a near search needs an index built with GZ_BM25_POSITIONS");
+    if (!nrwin && nq > 0) return fail(c, GZ_E_INVALID, "near-term offsets without windows");
+    for (int64_t q = 0; q < nq; ++q) {
+        if (nroff[q + 1] < nroff[q]) return fail(c, GZ_E_INVALID, "near-term offsets must not decrease");
+        if (nroff[q + 1] - nroff[q] > GZ_BM25_NEAR_MAX)
+            return fail(c, GZ_E_LIMIT, "%lld near terms; a query takes at most %d", (long long)(nroff[q + 1] - nroff[q]), GZ_BM25_NEAR_MAX);
+        if (nroff[q + 1] > nroff[q] && nrwin[q] < 1)
+            return fail(c, GZ_E_INVALID, "window = %lld; a near search takes a window >= 1", (long long)nrwin[q]);
+    }
+    if (nroff[nq] > nroff[0] && !nrterm) return fail(c, GZ_E_INVALID, "near-term offsets without terms");
+    for (int64_t j = nroff[0]; j < nroff[nq]; ++j)
+        if (nrterm[j] < -1 || nrterm[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "near term id %d out of range", nrterm[j]);
+    return GZ_OK;
+}
+
 // A chunk of queries at a time (its bitmaps hold at most bm25_search_chunk words, one row at least, at most 65535 rows): mark the
 // documents of every query word's postings in the row's bitmap, count and rank the bits, and read the counts back -- they size
 // what follows.  Then, for runs of rows whose candidate scores (rows x the largest count among them) stay within
@@ -1743,10 +1765,14 @@ int bm25_phrase_args(gz_bm25* ix, int64_t nq, const int32_t* phterm, const int64
 // GZ_BM25_MATCH_ANY and no excluded term, neither is launched and nothing more is allocated.
 // phoff (null: none) / phterm: the phrase stage (GZ_BM25_SR_PHRASE) then clears, in the rows that have phrase terms, the documents
 // in which they do not stand next to each other; without phrase terms nothing of it is launched, allocated or derived.
+// nroff (null: none) / nrterm / nrwin: the near stage (GZ_BM25_SR_NEAR, gz_near.inc) then clears, in the rows that have near terms,
+// the documents that do not hold all of them inside nrwin[row] consecutive words; without near terms nothing of it is launched,
+// allocated or derived either.
 int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
                        int64_t kk, bool count_only, int64_t* doc_dev, double* score_dev, int64_t* cnt_dev, int64_t* doc_host, double* score_host,
                        int64_t* cnt_host, int32_t mode = GZ_BM25_MATCH_ANY, const int32_t* xterm = nullptr, const int64_t* xoff = nullptr,
-                       const int32_t* phterm = nullptr, const int64_t* phoff = nullptr)
+                       const int32_t* phterm = nullptr, const int64_t* phoff = nullptr, const int32_t* nrterm = nullptr,
+                       const int64_t* nroff = nullptr, const int64_t* nrwin = nullptr)
 {
     gz_ctx* c = ix->c;
     DBuf* w = c->w_bm;
@@ -1784,6 +1810,22 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
         A.ctl = (uint32_t*)w[BMW_CTL].p;
         HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
     }
+    const int64_t nn = nroff ? nroff[nq] - nroff[0] : 0;
+    GzBm25Near NR{};
+    if (nn > 0) {
+        if ((rc = bm25_word_offsets(ix))) return rc;
+        if ((rc = bm_alloc(c, w[BMW_S_NRTERM], (size_t)nn * 4)) || (rc = bm_alloc(c, w[BMW_S_NROFF], (size_t)(nq + 1) * 8)) ||
+            (rc = bm_alloc(c, w[BMW_S_NRWIN], (size_t)nq * 8)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
+            (rc = copy_in(c, w[BMW_S_NRTERM].p, nrterm + nroff[0], (size_t)nn * 4, s)) ||
+            (rc = copy_in(c, w[BMW_S_NROFF].p, nroff, (size_t)(nq + 1) * 8, s)) || (rc = copy_in(c, w[BMW_S_NRWIN].p, nrwin, (size_t)nq * 8, s)))
+            return rc;
+        NR.S = A.S;
+        NR.seq = (const uint32_t*)ix->seq.p; NR.woff = (const uint32_t*)ix->woff.p; NR.n_words = ix->n_words;
+        NR.n_docs = N; NR.n_terms = ix->n_terms;
+        NR.sterm = (const int32_t*)w[BMW_S_NRTERM].p - nroff[0];
+        NR.ctl = (uint32_t*)w[BMW_CTL].p;
+        if (np <= 0) HIPCHK(c, hipMemsetAsync(NR.ctl, 0, 64, s));
+    }
     const int64_t* phoff_dev = np > 0 ? (const int64_t*)w[BMW_S_PHOFF].p : nullptr;
     const int64_t* xoff_dev = nx > 0 ? (const int64_t*)w[BMW_S_XOFF].p : nullptr;
     const int64_t chunk = c->opt.bm25_search_chunk;
@@ -1819,6 +1861,11 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
             if (mode == GZ_BM25_MATCH_ALL || A.xoff) gz_launch_bm25_search(GZ_BM25_SR_FILTER, A, rows, s);
             A.phoff = phoff_dev && phoff[q0 + rows] > phoff[q0] ? phoff_dev + q0 : nullptr;
             if (A.phoff) gz_launch_bm25_search(GZ_BM25_SR_PHRASE, A, rows, s);
+            if (nn > 0 && nroff[q0 + rows] > nroff[q0]) {       // (the chunk's rows; the offsets and windows stay the absolute ones)
+                NR.soff = (const int64_t*)w[BMW_S_NROFF].p + q0; NR.win = (const int64_t*)w[BMW_S_NRWIN].p + q0;
+                NR.bm = A.bm; NR.w64 = W64;
+                gz_launch_bm25_near(GZ_BM25_SR_NEAR, NR, rows, s);
+            }
         }
         gz_launch_bm25_search(GZ_BM25_SR_COUNT, A, rows, s);
         gz_launch_bm25_search(GZ_BM25_SR_ROWS, A, rows, s);
@@ -1828,6 +1875,10 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
             int64_t bad = 0;
             if ((rc = bm_read_u32(c, A.ctl + 1, bad))) return rc;
             if (bad) return fail(c, GZ_E_HIP, "BM25 phrase search: the index's fieldLens and word sequence contradict each other");
+        } else if (nn > 0) {
+            int64_t bad = 0;
+            if ((rc = bm_read_u32(c, NR.ctl + 1, bad))) return rc;
+            if (bad) return fail(c, GZ_E_HIP, "BM25 near search: the index's fieldLens and word sequence contradict each other");
         }
         if (cnt_host) for (int64_t r = 0; r < rows; ++r) cnt_host[q0 + r] = (int64_t)cnt[(size_t)r];
         if (count_only) continue;
@@ -1953,6 +2004,56 @@ int bm25_snippets_locked(gz_bm25* ix, const int32_t* terms, const int64_t* qoff,
     if ((rc = bm25_snip_flag(c, A))) return rc;
     if (ids_dev) return GZ_OK;
     if ((rc = copy_out(c, start_host, A.start_out, (size_t)n * 4, s)) || (rc = copy_out(c, hits_host, A.hits_out, (size_t)n * 4, s))) return rc;
+    return GZ_OK;
+}
+
+// ---- proximity: the cover of pairs (gz_bm25_cover[_device]; gz_near.inc) -----------------------------------------------------------
+// what the cover entry points check on top of bm25_snip_args: a query is a set of at most GZ_BM25_NEAR_MAX entries
+int bm25_cover_args(gz_bm25* ix, const int64_t* qoff, int64_t nq)
+{
+    for (int64_t q = 0; q < nq; ++q)
+        if (qoff[q + 1] - qoff[q] > GZ_BM25_NEAR_MAX)
+            return fail(ix->c, GZ_E_LIMIT, "a cover over %lld terms; a query takes at most %d", (long long)(qoff[q + 1] - qoff[q]), GZ_BM25_NEAR_MAX);
+    return GZ_OK;
+}
+
+// ids_dev and the three outputs in HBM, or (ids_dev null) ids_host in and the outputs out through the workspace
+int bm25_cover_locked(gz_bm25* ix, const int32_t* terms, const int64_t* qoff, int64_t nq, int64_t k, const int64_t* ids_dev, int32_t* start_dev,
+                      int32_t* len_dev, int32_t* words_dev, const int64_t* ids_host, int32_t* start_host, int32_t* len_host, int32_t* words_host)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = nq * k;
+    if (n == 0) return GZ_OK;
+    int rc;
+    if ((rc = bm25_word_offsets(ix))) return rc;
+    GzBm25Near A{};
+    if ((rc = bm25_query_in(ix, terms, nullptr, qoff, nq, nullptr, 0, A.S)) || (rc = bm_alloc(c, w[BMW_CTL], 64))) return rc;
+    A.seq = (const uint32_t*)ix->seq.p; A.woff = (const uint32_t*)ix->woff.p; A.n_words = ix->n_words;
+    A.n_docs = ix->n_docs; A.n_terms = ix->n_terms;
+    A.sterm = A.S.qterm; A.soff = A.S.qoff;
+    A.n_pairs = n; A.k = k;
+    A.ctl = (uint32_t*)w[BMW_CTL].p;
+    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    if (ids_dev) {
+        A.ids = ids_dev; A.start_out = start_dev; A.len_out = len_dev; A.words_out = words_dev;
+    } else {
+        if ((rc = bm_alloc(c, w[BMW_SN_IDS], (size_t)n * 8)) || (rc = bm_alloc(c, w[BMW_SN_OUT], (size_t)n * 12)) ||
+            (rc = copy_in(c, w[BMW_SN_IDS].p, ids_host, (size_t)n * 8, s)))
+            return rc;
+        A.ids = (const int64_t*)w[BMW_SN_IDS].p; A.start_out = (int32_t*)w[BMW_SN_OUT].p; A.len_out = A.start_out + n; A.words_out = A.len_out + n;
+    }
+    gz_launch_bm25_near(GZ_BM25_NR_COVER, A, 0, s);
+    int64_t bad = 0;
+    if ((rc = bm_read_u32(c, A.ctl + 1, bad))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, GZ_E_HIP, "BM25 cover: the index's fieldLens, pair table and word sequence contradict each other");
+    if (ids_dev) return GZ_OK;
+    if ((rc = copy_out(c, start_host, A.start_out, (size_t)n * 4, s)) || (rc = copy_out(c, len_host, A.len_out, (size_t)n * 4, s)) ||
+        (rc = copy_out(c, words_host, A.words_out, (size_t)n * 4, s)))
+        return rc;
     return GZ_OK;
 }
 
@@ -3929,6 +4030,74 @@ try {
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
                               mode, ex_terms, ex_off, ph_terms, ph_off);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_near(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries, const double params[6],
+                        int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off, const int32_t* ph_terms,
+                        const int64_t* ph_off, const int32_t* near_terms, const int64_t* near_off, const int64_t* near_window, int64_t* doc_out,
+                        double* score_out, int64_t* count_out)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out && score_out ? doc_out : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) ||
+        (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off)) || (rc = bm25_near_args(ix, n_queries, near_terms, near_off, near_window)))
+        return rc;
+    if (!count_out && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, nullptr, nullptr, nullptr, doc_out, score_out, count_out,
+                              mode, ex_terms, ex_off, ph_terms, ph_off, near_terms, near_off, near_window);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_near_device(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* query_off, int64_t n_queries,
+                               const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms, const int64_t* ex_off,
+                               const int32_t* ph_terms, const int64_t* ph_off, const int32_t* near_terms, const int64_t* near_off,
+                               const int64_t* near_window, int64_t* doc_out_dev, double* score_out_dev, int64_t* count_out_dev)
+try {
+    int rc = bm25_score_args(ix, terms, idf, query_off, n_queries, params, doc_out_dev && score_out_dev ? doc_out_dev : nullptr);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) ||
+        (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off)) || (rc = bm25_near_args(ix, n_queries, near_terms, near_off, near_window)))
+        return rc;
+    if (!count_out_dev && n_queries > 0) return fail(ix->c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, idf, query_off, n_queries, params, plus, kk, false, doc_out_dev, score_out_dev, count_out_dev, nullptr, nullptr,
+                              nullptr, mode, ex_terms, ex_off, ph_terms, ph_off, near_terms, near_off, near_window);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_match_count_near(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, int32_t mode, const int32_t* ex_terms,
+                             const int64_t* ex_off, const int32_t* ph_terms, const int64_t* ph_off, const int32_t* near_terms,
+                             const int64_t* near_off, const int64_t* near_window, int64_t* count_out)
+try {
+    int rc = bm25_match_args(ix, terms, query_off, n_queries, count_out);
+    if (rc || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off)) || (rc = bm25_phrase_args(ix, n_queries, ph_terms, ph_off)) ||
+        (rc = bm25_near_args(ix, n_queries, near_terms, near_off, near_window)))
+        return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
+                              mode, ex_terms, ex_off, ph_terms, ph_off, near_terms, near_off, near_window);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_cover(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids, int64_t k, int32_t* start_out,
+                  int32_t* len_out, int32_t* words_out)
+try {
+    int rc = bm25_snip_args(ix, terms, query_off, n_queries, k);
+    if (rc || (rc = bm25_cover_args(ix, query_off, n_queries))) return rc;
+    gz_ctx* c = ix->c;
+    if (n_queries * k > 0 && (!ids || !start_out || !len_out || !words_out)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if ((rc = bm25_snip_ids(ix, ids, n_queries * k))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_cover_locked(ix, terms, query_off, n_queries, k, nullptr, nullptr, nullptr, nullptr, ids, start_out, len_out, words_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_cover_device(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids_dev, int64_t k,
+                         int32_t* start_out_dev, int32_t* len_out_dev, int32_t* words_out_dev)
+try {
+    int rc = bm25_snip_args(ix, terms, query_off, n_queries, k);
+    if (rc || (rc = bm25_cover_args(ix, query_off, n_queries))) return rc;
+    gz_ctx* c = ix->c;
+    if (n_queries * k > 0 && (!ids_dev || !start_out_dev || !len_out_dev || !words_out_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_cover_locked(ix, terms, query_off, n_queries, k, ids_dev, start_out_dev, len_out_dev, words_out_dev, nullptr, nullptr, nullptr, nullptr);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_snippets(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids, int64_t k, int64_t width,

@@ -349,3 +349,25 @@ struct GzBm25Snip {
 };
 enum { GZ_BM25_SN_WINDOW, GZ_BM25_SN_COUNT, GZ_BM25_SN_FILL };
 void gz_launch_bm25_snippet(int step, const GzBm25Snip& A, hipStream_t s);
+
+// BM25 proximity (gz_near.inc): the smallest window of a document of a positional index that holds every term of a set.  Set r =
+// sterm[soff[r] .. soff[r + 1]) (absolute indices; at most GZ_NEAR_MAX; a repeated term counts once).
+struct GzBm25Near {
+    GzBm25Score S;                                  // the index's signatures and pair table (nothing else of it is read)
+    const uint32_t* seq; const uint32_t* woff; int64_t n_words, n_docs, n_terms;    // document d = seq[woff[d] .. woff[d + 1])
+    const int32_t* sterm; const int64_t* soff;
+    // the near stage of a search chunk (GZ_BM25_SR_NEAR, behind GZ_BM25_SR_PHRASE): of the documents marked in row r only those stay
+    // that hold every term of set r inside some win[r] consecutive words; a term -1 clears the row, a row without terms is left alone
+    const int64_t* win;                             // [rows] >= 1 where the row has terms
+    unsigned long long* bm; int64_t w64;            // [rows, w64] the chunk's bitmaps (GzBm25Search::bm)
+    // the cover of pairs (GZ_BM25_NR_COVER): pair r = (query r / k, document ids[r]), set = the query's terms (-1 is ignored)
+    const int64_t* ids; int64_t n_pairs, k;
+    int32_t* start_out; int32_t* len_out; int32_t* words_out;   // [n_pairs] the shortest window with every term the document holds
+                                                    // (ties: the smallest start), its length, and how many terms that is; (0, 0, 0)
+                                                    // without any, (-1, 0, 0) for an id outside [0, n_docs)
+    uint32_t* ctl;                                  // [1] the word offsets contradict n_words, or the pair table the words
+};
+constexpr int GZ_NEAR_MAX = 64;           // == GZ_BM25_NEAR_MAX of the public header: a lane per term of the set
+enum { GZ_BM25_SR_NEAR, GZ_BM25_NR_COVER };
+// rows: of the chunk (GZ_BM25_SR_NEAR)
+void gz_launch_bm25_near(int step, const GzBm25Near& A, int64_t rows, hipStream_t s);

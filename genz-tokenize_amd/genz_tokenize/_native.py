@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GZ_LIBRARY") or os.path.join(_HERE, "libgenz_tokenize
 GZ_OK, GZ_E_INVALID, GZ_E_UTF8, GZ_E_HIP, GZ_E_NOTABLES = 0, -1, -2, -3, -4
 GZ_E_CAPACITY, GZ_E_LIMIT, GZ_E_NOMEM, GZ_E_RCCL, GZ_E_NODEVICE = -5, -6, -7, -8, -9
 GZ_BM25_POSITIONS, GZ_BM25_PHRASE_MAX = 1, 64
+GZ_BM25_NEAR_MAX = 64
 GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP_WORDS = 0x1, 0x2, 0x4, 0x100, 0x200, 0x400
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
@@ -40,6 +41,7 @@ SYMBOLS = [
     "gz_bm25_build_ex", "gz_bm25_build_device_ex", "gz_bm25_flags", "gz_bm25_sequence",
     "gz_bm25_search_phrase", "gz_bm25_search_phrase_device", "gz_bm25_match_count_phrase",
     "gz_bm25_snippets", "gz_bm25_snippets_device", "gz_bm25_occurrences",
+    "gz_bm25_search_near", "gz_bm25_search_near_device", "gz_bm25_match_count_near", "gz_bm25_cover", "gz_bm25_cover_device",
 ]
 
 _lib = None
@@ -161,6 +163,12 @@ def load_library():
         L.gz_bm25_snippets.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
         L.gz_bm25_snippets_device.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
         L.gz_bm25_occurrences.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]
+    if hasattr(L, "gz_bm25_search_near"):
+        L.gz_bm25_search_near.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_bm25_search_near_device.argtypes = [vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_bm25_match_count_near.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_bm25_cover.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp]
+        L.gz_bm25_cover_device.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -648,13 +656,15 @@ class Context:
 
     def bm25_search(self, index: int, terms: np.ndarray, idf: np.ndarray, query_off: np.ndarray, params, plus: bool, k: int,
                     d_ids: int | None = None, d_scores: int | None = None, d_counts: int | None = None,
-                    mode: int = 0, ex_terms=None, ex_off=None, ph_terms=None, ph_off=None):
+                    mode: int = 0, ex_terms=None, ex_off=None, ph_terms=None, ph_off=None, nr_terms=None, nr_off=None, nr_window=None):
         """(ids int64 [Q, k'], scores float64 [Q, k'], counts int64 [Q]) with k' = min(k, documents): the best MATCHING documents of
         every query and how many match; positions behind a row's count hold -1 / NaN.  A document matches when it holds at least
         one of the query's words (mode 0) or every one of them (mode 1), and none of the terms ex_terms[ex_off[q]:ex_off[q + 1]]
         (ex_off None: no exclusions).  With mode 0 and ex_off None the call is gz_bm25_search[_device], else gz_bm25_search_bool[_device].
         ph_off (None: no phrases) / ph_terms: the terms ph_terms[ph_off[q]:ph_off[q + 1]] must stand next to each other in this order
         in the document (a positional index only): the call is gz_bm25_search_phrase[_device].
+        nr_off (None: no near sets) / nr_terms / nr_window (int64 [Q]): every term of nr_terms[nr_off[q]:nr_off[q + 1]] must stand
+        inside some nr_window[q] consecutive words of the document, in any order: the call is gz_bm25_search_near[_device].
         With d_ids / d_scores / d_counts (device pointers, all three): enqueued into them, sync() waits."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         idf = np.ascontiguousarray(idf, dtype=np.float64)
@@ -664,17 +674,22 @@ class Context:
         nq = len(query_off) - 1
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
                 1 if plus else 0, int(k)]
-        plain = mode == 0 and ex_off is None and ph_off is None
+        plain = mode == 0 and ex_off is None and ph_off is None and nr_off is None
         if not plain:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
             args += [int(mode)] + ex
-        if ph_off is not None:
+        if ph_off is not None or nr_off is not None:
             ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
             args += ph
+        if nr_off is not None:
+            nr_terms, nr_off, nr_window, nr = self._bm25_near(nq, nr_terms, nr_off, nr_window)
+            args += nr
         if d_ids is not None or d_scores is not None or d_counts is not None:
             fn = self.lib.gz_bm25_search_device if plain else self.lib.gz_bm25_search_bool_device
             if ph_off is not None:
                 fn = self.lib.gz_bm25_search_phrase_device
+            if nr_off is not None:
+                fn = self.lib.gz_bm25_search_near_device
             self._check(fn(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
             return None
         kk = max(0, min(int(k), self.bm25_info(index)[0]))
@@ -684,6 +699,8 @@ class Context:
         fn = self.lib.gz_bm25_search if plain else self.lib.gz_bm25_search_bool
         if ph_off is not None:
             fn = self.lib.gz_bm25_search_phrase
+        if nr_off is not None:
+            fn = self.lib.gz_bm25_search_near
         self._check(fn(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
         return ids, scores, counts[:nq]
 
@@ -697,17 +714,29 @@ class Context:
         ex_terms = np.ascontiguousarray(ex_terms if ex_terms is not None else [], dtype=np.int32)
         return ex_terms, ex_off, [_ptr(ex_terms) if len(ex_terms) else None, _ptr(ex_off)]
 
+    @staticmethod
+    def _bm25_near(nq: int, nr_terms, nr_off, nr_window):
+        """the near terms and windows of a near search as contiguous arrays (kept alive by the caller) and their three C arguments"""
+        nr_terms, nr_off, nr = Context._bm25_exclusions(nq, nr_terms, nr_off)
+        nr_window = np.ascontiguousarray(nr_window if nr_window is not None else [], dtype=np.int64)
+        return nr_terms, nr_off, nr_window, nr + [_ptr(nr_window) if len(nr_window) else None]
+
     def bm25_match_count(self, index: int, terms: np.ndarray, query_off: np.ndarray, mode: int = 0, ex_terms=None,
-                         ex_off=None, ph_terms=None, ph_off=None) -> np.ndarray:
+                         ex_off=None, ph_terms=None, ph_off=None, nr_terms=None, nr_off=None, nr_window=None) -> np.ndarray:
         """int64 [Q]: the documents that match each query -- counts of bm25_search alone (mode, ex_terms, ex_off, ph_terms, ph_off as
         there; with mode 0 and ex_off None the call is gz_bm25_match_count, else gz_bm25_match_count_bool; with ph_off
-        gz_bm25_match_count_phrase)."""
+        gz_bm25_match_count_phrase; with nr_off gz_bm25_match_count_near)."""
         terms = np.ascontiguousarray(terms, dtype=np.int32)
         query_off = np.ascontiguousarray(query_off, dtype=np.int64)
         nq = len(query_off) - 1
         counts = np.zeros(max(nq, 1), dtype=np.int64)
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq]
-        if ph_off is not None:
+        if nr_off is not None:
+            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
+            nr_terms, nr_off, nr_window, nr = self._bm25_near(nq, nr_terms, nr_off, nr_window)
+            self._check(self.lib.gz_bm25_match_count_near(*args, int(mode), *ex, *ph, *nr, _ptr(counts)))
+        elif ph_off is not None:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
             ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
             self._check(self.lib.gz_bm25_match_count_phrase(*args, int(mode), *ex, *ph, _ptr(counts)))
@@ -761,6 +790,24 @@ class Context:
         if t:
             self._check(self.lib.gz_bm25_occurrences(C.c_void_p(index), *args, _ptr(off), _ptr(pos), _ptr(word), t))
         return pos[:t], word[:t], off
+
+    def bm25_cover(self, index: int, terms: np.ndarray, query_off: np.ndarray, ids: np.ndarray):
+        """(starts, lengths, words), each int32 [Q, k], of a positional index: for every pair (query q, document ids[q, j]) the
+        shortest window of the document that holds every term of the query which the document holds at all -- ties to the smallest
+        start -- and how many distinct terms that is; (0, 0, 0) for a document with none, (-1, 0, 0) for id -1 (gz_bm25_cover)."""
+        terms, query_off, ids, nq, args = self._bm25_pairs(terms, query_off, ids)
+        out = [np.empty(ids.shape, dtype=np.int32) for _ in range(3)]
+        self._check(self.lib.gz_bm25_cover(C.c_void_p(index), *args, *[_ptr(o) if o.size else None for o in out]))
+        return tuple(out)
+
+    def bm25_cover_device(self, index: int, terms: np.ndarray, query_off: np.ndarray, d_ids: int, k: int, d_starts: int, d_lengths: int,
+                          d_words: int) -> None:
+        """bm25_cover with the ids (int64 [Q, k]) and the three outputs (int32 [Q, k]) in device memory: what bm25_search wrote into
+        d_ids goes straight in.  An id outside [-1, documents) counts as -1 (gz_bm25_cover_device)."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        query_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        self._check(self.lib.gz_bm25_cover_device(C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), len(query_off) - 1,
+                                                  C.c_void_p(d_ids), int(k), C.c_void_p(d_starts), C.c_void_p(d_lengths), C.c_void_p(d_words)))
 
     def exchange_select(self, back: int):
         """Exchange operations issued from now on belong to the encode call `back` calls before the latest one."""

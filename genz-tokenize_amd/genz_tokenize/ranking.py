@@ -42,6 +42,17 @@ pair; nothing but the word offsets is derived for them -- no postings -- and the
 `snippet_texts(queries, ids, width, mark)` joins the windows' words on the host, splitting only the texts of the ids it was given,
 and wraps the query's words in `mark`.  An index built without positions refuses all three with ValueError.
 
+Proximity: the third reader of `seq` answers "these words close to each other, in any order" and its dual, "the shortest passage
+that holds them".  `search_near(queries, k, near, window)` is `search` (with match, exclude and phrase as there) restricted to the
+documents in which some `window[q]` consecutive words hold every word of `near[q]`; `count_near(queries, near, window)` only counts.
+The near words are a set and a filter only -- they enter no score; a window never reaches into a neighbouring document, and a
+window as long as the document means "holds all of them".  One more kernel behind the phrase stage (gz_bm25_sr_near_kernel,
+csrc/gz_near.inc) rejects a marked document that lacks a near word, else walks its slice of seq with the near terms in the lanes:
+per term a ballot of its occurrences and a carry across trips give every position the shortest window that ends there.
+`cover(queries, ids)` runs the same walk per (query, document) pair, a wave each, and gives the shortest window that holds every
+distinct query word the document holds at all -- the smallest start among the shortest -- with the number of those words.  At most
+64 distinct words per near set or cover query; an index built without positions refuses all three with ValueError.
+
 Growth: `add_documents(more)` appends to the live index on the GPU (gz_bm25_append): afterwards the object behaves exactly like
 one constructed over the old and the new documents together, without the old documents being packed, copied or indexed again.
 
@@ -446,6 +457,93 @@ class BM25:
                 texts.append(" ".join(win))
             out.append(texts)
         return out
+
+    # ---- proximity: words within a window of each other, and the smallest window that holds them ----------------------
+    def _near_args(self, queries, near, window, match, exclude, phrase):
+        """validation of search_near / count_near, all of it before any native call -> (queries, mode, exclude, phrase, near,
+        windows int64 [Q])"""
+        mode = self._match(match)
+        queries = _strings(queries, "queries")
+        near = _strings(near, "near")
+        if isinstance(window, numbers.Integral):
+            windows = [window] * len(queries)
+        else:
+            try:
+                windows = [] if isinstance(window, (str, bytes)) else list(window)
+            except TypeError:
+                windows = []
+            if not windows and not isinstance(window, (list, tuple, np.ndarray)):
+                raise TypeError("window must be int or one int per query, not %s" % type(window).__name__)
+        for w in windows:
+            if isinstance(w, bool) or not isinstance(w, numbers.Integral):
+                raise TypeError("window must be int, not %s" % type(w).__name__)
+        queries, mode, exclude, phrase = self._bool_args(queries, match, exclude, phrase)
+        if len(near) != len(queries):
+            raise ValueError("near has %d items for %d queries" % (len(near), len(queries)))
+        if len(windows) != len(queries):
+            raise ValueError("window has %d items for %d queries" % (len(windows), len(queries)))
+        for w in windows:
+            if int(w) < 1:
+                raise ValueError("window must be >= 1, not %d" % w)
+        if not getattr(self, "_positions", False):
+            raise ValueError("near needs an index built with positions=True")
+        return queries, mode, exclude, phrase, near, np.array([min(int(w), 1 << 62) for w in windows], dtype=np.int64)
+
+    def _sets(self, strings):
+        """the DISTINCT words of every string, in the order of their first occurrence -> (term ids, int64 offsets); a word no
+        document holds has term -1"""
+        split = [list(dict.fromkeys(x.split())) for x in strings]
+        off = np.zeros(len(split) + 1, dtype=np.int64)
+        if split:
+            np.cumsum([len(w) for w in split], out=off[1:])
+        words = [w for ws in split for w in ws]
+        return (self._lookup(words)[0] if words else np.zeros(0, np.int32)), off
+
+    def _near_native(self, queries, exclude, phrase, near):
+        nq, terms, idf, qoff = self._queries(queries)
+        xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
+        pterms, poff = self._exclusions(phrase, nq) if phrase is not None else (None, None)
+        nterms, noff = self._sets(near)
+        return terms, idf, qoff, dict(ex_terms=xterms, ex_off=xoff, ph_terms=pterms, ph_off=poff, nr_terms=nterms, nr_off=noff)
+
+    def search_near(self, queries: Sequence[str], k: int, near: Sequence[str], window, match: str = "any",
+                    exclude: Optional[Sequence[str]] = None, phrase: Optional[Sequence[str]] = None):
+        """(ids, scores, counts) with the dtypes, shapes, order and padding of `search`, restricted to the documents that ALSO hold
+        the words of near[q] close to each other.  With W = documents[d].split(), S = set(near[q].split()) and w = window[q] (an int
+        for every query, or one int per query; >= 1): d matches iff it matches under match / exclude / phrase exactly as `search`
+        defines it AND (S is empty or S <= set(W[i:i + w]) for some i in range(max(1, len(W) - w + 1))) -- the words in any order,
+        repeated words counting once.  A near word that no document holds matches nothing, an empty near[q] is no constraint,
+        w < len(S) can match nothing, w >= len(W) means "holds all of them", and a window never reaches into a neighbouring
+        document.  Near is a filter only: its words enter no score and no idf.  With near=[""] * len(queries) the result is
+        `search`'s, bit for bit.  More than 64 distinct words in a near[q] raise _native.GzError (GZ_E_LIMIT).  TypeError: a near
+        item that is no str, a window that is bool or no int; ValueError: near or window of another length than queries, a window
+        < 1, an index built without positions=True; everything else as `search`."""
+        k = self._k(k)
+        queries, mode, exclude, phrase, near, windows = self._near_args(queries, near, window, match, exclude, phrase)
+        terms, idf, qoff, kw = self._near_native(queries, exclude, phrase, near)
+        plus = isinstance(self, BM25Plus)
+        return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, nr_window=windows, **kw)
+
+    def count_near(self, queries: Sequence[str], near: Sequence[str], window, match: str = "any",
+                   exclude: Optional[Sequence[str]] = None, phrase: Optional[Sequence[str]] = None) -> np.ndarray:
+        """int64 [len(queries)]: counts of search_near(queries, k, near, window, match, exclude, phrase) alone."""
+        queries, mode, exclude, phrase, near, windows = self._near_args(queries, near, window, match, exclude, phrase)
+        terms, _, qoff, kw = self._near_native(queries, exclude, phrase, near)
+        return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, nr_window=windows, **kw)
+
+    def cover(self, queries: Sequence[str], ids):
+        """(starts, lengths, words), each int32 [Q, k], for ids [Q, k] (as `snippets` takes them): the shortest passage of document
+        d = ids[q, j] that holds all the query words it has.  With W = documents[d].split() and R = set(queries[q].split()) &
+        set(W): words[q, j] = len(R); over all windows W[i:i2] with R <= set(W[i:i2]), the one with the smallest (i2 - i, i):
+        starts[q, j] = i, lengths[q, j] = i2 - i.  A document with none of the words gives (0, 0, 0), id -1 gives (-1, 0, 0);
+        words unknown to the index are ignored, and words == len(set(queries[q].split())) says that the cover is complete.
+        Computed on the GPU from the positional store, a wave per pair.  More than 64 distinct words in a query raise
+        _native.GzError (GZ_E_LIMIT); every other error as `snippets` (no width)."""
+        queries, ids = self._snippet_args(queries, ids)
+        if ids.size == 0:
+            return tuple(np.zeros(ids.shape, dtype=np.int32) for _ in range(3))
+        terms, qoff = self._sets(queries)
+        return self._ctx.bm25_cover(self._index, terms, qoff, ids)
 
     def get_top_n(self, query: str, documents: Optional[Sequence] = None, n: int = 5) -> list:
         """The n best documents for query, best first (rank_bm25's get_top_n): [documents[i] for i in top_k([query], n)[0][0]].

@@ -495,6 +495,44 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          occurrences or more in one call, or 2^31 pairs; every other error as gz_bm25_snippets (no width).  A
  *                          count kernel (ballot popcounts per pair), the scan of the counts, a fill kernel that writes at the
  *                          pair's base + the set bits of the ballot below the lane: no atomic decides an order.
+ *   gz_bm25_search_near    gz_bm25_search_phrase with a proximity constraint per query on top: the positional index's third reader.
+ *                          With S = the SET of near_terms[near_off[q] .. near_off[q + 1]) (the ex_terms / ex_off conventions; a
+ *                          repeated id counts once; near_off NULL: no near sets, the call is gz_bm25_search_phrase), w =
+ *                          near_window[q] (int64 [n_queries], read only when near_off is not NULL) and seq(d) the term ids of
+ *                          document d's n words in order: d matches q iff it matches under mode, ex_terms and ph_terms as there
+ *                          AND S is empty or some min(w, n) consecutive words of d hold every term of S, in any order.  So a set
+ *                          with a term -1 matches nothing, neither does a window smaller than the set; a window of n or more means
+ *                          "holds all of them", a window never reaches into a neighbouring document, and a set of one term with
+ *                          window 1 is that one-word phrase.  A filter only: the near terms enter no score; scores, order,
+ *                          count_out, the rows and their padding are gz_bm25_search's with this set of matching documents.  Needs
+ *                          an index built with GZ_BM25_POSITIONS (else GZ_E_INVALID, also for empty sets); GZ_E_INVALID: a near id
+ *                          outside [-1, n_terms), near_off decreasing, a non-empty range with near_terms NULL, near_window NULL, a
+ *                          window < 1 in a row that has near terms; GZ_E_LIMIT: a range of more than GZ_BM25_NEAR_MAX entries;
+ *                          every other error as gz_bm25_search_phrase.  On any error the index answers every call as before.  One
+ *                          more stage behind the phrase stage: a wave per 64-bit word of a row's bitmap, lane j holding term j of
+ *                          the set, rejects a marked document that lacks a term (signature, pair table) and else walks the
+ *                          document's range of seq 64 positions a trip: for every term a ballot of its occurrences, a lane's last
+ *                          occurrence at or before it from the ballot or from a carry of the trips before, the minimum over the
+ *                          terms = the start of the shortest window ending there; the document stays at the first trip with a
+ *                          window of at most w words.  Without near terms nothing of it is launched, allocated or derived.
+ *   gz_bm25_search_near_device  the same with the three outputs in HBM, as gz_bm25_search_device
+ *   gz_bm25_match_count_near    count_out[q] of gz_bm25_search_near alone (host memory)
+ *   gz_bm25_cover          the shortest passage of a document that holds all the query words it has.  terms / query_off / ids / k and
+ *                          the pairs as gz_bm25_snippets, but a query is a SET of at most GZ_BM25_NEAR_MAX entries (a repeated id
+ *                          counts once, -1 is ignored).  With R = the terms of the set that document ids[r] holds at all:
+ *                          words_out[r] = |R|; over all windows [i, j) of the document's words that hold every term of R, the one
+ *                          with the smallest (j - i, i): start_out[r] = i, len_out[r] = j - i (all int32, host memory).  R empty
+ *                          gives (0, 0, 0); an id -1 gives start -1, length 0, words 0.  words_out[r] == the distinct known terms
+ *                          of the query says that the cover is complete.  GZ_E_INVALID: an index without GZ_BM25_POSITIONS, a
+ *                          term outside [-1, n_terms), query_off decreasing, k < 0, an id outside [-1, n_docs) (checked before
+ *                          any launch: nothing is written); GZ_E_LIMIT: a query range of more than GZ_BM25_NEAR_MAX entries, 2^31
+ *                          pairs or more; GZ_E_HIP: the index contradicts itself.  n_queries * k == 0: GZ_OK, nothing written.
+ *                          Derives the word offsets if the index has none and nothing else.  A wave per pair: the terms the
+ *                          document lacks (signature, pair table) leave the set, then the walk of gz_bm25_search_near keeps the
+ *                          wave minimum of (length << 32) | start.  The index is not modified.
+ *   gz_bm25_cover_device   the same with ids and the three outputs in HBM: the doc_out of gz_bm25_search_near_device (or of any
+ *                          _device search) goes straight in.  The ids are not looked at by the host: an id outside [-1, n_docs) is
+ *                          treated as -1 and never read through.  The call returns after the kernel has run.
  *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
@@ -544,6 +582,7 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
 #define GZ_BM25_MATCH_ALL 1
 #define GZ_BM25_POSITIONS 1
 #define GZ_BM25_PHRASE_MAX 64
+#define GZ_BM25_NEAR_MAX 64
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
@@ -588,6 +627,22 @@ int  gz_bm25_search_phrase_device(gz_bm25 *index, const int32_t *terms, const do
 int  gz_bm25_match_count_phrase(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
                                 const int32_t *ex_terms, const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off,
                                 int64_t *count_out);
+int  gz_bm25_search_near(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                         const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms, const int64_t *ex_off,
+                         const int32_t *ph_terms, const int64_t *ph_off, const int32_t *near_terms, const int64_t *near_off,
+                         const int64_t *near_window, int64_t *doc_out, double *score_out, int64_t *count_out);
+int  gz_bm25_search_near_device(gz_bm25 *index, const int32_t *terms, const double *idf, const int64_t *query_off, int64_t n_queries,
+                                const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t *ex_terms,
+                                const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off, const int32_t *near_terms,
+                                const int64_t *near_off, const int64_t *near_window, int64_t *doc_out_dev, double *score_out_dev,
+                                int64_t *count_out_dev);
+int  gz_bm25_match_count_near(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, int32_t mode,
+                              const int32_t *ex_terms, const int64_t *ex_off, const int32_t *ph_terms, const int64_t *ph_off,
+                              const int32_t *near_terms, const int64_t *near_off, const int64_t *near_window, int64_t *count_out);
+int  gz_bm25_cover(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids, int64_t k,
+                   int32_t *start_out, int32_t *len_out, int32_t *words_out);
+int  gz_bm25_cover_device(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids_dev,
+                          int64_t k, int32_t *start_out_dev, int32_t *len_out_dev, int32_t *words_out_dev);
 int  gz_bm25_snippets(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids, int64_t k,
                       int64_t width, int32_t *start_out, int32_t *hits_out);
 int  gz_bm25_snippets_device(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids_dev,

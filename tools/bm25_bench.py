@@ -4,6 +4,7 @@
     python tools/bm25_bench.py --search-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --phrase-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --snippet-only [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --near-only [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -76,6 +77,14 @@ width 32:
   snippet_host_loop_q256_k{10,1000}_ms    the host route they replace: texts[d].split() and the definition's loop over the starts for
                        every pair, plain Python (one repetition; k = 1000 only when the k = 10 figure scaled to its pairs stays under a minute)
   snippet_pairs_k* / snippet_pair_words_k* / occurrences_total_k*   pairs with a document, the words of their documents, all occurrences
+Proximity (gz_bm25_search_near_device, gz_bm25_cover_device; --near-only: the phrase rows above and these, in one invocation and one
+timing loop, and with --out they are merged into the file's record instead of replacing it).  The 256 two-word queries of the phrase
+rows, the two words as the near set, window 8:
+  near_all_w8_q256_k10_ms  mode "all" with the near set (gz_bm25_search_near_device + gz_sync), alternating with the phrase rows
+  near_any_w8_q256_k10_ms  the same with mode "any": every document with one of the two words is marked and goes through the near step
+  near_match_fraction_all / _any   mean(count) / N over the 256 queries
+  cover_device_q256_k{10,1000}_ms  gz_bm25_cover_device + gz_sync over the ids that the mode "any" near search with that k left in HBM
+  cover_pairs_k* / cover_pair_words_k*   pairs with a document, the words of their documents
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
 import argparse
 import json
@@ -338,8 +347,8 @@ def search_rows(ctx, res, ix, n, d_text, d_off, nbytes, terms, idf, params, d_id
         res["search_rare_q%d_k10_over_topk" % q] = round(res["search_rare_q%d_k10_ms" % q] / res["topk_rare_q%d_k10_ms" % q], 3)
 
 
-def phrase_rows(ctx, res, t, o, reps):
-    """the phrase rows of the docstring"""
+def phrase_rows(ctx, res, t, o, reps, near=False):
+    """the phrase rows of the docstring; near: the proximity rows beside them"""
     n, nbytes = len(o) - 1, int(o[-1])
     new = hasattr(ctx.lib, "gz_bm25_search_phrase_device")
     d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
@@ -385,10 +394,14 @@ def phrase_rows(ctx, res, t, o, reps):
     rows = [("phrase_all_q256_k10", 1, False, "phrase_match_fraction_all")]
     if new:
         rows += [("phrase_search_q256_k10", 1, True, "phrase_match_fraction_phrase"), ("phrase_any_q256_k10", 0, True, "phrase_match_fraction_any_phrase")]
+    near = near and hasattr(ctx.lib, "gz_bm25_search_near_device")
+    near_kw = dict(nr_terms=terms, nr_off=qoff, nr_window=np.full(256, 8, np.int64))
+    if near:
+        rows += [("near_all_w8_q256_k10", 1, "near", "near_match_fraction_all"), ("near_any_w8_q256_k10", 0, "near", "near_match_fraction_any")]
     ts = {r[0]: [] for r in rows}
     for rep in range(reps + 1):                                      # (the first round is the warm-up of all)
         for key, mode, phrase, frac in rows:
-            kw = dict(ph_terms=terms, ph_off=qoff) if phrase else {}
+            kw = near_kw if phrase == "near" else dict(ph_terms=terms, ph_off=qoff) if phrase else {}
             t0 = time.perf_counter()
             ctx.bm25_search(ix, terms, idf, qoff, params, False, 10, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt, mode=mode, **kw)
             ctx.sync()
@@ -404,6 +417,31 @@ def phrase_rows(ctx, res, t, o, reps):
         res[key + "_ms"], res[key + "_all_ms"] = float(np.median(ts[key])), [round(x, 3) for x in ts[key]]
     if new:
         res["phrase_over_all"] = round(res["phrase_search_q256_k10_ms"] / res["phrase_all_q256_k10_ms"], 3)
+    if near:
+        res["near_all_over_phrase"] = round(res["near_all_w8_q256_k10_ms"] / res["phrase_search_q256_k10_ms"], 3)
+        res["near_any_over_phrase_any"] = round(res["near_any_w8_q256_k10_ms"] / res["phrase_any_q256_k10_ms"], 3)
+        for k in (10, 1000):
+            c_ids, c_sc = ctx.alloc(256 * k * 8), ctx.alloc(256 * k * 8)
+            c_out = [ctx.alloc(256 * k * 4) for _ in range(3)]
+            ctx.bm25_search(ix, terms, idf, qoff, params, False, k, d_ids=c_ids, d_scores=c_sc, d_counts=d_cnt, mode=0, **near_kw)
+            ctx.sync()
+
+            def cover():
+                ctx.bm25_cover_device(ix, terms, qoff, c_ids, k, *c_out)
+                ctx.sync()
+            res["cover_device_q256_k%d_ms" % k], res["cover_device_q256_k%d_all_ms" % k] = median_ms(cover, reps)
+            ids = np.empty(256 * k, np.int64)
+            ctx.d2h(ids, c_ids)
+            got = [np.empty(256 * k, np.int32) for _ in range(3)]
+            for g, d in zip(got, c_out):
+                ctx.d2h(g, d)
+            have = ids >= 0
+            # (every id came out of the near search: the cover is complete and fits the window)
+            assert (got[0][~have] == -1).all() and (got[1][have] >= 1).all() and (got[1][have] <= 8).all() and (got[2][have] >= 1).all()
+            res["cover_pairs_k%d" % k] = int(have.sum())
+            res["cover_pair_words_k%d" % k] = int(np.asarray(lens, dtype=np.int64)[ids[have]].sum())
+            for d in [c_ids, c_sc] + c_out:
+                ctx.free(d)
     for d in (d_ids, d_sc, d_cnt, d_text, d_off):
         ctx.free(d)
     ctx.bm25_destroy(ix)
@@ -488,6 +526,7 @@ def main():
     ap.add_argument("--search-only", action="store_true", help="only the build, top-k (k = 10) and search rows; with --out they are merged into the file")
     ap.add_argument("--phrase-only", action="store_true", help="only the phrase rows; with --out they are merged into the file")
     ap.add_argument("--snippet-only", action="store_true", help="only the snippet rows; with --out they are merged into the file")
+    ap.add_argument("--near-only", action="store_true", help="only the phrase and the proximity rows; with --out they are merged into the file")
     a = ap.parse_args()
     if a.search_only:
         a.remove = a.compact = a.append = 0
@@ -495,13 +534,13 @@ def main():
     n, nbytes = len(o) - 1, int(o[-1])
     ctx = _native.Context()
     res = dict(corpus="configs[2]", docs=n, text_bytes=nbytes, reps=a.reps)
-    if a.phrase_only:
-        phrase_rows(ctx, res, t, o, a.reps)
+    if a.phrase_only or a.near_only:
+        phrase_rows(ctx, res, t, o, a.reps, near=a.near_only)
         print(json.dumps(res))
         if a.out:
             old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
-            old.update({k: v for k, v in res.items() if k.startswith("phrase_")})
-            old["phrase_rows_run"] = dict(docs=n, reps=a.reps)
+            old.update({k: v for k, v in res.items() if k.startswith(("phrase_", "near_", "cover_"))})
+            old["near_rows_run" if a.near_only else "phrase_rows_run"] = dict(docs=n, reps=a.reps)
             with open(a.out, "w") as f:
                 f.write(json.dumps(old) + "\n")
         return
