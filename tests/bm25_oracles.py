@@ -7,6 +7,10 @@
                                      row q = [i for i in argsort(-S[q], stable) if matched[q, i]][:k'], -1 / the NaN PAD behind it
     gather / check_rows              the same for a batch that repeats a few distinct (query, exclude) pairs: the oracle once per
                                      pair, its rows gathered
+    decoded                          term_sequences() as lists of words, to set against [d.split() for d in documents]
+    vocab_oracle                     vocabulary(): the words of d.split() in first-occurrence order and their document frequencies
+    WS / NEAR / sweep_docs           the document-side inputs: the 29 str.isspace() code points, their non-whitespace neighbours in the
+                                     UTF-8 byte space, and every one of them at every byte offset of the first two 64-byte tiles
 ids and counts are compared with ==, scores as uint64 bit patterns: there are no tolerances."""
 import numpy as np
 
@@ -119,3 +123,53 @@ def check(got, S, m, k, what=""):
 
 def same(a, b):
     return len(a) == len(b) and all(np.array_equal(bits(x), bits(y)) if x.dtype == np.float64 else np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def decoded(m, compacted=False):
+    """term_sequences() as lists of words: through vocabulary() on a compacted index, else through _lookup of the current words"""
+    terms, off = m.term_sequences()
+    assert terms.dtype == np.int32 and off.dtype == np.int64 and off.shape == (m.num_doc + 1,) and terms.shape == (int(off[-1]),)
+    if compacted:
+        words = m.vocabulary()[0]
+        name = dict(enumerate(words))
+    else:
+        words = sorted({w for t in m._texts for w in t.split()})
+        ids = m._lookup(words)[0].tolist() if words else []
+        assert len(set(ids)) == len(ids) and -1 not in ids
+        name = dict(zip(ids, words))
+    t, o = terms.tolist(), off.tolist()
+    return [[name[x] for x in t[o[d]:o[d + 1]]] for d in range(m.num_doc)]
+
+
+def vocab_oracle(docs):
+    """(words in the order of their first occurrence over d.split(), df list): what vocabulary() must return"""
+    df = {}
+    for d in docs:
+        for w in dict.fromkeys(d.split()):
+            df[w] = df.get(w, 0) + 1
+    return list(df), list(df.values())
+
+
+# ---- document-side inputs: where str.split() cuts, against the 64-byte tiles of the word walk -----------------------------------------
+WS = [chr(c) for c in range(0x110000) if chr(c).isspace()]               # the 29 code points: 10 of 1 byte, 2 of 2 bytes, 17 of 3 bytes
+# not whitespace, but next to it in the UTF-8 byte space: the controls around 09..0D and 1C..20, the C1 neighbours of 85 and A0, 85 / A0
+# behind another lead byte, the neighbours of 1680, 2000..200A, 2028, 2029, 202F, 205F and 3000, the former whitespace 180E and 200B,
+# and other lead bytes (EF, EE, ED of a lone surrogate, F0, F4)
+NEAR = [chr(c) for c in (0x00, 0x08, 0x0E, 0x1B, 0x21, 0x7F,
+                         0x80, 0x84, 0x86, 0x9F, 0xA1,
+                         0x0485, 0x04A0,
+                         0x167F, 0x1681, 0x180E, 0x1FFF,
+                         0x200B, 0x200C, 0x2027, 0x202A, 0x202E, 0x2030, 0x205E, 0x2060, 0x2FFF, 0x3001,
+                         0xFEFF, 0xE000, 0xD800, 0x1F600, 0x10FFFF)]
+SWEEP_K = range(0, 131)
+
+
+def encoded(text):
+    """the bytes of a document as the index sees them (_packing.pack: UTF-8 with surrogatepass)"""
+    return text.encode("utf-8", "surrogatepass")
+
+
+def sweep_docs():
+    """"x" * k + c + tail for every c of WS + NEAR, k in 0 .. 130 and tail in ("y", "", c + "z"): c's first byte at every lane of the
+    first two tiles and at the start of the third; followed by a word, ending the document, and doubled"""
+    return ["x" * k + c + tail for c in WS + NEAR for k in SWEEP_K for tail in ("y", "", c + "z")]

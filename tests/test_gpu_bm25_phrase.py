@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bm25_restate as R
+from bm25_oracles import decoded
 from genz_tokenize import _native
 from genz_tokenize._packing import pack
 from genz_tokenize.ranking import BM25, BM25Plus
@@ -88,22 +89,6 @@ def check_model(m, docs, queries, phrases, ks, excludes=(None,), modes=MODES, wh
             for k in ks:
                 check(m.search(queries, k, match=mode, exclude=ex, phrase=phrases), S, mt, k, (what, mode, e, k))
             assert np.array_equal(m.count_matches(queries, match=mode, exclude=ex, phrase=phrases), mt.sum(axis=1)), (what, mode, e)
-
-
-def decoded(m, compacted=False):
-    """term_sequences() as lists of words: through vocabulary() on a compacted index, else through _lookup of the current words"""
-    terms, off = m.term_sequences()
-    assert terms.dtype == np.int32 and off.dtype == np.int64 and off.shape == (m.num_doc + 1,) and terms.shape == (int(off[-1]),)
-    if compacted:
-        words = m.vocabulary()[0]
-        name = dict(enumerate(words))
-    else:
-        words = sorted({w for t in m._texts for w in t.split()})
-        ids = m._lookup(words)[0].tolist() if words else []
-        assert len(set(ids)) == len(ids) and -1 not in ids
-        name = dict(zip(ids, words))
-    t, o = terms.tolist(), off.tolist()
-    return [[name[x] for x in t[o[d]:o[d + 1]]] for d in range(m.num_doc)]
 
 
 # ---- 1: a random small corpus --------------------------------------------------------------------------------------------------------
