@@ -174,7 +174,7 @@ struct gz_ctx {
     bool building_words = false;         // the whole-word table is being built: ignore diagnostics
     GzOptions opt;                       // test / experiment switches (gz_debug_set): a copy of the process-wide defaults at creation
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
-    DBuf w_bm[64];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
+    DBuf w_bm[72];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
 };
 
@@ -978,6 +978,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_S_PHTERM, BMW_S_PHOFF,                                                   // the phrase terms of a phrase search
        BMW_SN_IDS, BMW_SN_OUT, BMW_SN_CNT, BMW_SN_OFF, BMW_SN_POS, BMW_SN_WORD,     // snippets and occurrences (bm25_snip_*)
        BMW_S_NRTERM, BMW_S_NROFF, BMW_S_NRWIN,                                      // the near terms and windows of a near search
+       BMW_VC_WORDS, BMW_VC_OFF, BMW_VC_CNT, BMW_VC_OUT,                            // the words, counts and outputs of a vocabulary query (bm25_vocab_locked)
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1615,6 +1616,114 @@ int bm25_topk_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const
         HIPCHK(c, hipGetLastError());
         if (!doc_dev && ((rc = copy_out(c, doc_host + q0 * kk, T.doc_out, (size_t)(rows * kk) * 8, s)) ||
                          (rc = copy_out(c, score_host + q0 * kk, T.score_out, (size_t)(rows * kk) * 8, s))))
+            return rc;
+    }
+    return GZ_OK;
+}
+
+// ---- vocabulary queries (gz_bm25_similar, gz_bm25_prefix, gz_bm25_term_bytes; gz_vocab.inc) --------------------------------------
+static_assert(GZ_VOCAB_EDIT_MAX == GZ_BM25_EDIT_MAX, "the distance kernel holds a state bit per code point of the query word");
+
+// A packed word's code points behind `out`, read as gz_vocab.inc's kernel reads the terms: structural UTF-8 -- the lead byte's class
+// and as many continuation bytes; surrogates and overlong forms pass.  False: the bytes are not that.
+bool vc_decode(const uint8_t* p, int64_t n, std::vector<uint32_t>& out)
+{
+    for (int64_t i = 0; i < n;) {
+        const uint32_t b0 = p[i];
+        const int want = b0 < 0x80 ? 1 : b0 < 0xC0 ? 0 : b0 < 0xE0 ? 2 : b0 < 0xF0 ? 3 : b0 < 0xF8 ? 4 : 0;
+        if (!want || i + want > n) return false;
+        uint32_t cp = want == 1 ? b0 : want == 2 ? (b0 & 0x1F) : want == 3 ? (b0 & 0x0F) : (b0 & 0x07);
+        for (int k = 1; k < want; ++k) {
+            if ((p[i + k] & 0xC0) != 0x80) return false;
+            cp = (cp << 6) | (p[i + k] & 0x3F);
+        }
+        out.push_back(cp);
+        i += want;
+    }
+    return true;
+}
+
+int bm25_vocab_args(gz_bm25* ix, const uint8_t* words, const int64_t* word_off, int64_t n, int64_t k)
+{
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!word_off || n < 0) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (k < 1) return fail(c, GZ_E_INVALID, "k = %lld; a vocabulary query takes k >= 1", (long long)k);
+    const int64_t nbytes = word_off[n] - word_off[0];
+    if (nbytes < 0 || (nbytes > 0 && !words)) return fail(c, GZ_E_INVALID, "bad word offsets");
+    for (int64_t i = 0; i < n; ++i) if (word_off[i + 1] < word_off[i]) return fail(c, GZ_E_INVALID, "word offsets must not decrease");
+    return GZ_OK;
+}
+
+// Key rows of a chunk of words at a time in the context's workspace (at most bm25_vocab_chunk doubles, one row at least, at most
+// 65535 rows), the selection levels over them, and the chunk's unpacked rows to the host.  cps / cpoff: the words' code points
+// (gz_bm25_similar); null: a prefix query over the packed bytes.  The canonical numbering is scratch, as in gz_bm25_terms.
+int bm25_vocab_locked(gz_bm25* ix, const uint8_t* words, const int64_t* word_off, int64_t nq, const std::vector<uint32_t>* cps,
+                      const std::vector<uint32_t>* cpoff, int32_t max_edits, int64_t k, int64_t* ids_out, int32_t* dist_out, int32_t* df_out,
+                      int64_t* count_out)
+{
+    gz_ctx* c = ix->c;
+    DBuf* w = c->w_bm;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t T = ix->n_live, kk = k < T ? k : T;
+    if (kk > GZ_BM25_TOPK_MAX)
+        return fail(c, GZ_E_LIMIT, "k = %lld over %lld terms; a vocabulary query takes at most %d", (long long)k, (long long)T, GZ_BM25_TOPK_MAX);
+    if (nq == 0) return GZ_OK;
+    if (!count_out || (kk > 0 && (!ids_out || !df_out || (cps && !dist_out)))) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (T == 0) {
+        std::memset(count_out, 0, (size_t)nq * 8);
+        return GZ_OK;
+    }
+    BmDrain drain{c};
+    GzBm25Cp C;
+    int64_t B = 0, bad = 0;
+    int rc;
+    if ((rc = bm25_number(c, ix, C, B)) || (rc = bm_read_u32(c, C.ctl + 1, bad))) return rc;
+    if (bad) return fail(c, GZ_E_HIP, "BM25 vocabulary: the index's entries and df contradict each other");
+    const int64_t rmax = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>((int64_t)c->opt.bm25_vocab_chunk / T, 1), 65535), nq);
+    const int64_t tile = bm25_topk_tile(c, rmax, T, kk);
+    int64_t m1, m2;
+    gz_topk_sizes(T, tile, kk, m1, m2);
+    const int64_t nbytes = word_off[nq] - word_off[0];
+    const size_t wbytes = cps ? cps->size() * 4 : (size_t)nbytes, obytes = cps ? (size_t)(nq + 1) * 4 : (size_t)(nq + 1) * 8;
+    if ((rc = bm_alloc(c, w[BMW_SCORES], (size_t)(rmax * T) * 8)) || (rc = bm_alloc(c, w[BMW_CKEY0], (size_t)(rmax * m1) * 8)) ||
+        (rc = bm_alloc(c, w[BMW_CIDX0], (size_t)(rmax * m1) * 4)) || (rc = bm_alloc(c, w[BMW_CKEY1], (size_t)(rmax * m2) * 8)) ||
+        (rc = bm_alloc(c, w[BMW_CIDX1], (size_t)(rmax * m2) * 4)) || (rc = bm_alloc(c, w[BMW_TOUT], (size_t)(rmax * kk) * 16)) ||
+        (rc = bm_alloc(c, w[BMW_VC_WORDS], wbytes + 16)) || (rc = bm_alloc(c, w[BMW_VC_OFF], obytes)) ||
+        (rc = bm_alloc(c, w[BMW_VC_CNT], (size_t)rmax * 4)) || (rc = bm_alloc(c, w[BMW_VC_OUT], (size_t)(rmax * kk) * 16 + (size_t)rmax * 8)))
+        return rc;
+    if (cps) {
+        if ((rc = copy_in(c, w[BMW_VC_WORDS].p, cps->data(), wbytes, s)) || (rc = copy_in(c, w[BMW_VC_OFF].p, cpoff->data(), obytes, s))) return rc;
+    } else if ((nbytes && (rc = copy_in(c, w[BMW_VC_WORDS].p, words + word_off[0], wbytes, s))) ||
+               (rc = copy_in(c, w[BMW_VC_OFF].p, word_off, obytes, s)))
+        return rc;
+    GzBm25Vocab V{};
+    V.tb = C.tb; V.tstart = C.tstart; V.df = C.df; V.order = C.order; V.nlen = C.nlen; V.n_new = T;
+    V.max_edits = max_edits; V.prefix = cps ? 0 : 1;
+    V.keys = (double*)w[BMW_SCORES].p; V.cnt = (uint32_t*)w[BMW_VC_CNT].p;
+    V.sel_id = (const int64_t*)w[BMW_TOUT].p; V.sel_key = (const double*)w[BMW_TOUT].p + rmax * kk; V.k = kk;
+    V.ids_out = (int64_t*)w[BMW_VC_OUT].p; V.cnt_out = V.ids_out + rmax * kk;
+    V.dist_out = (int32_t*)(V.cnt_out + rmax); V.df_out = V.dist_out + rmax * kk;
+    GzTopk K{};
+    K.scores = V.keys; K.n_docs = T; K.k = kk; K.tile = tile;
+    K.ckey[0] = (unsigned long long*)w[BMW_CKEY0].p; K.cidx[0] = (uint32_t*)w[BMW_CIDX0].p;
+    K.ckey[1] = (unsigned long long*)w[BMW_CKEY1].p; K.cidx[1] = (uint32_t*)w[BMW_CIDX1].p;
+    K.doc_out = (int64_t*)w[BMW_TOUT].p; K.score_out = (double*)w[BMW_TOUT].p + rmax * kk;
+    for (int64_t q0 = 0; q0 < nq; q0 += rmax) {
+        const int64_t rows = std::min(rmax, nq - q0);
+        V.rows = K.rows = rows;
+        if (cps) { V.cps = (const uint32_t*)w[BMW_VC_WORDS].p; V.cpoff = (const uint32_t*)w[BMW_VC_OFF].p + q0; }
+        else { V.wbytes = (const uint8_t*)w[BMW_VC_WORDS].p - word_off[0]; V.woff = (const int64_t*)w[BMW_VC_OFF].p + q0; }
+        HIPCHK(c, hipMemsetAsync(V.cnt, 0, (size_t)rows * 4, s));
+        gz_launch_bm25_vocab(cps ? GZ_BM25_VC_EDIT : GZ_BM25_VC_PREFIX, V, s);
+        gz_launch_topk(K, s);
+        gz_launch_bm25_vocab(GZ_BM25_VC_UNPACK, V, s);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = copy_out(c, ids_out + q0 * kk, V.ids_out, (size_t)(rows * kk) * 8, s)) ||
+            (cps && (rc = copy_out(c, dist_out + q0 * kk, V.dist_out, (size_t)(rows * kk) * 4, s))) ||
+            (rc = copy_out(c, df_out + q0 * kk, V.df_out, (size_t)(rows * kk) * 4, s)) ||
+            (rc = copy_out(c, count_out + q0, V.cnt_out, (size_t)rows * 8, s)))
             return rc;
     }
     return GZ_OK;
@@ -3793,6 +3902,88 @@ try {
     if (term_off && (rc = copy_out(c, term_off, C.tstart2, (size_t)(T1 + 1) * 8, s))) return rc;
     if (df && (rc = copy_out(c, df, C.df2, (size_t)T1 * 4, s))) return rc;
     if (bytes && (rc = copy_out(c, bytes, C.arena, (size_t)B, s))) return rc;
+    return GZ_OK;
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_similar(gz_bm25* ix, const uint8_t* words, const int64_t* word_off, int64_t n_words, int32_t max_edits, int64_t k,
+                    int64_t* ids_out, int32_t* dist_out, int32_t* df_out, int64_t* count_out)
+try {
+    int rc = bm25_vocab_args(ix, words, word_off, n_words, k);
+    if (rc) return rc;
+    gz_ctx* c = ix->c;
+    if (max_edits < 0 || max_edits > GZ_BM25_EDIT_MAX)
+        return fail(c, GZ_E_INVALID, "max_edits = %d; a vocabulary query takes 0 .. %d", max_edits, GZ_BM25_EDIT_MAX);
+    std::vector<uint32_t> cps, cpoff((size_t)n_words + 1, 0u);
+    for (int64_t i = 0; i < n_words; ++i) {
+        const int64_t nb = word_off[i + 1] - word_off[i];
+        if (nb && !vc_decode(words + word_off[i], nb, cps)) return fail(c, GZ_E_INVALID, "word %lld is not UTF-8", (long long)i);
+        const size_t m = cps.size() - cpoff[(size_t)i];
+        if (m > (size_t)GZ_BM25_EDIT_MAX)
+            return fail(c, GZ_E_LIMIT, "word %lld has %lld code points; a vocabulary query takes at most %d", (long long)i, (long long)m, GZ_BM25_EDIT_MAX);
+        cpoff[(size_t)i + 1] = (uint32_t)cps.size();
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    return bm25_vocab_locked(ix, words, word_off, n_words, &cps, &cpoff, max_edits, k, ids_out, dist_out, df_out, count_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_prefix(gz_bm25* ix, const uint8_t* words, const int64_t* word_off, int64_t n_words, int64_t k, int64_t* ids_out, int32_t* df_out,
+                   int64_t* count_out)
+try {
+    const int rc = bm25_vocab_args(ix, words, word_off, n_words, k);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ix->c->mu);
+    return bm25_vocab_locked(ix, words, word_off, n_words, nullptr, nullptr, 0, k, ids_out, nullptr, df_out, count_out);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_term_bytes(gz_bm25* ix, const int64_t* ids, int64_t n_ids, int64_t* off_out, uint8_t* bytes, int64_t bytes_cap)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_ids < 0 || (n_ids > 0 && !ids) || (!off_out && !bytes) || (bytes && bytes_cap < 0)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t T = ix->n_live;
+    for (int64_t i = 0; i < n_ids; ++i)
+        if (ids[i] < -1 || ids[i] >= T) return fail(c, GZ_E_INVALID, "term id %lld out of range for %lld terms", (long long)ids[i], (long long)T);
+    if (n_ids == 0) {
+        if (off_out) off_out[0] = 0;
+        return GZ_OK;
+    }
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    BmDrain drain{c};
+    std::vector<uint32_t> len((size_t)n_ids, 0u);
+    std::vector<int64_t> off((size_t)n_ids + 1, 0);
+    GzBm25Vocab V{};
+    int rc;
+    if (T > 0) {
+        GzBm25Cp C;
+        int64_t B = 0, bad = 0;
+        if ((rc = bm25_number(c, ix, C, B)) || (rc = bm_read_u32(c, C.ctl + 1, bad))) return rc;
+        if (bad) return fail(c, GZ_E_HIP, "BM25 vocabulary: the index's entries and df contradict each other");
+        if ((rc = bm_alloc(c, w[BMW_VC_WORDS], (size_t)n_ids * 8)) || (rc = bm_alloc(c, w[BMW_VC_CNT], (size_t)n_ids * 4)) ||
+            (rc = copy_in(c, w[BMW_VC_WORDS].p, ids, (size_t)n_ids * 8, s)))
+            return rc;
+        V.tb = C.tb; V.tstart = C.tstart; V.df = C.df; V.order = C.order; V.nlen = C.nlen; V.n_new = T;
+        V.ids = (const int64_t*)w[BMW_VC_WORDS].p; V.n_ids = n_ids; V.len_out = (uint32_t*)w[BMW_VC_CNT].p;
+        gz_launch_bm25_vocab(GZ_BM25_VC_LEN, V, s);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = copy_out(c, len.data(), V.len_out, (size_t)n_ids * 4, s))) return rc;
+    }
+    for (int64_t i = 0; i < n_ids; ++i) off[(size_t)i + 1] = off[(size_t)i] + (int64_t)len[(size_t)i];
+    const int64_t total = off[(size_t)n_ids];
+    if (bytes && bytes_cap < total)
+        return fail(c, GZ_E_CAPACITY, "BM25 term bytes: %lld bytes, room for %lld", (long long)total, (long long)bytes_cap);
+    if (bytes && total > 0) {
+        if ((rc = bm_alloc(c, w[BMW_VC_OFF], (size_t)(n_ids + 1) * 8)) || (rc = bm_alloc(c, w[BMW_VC_OUT], (size_t)total + 16)) ||
+            (rc = copy_in(c, w[BMW_VC_OFF].p, off.data(), (size_t)(n_ids + 1) * 8, s)))
+            return rc;
+        V.boff = (const int64_t*)w[BMW_VC_OFF].p; V.bytes = (uint8_t*)w[BMW_VC_OUT].p;
+        gz_launch_bm25_vocab(GZ_BM25_VC_GATHER, V, s);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = copy_out(c, bytes, V.bytes, (size_t)total, s))) return rc;
+    }
+    if (off_out) std::memcpy(off_out, off.data(), (size_t)(n_ids + 1) * 8);
     return GZ_OK;
 } GZ_CATCH(ix ? ix->c : nullptr)
 

@@ -284,6 +284,33 @@ inline void gz_topk_sizes(int64_t n_docs, int64_t tile, int64_t k, int64_t& m1, 
 }
 void gz_launch_topk(const GzTopk& T, hipStream_t s);
 
+// BM25 vocabulary queries (gz_vocab.inc): query words against every live term, addressed by the canonical numbering of GzBm25Cp
+// (new id n = table term order[n], nlen[n] bytes at tb + tstart[order[n]]); the index is only read
+constexpr int GZ_VOCAB_EDIT_MAX = 64;     // == GZ_BM25_EDIT_MAX of the public header: a query word's code points, one state bit each
+struct GzBm25Vocab {
+    const uint8_t* tb; const int64_t* tstart; const uint32_t* df; const uint32_t* order; const uint32_t* nlen;
+    int64_t n_new;                        // live terms
+    // the chunk: `rows` words.  GZ_BM25_VC_EDIT: word r = code points cps[cpoff[r] .. cpoff[r + 1]) (at most GZ_VOCAB_EDIT_MAX);
+    // GZ_BM25_VC_PREFIX: word r = wbytes[woff[r] .. woff[r + 1])
+    const uint32_t* cps; const uint32_t* cpoff;
+    const uint8_t* wbytes; const int64_t* woff;
+    int64_t rows;
+    int32_t max_edits;
+    double* keys;                         // [rows, n_new] -(distance * 2^32) + df of a matching term (prefix: df), else NaN
+    uint32_t* cnt;                        // [rows] matching terms (cleared by the caller)
+    // GZ_BM25_VC_UNPACK: the selection over the key rows (gz_launch_topk's doc_out / score_out) -> the outputs
+    const int64_t* sel_id; const double* sel_key; int64_t k;
+    int32_t prefix;                       // 1: the keys are df alone
+    int64_t* ids_out; int32_t* dist_out; int32_t* df_out;     // [rows, k]; -1 / -1 / 0 from cnt[r] on (dist_out may be null)
+    int64_t* cnt_out;                     // [rows]
+    // GZ_BM25_VC_LEN / GZ_BM25_VC_GATHER: listed terms (canonical ids; -1: no term)
+    const int64_t* ids; int64_t n_ids;
+    uint32_t* len_out;                    // [n_ids] bytes of every listed term
+    const int64_t* boff; uint8_t* bytes;  // [n_ids + 1] the lengths' exclusive scan; term i -> bytes[boff[i] .. boff[i + 1])
+};
+enum { GZ_BM25_VC_EDIT, GZ_BM25_VC_PREFIX, GZ_BM25_VC_UNPACK, GZ_BM25_VC_LEN, GZ_BM25_VC_GATHER };
+void gz_launch_bm25_vocab(int step, const GzBm25Vocab& V, hipStream_t s);
+
 // BM25 search (gz_search.inc): term-major postings, and the matching documents of every query counted, scored and ranked
 constexpr int GZ_SEARCH_TILE = 2048;      // bitmap words per workgroup of the counting / candidate kernels (8 per thread)
 struct GzBm25Post {

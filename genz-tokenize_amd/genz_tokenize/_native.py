@@ -19,6 +19,7 @@ GZ_OK, GZ_E_INVALID, GZ_E_UTF8, GZ_E_HIP, GZ_E_NOTABLES = 0, -1, -2, -3, -4
 GZ_E_CAPACITY, GZ_E_LIMIT, GZ_E_NOMEM, GZ_E_RCCL, GZ_E_NODEVICE = -5, -6, -7, -8, -9
 GZ_BM25_POSITIONS, GZ_BM25_PHRASE_MAX = 1, 64
 GZ_BM25_NEAR_MAX = 64
+GZ_BM25_EDIT_MAX = 64
 GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP_WORDS = 0x1, 0x2, 0x4, 0x100, 0x200, 0x400
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
@@ -42,6 +43,7 @@ SYMBOLS = [
     "gz_bm25_search_phrase", "gz_bm25_search_phrase_device", "gz_bm25_match_count_phrase",
     "gz_bm25_snippets", "gz_bm25_snippets_device", "gz_bm25_occurrences",
     "gz_bm25_search_near", "gz_bm25_search_near_device", "gz_bm25_match_count_near", "gz_bm25_cover", "gz_bm25_cover_device",
+    "gz_bm25_similar", "gz_bm25_prefix", "gz_bm25_term_bytes",
 ]
 
 _lib = None
@@ -169,6 +171,10 @@ def load_library():
         L.gz_bm25_match_count_near.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gz_bm25_cover.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp]
         L.gz_bm25_cover_device.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp]
+    if hasattr(L, "gz_bm25_similar"):
+        L.gz_bm25_similar.argtypes = [vp, vp, vp, i64, i32, i64, vp, vp, vp, vp]
+        L.gz_bm25_prefix.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp]
+        L.gz_bm25_term_bytes.argtypes = [vp, vp, i64, vp, vp, i64]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -581,6 +587,49 @@ class Context:
         if off[t]:
             self._check(self.lib.gz_bm25_terms(C.c_void_p(index), None, None, _ptr(data), int(off[t])))
         return off, data[:int(off[t])], df[:t]
+
+    def bm25_similar(self, index: int, words: np.ndarray, word_off: np.ndarray, max_edits: int, k: int):
+        """packed words -> (ids int64 [W, k'], dist int32 [W, k'], df int32 [W, k'], counts int64 [W]) with k' = min(k, live terms):
+        the terms within max_edits of every word in ascending (distance, -df, id), ids as bm25_terms numbers them; -1 / -1 / 0 behind
+        a row's count.  The index is not modified."""
+        words = np.ascontiguousarray(words, dtype=np.uint8)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        n = len(word_off) - 1
+        kk = max(0, min(int(k), self.bm25_info(index)[1]))
+        ids = np.empty((n, kk), dtype=np.int64)
+        dist = np.empty((n, kk), dtype=np.int32)
+        df = np.empty((n, kk), dtype=np.int32)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self.lib.gz_bm25_similar(C.c_void_p(index), _ptr(words) if len(words) else None, _ptr(word_off), n, int(max_edits), int(k),
+                                             _ptr(ids) if ids.size else None, _ptr(dist) if dist.size else None,
+                                             _ptr(df) if df.size else None, _ptr(counts)))
+        return ids, dist, df, counts[:n]
+
+    def bm25_prefix(self, index: int, words: np.ndarray, word_off: np.ndarray, k: int):
+        """packed words -> (ids int64 [W, k'], df int32 [W, k'], counts int64 [W]): the terms that start with every word in ascending
+        (-df, id); shapes, ids and padding as bm25_similar."""
+        words = np.ascontiguousarray(words, dtype=np.uint8)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        n = len(word_off) - 1
+        kk = max(0, min(int(k), self.bm25_info(index)[1]))
+        ids = np.empty((n, kk), dtype=np.int64)
+        df = np.empty((n, kk), dtype=np.int32)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        self._check(self.lib.gz_bm25_prefix(C.c_void_p(index), _ptr(words) if len(words) else None, _ptr(word_off), n, int(k),
+                                            _ptr(ids) if ids.size else None, _ptr(df) if df.size else None, _ptr(counts)))
+        return ids, df, counts[:n]
+
+    def bm25_term_bytes(self, index: int, ids: np.ndarray):
+        """(off int64 [n + 1], bytes uint8 [off[n]]) of the listed terms (ids as bm25_terms numbers them; -1: no term, no bytes):
+        only these terms' bytes are gathered and copied."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        n = len(ids)
+        off = np.zeros(n + 1, dtype=np.int64)
+        self._check(self.lib.gz_bm25_term_bytes(C.c_void_p(index), _ptr(ids) if n else None, n, _ptr(off), None, 0))     # sizes first
+        data = np.empty(max(int(off[n]), 1), dtype=np.uint8)
+        if off[n]:
+            self._check(self.lib.gz_bm25_term_bytes(C.c_void_p(index), _ptr(ids), n, None, _ptr(data), int(off[n])))
+        return off, data[:int(off[n])]
 
     def bm25_footprint(self, index: int):
         """(text bytes in use, terms held in the term table -- dead ones included, device bytes allocated to the index)"""

@@ -66,6 +66,17 @@ GPU from the index itself (gz_bm25_compact): afterwards the index is the one a f
 ids and device memory included -- without any string being packed, tokenised or hashed again.  `footprint()` tells when that is
 worth it, and `vocabulary()` reads the current words and their document frequencies (gz_bm25_terms) in any state of the index.
 
+Vocabulary lookup: everything above starts from an exact, byte-for-byte lookup of the query's words, so a word that is one letter
+off -- `cong nghe` for `công nghệ`, a dropped tone mark, half a word -- matches nothing.  `similar_words(words, max_edits, k)`
+gives, for every word, the terms of the index within `max_edits` edits of it (Levenshtein distance over code points), the closest
+first, the more frequent first among equally close ones, with distances, document frequencies and the number of such terms;
+`prefix_words(prefixes, k)` the most frequent terms that start with a prefix.  Both compare every word with every live term on the
+GPU (csrc/gz_vocab.inc: a bit-parallel distance recurrence with the query word as the pattern, a lane per term, hence at most 64
+code points a word) and select the k best with `top_k`'s selection; the ids are `vocabulary()`'s in any state of the index, which
+is not modified.  `term_texts(ids)` reads back the words of given ids only.  `suggest`, `complete` and `correct(queries)` compose
+them on the host: (word, distance, df) lists, (word, df) lists, and the queries with every unknown word replaced by its best match.
+`search` itself stays exact: pass it `correct(queries)` to search for what was meant.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -202,6 +213,114 @@ class BM25:
         the term table, dead ones included, "device_bytes": device memory allocated to the index}"""
         t, n, d = self._ctx.bm25_footprint(self._index)
         return {"text_bytes": t, "table_terms": n, "device_bytes": d}
+
+    # ---- words that look like a given one: typo-tolerant and prefix lookup over the vocabulary --------------------------
+    @staticmethod
+    def _edits(max_edits) -> int:
+        if isinstance(max_edits, bool) or not isinstance(max_edits, numbers.Integral):
+            raise TypeError("max_edits must be int, not %s" % type(max_edits).__name__)
+        max_edits = int(max_edits)
+        if not 0 <= max_edits <= _native.GZ_BM25_EDIT_MAX:
+            raise ValueError("max_edits must lie in [0, %d], not %d" % (_native.GZ_BM25_EDIT_MAX, max_edits))
+        return max_edits
+
+    def _n_terms(self) -> int:
+        """T = len(vocabulary()[0]): host bookkeeping of the index, no device work"""
+        return self._ctx.bm25_info(self._index)[1]
+
+    def similar_words(self, words: Sequence[str], max_edits: int = 2, k: int = 10):
+        """(ids int64 [W, k'], dist int32 [W, k'], df int32 [W, k'], counts int64 [W]), k' = min(k, T) with V, DF = vocabulary() and
+        T = len(V).  With ed(a, b) the Levenshtein distance of two str as sequences of code points (unit-cost insertion, deletion,
+        substitution; no transposition; a lone surrogate is one code point): the matching terms of words[w] are
+        {i : ed(words[w], V[i]) <= max_edits}, counts[w] is their number (it may exceed k') and row w holds the first k' of
+        sorted(matching, key=lambda i: (ed(words[w], V[i]), -DF[i], i)) with their distances and document frequencies; positions from
+        counts[w] on hold id -1, dist -1, df 0.  A word of the vocabulary comes first with distance 0; "" is a word like any other
+        (its distance to a term is the term's length); the words are not split.  The ids index vocabulary() in any state of the
+        index -- after appends and removals too -- and are `_lookup`'s once it is compacted.  Every word is compared with every
+        live term on the GPU and the rows are selected there; the index is not modified.  TypeError: a word that is no str, k or
+        max_edits that is bool or no int; ValueError: k < 1, max_edits outside [0, 64]; _native.GzError (GZ_E_LIMIT): a word of
+        more than 64 code points, k' above 1024."""
+        words = _strings(words, "words")
+        max_edits = self._edits(max_edits)
+        k = self._k(k)
+        kk = min(k, self._n_terms())
+        if not words:
+            return (np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.int32), np.zeros((0, kk), dtype=np.int32),
+                    np.zeros(0, dtype=np.int64))
+        buf, off = _pack(words)
+        return self._ctx.bm25_similar(self._index, buf, off, max_edits, k)
+
+    def prefix_words(self, prefixes: Sequence[str], k: int = 10):
+        """(ids int64 [W, k'], df int32 [W, k'], counts int64 [W]): as `similar_words` for the terms with
+        V[i].startswith(prefixes[w]), in the order (-DF[i], i) -- the most frequent completions first.  "" matches every term."""
+        prefixes = _strings(prefixes, "prefixes")
+        k = self._k(k)
+        kk = min(k, self._n_terms())
+        if not prefixes:
+            return np.zeros((0, kk), dtype=np.int64), np.zeros((0, kk), dtype=np.int32), np.zeros(0, dtype=np.int64)
+        buf, off = _pack(prefixes)
+        return self._ctx.bm25_prefix(self._index, buf, off, k)
+
+    def term_texts(self, ids) -> list:
+        """The words with these ids of vocabulary()'s numbering (what similar_words / prefix_words return): any integer array or
+        nesting of lists of ids gives the same nesting of str, id -1 gives "".  Only the requested terms' bytes are gathered on the
+        GPU and copied back; the vocabulary is not read.  TypeError: ids that are no integers; IndexError: an id outside [-1, T)."""
+        if isinstance(ids, np.ndarray):
+            if ids.dtype == np.bool_ or not np.issubdtype(ids.dtype, np.integer):
+                raise TypeError("ids must be integers, not %s" % ids.dtype)
+            ids = ids.tolist()
+        flat = []
+
+        def walk(x):
+            if isinstance(x, (list, tuple)):
+                return [walk(y) for y in x]
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+                raise TypeError("ids must be integers, not %s" % type(x).__name__)
+            flat.append(int(x))
+            return len(flat) - 1
+
+        nest = walk(ids)
+        if flat:
+            n_terms = self._n_terms()
+            if min(flat) < -1 or max(flat) >= n_terms:
+                raise IndexError("term ids must lie in [-1, %d)" % n_terms)
+            off, data = self._ctx.bm25_term_bytes(self._index, np.array(flat, dtype=np.int64))
+            raw, off = data.tobytes(), off.tolist()
+            texts = [raw[off[i]:off[i + 1]].decode("utf-8", "surrogatepass") for i in range(len(flat))]
+
+        def fill(x):
+            return [fill(y) for y in x] if isinstance(x, list) else texts[x]
+
+        return fill(nest)
+
+    def suggest(self, words: Sequence[str], max_edits: int = 2, k: int = 10) -> list:
+        """A list of W lists of (word, distance, df): `similar_words` with the ids as `term_texts` spells them, without the padding."""
+        ids, dist, df, counts = self.similar_words(words, max_edits, k)
+        texts = self.term_texts(ids)
+        return [list(zip(t[:c], d[:c], f[:c])) for t, d, f, c in zip(texts, dist.tolist(), df.tolist(), counts.tolist())]
+
+    def complete(self, prefixes: Sequence[str], k: int = 10) -> list:
+        """A list of W lists of (word, df): `prefix_words` with the ids as `term_texts` spells them, without the padding."""
+        ids, df, counts = self.prefix_words(prefixes, k)
+        texts = self.term_texts(ids)
+        return [list(zip(t[:c], f[:c])) for t, f, c in zip(texts, df.tolist(), counts.tolist())]
+
+    def correct(self, queries: Sequence[str], max_edits: int = 2) -> list:
+        """A list of str: " ".join over q.split() of every query, a word the index holds kept, any other replaced by its best
+        `similar_words` match (the smallest (distance, -df, id) within max_edits) when there is one, else kept.  One lookup and one
+        similar_words call for the whole batch."""
+        split = [q.split() for q in _strings(queries, "queries")]
+        max_edits = self._edits(max_edits)
+        words = [w for ws in split for w in ws]
+        fixed = {}
+        if words:
+            terms = self._lookup(words)[0].tolist()
+            unknown = list(dict.fromkeys(w for w, t in zip(words, terms) if t < 0))
+            ids, _, _, counts = self.similar_words(unknown, max_edits, 1)
+            if unknown and ids.shape[1]:
+                best = self.term_texts(ids[:, 0])
+                fixed = {w: b for w, b, c in zip(unknown, best, counts.tolist()) if c}
+        return [" ".join(fixed.get(w, w) for w in ws) for ws in split]
 
     # ---- the reference's per-document lists, built lazily on the host -------------------------------------------------
     @property

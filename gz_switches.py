@@ -7,6 +7,9 @@ and bench.py's diagnostic modes say what they want in ONE variable of their own,
 
 and call `apply()` once, before any context exists: every pair goes to gz_debug_set(NULL, key, value) -- the process-wide
 defaults that contexts created afterwards copy and that the table builder reads.  Not part of the product package.
+
+The keys, their ranges and defaults are listed at gz_debug_set in include/genz_tokenize.h.  The chunk sizes of the ranking calls,
+which a test lowers to force several chunks with a small batch: bm25_topk_chunk, bm25_search_chunk, bm25_vocab_chunk.
 """
 import os
 import sys

@@ -247,6 +247,8 @@ int64_t gz_limit(int which);
  *   bm25_topk_tile (0..4096; 0)  BM25 top-k: documents per workgroup of the first selection level (0: chosen per call)
  *   bm25_search_chunk (1..2^30; 2^27)  BM25 search: doubles of candidate scores held in the context's workspace at a time (queries
  *                              are marked, scored and ranked a chunk at a time, one row at least; the chunk's bitmap words obey it too)
+ *   bm25_vocab_chunk (1..2^30; 2^23)  BM25 vocabulary queries (gz_bm25_similar, gz_bm25_prefix): doubles of key rows held in the
+ *                              context's workspace at a time (the words are compared and ranked a chunk at a time, one row at least)
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -571,6 +573,28 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *                          and df (either may be NULL), and B = term_off[T] is the room the bytes need; a second call with
  *                          bytes != NULL and bytes_cap >= B copies them (and fills term_off / df again where they are not NULL).
  *                          bytes_cap < B: GZ_E_CAPACITY, nothing written.  term_off and bytes both NULL: GZ_E_INVALID.
+ *   gz_bm25_similar        typo-tolerant word lookup over the vocabulary of an index in any state, which is not modified.  The ids are
+ *                          those of gz_bm25_terms (T live terms in first-occurrence order).  words / word_off: n_words packed words
+ *                          as for gz_bm25_lookup (host buffers; a word is taken whole, whitespace included).  For word w the
+ *                          matching terms are those within max_edits (0 .. GZ_BM25_EDIT_MAX) of it in Levenshtein distance -- unit
+ *                          cost insertion, deletion, substitution of code points, no transposition; the empty word's distance to a
+ *                          term is the term's length.  count_out[w] = their number (it may exceed k'), and row w of the
+ *                          [n_words, k'] outputs, k' = min(k, T), holds the first k' of them in ascending (distance, -df, id) with
+ *                          their distances and dfs; positions from count_out[w] on hold id -1, distance -1, df 0.  Every word is
+ *                          compared with every live term on the device (gz_vocab.inc: a bit-parallel recurrence, a lane per term),
+ *                          a chunk of words at a time (switch bm25_vocab_chunk), and ranked by gz_bm25_topk's selection; only the
+ *                          outputs cross.  GZ_E_INVALID: k < 1, max_edits out of range, decreasing offsets, bytes that are not
+ *                          structurally valid UTF-8 (lead and continuation bytes; surrogates pass); GZ_E_LIMIT: a word of more
+ *                          than GZ_BM25_EDIT_MAX code points, k' above GZ_BM25_TOPK_MAX.  Nothing is written on an error.
+ *   gz_bm25_prefix         the same for "terms that start with the word": byte-wise, which for structurally valid UTF-8 is
+ *                          code-point-wise; the empty word matches every term.  Order (-df, id); outputs, padding, k and errors as
+ *                          gz_bm25_similar (no distances, a word of any length, its bytes are not examined).
+ *   gz_bm25_term_bytes     the bytes of listed terms only: ids[n_ids] are ids of gz_bm25_terms' numbering, -1 = no term (no bytes).
+ *                          Sizes first, as gz_bm25_terms: a call with bytes == NULL fills off_out[n_ids + 1] (term i of the list =
+ *                          bytes[off_out[i] .. off_out[i + 1]), off_out[0] = 0); a call with bytes != NULL and bytes_cap >=
+ *                          off_out[n_ids] gathers them on the device and copies them (off_out is filled again unless NULL).
+ *                          bytes_cap too small: GZ_E_CAPACITY, nothing written.  GZ_E_INVALID: an id outside [-1, T), off_out and
+ *                          bytes both NULL.  The vocabulary as a whole is not read back.
  *   gz_bm25_footprint      host bookkeeping, no device work: out[0] = bytes of the text copy in use (what GZ_E_LIMIT of an append
  *                          counts), out[1] = terms held in the term table, dead ones included, out[2] = device bytes allocated
  *                          to the index's ten buffers, capacities included, to its postings while they exist and, for a
@@ -583,6 +607,7 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
 #define GZ_BM25_POSITIONS 1
 #define GZ_BM25_PHRASE_MAX 64
 #define GZ_BM25_NEAR_MAX 64
+#define GZ_BM25_EDIT_MAX 64
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
@@ -655,6 +680,12 @@ int  gz_bm25_remove(gz_bm25 *index, const int64_t *doc_ids, int64_t n_ids);
 int  gz_bm25_remove_device(gz_bm25 *index, const int64_t *doc_ids_dev, int64_t n_ids);
 int  gz_bm25_compact(gz_bm25 *index);
 int  gz_bm25_terms(gz_bm25 *index, int64_t *term_off, int32_t *df, uint8_t *bytes, int64_t bytes_cap);
+int  gz_bm25_similar(gz_bm25 *index, const uint8_t *words, const int64_t *word_off, int64_t n_words, int32_t max_edits, int64_t k,
+                     int64_t *ids_out, int32_t *dist_out, int32_t *df_out, int64_t *count_out);
+int  gz_bm25_prefix(gz_bm25 *index, const uint8_t *words, const int64_t *word_off, int64_t n_words, int64_t k, int64_t *ids_out,
+                    int32_t *df_out, int64_t *count_out);
+int  gz_bm25_term_bytes(gz_bm25 *index, const int64_t *ids, int64_t n_ids, int64_t *off_out /* n_ids + 1 */, uint8_t *bytes,
+                        int64_t bytes_cap);
 int  gz_bm25_footprint(gz_bm25 *index, int64_t out[3]);
 void gz_bm25_destroy(gz_bm25 *index);
 

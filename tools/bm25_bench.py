@@ -3,6 +3,7 @@
     python tools/bm25_bench.py [--docs 1000000] [--reps 5] [--remove 10000] [--compact 10000] [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --search-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --phrase-only [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --vocab-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --snippet-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --near-only [--out profiles/bm25_bench.json]
 
@@ -85,6 +86,17 @@ rows, the two words as the near set, window 8:
   near_match_fraction_all / _any   mean(count) / N over the 256 queries
   cover_device_q256_k{10,1000}_ms  gz_bm25_cover_device + gz_sync over the ids that the mode "any" near search with that k left in HBM
   cover_pairs_k* / cover_pair_words_k*   pairs with a document, the words of their documents
+Vocabulary (gz_bm25_similar, gz_bm25_prefix, gz_bm25_term_bytes; --vocab-only: these rows alone, and with --out they are merged into the
+file's record instead of replacing it).  The index is gz_bm25_build_device over the corpus; the W words are terms of the vocabulary
+(fixed seed) with one random edit each -- a code point substituted, deleted or inserted; a host clock around the call (its outputs
+are on the host when it returns):
+  vocab_similar_w{1,64,256}_ms   gz_bm25_similar, max_edits 2, k 10
+  vocab_prefix_w{1,64,256}_ms    gz_bm25_prefix over the first three code points of the same words, k 10
+  vocab_term_texts_w{1,64,256}_ms  gz_bm25_term_bytes of the W * 10 ids the similar call returned: both calls of the sizes-first protocol
+  vocab_host_read_ms / vocab_host_loop_w1_ms   the host route they replace: gz_bm25_terms into a list of str, and one word against it in
+                       plain Python (terms whose length differs by more than 2 skipped, a two-row Levenshtein for the rest; one repetition)
+  vocab_similar_ms_per_word_w64 / _w256, vocab_key_rows_per_chunk, vocab_key_bytes   time / W, and the key rows held at a time:
+                       min(W, max(1, 2^23 // terms)) rows of terms doubles (switch bm25_vocab_chunk)
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
 import argparse
 import json
@@ -510,6 +522,62 @@ def snippet_rows(ctx, res, t, o, reps):
     del m
 
 
+def vocab_rows(ctx, res, t, o, reps):
+    """the vocabulary rows of the docstring"""
+    n, nbytes = len(o) - 1, int(o[-1])
+    d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
+    ctx.h2d(d_text, t)
+    ctx.h2d(d_off, o)
+    ix = ctx.bm25_build_device(d_text, d_off, n, nbytes)
+    T = ctx.bm25_info(ix)[1]
+    res["terms"] = T
+
+    def read():
+        off, data, _ = ctx.bm25_terms(ix)
+        raw, off = data.tobytes(), off.tolist()
+        return [raw[off[i]:off[i + 1]].decode("utf-8", "surrogatepass") for i in range(len(off) - 1)]
+    res["vocab_host_read_ms"], res["vocab_host_read_all_ms"] = median_ms(read, reps)
+    V = read()
+    rng = np.random.default_rng(7)
+    words = []
+    for i in rng.integers(T, size=256):
+        w, c = V[int(i)], "abcdeghimnotu"[int(rng.integers(13))]
+        p, op = int(rng.integers(len(w) + 1)), int(rng.integers(3))
+        words.append(w[:p] + c + w[p:] if op == 0 or len(w) < 2 else w[:min(p, len(w) - 1)] + (c if op == 1 else "") + w[min(p, len(w) - 1) + 1:])
+    rows = max(1, (1 << 23) // max(T, 1))
+    for W in (1, 64, 256):
+        wb, wo = pack(words[:W])
+        pb, po = pack([w[:3] for w in words[:W]])
+        res["vocab_similar_w%d_ms" % W], res["vocab_similar_w%d_all_ms" % W] = median_ms(lambda: ctx.bm25_similar(ix, wb, wo, 2, 10), reps)
+        res["vocab_prefix_w%d_ms" % W], res["vocab_prefix_w%d_all_ms" % W] = median_ms(lambda: ctx.bm25_prefix(ix, pb, po, 10), reps)
+        ids, dist, df, counts = ctx.bm25_similar(ix, wb, wo, 2, 10)
+        res["vocab_term_texts_w%d_ms" % W], res["vocab_term_texts_w%d_all_ms" % W] = median_ms(lambda: ctx.bm25_term_bytes(ix, ids), reps)
+        res["vocab_similar_mean_count_w%d" % W] = float(counts.mean())
+        if W > 1:
+            res["vocab_similar_ms_per_word_w%d" % W] = res["vocab_similar_w%d_ms" % W] / W
+    res["vocab_key_rows_per_chunk"], res["vocab_key_bytes"] = min(256, rows), min(256, rows) * T * 8
+
+    def lev(a, b):
+        prev = list(range(len(b) + 1))
+        for i, ca in enumerate(a, 1):
+            cur = [i]
+            for j, cb in enumerate(b, 1):
+                cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ca != cb)))
+            prev = cur
+        return prev[-1]
+    w = words[0]
+    ids, dist, df, counts = ctx.bm25_similar(ix, *pack([w]), 2, 10)
+    _, _, DF = ctx.bm25_terms(ix)
+    DF = DF.tolist()
+    t0 = time.perf_counter()
+    m = sorted((d, -DF[i], i) for i, x in enumerate(V) if abs(len(x) - len(w)) <= 2 for d in (lev(w, x),) if d <= 2)
+    res["vocab_host_loop_w1_ms"] = (time.perf_counter() - t0) * 1e3
+    assert int(counts[0]) == len(m) and ids[0].tolist()[:len(m)] == [x[2] for x in m[:10]] and dist[0].tolist()[:len(m)] == [x[0] for x in m[:10]]
+    ctx.bm25_destroy(ix)
+    ctx.free(d_text)
+    ctx.free(d_off)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -527,6 +595,7 @@ def main():
     ap.add_argument("--phrase-only", action="store_true", help="only the phrase rows; with --out they are merged into the file")
     ap.add_argument("--snippet-only", action="store_true", help="only the snippet rows; with --out they are merged into the file")
     ap.add_argument("--near-only", action="store_true", help="only the phrase and the proximity rows; with --out they are merged into the file")
+    ap.add_argument("--vocab-only", action="store_true", help="only the vocabulary rows; with --out they are merged into the file")
     a = ap.parse_args()
     if a.search_only:
         a.remove = a.compact = a.append = 0
@@ -541,6 +610,16 @@ def main():
             old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
             old.update({k: v for k, v in res.items() if k.startswith(("phrase_", "near_", "cover_"))})
             old["near_rows_run" if a.near_only else "phrase_rows_run"] = dict(docs=n, reps=a.reps)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
+    if a.vocab_only:
+        vocab_rows(ctx, res, t, o, a.reps)
+        print(json.dumps(res))
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith("vocab_")})
+            old["vocab_rows_run"] = dict(docs=n, reps=a.reps)
             with open(a.out, "w") as f:
                 f.write(json.dumps(old) + "\n")
         return
