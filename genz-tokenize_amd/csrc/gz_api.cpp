@@ -979,6 +979,7 @@ enum { BMW_OFF, BMW_WOFF, BMW_BSUM, BMW_CTL, BMW_WSTART, BMW_WEND, BMW_WDOC, BMW
        BMW_SN_IDS, BMW_SN_OUT, BMW_SN_CNT, BMW_SN_OFF, BMW_SN_POS, BMW_SN_WORD,     // snippets and occurrences (bm25_snip_*)
        BMW_S_NRTERM, BMW_S_NROFF, BMW_S_NRWIN,                                      // the near terms and windows of a near search
        BMW_VC_WORDS, BMW_VC_OFF, BMW_VC_CNT, BMW_VC_OUT,                            // the words, counts and outputs of a vocabulary query (bm25_vocab_locked)
+       BMW_G_GOFF, BMW_G_AOFF, BMW_G_IDF, BMW_G_MASK,                               // the groups of a grouped search (bm25_search_locked)
        BMW_COUNT };
 static_assert(BMW_COUNT <= (int)(sizeof(gz_ctx::w_bm) / sizeof(DBuf)), "gz_ctx::w_bm is too small");
 
@@ -1863,6 +1864,68 @@ int bm25_near_args(gz_bm25* ix, int64_t nq, const int32_t* nrterm, const int64_t
     return GZ_OK;
 }
 
+static_assert(GZ_GROUP_MAX == GZ_BM25_GROUP_MAX, "the group kernels and the public header agree on a group's size");
+
+// what the _groups entry points check before anything is allocated or launched: group g of query q (group_off[q] <= g <
+// group_off[q + 1]) = the alternatives alt_terms[alt_off[g] .. alt_off[g + 1]), each in [-1, n_terms)
+int bm25_group_args(gz_bm25* ix, const int32_t* aterm, const int64_t* aoff, const double* gidf, bool need_idf, const int64_t* goff, int64_t nq)
+{
+    gz_ctx* c = ix->c;
+    if (!goff || nq < 0) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (goff[0] < 0) return fail(c, GZ_E_INVALID, "bad group offsets");
+    for (int64_t q = 0; q < nq; ++q) if (goff[q + 1] < goff[q]) return fail(c, GZ_E_INVALID, "group offsets must not decrease");
+    const int64_t g0 = goff[0], g1 = goff[nq];
+    if (g1 == g0) return GZ_OK;
+    if (!aoff || (need_idf && !gidf)) return fail(c, GZ_E_INVALID, "group offsets without alternatives or idf");
+    if (aoff[g0] < 0) return fail(c, GZ_E_INVALID, "bad alternative offsets");
+    for (int64_t g = g0; g < g1; ++g) if (aoff[g + 1] < aoff[g]) return fail(c, GZ_E_INVALID, "alternative offsets must not decrease");
+    if (aoff[g1] > aoff[g0] && !aterm) return fail(c, GZ_E_INVALID, "alternative offsets without terms");
+    for (int64_t j = aoff[g0]; j < aoff[g1]; ++j)
+        if (aterm[j] < -1 || aterm[j] >= ix->n_terms) return fail(c, GZ_E_INVALID, "alternative term id %d out of range", aterm[j]);
+    return GZ_OK;
+}
+
+// The groups of a call as the kernels take them (gz_groups.inc), all offsets from 0: the DISTINCT alternatives of every group that
+// are terms at all (-1 dropped, a repeat counted once; ascending id, which no answer depends on), the groups of every row, and
+// the row boundaries of the flat alternative list -- the "query offsets" of the word and marking kernels.
+struct BmGroups {
+    std::vector<int32_t> aterm;
+    std::vector<int64_t> aoff, goff, rowoff;
+    const double* gidf = nullptr;         // of the first group (null: a match count)
+    int64_t ng = 0;
+};
+
+// (host memory only, before any launch) GZ_E_LIMIT: a group of more than GZ_BM25_GROUP_MAX distinct alternatives
+int bm25_group_pack(gz_bm25* ix, const int32_t* aterm, const int64_t* aoff, const double* gidf, const int64_t* goff, int64_t nq, BmGroups& G)
+{
+    gz_ctx* c = ix->c;
+    const int64_t g0 = goff[0];
+    G.ng = goff[nq] - g0;
+    alloc_site(c);
+    G.goff.resize((size_t)nq + 1);
+    G.rowoff.resize((size_t)nq + 1);
+    G.aoff.resize((size_t)G.ng + 1);
+    G.aoff[0] = 0;
+    std::vector<int32_t> one;
+    for (int64_t g = 0; g < G.ng; ++g) {
+        one.clear();
+        if (aoff[g0 + g + 1] > aoff[g0 + g]) one.assign(aterm + aoff[g0 + g], aterm + aoff[g0 + g + 1]);
+        one.erase(std::remove(one.begin(), one.end(), -1), one.end());
+        std::sort(one.begin(), one.end());
+        one.erase(std::unique(one.begin(), one.end()), one.end());
+        if ((int64_t)one.size() > GZ_BM25_GROUP_MAX)
+            return fail(c, GZ_E_LIMIT, "a group of %lld distinct alternatives; a group takes at most %d", (long long)one.size(), GZ_BM25_GROUP_MAX);
+        G.aterm.insert(G.aterm.end(), one.begin(), one.end());
+        G.aoff[(size_t)g + 1] = (int64_t)G.aterm.size();
+    }
+    for (int64_t q = 0; q <= nq; ++q) {
+        G.goff[(size_t)q] = goff[q] - g0;
+        G.rowoff[(size_t)q] = G.aoff[(size_t)(goff[q] - g0)];
+    }
+    G.gidf = gidf && G.ng ? gidf + g0 : nullptr;
+    return GZ_OK;
+}
+
 // A chunk of queries at a time (its bitmaps hold at most bm25_search_chunk words, one row at least, at most 65535 rows): mark the
 // documents of every query word's postings in the row's bitmap, count and rank the bits, and read the counts back -- they size
 // what follows.  Then, for runs of rows whose candidate scores (rows x the largest count among them) stay within
@@ -1877,11 +1940,15 @@ int bm25_near_args(gz_bm25* ix, int64_t nq, const int32_t* nrterm, const int64_t
 // nroff (null: none) / nrterm / nrwin: the near stage (GZ_BM25_SR_NEAR, gz_near.inc) then clears, in the rows that have near terms,
 // the documents that do not hold all of them inside nrwin[row] consecutive words; without near terms nothing of it is launched,
 // allocated or derived either.
+// grp (null: none): a search over word groups (gz_groups.inc).  terms / qoff are then the packed alternatives and their row
+// boundaries (grp->aterm, grp->rowoff; idf is not read): words and marking run unchanged over them, the group driver stands in for
+// GZ_BM25_SR_DRIVER, the group filter for GZ_BM25_SR_FILTER and the group score for GZ_BM25_SR_SCORE.  Without groups nothing of
+// it is launched or allocated.
 int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, const int64_t* qoff, int64_t nq, const double* P, int32_t plus,
                        int64_t kk, bool count_only, int64_t* doc_dev, double* score_dev, int64_t* cnt_dev, int64_t* doc_host, double* score_host,
                        int64_t* cnt_host, int32_t mode = GZ_BM25_MATCH_ANY, const int32_t* xterm = nullptr, const int64_t* xoff = nullptr,
                        const int32_t* phterm = nullptr, const int64_t* phoff = nullptr, const int32_t* nrterm = nullptr,
-                       const int64_t* nroff = nullptr, const int64_t* nrwin = nullptr)
+                       const int64_t* nroff = nullptr, const int64_t* nrwin = nullptr, const BmGroups* grp = nullptr)
 {
     gz_ctx* c = ix->c;
     DBuf* w = c->w_bm;
@@ -1935,6 +2002,20 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
         NR.ctl = (uint32_t*)w[BMW_CTL].p;
         if (np <= 0) HIPCHK(c, hipMemsetAsync(NR.ctl, 0, 64, s));
     }
+    GzBm25Group G{};
+    if (grp) {
+        const int64_t ng = grp->ng;
+        if ((rc = bm_alloc(c, w[BMW_G_GOFF], (size_t)(nq + 1) * 8)) || (rc = bm_alloc(c, w[BMW_G_AOFF], (size_t)(ng + 1) * 8)) ||
+            (rc = bm_alloc(c, w[BMW_G_IDF], (size_t)ng * 8)) || (rc = bm_alloc(c, w[BMW_G_MASK], (size_t)ng * 32)) ||
+            (rc = copy_in(c, w[BMW_G_GOFF].p, grp->goff.data(), (size_t)(nq + 1) * 8, s)) ||
+            (rc = copy_in(c, w[BMW_G_AOFF].p, grp->aoff.data(), (size_t)(ng + 1) * 8, s)) ||
+            (grp->gidf && (rc = copy_in(c, w[BMW_G_IDF].p, grp->gidf, (size_t)ng * 8, s))))
+            return rc;
+        G.aoff = (const int64_t*)w[BMW_G_AOFF].p; G.gidf = (const double*)w[BMW_G_IDF].p;
+        G.gmask = (unsigned long long*)w[BMW_G_MASK].p; G.n_groups = ng;
+        G.A.qterm = A.S.qterm;
+        gz_launch_bm25_groups(GZ_BM25_GR_MASK, G, 0, s);
+    }
     const int64_t* phoff_dev = np > 0 ? (const int64_t*)w[BMW_S_PHOFF].p : nullptr;
     const int64_t* xoff_dev = nx > 0 ? (const int64_t*)w[BMW_S_XOFF].p : nullptr;
     const int64_t chunk = c->opt.bm25_search_chunk;
@@ -1963,11 +2044,18 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
         HIPCHK(c, hipMemsetAsync(A.bm, 0, (size_t)(rows * W64) * 8, s));
         if (A.n_qw > 0) {
             gz_launch_bm25_search(GZ_BM25_SR_WORDS, A, rows, s);
-            if (mode == GZ_BM25_MATCH_ALL) gz_launch_bm25_search(GZ_BM25_SR_DRIVER, A, rows, s);
+            A.xoff = xoff_dev && xoff[q0 + rows] > xoff[q0] ? xoff_dev + q0 : nullptr;
+            if (grp) { G.A = A; G.goff = (const int64_t*)w[BMW_G_GOFF].p + q0; }        // (the chunk's rows; the group indices stay absolute)
+            if (mode == GZ_BM25_MATCH_ALL) {
+                if (grp) gz_launch_bm25_groups(GZ_BM25_GR_DRIVER, G, rows, s);
+                else gz_launch_bm25_search(GZ_BM25_SR_DRIVER, A, rows, s);
+            }
             if ((rc = bm_scan(c, A.wns, A.n_qw, A.wsoff))) return rc;
             gz_launch_bm25_search(GZ_BM25_SR_MARK, A, rows, s);
-            A.xoff = xoff_dev && xoff[q0 + rows] > xoff[q0] ? xoff_dev + q0 : nullptr;
-            if (mode == GZ_BM25_MATCH_ALL || A.xoff) gz_launch_bm25_search(GZ_BM25_SR_FILTER, A, rows, s);
+            if (mode == GZ_BM25_MATCH_ALL || A.xoff) {
+                if (grp) gz_launch_bm25_groups(GZ_BM25_GR_FILTER, G, rows, s);
+                else gz_launch_bm25_search(GZ_BM25_SR_FILTER, A, rows, s);
+            }
             A.phoff = phoff_dev && phoff[q0 + rows] > phoff[q0] ? phoff_dev + q0 : nullptr;
             if (A.phoff) gz_launch_bm25_search(GZ_BM25_SR_PHRASE, A, rows, s);
             if (nn > 0 && nroff[q0 + rows] > nroff[q0]) {       // (the chunk's rows; the offsets and windows stay the absolute ones)
@@ -2014,7 +2102,12 @@ int bm25_search_locked(gz_bm25* ix, const int32_t* terms, const double* idf, con
                 A.cand = (uint32_t*)w[BMW_S_CAND].p; A.csc = (double*)w[BMW_S_CSC].p;
                 A.pos = (const int64_t*)w[BMW_S_POS].p; A.psc = (const double*)w[BMW_S_PSC].p;
                 gz_launch_bm25_search(GZ_BM25_SR_CAND, A, n, s);
-                gz_launch_bm25_search(GZ_BM25_SR_SCORE, A, n, s);
+                if (grp) {
+                    G.A = A; G.goff = (const int64_t*)w[BMW_G_GOFF].p + q0;
+                    gz_launch_bm25_groups(GZ_BM25_GR_SCORE, G, n, s);
+                } else {
+                    gz_launch_bm25_search(GZ_BM25_SR_SCORE, A, n, s);
+                }
                 GzTopk T{};
                 T.scores = A.csc; T.n_docs = M; T.rows = n; T.k = k2; T.tile = tile;
                 T.ckey[0] = (unsigned long long*)w[BMW_CKEY0].p; T.cidx[0] = (uint32_t*)w[BMW_CIDX0].p;
@@ -4266,6 +4359,57 @@ try {
     std::lock_guard<std::mutex> lk(ix->c->mu);
     return bm25_search_locked(ix, terms, nullptr, query_off, n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr, nullptr, count_out,
                               mode, ex_terms, ex_off, ph_terms, ph_off, near_terms, near_off, near_window);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_groups(gz_bm25* ix, const int32_t* alt_terms, const int64_t* alt_off, const double* group_idf, const int64_t* group_off,
+                          int64_t n_queries, const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms,
+                          const int64_t* ex_off, int64_t* doc_out, double* score_out, int64_t* count_out)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!params || n_queries < 0 || ((!doc_out || !score_out) && n_queries > 0 && ix->n_docs > 0) || (!count_out && n_queries > 0))
+        return fail(c, GZ_E_INVALID, "bad arguments");
+    int rc = bm25_group_args(ix, alt_terms, alt_off, group_idf, true, group_off, n_queries);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    BmGroups G;
+    if ((rc = bm25_group_pack(ix, alt_terms, alt_off, group_idf, group_off, n_queries, G))) return rc;
+    return bm25_search_locked(ix, G.aterm.data(), nullptr, G.rowoff.data(), n_queries, params, plus, kk, false, nullptr, nullptr, nullptr, doc_out,
+                              score_out, count_out, mode, ex_terms, ex_off, nullptr, nullptr, nullptr, nullptr, nullptr, &G);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_search_groups_device(gz_bm25* ix, const int32_t* alt_terms, const int64_t* alt_off, const double* group_idf, const int64_t* group_off,
+                                 int64_t n_queries, const double params[6], int32_t plus, int64_t k, int32_t mode, const int32_t* ex_terms,
+                                 const int64_t* ex_off, int64_t* doc_out_dev, double* score_out_dev, int64_t* count_out_dev)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (!params || n_queries < 0 || ((!doc_out_dev || !score_out_dev) && n_queries > 0 && ix->n_docs > 0) || (!count_out_dev && n_queries > 0))
+        return fail(c, GZ_E_INVALID, "bad arguments");
+    int rc = bm25_group_args(ix, alt_terms, alt_off, group_idf, true, group_off, n_queries);
+    int64_t kk = 0;
+    if (rc || (rc = bm25_topk_k(ix, k, kk)) || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    BmGroups G;
+    if ((rc = bm25_group_pack(ix, alt_terms, alt_off, group_idf, group_off, n_queries, G))) return rc;
+    return bm25_search_locked(ix, G.aterm.data(), nullptr, G.rowoff.data(), n_queries, params, plus, kk, false, doc_out_dev, score_out_dev,
+                              count_out_dev, nullptr, nullptr, nullptr, mode, ex_terms, ex_off, nullptr, nullptr, nullptr, nullptr, nullptr, &G);
+} GZ_CATCH(ix ? ix->c : nullptr)
+
+int gz_bm25_match_count_groups(gz_bm25* ix, const int32_t* alt_terms, const int64_t* alt_off, const int64_t* group_off, int64_t n_queries,
+                               int32_t mode, const int32_t* ex_terms, const int64_t* ex_off, int64_t* count_out)
+try {
+    if (!ix) return GZ_E_INVALID;
+    gz_ctx* c = ix->c;
+    if (n_queries < 0 || (!count_out && n_queries > 0)) return fail(c, GZ_E_INVALID, "bad arguments");
+    int rc = bm25_group_args(ix, alt_terms, alt_off, nullptr, false, group_off, n_queries);
+    if (rc || (rc = bm25_bool_args(ix, n_queries, mode, ex_terms, ex_off))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    BmGroups G;
+    if ((rc = bm25_group_pack(ix, alt_terms, alt_off, nullptr, group_off, n_queries, G))) return rc;
+    return bm25_search_locked(ix, G.aterm.data(), nullptr, G.rowoff.data(), n_queries, nullptr, 0, 0, true, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, count_out, mode, ex_terms, ex_off, nullptr, nullptr, nullptr, nullptr, nullptr, &G);
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_cover(gz_bm25* ix, const int32_t* terms, const int64_t* query_off, int64_t n_queries, const int64_t* ids, int64_t k, int32_t* start_out,

@@ -361,6 +361,22 @@ enum { GZ_BM25_SR_WORDS, GZ_BM25_SR_MARK, GZ_BM25_SR_COUNT, GZ_BM25_SR_ROWS, GZ_
 // rows: of the chunk (WORDS, DRIVER, MARK, FILTER, PHRASE, COUNT, ROWS), else of the launch (from row0)
 void gz_launch_bm25_search(int step, const GzBm25Search& A, int64_t rows, hipStream_t s);
 
+// BM25 search over word groups (gz_groups.inc): a group of alternative terms counts as one query word.  The chunk's GzBm25Search
+// carries the flat alternative list as its word list (qterm; qoff[r] = aoff[goff[r]], so WORDS and MARK run unchanged); qidf is
+// not read.  The alternatives of a group are distinct and valid: the entry point drops -1 and repeats.
+struct GzBm25Group {
+    GzBm25Search A;
+    const int64_t* goff;                  // [rows + 1] row r = groups goff[r] .. goff[r + 1] (absolute indices into aoff / gidf / gmask)
+    const int64_t* aoff;                  // [n_groups + 1] group g = alternatives aoff[g] .. aoff[g + 1] (absolute indices into A.qterm)
+    const double* gidf;                   // [n_groups] the idf of every group (host-computed)
+    unsigned long long* gmask;            // [n_groups, 4] the OR of the alternatives' signature bits (GZ_BM25_GR_MASK writes it)
+    int64_t n_groups;                     // of the whole call (GZ_BM25_GR_MASK)
+};
+constexpr int GZ_GROUP_MAX = 64;          // == GZ_BM25_GROUP_MAX of the public header: distinct alternatives of a group
+enum { GZ_BM25_GR_MASK, GZ_BM25_GR_DRIVER, GZ_BM25_GR_FILTER, GZ_BM25_GR_SCORE };
+// rows: of the chunk (DRIVER, FILTER), of the launch from row0 (SCORE); MASK covers every group of the call
+void gz_launch_bm25_groups(int step, const GzBm25Group& G, int64_t rows, hipStream_t s);
+
 // BM25 snippets (gz_snippet.inc): where the query's words stand inside given documents of a positional index.  A pair r is
 // (query r / k, document ids[r]); document d = seq[woff[d] .. woff[d + 1]).  An id outside [0, n_docs) is a pair without words.
 struct GzBm25Snip {

@@ -694,6 +694,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_topk.inc"
 #include "gz_vocab.inc"
 #include "gz_search.inc"
+#include "gz_groups.inc"
 #include "gz_snippet.inc"
 #include "gz_near.inc"
 

@@ -20,6 +20,7 @@ GZ_E_CAPACITY, GZ_E_LIMIT, GZ_E_NOMEM, GZ_E_RCCL, GZ_E_NODEVICE = -5, -6, -7, -8
 GZ_BM25_POSITIONS, GZ_BM25_PHRASE_MAX = 1, 64
 GZ_BM25_NEAR_MAX = 64
 GZ_BM25_EDIT_MAX = 64
+GZ_BM25_GROUP_MAX = 64
 GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP_WORDS = 0x1, 0x2, 0x4, 0x100, 0x200, 0x400
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
@@ -44,6 +45,7 @@ SYMBOLS = [
     "gz_bm25_snippets", "gz_bm25_snippets_device", "gz_bm25_occurrences",
     "gz_bm25_search_near", "gz_bm25_search_near_device", "gz_bm25_match_count_near", "gz_bm25_cover", "gz_bm25_cover_device",
     "gz_bm25_similar", "gz_bm25_prefix", "gz_bm25_term_bytes",
+    "gz_bm25_search_groups", "gz_bm25_search_groups_device", "gz_bm25_match_count_groups",
 ]
 
 _lib = None
@@ -175,6 +177,10 @@ def load_library():
         L.gz_bm25_similar.argtypes = [vp, vp, vp, i64, i32, i64, vp, vp, vp, vp]
         L.gz_bm25_prefix.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp]
         L.gz_bm25_term_bytes.argtypes = [vp, vp, i64, vp, vp, i64]
+    if hasattr(L, "gz_bm25_search_groups"):
+        L.gz_bm25_search_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+        L.gz_bm25_search_groups_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+        L.gz_bm25_match_count_groups.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -794,6 +800,52 @@ class Context:
         else:
             ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
             self._check(self.lib.gz_bm25_match_count_bool(*args, int(mode), *ex, _ptr(counts)))
+        return counts[:nq]
+
+    @staticmethod
+    def _bm25_groups(alt_terms, alt_off, group_off):
+        """the groups of a grouped search as contiguous arrays (kept alive by the caller): alternatives, their offsets per group,
+        the groups' offsets per query"""
+        alt_terms = np.ascontiguousarray(alt_terms, dtype=np.int32)
+        alt_off = np.ascontiguousarray(alt_off, dtype=np.int64)
+        group_off = np.ascontiguousarray(group_off, dtype=np.int64)
+        assert alt_off.ndim == 1 and group_off.ndim == 1 and len(alt_off) >= 1 and len(group_off) >= 1
+        return alt_terms, alt_off, group_off
+
+    def bm25_search_groups(self, index: int, alt_terms: np.ndarray, alt_off: np.ndarray, group_idf: np.ndarray, group_off: np.ndarray,
+                           params, plus: bool, k: int, mode: int = 0, ex_terms=None, ex_off=None, d_ids: int | None = None,
+                           d_scores: int | None = None, d_counts: int | None = None):
+        """bm25_search over word groups (gz_bm25_search_groups[_device]): query q = the groups group_off[q]:group_off[q + 1], group g =
+        the alternatives alt_terms[alt_off[g]:alt_off[g + 1]] (-1 and repeats are ignored; at most 64 distinct) with idf group_idf[g].
+        A group counts as one query word: matched by any alternative, f = the sum of their counts.  mode / ex_terms / ex_off and the
+        outputs (or d_ids / d_scores / d_counts) as bm25_search."""
+        alt_terms, alt_off, group_off = self._bm25_groups(alt_terms, alt_off, group_off)
+        group_idf = np.ascontiguousarray(group_idf, dtype=np.float64)
+        P = np.ascontiguousarray(params, dtype=np.float64)
+        assert P.shape == (6,)
+        nq = len(group_off) - 1
+        ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+        args = [C.c_void_p(index), _ptr(alt_terms) if len(alt_terms) else None, _ptr(alt_off), _ptr(group_idf) if len(group_idf) else None,
+                _ptr(group_off), nq, _ptr(P), 1 if plus else 0, int(k), int(mode)] + ex
+        if d_ids is not None or d_scores is not None or d_counts is not None:
+            self._check(self.lib.gz_bm25_search_groups_device(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
+            return None
+        kk = max(0, min(int(k), self.bm25_info(index)[0]))
+        ids = np.empty((nq, kk), dtype=np.int64)
+        scores = np.empty((nq, kk), dtype=np.float64)
+        counts = np.zeros(max(nq, 1), dtype=np.int64)
+        self._check(self.lib.gz_bm25_search_groups(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
+        return ids, scores, counts[:nq]
+
+    def bm25_match_count_groups(self, index: int, alt_terms: np.ndarray, alt_off: np.ndarray, group_off: np.ndarray, mode: int = 0,
+                                ex_terms=None, ex_off=None) -> np.ndarray:
+        """int64 [Q]: counts of bm25_search_groups alone (gz_bm25_match_count_groups)"""
+        alt_terms, alt_off, group_off = self._bm25_groups(alt_terms, alt_off, group_off)
+        nq = len(group_off) - 1
+        counts = np.zeros(max(nq, 1), dtype=np.int64)
+        ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
+        self._check(self.lib.gz_bm25_match_count_groups(C.c_void_p(index), _ptr(alt_terms) if len(alt_terms) else None, _ptr(alt_off),
+                                                        _ptr(group_off), nq, int(mode), *ex, _ptr(counts)))
         return counts[:nq]
 
     @staticmethod

@@ -77,6 +77,19 @@ is not modified.  `term_texts(ids)` reads back the words of given ids only.  `su
 them on the host: (word, distance, df) lists, (word, df) lists, and the queries with every unknown word replaced by its best match.
 `search` itself stays exact: pass it `correct(queries)` to search for what was meant.
 
+Word groups: `correct` replaces a word by ONE guess.  `search_groups(groups, k, match, exclude)` searches for a word "in some
+spelling" instead: a query is a list of groups, a group a list of alternative words that count as one query word -- a document
+holds the group when it holds any alternative, the group's f is the sum of their counts and its df the number of documents that
+hold any of them, so the variants share one idf (`group_df`, cached per group on the host) and a misspelling that is rare in the
+corpus does not outrank the correct word by its idf.  match="all" is an AND of ORs.  On the GPU (csrc/gz_groups.inc) the flat
+alternative list is marked like a word list; with match="all" only the group with the smallest sum of postings-list lengths (an
+upper bound of its union), and a filter and a score kernel add up a group's alternatives per document behind a 256-bit mask of the
+group's signature bits (gz_bm25_search_groups); everything behind the bitmap is `search`'s.  With singleton groups the result is
+`search`'s, bit for bit.  `count_groups` only counts.  `expand(queries, max_edits, limit, only_unknown, prefix_last)` builds the
+groups from `similar_words` / `prefix_words` (fuzzy words; the last word as a prefix), and `search_fuzzy(queries, k, ...)` is
+`search_groups(expand(...))`: `cong nghe` retrieves the documents with `công nghệ`, `cộng nghệ`, ... ranked together.  At most
+64 distinct alternatives a group; `phrase=` and `near` do not combine with groups.
+
 What stays on the host, as in the reference: `avgFieldLen = np.mean(fieldLens)` and every idf, computed per query word by the
 reference's scalar expression `np.log(1+(N-df+0.5)/(df+0.5))` (np.log is not correctly rounded, and its scalar and array loops may
 differ by an ulp: the device never computes a logarithm).  `documents` (the word lists) and `frequency_word_in_doc` (dicts in
@@ -149,6 +162,7 @@ class BM25:
         self.fieldLens.extend(lens[old:].tolist())
         self.avgFieldLen = np.mean(lens)                         # (the constructor's expression over all the lengths)
         self._idf.clear()                                        # N and df changed
+        self.__dict__.pop("_group_idf", None)                    # (the word groups' df and idf: search_groups)
         if self._documents is not None:
             self._documents.extend(t.split() for t in more)
         self._freq = None                                        # (rebuilt on the next access)
@@ -179,6 +193,7 @@ class BM25:
         self.fieldLens = lens.tolist()
         self.avgFieldLen = np.mean(lens)                         # (nan and a RuntimeWarning when nothing is left, as BM25([]))
         self._idf.clear()                                        # N and df changed
+        self.__dict__.pop("_group_idf", None)                    # (the word groups' df and idf: search_groups)
         if self._documents is not None:
             self._documents = list(itertools.compress(self._documents, keep))
         self._freq = None                                        # (rebuilt on the next access)
@@ -484,6 +499,182 @@ class BM25:
             return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
         pterms, poff = self._exclusions(phrase, nq)
         return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff, ph_terms=pterms, ph_off=poff)
+
+    # ---- word groups: alternatives that count as one query word; fuzzy and prefix search over them -----------------------
+    def _group_args(self, groups, match, exclude):
+        """validation of search_groups / count_groups / group_df, all of it before any native call -> (groups as lists of lists of
+        lists of str, mode, exclude)"""
+        mode = self._match(match)
+        if isinstance(groups, (str, bytes)):
+            raise TypeError("groups must be a list of queries, not %s" % type(groups).__name__)
+        out = []
+        for query in groups:
+            if isinstance(query, (str, bytes)) or not isinstance(query, (list, tuple)):
+                raise TypeError("a query must be a list of groups, not %s" % type(query).__name__)
+            gs = []
+            for group in query:
+                if isinstance(group, (str, bytes)) or not isinstance(group, (list, tuple)):
+                    raise TypeError("a group must be a list of str, not %s" % type(group).__name__)
+                gs.append(_strings(group, "alternatives"))
+            out.append(gs)
+        if exclude is not None:
+            exclude = _strings(exclude, "exclude")
+            if len(exclude) != len(out):
+                raise ValueError("exclude has %d items for %d queries" % (len(exclude), len(out)))
+        return out, mode, exclude
+
+    def _group_arrays(self, groups):
+        """validated groups -> ({alternative: (term id, df)}, the groups one after the other, alt_terms int32, alt_off int64 [G + 1],
+        group_off int64 [Q + 1]): one lookup of the distinct alternatives; -1 and repeats stay in alt_terms, the library drops them"""
+        words = list(dict.fromkeys(a for q in groups for g in q for a in g))
+        if words:
+            terms, dfs = self._lookup(words)
+            known = {w: (t, d) for w, t, d in zip(words, terms.tolist(), dfs.tolist())}
+        else:
+            known = {}
+        flat = [g for q in groups for g in q]
+        alt_terms = np.array([known[a][0] for g in flat for a in g], dtype=np.int32)
+        alt_off = np.zeros(len(flat) + 1, dtype=np.int64)
+        if flat:
+            np.cumsum([len(g) for g in flat], out=alt_off[1:])
+        group_off = np.zeros(len(groups) + 1, dtype=np.int64)
+        if groups:
+            np.cumsum([len(q) for q in groups], out=group_off[1:])
+        return known, flat, alt_terms, alt_off, group_off
+
+    def _group_pack(self, groups):
+        """validated groups -> (alt_terms int32, alt_off int64 [G + 1], group_off int64 [Q + 1], df list [G], idf float64 [G]).
+        The df of a group with several known alternatives is a match count ("any") of them as a query, one call for all such
+        groups that the cache does not hold; a group with one known alternative has its df."""
+        known, flat, alt_terms, alt_off, group_off = self._group_arrays(groups)
+        cache = self.__dict__.setdefault("_group_idf", {})
+        keys, pending = [], {}
+        for g in flat:
+            key = frozenset(a for a in g if known[a][0] >= 0)
+            keys.append(key)
+            if key not in cache and key not in pending:
+                if len(key) == 0:
+                    pending[key] = 0
+                elif len(key) == 1:
+                    pending[key] = known[next(iter(key))][1]
+                else:
+                    pending[key] = None
+        multi = [key for key, v in pending.items() if v is None]
+        if multi:
+            lists = [[known[a][0] for a in key] for key in multi]
+            moff = np.zeros(len(lists) + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in lists], out=moff[1:])
+            counts = self._ctx.bm25_match_count(self._index, np.array([t for x in lists for t in x], dtype=np.int32), moff)
+            for key, c in zip(multi, counts.tolist()):
+                pending[key] = c
+        for key, df in pending.items():
+            cache[key] = (df, np.log(1+(self.num_doc-df+0.5)/(df+0.5)))            # ranking.py:31 with the group's df
+        df = [cache[key][0] for key in keys]
+        idf = np.array([cache[key][1] for key in keys], dtype=np.float64)
+        return alt_terms, alt_off, group_off, df, idf
+
+    def search_groups(self, groups, k: int, match: str = "any", exclude: Optional[Sequence[str]] = None):
+        """`search` over WORD GROUPS: groups[q] is a list of groups and a group a list of alternative words (str, looked up as given,
+        never split) that count as ONE query word.  With A_g the distinct alternatives of group g that the index holds and c(a, d)
+        the count of word a in document d: f_g(d) = sum(c(a, d) for a in A_g), df_g = #{d : f_g(d) > 0} and
+        idf_g = np.log(1+(N-df_g+0.5)/(df_g+0.5)); the score is get_score's sum with group g where a word stands (f_g, idf_g; groups
+        in order, a group listed twice summed twice).  match="any": d matches iff some f_g(d) > 0; match="all": iff there is a group
+        and every f_g(d) > 0.  A group without a known alternative is a word that no document holds.  exclude, the outputs
+        (ids, scores, counts), their order and padding are `search`'s; with every group a single word the result equals
+        search(queries, k, match, exclude) bit for bit.  A misspelling that is rare in the corpus therefore does not outrank the
+        correct spelling by its idf: the variants share one df.  At most 64 distinct known alternatives a group (_native.GzError,
+        GZ_E_LIMIT).  TypeError: an alternative that is no str, a str where a list is due; ValueError: a bad match, an exclude of
+        another length -- all before any native call."""
+        k = self._k(k)
+        groups, mode, exclude = self._group_args(groups, match, exclude)
+        alt_terms, alt_off, group_off, _, idf = self._group_pack(groups)
+        xterms, xoff = self._exclusions(exclude, len(groups)) if exclude is not None else (None, None)
+        plus = isinstance(self, BM25Plus)
+        return self._ctx.bm25_search_groups(self._index, alt_terms, alt_off, idf, group_off, self._params(), plus, k, mode=mode,
+                                            ex_terms=xterms, ex_off=xoff)
+
+    def count_groups(self, groups, match: str = "any", exclude: Optional[Sequence[str]] = None) -> np.ndarray:
+        """int64 [len(groups)]: counts of search_groups(groups, k, match, exclude) alone."""
+        groups, mode, exclude = self._group_args(groups, match, exclude)
+        _, _, alt_terms, alt_off, group_off = self._group_arrays(groups)
+        xterms, xoff = self._exclusions(exclude, len(groups)) if exclude is not None else (None, None)
+        return self._ctx.bm25_match_count_groups(self._index, alt_terms, alt_off, group_off, mode=mode, ex_terms=xterms, ex_off=xoff)
+
+    def group_df(self, groups) -> list:
+        """df_g of every group, in the nesting of `groups` without the innermost level: the documents that hold at least one of
+        the group's alternatives."""
+        groups, _, _ = self._group_args(groups, "any", None)
+        df = self._group_pack(groups)[3]
+        it = iter(df)
+        return [[next(it) for _ in q] for q in groups]
+
+    @staticmethod
+    def _limit(limit) -> int:
+        if isinstance(limit, bool) or not isinstance(limit, numbers.Integral):
+            raise TypeError("limit must be int, not %s" % type(limit).__name__)
+        limit = int(limit)
+        if not 1 <= limit <= _native.GZ_BM25_GROUP_MAX:
+            raise ValueError("limit must lie in [1, %d], not %d" % (_native.GZ_BM25_GROUP_MAX, limit))
+        return limit
+
+    def _expand(self, split, max_edits: int, limit: int, only_unknown: bool, prefix_last: bool) -> list:
+        """expand() behind its validation: split = the queries' words"""
+        words = list(dict.fromkeys(w for ws in split for w in ws))
+        if not words:
+            return [[] for _ in split]
+        held = {w: t >= 0 for w, t in zip(words, self._lookup(words)[0].tolist())}
+        last = set(ws[-1] for ws in split if ws) if prefix_last else set()
+        inner = set(w for ws in split for w in (ws[:-1] if prefix_last else ws))
+        fuzzy = [w for w in words if w in inner and max_edits > 0 and not (only_unknown and held[w])]
+        similar, completions = {}, {}
+        if self._n_terms() > 0:
+            if fuzzy:
+                ids, _, _, counts = self.similar_words(fuzzy, max_edits, limit)
+                for w, t, c in zip(fuzzy, self.term_texts(ids), counts.tolist()):
+                    similar[w] = t[:c]
+            if last:
+                tails = [w for w in words if w in last]
+                ids, _, counts = self.prefix_words(tails, limit)
+                for w, t, c in zip(tails, self.term_texts(ids), counts.tolist()):
+                    completions[w] = t[:c]
+        out = []
+        for ws in split:
+            gs = []
+            for i, w in enumerate(ws):
+                if prefix_last and i == len(ws) - 1:
+                    g = ([w] if held[w] else []) + [v for v in completions.get(w, []) if v != w]
+                    g = g[:limit]
+                else:
+                    g = list(similar.get(w, []))
+                gs.append(g if g else [w])
+            out.append(gs)
+        return out
+
+    def expand(self, queries: Sequence[str], max_edits: int = 1, limit: int = 8, only_unknown: bool = True, prefix_last: bool = False) -> list:
+        """The groups that `search_groups` takes, for a typo-tolerant search of `queries`: one group per word of q.split(), in order,
+        repeats kept.  The group of a word w is [w] if max_edits == 0, or only_unknown and the index holds w; else the words of
+        similar_words([w], max_edits, limit) in its order (distance, more frequent first) -- w itself first where the index holds
+        it -- or [w] if no term is within reach.  prefix_last=True handles the LAST word of every query as half-typed instead: [w]
+        first if the index holds w, then the words of prefix_words([w], limit) in its order other than w, cut at limit entries; [w]
+        if nothing results.  limit lies in [1, 64].  Composed on the host of one lookup, one similar_words, one prefix_words call
+        and term_texts, over the distinct words of the batch; right in every state of the index."""
+        split = [q.split() for q in _strings(queries, "queries")]
+        return self._expand(split, self._edits(max_edits), self._limit(limit), bool(only_unknown), bool(prefix_last))
+
+    def search_fuzzy(self, queries: Sequence[str], k: int, max_edits: int = 1, limit: int = 8, only_unknown: bool = True,
+                     prefix_last: bool = False, match: str = "any", exclude: Optional[Sequence[str]] = None):
+        """search_groups(expand(queries, max_edits, limit, only_unknown, prefix_last), k, match, exclude): `cong nghe` finds the
+        documents with `công nghệ` and its other spellings, ranked together as one word each; with prefix_last the last word matches
+        its completions.  With max_edits=0 and prefix_last=False it equals search(queries, k, match, exclude) bit for bit."""
+        k = self._k(k)
+        self._match(match)
+        split = [q.split() for q in _strings(queries, "queries")]
+        max_edits, limit = self._edits(max_edits), self._limit(limit)
+        if exclude is not None:
+            exclude = _strings(exclude, "exclude")
+            if len(exclude) != len(split):
+                raise ValueError("exclude has %d items for %d queries" % (len(exclude), len(split)))
+        return self.search_groups(self._expand(split, max_edits, limit, bool(only_unknown), bool(prefix_last)), k, match, exclude)
 
     # ---- inside a document: snippets and the positions of the query's words ---------------------------------------------
     def _snippet_args(self, queries, ids, width=1):

@@ -535,7 +535,28 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
  *   gz_bm25_cover_device   the same with ids and the three outputs in HBM: the doc_out of gz_bm25_search_near_device (or of any
  *                          _device search) goes straight in.  The ids are not looked at by the host: an id outside [-1, n_docs) is
  *                          treated as -1 and never read through.  The call returns after the kernel has run.
- *   gz_bm25_append         n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
+ *   gz_bm25_search_groups  gz_bm25_search_bool over WORD GROUPS: a group is a set of alternative terms that counts as one query word
+ *                          -- the primitive under fuzzy, prefix and synonym search.  Query q = the groups group_off[q] ..
+ *                          group_off[q + 1]; group g = the alternatives alt_terms[alt_off[g] .. alt_off[g + 1]) with the idf
+ *                          group_idf[g] (absolute indices, as query_off / ex_off; host memory).  With A_g the DISTINCT alternatives
+ *                          of g that are not -1 (a repeat counts once) and c(a, d) the count of term a in document d:
+ *                          f_g(d) = the sum of c(a, d) over A_g.  mode GZ_BM25_MATCH_ANY: d matches iff some f_g(d) > 0;
+ *                          GZ_BM25_MATCH_ALL: iff the query has a group and every f_g(d) > 0 (an empty A_g: nothing matches);
+ *                          ex_terms / ex_off as gz_bm25_search_bool.  The score is gz_bm25_score's sum with group g where a word
+ *                          stands: f = f_g(d), idf = group_idf[g], groups in order, a group listed twice summed twice; the caller
+ *                          computes group_idf from df_g = the documents with f_g > 0 (gz_bm25_match_count over A_g as a query).
+ *                          With every group a single term the outputs equal gz_bm25_search_bool's bit for bit.  Outputs, order,
+ *                          padding and k as gz_bm25_search.  GZ_E_INVALID (checked before any launch, nothing written): NULL
+ *                          group_off / params / outputs, NULL alt_off or group_idf with groups, NULL alt_terms with alternatives,
+ *                          decreasing or negative offsets, a term outside [-1, n_terms), a bad mode, k < 1, bad ex_off;
+ *                          GZ_E_LIMIT: a group of more than GZ_BM25_GROUP_MAX distinct alternatives, k' above GZ_BM25_TOPK_MAX.
+ *                          On the device (gz_groups.inc): the flat alternative list is marked as a word list; with
+ *                          GZ_BM25_MATCH_ALL only the group with the smallest sum of postings-list lengths; a filter and a score
+ *                          kernel add up a group's alternatives per document, behind a 256-bit mask of the group's signature bits
+ *                          that rejects most documents without a probe.  The index is not modified.
+ *   gz_bm25_search_groups_device  the same with the three outputs in HBM, as gz_bm25_search_device
+ *   gz_bm25_match_count_groups    count_out[q] of gz_bm25_search_groups alone (host memory; no idf, no params, no k)
+ *   gz_bm25_append        n_docs more documents behind the index's own (host text / offsets as gz_bm25_build): afterwards the index
  *                          answers every call above exactly as one built over all the documents in one go does -- term ids, df,
  *                          fieldLens, scores and top-k to the bit.  The batch's words are resolved against the live term table,
  *                          only its unknown words are de-duplicated, and the per-document arrays grow at their tails; the index's
@@ -608,6 +629,7 @@ int  gz_expand_block(gz_ctx *ctx, const int32_t *block_dev, int32_t bits, int64_
 #define GZ_BM25_PHRASE_MAX 64
 #define GZ_BM25_NEAR_MAX 64
 #define GZ_BM25_EDIT_MAX 64
+#define GZ_BM25_GROUP_MAX 64
 typedef struct gz_bm25 gz_bm25;
 int  gz_bm25_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_bm25 **out);
 int  gz_bm25_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
@@ -668,6 +690,15 @@ int  gz_bm25_cover(gz_bm25 *index, const int32_t *terms, const int64_t *query_of
                    int32_t *start_out, int32_t *len_out, int32_t *words_out);
 int  gz_bm25_cover_device(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids_dev,
                           int64_t k, int32_t *start_out_dev, int32_t *len_out_dev, int32_t *words_out_dev);
+int  gz_bm25_search_groups(gz_bm25 *index, const int32_t *alt_terms, const int64_t *alt_off, const double *group_idf,
+                           const int64_t *group_off, int64_t n_queries, const double params[6], int32_t plus, int64_t k, int32_t mode,
+                           const int32_t *ex_terms, const int64_t *ex_off, int64_t *doc_out, double *score_out, int64_t *count_out);
+int  gz_bm25_search_groups_device(gz_bm25 *index, const int32_t *alt_terms, const int64_t *alt_off, const double *group_idf,
+                                  const int64_t *group_off, int64_t n_queries, const double params[6], int32_t plus, int64_t k,
+                                  int32_t mode, const int32_t *ex_terms, const int64_t *ex_off, int64_t *doc_out_dev,
+                                  double *score_out_dev, int64_t *count_out_dev);
+int  gz_bm25_match_count_groups(gz_bm25 *index, const int32_t *alt_terms, const int64_t *alt_off, const int64_t *group_off,
+                                int64_t n_queries, int32_t mode, const int32_t *ex_terms, const int64_t *ex_off, int64_t *count_out);
 int  gz_bm25_snippets(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids, int64_t k,
                       int64_t width, int32_t *start_out, int32_t *hits_out);
 int  gz_bm25_snippets_device(gz_bm25 *index, const int32_t *terms, const int64_t *query_off, int64_t n_queries, const int64_t *ids_dev,

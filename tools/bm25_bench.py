@@ -6,6 +6,7 @@
     python tools/bm25_bench.py --vocab-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --snippet-only [--out profiles/bm25_bench.json]
     python tools/bm25_bench.py --near-only [--out profiles/bm25_bench.json]
+    python tools/bm25_bench.py --groups-only [--out profiles/bm25_bench.json]
 
 Host clock around call + synchronisation, after a warm-up call, median of --reps:
   build_device_ms      gz_bm25_build_device over text and offsets already in HBM (the call returns a finished index)
@@ -97,6 +98,18 @@ are on the host when it returns):
                        plain Python (terms whose length differs by more than 2 skipped, a two-row Levenshtein for the rest; one repetition)
   vocab_similar_ms_per_word_w64 / _w256, vocab_key_rows_per_chunk, vocab_key_bytes   time / W, and the key rows held at a time:
                        min(W, max(1, 2^23 // terms)) rows of terms doubles (switch bm25_vocab_chunk)
+Word groups (gz_bm25_search_groups_device; --groups-only: these rows alone, and with --out they are merged into the file's record
+instead of replacing it).  The index is gz_bm25_build_device over the corpus; 256 queries of 2-4 distinct words, the first words of
+documents drawn with a fixed seed; k = 10, outputs in HBM, gz_sync before the clock stops; the four calls of a case are interleaved
+in every repetition.  An older build (through GZ_LIBRARY) gives the plain rows alone:
+  groups_groups_single_{any,all}_q256_k10_ms   every word a group of its own ...
+  groups_plain_single_{any,all}_q256_k10_ms    ... against gz_bm25_search[_bool]_device over the same words
+  groups_groups_alt8_{any,all}_q256_k10_ms     every word a group of up to 8 alternatives: the word and its nearest terms
+                       (gz_bm25_similar, max_edits 2), with the group's df from gz_bm25_match_count ...
+  groups_plain_alt8_{any,all}_q256_k10_ms      ... against the plain search over the flattened alternatives as words: mode "any" marks
+                       the same postings and probes as many (candidate, term) pairs; mode "all" there demands every spelling at once,
+                       marks one word's postings and finds next to nothing -- it is no like-for-like row
+  groups_*_match_fraction   mean(count) / N of each;  groups_alt8_mean_size   alternatives a group
 Per-kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script (--reps 2)."""
 import argparse
 import json
@@ -578,6 +591,75 @@ def vocab_rows(ctx, res, t, o, reps):
     ctx.free(d_off)
 
 
+def groups_rows(ctx, res, t, o, reps):
+    """the word-group rows of the docstring"""
+    n, nbytes = len(o) - 1, int(o[-1])
+    d_text, d_off = ctx.alloc(nbytes), ctx.alloc(8 * (n + 1))
+    ctx.h2d(d_text, t)
+    ctx.h2d(d_off, o)
+    ix = ctx.bm25_build_device(d_text, d_off, n, nbytes)             # (a fresh build: the canonical ids are the lookup's)
+    raw = t.tobytes()
+    rng = np.random.default_rng(11)
+    queries = []
+    for d in rng.integers(n, size=4096):
+        words = list(dict.fromkeys(raw[int(o[d]):int(o[d + 1])].decode("utf-8").split()))
+        size = 2 + len(queries) % 3
+        if len(words) >= size:
+            queries.append(words[:size])
+        if len(queries) == 256:
+            break
+    assert len(queries) == 256
+    words = [w for q in queries for w in q]
+    goff = np.zeros(257, np.int64)
+    np.cumsum([len(q) for q in queries], out=goff[1:])
+    G = len(words)
+    terms, df = ctx.bm25_lookup(ix, *pack(words))
+    assert (terms >= 0).all()
+    ids, _, adf, counts = ctx.bm25_similar(ix, *pack(words), 2, 8)   # the word itself first, then the nearest terms, 8 in all
+    assert (ids[:, 0] == terms).all()
+    alts = [ids[g, :min(8, int(counts[g]))].astype(np.int32) for g in range(G)]
+    aoff8 = np.zeros(G + 1, np.int64)
+    np.cumsum([len(a) for a in alts], out=aoff8[1:])
+    aterm8 = np.concatenate(alts)
+    adf8 = np.concatenate([adf[g, :len(alts[g])] for g in range(G)])
+    res["groups_alt8_mean_size"] = float(aoff8[-1] / G)
+
+    def idf_of(d):
+        return np.array([np.log(1+(n-int(x)+0.5)/(int(x)+0.5)) for x in d])
+    gdf8 = ctx.bm25_match_count(ix, aterm8, aoff8)                   # df of a group: the documents that hold any alternative
+    params = [2.2, 1.2, 0.25, 0.75, float(ctx.bm25_field_lengths(ix).mean()), 0.0]
+    cases = {
+        # name: (grouped arguments, the plain search that marks the same postings and probes as many candidates)
+        "single": ((terms, np.arange(G + 1, dtype=np.int64), idf_of(df), goff), (terms, idf_of(df), goff)),
+        "alt8": ((aterm8, aoff8, idf_of(gdf8), goff), (aterm8, idf_of(adf8), aoff8[goff])),
+    }
+    grouped = hasattr(ctx.lib, "gz_bm25_search_groups")              # (an older build through GZ_LIBRARY gives the plain rows alone)
+    d_ids, d_sc, d_cnt = ctx.alloc(256 * 10 * 8), ctx.alloc(256 * 10 * 8), ctx.alloc(256 * 8)
+    for name, (ga, pa) in cases.items():
+        ts = {}
+        for rep in range(reps + 1):                                  # (the first round is the warm-up of all four; interleaved)
+            for mode in (0, 1):
+                for kind in ("groups", "plain") if grouped else ("plain",):
+                    t0 = time.perf_counter()
+                    if kind == "groups":
+                        ctx.bm25_search_groups(ix, ga[0], ga[1], ga[2], ga[3], params, False, 10, mode=mode, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt)
+                    else:
+                        ctx.bm25_search(ix, pa[0], pa[1], pa[2], params, False, 10, d_ids=d_ids, d_scores=d_sc, d_counts=d_cnt, mode=mode)
+                    ctx.sync()
+                    if rep:
+                        ts.setdefault((kind, mode), []).append((time.perf_counter() - t0) * 1e3)
+                    if rep == reps:
+                        cnt = np.empty(256, np.int64)
+                        ctx.d2h(cnt, d_cnt)
+                        res["groups_%s_%s_%s_match_fraction" % (kind, name, ("any", "all")[mode])] = float(cnt.mean() / n)
+        for (kind, mode), v in ts.items():
+            key = "groups_%s_%s_%s_q256_k10" % (kind, name, ("any", "all")[mode])
+            res[key + "_ms"], res[key + "_all_ms"] = float(np.median(v)), [round(x, 3) for x in v]
+    for d in (d_ids, d_sc, d_cnt, d_text, d_off):
+        ctx.free(d)
+    ctx.bm25_destroy(ix)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -596,6 +678,7 @@ def main():
     ap.add_argument("--snippet-only", action="store_true", help="only the snippet rows; with --out they are merged into the file")
     ap.add_argument("--near-only", action="store_true", help="only the phrase and the proximity rows; with --out they are merged into the file")
     ap.add_argument("--vocab-only", action="store_true", help="only the vocabulary rows; with --out they are merged into the file")
+    ap.add_argument("--groups-only", action="store_true", help="only the word-group rows; with --out they are merged into the file")
     a = ap.parse_args()
     if a.search_only:
         a.remove = a.compact = a.append = 0
@@ -610,6 +693,16 @@ def main():
             old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
             old.update({k: v for k, v in res.items() if k.startswith(("phrase_", "near_", "cover_"))})
             old["near_rows_run" if a.near_only else "phrase_rows_run"] = dict(docs=n, reps=a.reps)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(old) + "\n")
+        return
+    if a.groups_only:
+        groups_rows(ctx, res, t, o, a.reps)
+        print(json.dumps(res))
+        if a.out:
+            old = json.loads(open(a.out).read()) if os.path.exists(a.out) else {}
+            old.update({k: v for k, v in res.items() if k.startswith("groups_")})
+            old["groups_rows_run"] = dict(docs=n, reps=a.reps)
             with open(a.out, "w") as f:
                 f.write(json.dumps(old) + "\n")
         return
