@@ -727,37 +727,33 @@ class Context:
         P = np.ascontiguousarray(params, dtype=np.float64)
         assert P.shape == (6,)
         nq = len(query_off) - 1
+        width, lists, _keep = self._bm25_lists(nq, mode, ex_terms, ex_off, ph_terms, ph_off, nr_terms, nr_off, nr_window)
         args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(idf) if len(idf) else None, _ptr(query_off), nq, _ptr(P),
-                1 if plus else 0, int(k)]
-        plain = mode == 0 and ex_off is None and ph_off is None and nr_off is None
-        if not plain:
-            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
-            args += [int(mode)] + ex
-        if ph_off is not None or nr_off is not None:
-            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
-            args += ph
-        if nr_off is not None:
-            nr_terms, nr_off, nr_window, nr = self._bm25_near(nq, nr_terms, nr_off, nr_window)
-            args += nr
+                1 if plus else 0, int(k)] + lists
         if d_ids is not None or d_scores is not None or d_counts is not None:
-            fn = self.lib.gz_bm25_search_device if plain else self.lib.gz_bm25_search_bool_device
-            if ph_off is not None:
-                fn = self.lib.gz_bm25_search_phrase_device
-            if nr_off is not None:
-                fn = self.lib.gz_bm25_search_near_device
-            self._check(fn(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
+            self._check(getattr(self.lib, "gz_bm25_search%s_device" % width)(*args, C.c_void_p(d_ids), C.c_void_p(d_scores), C.c_void_p(d_counts)))
             return None
         kk = max(0, min(int(k), self.bm25_info(index)[0]))
         ids = np.empty((nq, kk), dtype=np.int64)
         scores = np.empty((nq, kk), dtype=np.float64)
         counts = np.zeros(max(nq, 1), dtype=np.int64)
-        fn = self.lib.gz_bm25_search if plain else self.lib.gz_bm25_search_bool
-        if ph_off is not None:
-            fn = self.lib.gz_bm25_search_phrase
-        if nr_off is not None:
-            fn = self.lib.gz_bm25_search_near
-        self._check(fn(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None, _ptr(counts)))
+        self._check(getattr(self.lib, "gz_bm25_search" + width)(*args, _ptr(ids) if ids.size else None, _ptr(scores) if scores.size else None,
+                                                                 _ptr(counts)))
         return ids, scores, counts[:nq]
+
+    # the search entry points by the widest list a call gives: every width takes the lists of the narrower ones before its own
+    _BM25_WIDTHS = ("", "_bool", "_phrase", "_near")
+
+    @classmethod
+    def _bm25_lists(cls, nq: int, mode, ex_terms, ex_off, ph_terms, ph_off, nr_terms, nr_off, nr_window):
+        """(suffix of the entry point, the C arguments between k and the outputs, the arrays behind them -- kept alive by the caller):
+        near terms make it _near, else phrase terms _phrase, else a mode other than 0 or exclusions _bool, else the plain call"""
+        n = 3 if nr_off is not None else 2 if ph_off is not None else 1 if mode != 0 or ex_off is not None else 0
+        ex_terms, ex_off, ex = cls._bm25_exclusions(nq, ex_terms, ex_off)
+        ph_terms, ph_off, ph = cls._bm25_exclusions(nq, ph_terms, ph_off)
+        nr_terms, nr_off, nr_window, nr = cls._bm25_near(nq, nr_terms, nr_off, nr_window) if n == 3 else (None, None, None, [])
+        args = [a for part in ([int(mode)] + ex, ph, nr)[:n] for a in part]
+        return cls._BM25_WIDTHS[n], args, (ex_terms, ex_off, ph_terms, ph_off, nr_terms, nr_off, nr_window)
 
     @staticmethod
     def _bm25_exclusions(nq: int, ex_terms, ex_off):
@@ -785,21 +781,9 @@ class Context:
         query_off = np.ascontiguousarray(query_off, dtype=np.int64)
         nq = len(query_off) - 1
         counts = np.zeros(max(nq, 1), dtype=np.int64)
-        args = [C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq]
-        if nr_off is not None:
-            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
-            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
-            nr_terms, nr_off, nr_window, nr = self._bm25_near(nq, nr_terms, nr_off, nr_window)
-            self._check(self.lib.gz_bm25_match_count_near(*args, int(mode), *ex, *ph, *nr, _ptr(counts)))
-        elif ph_off is not None:
-            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
-            ph_terms, ph_off, ph = self._bm25_exclusions(nq, ph_terms, ph_off)
-            self._check(self.lib.gz_bm25_match_count_phrase(*args, int(mode), *ex, *ph, _ptr(counts)))
-        elif mode == 0 and ex_off is None:
-            self._check(self.lib.gz_bm25_match_count(*args, _ptr(counts)))
-        else:
-            ex_terms, ex_off, ex = self._bm25_exclusions(nq, ex_terms, ex_off)
-            self._check(self.lib.gz_bm25_match_count_bool(*args, int(mode), *ex, _ptr(counts)))
+        width, lists, _keep = self._bm25_lists(nq, mode, ex_terms, ex_off, ph_terms, ph_off, nr_terms, nr_off, nr_window)
+        self._check(getattr(self.lib, "gz_bm25_match_count" + width)(C.c_void_p(index), _ptr(terms) if len(terms) else None, _ptr(query_off), nq,
+                                                                      *lists, _ptr(counts)))
         return counts[:nq]
 
     @staticmethod

@@ -477,12 +477,9 @@ class BM25:
         queries, mode, exclude, phrase = self._bool_args(queries, match, exclude, phrase)
         nq, terms, idf, qoff = self._queries(queries)
         plus = isinstance(self, BM25Plus)
-        if mode == 0 and exclude is None and phrase is None:
-            return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k)
         xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
-        if phrase is None:
-            return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff)
-        pterms, poff = self._exclusions(phrase, nq)           # (the same packing: term -1 for a word no document holds)
+        # (the same packing for a phrase: term -1 for a word no document holds)
+        pterms, poff = self._exclusions(phrase, nq) if phrase is not None else (None, None)
         return self._ctx.bm25_search(self._index, terms, idf, qoff, self._params(), plus, k, mode=mode, ex_terms=xterms, ex_off=xoff,
                                      ph_terms=pterms, ph_off=poff)
 
@@ -492,12 +489,8 @@ class BM25:
         hold at least one word of each query; for a query of one word, its df."""
         queries, mode, exclude, phrase = self._bool_args(queries, match, exclude, phrase)
         nq, terms, _, qoff = self._queries(queries)
-        if mode == 0 and exclude is None and phrase is None:
-            return self._ctx.bm25_match_count(self._index, terms, qoff)
         xterms, xoff = self._exclusions(exclude, nq) if exclude is not None else (None, None)
-        if phrase is None:
-            return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff)
-        pterms, poff = self._exclusions(phrase, nq)
+        pterms, poff = self._exclusions(phrase, nq) if phrase is not None else (None, None)
         return self._ctx.bm25_match_count(self._index, terms, qoff, mode=mode, ex_terms=xterms, ex_off=xoff, ph_terms=pterms, ph_off=poff)
 
     # ---- word groups: alternatives that count as one query word; fuzzy and prefix search over them -----------------------

@@ -236,7 +236,7 @@ def test_allocation_failure_in_the_host_builder_is_an_error_code(tmp_path):
     that throws std::bad_alloc at the k-th allocation and sweeps k over a build of the bundled tables (the first 400 allocations one
     by one, then every 997th of the ~50 000): every failure point -- on the calling thread or on the builder's helper threads -- must
     come back as GZ_E_NOMEM with no tables, never as std::terminate (a silent SIGABRT, rc -6 here).  The GPU-side entry points have the
-    same barrier (function-try-blocks, gz_api.cpp) and their own injection test in tests/test_gpu_parity.py."""
+    same barrier (function-try-blocks, gz_api.cpp and gz_bm25_api.inc) and their own injection test in tests/test_gpu_parity.py."""
     import os
     import subprocess
     from conftest import ROOT, DATA
