@@ -1,6 +1,9 @@
 // The BM25 index behind the C ABI: the index, its workspace and the host code of every gz_bm25_* call, then the entry points.
 // Included by gz_api.cpp behind gz_ctx, fail, HIPCHK, ensure and the copy helpers; the kernels are in gz_bm25.inc, gz_topk.inc,
 // gz_vocab.inc, gz_search.inc, gz_groups.inc, gz_snippet.inc and gz_near.inc.
+// What changes a live index -- append, remove, compact -- has one shape: a core in three phases (A: workspace and tails only, B: every
+// remaining allocation, through bm_stage and its size rule, C: one commit() that nothing below can undo), run by bm25_change, which
+// owns the lock, the stage-before-drain order and the dropping of the derived lists.  The searches have theirs in bm25_search_entry.
 
 // ---- BM25 index (gz_bm25.inc) ------------------------------------------------------------------------------------------
 struct gz_bm25 {
@@ -195,18 +198,26 @@ struct BmStage {
     void commit() { for (int i = 0; i < n; ++i) std::swap(*live[i], fresh[i]); }
 };
 
-// `need` bytes behind *p, the first `keep` of them the live buffer's: the live buffer itself when it has the room, else a staged
-// copy of at least twice its capacity.  renew: always a staged buffer, of `need` bytes, nothing copied (a table to re-hash into).
-int bm_reserve(gz_ctx* c, BmStage& st, DBuf& live, size_t keep, size_t need, void** p, bool renew = false)
+// How large a staged buffer is.  Grow (an append): the live buffer itself while it has the room, else a staged one of at least twice
+// its capacity.  Same (a removal): the live one's capacity, so that a later append finds the same room.  Exact (a compaction, a
+// table to re-hash into, the derived lists): what a build gives a buffer of `need` bytes (bm_alloc's).
+enum class BmSize { Grow, Same, Exact };
+
+// `need` bytes behind *p, the first `keep` of them copied from the live buffer: a fresh buffer in the stage -- or, BmSize::Grow with
+// room, the live buffer itself.  An allocation site of the inject_bad_alloc switch either way.
+int bm_stage(gz_ctx* c, BmStage& st, DBuf& live, size_t keep, size_t need, BmSize size, void** p)
 {
     alloc_site(c);
-    if (!renew && live.p && need <= live.cap) { *p = live.p; return GZ_OK; }
-    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 append: stage overflow");
+    if (size == BmSize::Grow && live.p && need <= live.cap) { *p = live.p; return GZ_OK; }
+    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 index: stage overflow");
+    const size_t bytes = size == BmSize::Grow ? std::max(need, 2 * live.cap)
+                       : size == BmSize::Same ? std::max(need ? need : 16, live.cap > 256 ? live.cap - 256 : 0)    // (ensure adds the 256 again)
+                       : need ? need : 16;
     DBuf& f = st.fresh[st.n];
-    int rc = ensure(c, f, renew ? need : std::max(need, 2 * live.cap));
+    int rc = ensure(c, f, bytes);
     if (rc) return rc;
     st.live[st.n++] = &live;
-    if (keep && !renew) HIPCHK(c, hipMemcpyAsync(f.p, live.p, keep, hipMemcpyDeviceToDevice, c->stream));
+    if (keep) HIPCHK(c, hipMemcpyAsync(f.p, live.p, keep, hipMemcpyDeviceToDevice, c->stream));
     *p = f.p;
     return GZ_OK;
 }
@@ -228,8 +239,8 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     // ---- phase A: text, word boundaries, known terms, de-duplication of the rest
     void* p_text = nullptr; void* p_dl = nullptr;
     const int64_t wmax = (add + n) / 2 + 1;
-    if ((rc = bm_reserve(c, st, ix->text, (size_t)used, (size_t)(used + add) + 16, &p_text)) ||
-        (rc = bm_reserve(c, st, ix->dl, (size_t)N0 * 4, (size_t)(N0 + n) * 4, &p_dl)) ||
+    auto grow = [&](DBuf& live, size_t keep, size_t need, void** p) { return bm_stage(c, st, live, keep, need, BmSize::Grow, p); };
+    if ((rc = grow(ix->text, (size_t)used, (size_t)(used + add) + 16, &p_text)) || (rc = grow(ix->dl, (size_t)N0 * 4, (size_t)(N0 + n) * 4, &p_dl)) ||
         (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(n + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
         (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((n > wmax ? n : wmax) / 4096 + 2) * 4)))
         return rc;
@@ -256,7 +267,7 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
         return rc;
     // the batch's term ids: workspace, or -- a positional index -- the tail of seq behind the index's own words
     void* p_seq = nullptr;
-    if (pos ? (rc = bm_reserve(c, st, ix->seq, (size_t)W0 * 4, (size_t)(W0 + W) * 4, &p_seq)) : (rc = bm_alloc(c, w[BMW_TERM], w1 * 4))) return rc;
+    if (pos ? (rc = grow(ix->seq, (size_t)W0 * 4, (size_t)(W0 + W) * 4, &p_seq)) : (rc = bm_alloc(c, w[BMW_TERM], w1 * 4))) return rc;
     A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
     A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
     A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
@@ -290,19 +301,16 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     // only once the pair table has been written)
     const int64_t T1 = T0 + Tn, P1 = E0 + W;
     void *p_tstart, *p_tlen, *p_df, *p_sig, *p_eoff, *p_ent;
-    if ((rc = bm_reserve(c, st, ix->tstart, (size_t)T0 * 8, (size_t)T1 * 8, &p_tstart)) ||
-        (rc = bm_reserve(c, st, ix->tlen, (size_t)T0 * 4, (size_t)T1 * 4, &p_tlen)) ||
-        (rc = bm_reserve(c, st, ix->df, (size_t)T0 * 4, (size_t)T1 * 4, &p_df)) ||
-        (rc = bm_reserve(c, st, ix->sig, (size_t)N0 * 32, (size_t)(N0 + n) * 32, &p_sig)) ||
-        (rc = bm_reserve(c, st, ix->eoff, (size_t)(N0 + 1) * 4, (size_t)(N0 + n + 1) * 4, &p_eoff)) ||
-        (rc = bm_reserve(c, st, ix->ent, (size_t)E0 * 8, (size_t)P1 * 8, &p_ent)))
+    if ((rc = grow(ix->tstart, (size_t)T0 * 8, (size_t)T1 * 8, &p_tstart)) || (rc = grow(ix->tlen, (size_t)T0 * 4, (size_t)T1 * 4, &p_tlen)) ||
+        (rc = grow(ix->df, (size_t)T0 * 4, (size_t)T1 * 4, &p_df)) || (rc = grow(ix->sig, (size_t)N0 * 32, (size_t)(N0 + n) * 32, &p_sig)) ||
+        (rc = grow(ix->eoff, (size_t)(N0 + 1) * 4, (size_t)(N0 + n + 1) * 4, &p_eoff)) || (rc = grow(ix->ent, (size_t)E0 * 8, (size_t)P1 * 8, &p_ent)))
         return rc;
     uint64_t tslots = ix->tmask + 1, pslots = ix->pmask + 1;
     void* p_ttab = ix->ttab.p; void* p_ptab = ix->ptab.p;
     if (2 * (uint64_t)T1 > tslots) {                          // load <= 1/2, as the build leaves it
         const uint64_t old = tslots;
         tslots = bm_pow2(4 * (uint64_t)T1 + 16);
-        if ((rc = bm_reserve(c, st, ix->ttab, 0, tslots * 16, &p_ttab, true))) return rc;
+        if ((rc = bm_stage(c, st, ix->ttab, 0, tslots * 16, BmSize::Exact, &p_ttab))) return rc;
         HIPCHK(c, hipMemsetAsync(p_ttab, 0, tslots * 16, s));
         gz_launch_bm25_rehash((const GzBm25Slot*)ix->ttab.p, (int64_t)old, (GzBm25Slot*)p_ttab, tslots - 1, s);
     }
@@ -310,7 +318,7 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
         const uint64_t old = pslots;
         pslots = bm_pow2(2 * ((uint64_t)P1 + (uint64_t)P1 / 3) + 16);
         if (pslots > (1ull << 32)) pslots = 1ull << 32;       // (slot numbers are 32-bit; P1 < 2^31 still fits at <= 3/4)
-        if ((rc = bm_reserve(c, st, ix->ptab, 0, pslots * 16, &p_ptab, true))) return rc;
+        if ((rc = bm_stage(c, st, ix->ptab, 0, pslots * 16, BmSize::Exact, &p_ptab))) return rc;
         HIPCHK(c, hipMemsetAsync(p_ptab, 0, pslots * 16, s));
         gz_launch_bm25_rehash((const GzBm25Slot*)ix->ptab.p, (int64_t)old, (GzBm25Slot*)p_ptab, pslots - 1, s);
     }
@@ -339,20 +347,6 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
 }
 
 // ---- remove (gz_bm25_remove) ---------------------------------------------------------------------------------------------------
-// a staged buffer of the live one's capacity (a later append finds the same room), the first `keep` bytes copied
-int bm_stage(gz_ctx* c, BmStage& st, DBuf& live, size_t keep, size_t need, void** p)
-{
-    alloc_site(c);
-    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 remove: stage overflow");
-    DBuf& f = st.fresh[st.n];
-    int rc = ensure(c, f, std::max(need ? need : 16, live.cap > 256 ? live.cap - 256 : 0));    // (ensure adds the 256 again)
-    if (rc) return rc;
-    st.live[st.n++] = &live;
-    if (keep) HIPCHK(c, hipMemcpyAsync(f.p, live.p, keep, hipMemcpyDeviceToDevice, c->stream));
-    *p = f.p;
-    return GZ_OK;
-}
-
 // The documents ids_dev[0 .. n_ids) leave the index.  Phase A marks them and scans the marks and the kept entry counts (workspace
 // only); phase B makes every allocation: staged fieldLens, signatures, eoff, entries, pair table and a copy of df; then the
 // kernels compact the live arrays into the staged ones, fill the pair table and take the removed documents off the copy of df --
@@ -403,12 +397,13 @@ int bm25_remove_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const int64_t* ids_dev
     // ---- phase B: every allocation of the call
     const uint64_t pslots = ix->pmask + 1;
     void *p_dl, *p_sig, *p_eoff, *p_ent, *p_ptab, *p_df;
-    if ((rc = bm_stage(c, st, ix->dl, 0, (size_t)N1 * 4, &p_dl)) || (rc = bm_stage(c, st, ix->sig, 0, (size_t)N1 * 32, &p_sig)) ||
-        (rc = bm_stage(c, st, ix->eoff, 0, (size_t)(N1 + 1) * 4, &p_eoff)) || (rc = bm_stage(c, st, ix->ent, 0, (size_t)E1 * 8, &p_ent)) ||
-        (rc = bm_stage(c, st, ix->ptab, 0, pslots * 16, &p_ptab)) || (rc = bm_stage(c, st, ix->df, (size_t)T * 4, (size_t)T * 4, &p_df)))
+    auto same = [&](DBuf& live, size_t keep, size_t need, void** p) { return bm_stage(c, st, live, keep, need, BmSize::Same, p); };
+    if ((rc = same(ix->dl, 0, (size_t)N1 * 4, &p_dl)) || (rc = same(ix->sig, 0, (size_t)N1 * 32, &p_sig)) ||
+        (rc = same(ix->eoff, 0, (size_t)(N1 + 1) * 4, &p_eoff)) || (rc = same(ix->ent, 0, (size_t)E1 * 8, &p_ent)) ||
+        (rc = same(ix->ptab, 0, pslots * 16, &p_ptab)) || (rc = same(ix->df, (size_t)T * 4, (size_t)T * 4, &p_df)))
         return rc;
     void* p_seq = nullptr;
-    if (pos && (rc = bm_stage(c, st, ix->seq, 0, (size_t)W1 * 4, &p_seq))) return rc;
+    if (pos && (rc = same(ix->seq, 0, (size_t)W1 * 4, &p_seq))) return rc;
     R.seq2 = (uint32_t*)p_seq;
     R.dl2 = (uint32_t*)p_dl; R.sig2 = (unsigned long long*)p_sig; R.eoff2 = (uint32_t*)p_eoff; R.ent2 = (uint2*)p_ent;
     R.ptab2 = (GzBm25Slot*)p_ptab; R.pmask2 = ix->pmask; R.df2 = (uint32_t*)p_df;
@@ -470,19 +465,6 @@ int bm25_number(gz_ctx* c, gz_bm25* ix, GzBm25Cp& C, int64_t& B)
     return GZ_OK;
 }
 
-// a staged buffer of exactly the size a build gives it (bm_alloc's), nothing copied
-int bm_stage_exact(gz_ctx* c, BmStage& st, DBuf& live, size_t need, void** p)
-{
-    alloc_site(c);
-    if (st.n >= BmStage::MAX) return fail(c, GZ_E_HIP, "BM25 compact: stage overflow");
-    DBuf& f = st.fresh[st.n];
-    int rc = ensure(c, f, need ? need : 16);
-    if (rc) return rc;
-    st.live[st.n++] = &live;
-    *p = f.p;
-    return GZ_OK;
-}
-
 // The index becomes the one a fresh build of its current documents gives, term ids included.  Phase A numbers the live terms
 // (workspace only); phase B makes every allocation: all ten buffers staged, each of the size gz_bm25_build gives it for the same
 // counts (the text: the live terms' bytes), so capacities that appends and removals left behind are given back; then the kernels
@@ -502,15 +484,16 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
     // ---- phase B: every allocation of the call, sized as bm25_build_core sizes them
     const uint64_t pslots = bm_pow2((uint64_t)ix->n_words + (uint64_t)ix->n_words / 3 + 16), tslots = bm_pow2(2 * (uint64_t)T1 + 16);
     void *p_text, *p_dl, *p_sig, *p_eoff, *p_ent, *p_ptab, *p_ttab, *p_tstart, *p_tlen, *p_df;
-    if ((rc = bm_stage_exact(c, st, ix->text, (size_t)B + 16, &p_text)) || (rc = bm_stage_exact(c, st, ix->dl, (size_t)N * 4, &p_dl)) ||
-        (rc = bm_stage_exact(c, st, ix->sig, (size_t)N * 32, &p_sig)) || (rc = bm_stage_exact(c, st, ix->eoff, (size_t)(N + 1) * 4, &p_eoff)) ||
-        (rc = bm_stage_exact(c, st, ix->ent, (size_t)E * 8, &p_ent)) || (rc = bm_stage_exact(c, st, ix->ptab, pslots * 16, &p_ptab)) ||
-        (rc = bm_stage_exact(c, st, ix->ttab, tslots * 16, &p_ttab)) || (rc = bm_stage_exact(c, st, ix->tstart, (size_t)T1 * 8, &p_tstart)) ||
-        (rc = bm_stage_exact(c, st, ix->tlen, (size_t)T1 * 4, &p_tlen)) || (rc = bm_stage_exact(c, st, ix->df, (size_t)T1 * 4, &p_df)))
+    auto exact = [&](DBuf& live, size_t need, void** p) { return bm_stage(c, st, live, 0, need, BmSize::Exact, p); };
+    if ((rc = exact(ix->text, (size_t)B + 16, &p_text)) || (rc = exact(ix->dl, (size_t)N * 4, &p_dl)) ||
+        (rc = exact(ix->sig, (size_t)N * 32, &p_sig)) || (rc = exact(ix->eoff, (size_t)(N + 1) * 4, &p_eoff)) ||
+        (rc = exact(ix->ent, (size_t)E * 8, &p_ent)) || (rc = exact(ix->ptab, pslots * 16, &p_ptab)) ||
+        (rc = exact(ix->ttab, tslots * 16, &p_ttab)) || (rc = exact(ix->tstart, (size_t)T1 * 8, &p_tstart)) ||
+        (rc = exact(ix->tlen, (size_t)T1 * 4, &p_tlen)) || (rc = exact(ix->df, (size_t)T1 * 4, &p_df)))
         return rc;
     const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
     void* p_seq = nullptr;
-    if (pos && (rc = bm_stage_exact(c, st, ix->seq, (size_t)ix->n_words * 4, &p_seq))) return rc;
+    if (pos && (rc = exact(ix->seq, (size_t)ix->n_words * 4, &p_seq))) return rc;
     if (pos) { C.seq = (const uint32_t*)ix->seq.p; C.seq2 = (uint32_t*)p_seq; C.n_words = ix->n_words; }
     C.arena = (uint8_t*)p_text; C.tstart2 = (int64_t*)p_tstart; C.tlen2 = (uint32_t*)p_tlen; C.df2 = (uint32_t*)p_df;
     C.ent2 = (uint2*)p_ent; C.sig2 = (unsigned long long*)p_sig; C.ptab2 = (GzBm25Slot*)p_ptab; C.pmask2 = pslots - 1;
@@ -534,6 +517,43 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
     return GZ_OK;
 }
 
+// ---- what every change of a live index goes through -----------------------------------------------------------------------------
+// the postings (gz_search.inc) leave: the index has changed (or is to equal a fresh build).  After the stream has drained: a search
+// enqueued into device memory may still read them.
+void bm25_drop_postings(gz_bm25* ix)
+{
+    if (!ix->has_post && !ix->has_woff) return;
+    hipStreamSynchronize(ix->c->stream);
+    release(ix->poff);
+    release(ix->pdoc);
+    release(ix->woff);                            // (a positional index's word offsets: derived from fieldLens in the same way)
+    ix->has_post = ix->has_woff = false;
+}
+
+// core(stage) under the context's lock, which the caller holds: one of the three cores above, behind whatever the entry point
+// still has to check or upload.  The stage is declared BEFORE the drain: whatever it still holds when the core returns -- the fresh
+// buffers of a failed call, the old ones of a successful one -- is freed after the stream has drained.  On success the derived
+// lists leave.
+template <class Core>
+int bm25_change_locked(gz_ctx* c, gz_bm25* ix, Core&& core)
+{
+    BmStage st;
+    BmDrain drain{c};
+    const int rc = core(st);
+    if (!rc) bm25_drop_postings(ix);
+    return rc;
+}
+
+// the same behind the lock and on the context's device: gz_bm25_append, gz_bm25_remove, their _device forms and gz_bm25_compact
+template <class Core>
+int bm25_change(gz_bm25* ix, Core&& core)
+{
+    gz_ctx* c = ix->c;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return bm25_change_locked(c, ix, core);
+}
+
 // The last step of a POSITIONAL build.  Such an index never needs the documents' text again, only its terms' bytes, so the build
 // ends in the canonical form a compaction gives: the text copy is the live terms' bytes in first-occurrence order and every
 // buffer has the size its counts ask for.  A fresh positional build and a compacted positional index of the same documents are
@@ -541,9 +561,7 @@ int bm25_compact_core(gz_ctx* c, gz_bm25* ix, BmStage& st)
 int bm25_build_finish(gz_ctx* c, gz_bm25* ix)
 {
     if (!(ix->flags & GZ_BM25_POSITIONS)) return GZ_OK;
-    BmStage st;                                              // (before the drain: what it still holds is freed after the stream has drained)
-    BmDrain drain{c};
-    return bm25_compact_core(c, ix, st);
+    return bm25_change_locked(c, ix, [&](BmStage& st) { return bm25_compact_core(c, ix, st); });       // (a fresh index has no lists to drop)
 }
 
 int bm_adopt(gz_ctx* c, std::unique_ptr<gz_bm25>& ix, gz_bm25** out)
@@ -797,18 +815,6 @@ int bm25_vocab_locked(gz_bm25* ix, const uint8_t* words, const int64_t* word_off
 }
 
 // ---- search (gz_bm25_search, gz_bm25_match_count; gz_search.inc) -----------------------------------------------------------------
-// the postings leave: the index has changed (or is to equal a fresh build).  After the stream has drained: a search enqueued into
-// device memory may still read them.
-void bm25_drop_postings(gz_bm25* ix)
-{
-    if (!ix->has_post && !ix->has_woff) return;
-    hipStreamSynchronize(ix->c->stream);
-    release(ix->poff);
-    release(ix->pdoc);
-    release(ix->woff);                            // (a positional index's word offsets: derived from fieldLens in the same way)
-    ix->has_post = ix->has_woff = false;
-}
-
 // The word offsets of a positional index as it is, unless it has them: woff = the scan of fieldLens, staged and entered after the
 // round trip as the postings are.  Its total must be the index's word count: the bound of every read of seq.
 int bm25_word_offsets(gz_bm25* ix)
@@ -820,7 +826,7 @@ int bm25_word_offsets(gz_bm25* ix)
     BmStage st;
     BmDrain drain{c};
     void* p_woff;
-    if ((rc = bm_stage_exact(c, st, ix->woff, (size_t)(N + 1) * 4, &p_woff)) || (rc = bm_alloc(c, c->w_bm[BMW_BSUM], (size_t)(N / 4096 + 2) * 4)))
+    if ((rc = bm_stage(c, st, ix->woff, 0, (size_t)(N + 1) * 4, BmSize::Exact, &p_woff)) || (rc = bm_alloc(c, c->w_bm[BMW_BSUM], (size_t)(N / 4096 + 2) * 4)))
         return rc;
     if ((rc = bm_scan(c, (const uint32_t*)ix->dl.p, N, (uint32_t*)p_woff))) return rc;
     int64_t total = 0;
@@ -846,7 +852,7 @@ int bm25_postings(gz_bm25* ix)
     BmStage st;
     BmDrain drain{c};
     void *p_poff, *p_pdoc;
-    if ((rc = bm_stage_exact(c, st, ix->poff, (size_t)(T + 1) * 4, &p_poff)) || (rc = bm_stage_exact(c, st, ix->pdoc, (size_t)E * 4, &p_pdoc)) ||
+    if ((rc = bm_stage(c, st, ix->poff, 0, (size_t)(T + 1) * 4, BmSize::Exact, &p_poff)) || (rc = bm_stage(c, st, ix->pdoc, 0, (size_t)E * 4, BmSize::Exact, &p_pdoc)) ||
         (rc = bm_alloc(c, w[BMW_P_CUR], (size_t)T * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
         (rc = bm_alloc(c, w[BMW_BSUM], (size_t)(T / 4096 + 2) * 4)))
         return rc;
@@ -1513,17 +1519,14 @@ try {
     const int64_t nbytes = text_off[n_docs] - text_off[0];
     if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
     for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = bm_limits(c, ix->text_bytes + nbytes, ix->n_docs + n_docs))) return rc;
-    BmStage st;
-    BmDrain drain{c};
-    if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
-    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
-    rc = bm25_append_core(c, ix, st, nbytes ? text + text_off[0] : nullptr, nullptr, (const int64_t*)c->w_bm[BMW_OFF].p, text_off[0], n_docs, nbytes);
-    if (!rc) bm25_drop_postings(ix);
-    return rc;
+    return bm25_change(ix, [&](BmStage& st) -> int {             // (the offsets through the workspace, then as the device form)
+        DBuf& off = c->w_bm[BMW_OFF];
+        int rc;
+        if ((rc = bm_limits(c, ix->text_bytes + nbytes, ix->n_docs + n_docs)) || (rc = bm_alloc(c, off, (size_t)(n_docs + 1) * 8)) ||
+            (rc = copy_in(c, off.p, text_off, (size_t)(n_docs + 1) * 8, c->stream)))
+            return rc;
+        return bm25_append_core(c, ix, st, nbytes ? text + text_off[0] : nullptr, nullptr, (const int64_t*)off.p, text_off[0], n_docs, nbytes);
+    });
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_append_device(gz_bm25* ix, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes)
@@ -1532,19 +1535,15 @@ try {
     gz_ctx* c = ix->c;
     if (n_docs < 0 || text_bytes < 0) return fail(c, GZ_E_INVALID, "bad arguments");
     if (n_docs == 0) return GZ_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = bm_limits(c, ix->text_bytes + text_bytes, ix->n_docs + n_docs))) return rc;     // (before anything is read)
-    if (!text_off_dev || (text_bytes > 0 && !text_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
-    BmStage st;
-    BmDrain drain{c};
-    int64_t off0 = 0;
-    if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
-    if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
-    rc = bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
-    if (!rc) bm25_drop_postings(ix);
-    return rc;
+    return bm25_change(ix, [&](BmStage& st) -> int {
+        int rc;
+        if ((rc = bm_limits(c, ix->text_bytes + text_bytes, ix->n_docs + n_docs))) return rc;     // (before anything is read)
+        if (!text_off_dev || (text_bytes > 0 && !text_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+        int64_t off0 = 0;
+        if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
+        if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+        return bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
+    });
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_remove(gz_bm25* ix, const int64_t* doc_ids, int64_t n_ids)
@@ -1553,16 +1552,12 @@ try {
     gz_ctx* c = ix->c;
     if (n_ids < 0 || (n_ids > 0 && !doc_ids)) return fail(c, GZ_E_INVALID, "bad arguments");
     if (n_ids == 0) return GZ_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    BmStage st;
-    BmDrain drain{c};
-    if ((rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)n_ids * 8))) return rc;
-    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, doc_ids, (size_t)n_ids * 8, c->stream))) return rc;
-    rc = bm25_remove_core(c, ix, st, (const int64_t*)c->w_bm[BMW_OFF].p, n_ids);
-    if (!rc) bm25_drop_postings(ix);
-    return rc;
+    return bm25_change(ix, [&](BmStage& st) -> int {             // (the ids through the workspace, then as the device form)
+        DBuf& ids = c->w_bm[BMW_OFF];
+        int rc;
+        if ((rc = bm_alloc(c, ids, (size_t)n_ids * 8)) || (rc = copy_in(c, ids.p, doc_ids, (size_t)n_ids * 8, c->stream))) return rc;
+        return bm25_remove_core(c, ix, st, (const int64_t*)ids.p, n_ids);
+    });
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_remove_device(gz_bm25* ix, const int64_t* doc_ids_dev, int64_t n_ids)
@@ -1571,26 +1566,14 @@ try {
     gz_ctx* c = ix->c;
     if (n_ids < 0 || (n_ids > 0 && !doc_ids_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
     if (n_ids == 0) return GZ_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    BmStage st;
-    BmDrain drain{c};
-    const int rc = bm25_remove_core(c, ix, st, doc_ids_dev, n_ids);
-    if (!rc) bm25_drop_postings(ix);
-    return rc;
+    return bm25_change(ix, [&](BmStage& st) { return bm25_remove_core(c, ix, st, doc_ids_dev, n_ids); });
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_compact(gz_bm25* ix)
 try {
     if (!ix) return GZ_E_INVALID;
-    gz_ctx* c = ix->c;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    BmStage st;
-    BmDrain drain{c};
-    const int rc = bm25_compact_core(c, ix, st);
-    if (!rc) bm25_drop_postings(ix);              // (a fresh build has none: device memory included)
-    return rc;
+    // (the derived lists leave as after every change: a fresh build has none, device memory included)
+    return bm25_change(ix, [&](BmStage& st) { return bm25_compact_core(ix->c, ix, st); });
 } GZ_CATCH(ix ? ix->c : nullptr)
 
 int gz_bm25_terms(gz_bm25* ix, int64_t* term_off, int32_t* df, uint8_t* bytes, int64_t bytes_cap)

@@ -1,6 +1,8 @@
 """A tiny corpus and one ctypes caller for the fifteen search entry points of the BM25 index (gz_bm25_search, _bool, _phrase, _near
 and _groups, each with a _device form and a gz_bm25_match_count* form): what test_gpu_bm25_search_refusals.py and
-test_gpu_bm25_search_doors.py share.  130 one-line documents over twelve words: a row's bitmap takes three 64-bit words."""
+test_gpu_bm25_search_doors.py share.  130 one-line documents over twelve words: a row's bitmap takes three 64-bit words.
+CHANGES / change() are the same for the nine entry points that make or change an index (test_gpu_bm25_change_refusals.py,
+test_gpu_bm25_change_life.py)."""
 import ctypes
 
 import numpy as np
@@ -73,4 +75,42 @@ def call(lib, index, entry, req):
             a = np.ascontiguousarray(v, dtype=_DTYPE[f])
             keep.append(a)
             args.append(ctypes.c_void_p(a.ctypes.data))
+    return getattr(lib, entry)(*args)
+
+
+# ---- the nine entry points that make or change an index -------------------------------------------------------------------------
+# entry point -> all its arguments, in the order of include/genz_tokenize.h
+CHANGES = {
+    "gz_bm25_build": ["ctx", "text", "text_off", "n_docs", "out"],
+    "gz_bm25_build_device": ["ctx", "text", "text_off", "n_docs", "text_bytes", "out"],
+    "gz_bm25_build_ex": ["ctx", "text", "text_off", "n_docs", "flags", "out"],
+    "gz_bm25_build_device_ex": ["ctx", "text", "text_off", "n_docs", "text_bytes", "flags", "out"],
+    "gz_bm25_append": ["index", "text", "text_off", "n_docs"],
+    "gz_bm25_append_device": ["index", "text", "text_off", "n_docs", "text_bytes"],
+    "gz_bm25_remove": ["index", "ids", "n_ids"],
+    "gz_bm25_remove_device": ["index", "ids", "n_ids"],
+    "gz_bm25_compact": ["index"],
+}
+assert len(CHANGES) == 9
+_CH_SCALAR = ("n_docs", "text_bytes", "flags", "n_ids")
+
+
+def is_build(entry):
+    return "build" in entry
+
+
+def change(lib, entry, req):
+    """lib.<entry>(...) with the arguments taken from req by name: the scalars are ints, every pointer is an address (int, host or
+    device as the entry point wants it) or None; `out` of a build is a ctypes.c_void_p to receive the handle, or None."""
+    args = []
+    for f in CHANGES[entry]:
+        v = req[f]
+        if f in _CH_SCALAR:
+            args.append(int(v))
+        elif v is None:
+            args.append(None)
+        elif f == "out":
+            args.append(ctypes.byref(v))
+        else:
+            args.append(ctypes.c_void_p(int(v)))
     return getattr(lib, entry)(*args)
