@@ -17,6 +17,9 @@ fixtures written here are data only (inputs + the reference's outputs):
   g6_decode.jsonl     Tokenize.decode on seeded random id lists (bundled tables, ids of '@@' pieces at the end of a
                       row, out-of-range / negative ids, a non-default unk_token) and on tiny tables whose words
                       contain spaces, '@@ ' and empty strings (file bytes stored base64)
+  g6b_decode_shapes.jsonl.gz  Tokenize.decode on the synthetic table and row lists of tests/decode_tables.py (token lengths around
+                      the 12-byte inline limit, rows around multiples of 64 tokens, unk strings, add_vocab_file); `make_golden.py g6b`
+                      writes the same bytes on every run
   g7_preprocess.jsonl.gz  the five text filters of genz_tokenize/preprocess.py (remove_html, convert_unicode,
                       remove_punctuations, remove_emoji, remove_URL) on hand-picked and seeded random strings, one
                       filter at a time and chained
@@ -361,6 +364,72 @@ def g6(tok):
     jl("g6_decode.jsonl", rows)
 
 
+# ------------------------------------------------------------------ G6b
+G6B_LONG = 4096          # a result of more bytes than this is stored as its SHA-256 and length (the 5000-byte words, the 4096-byte unk)
+
+
+def g6b():
+    """Tokenize.decode on the synthetic table of tests/decode_tables.py: the row lists `align`, `trips`, `nothing`, `ids` and
+    `unk_rows` under the default unk token, `ids` and `unk_rows` under each unk string of decode_tables.UNKS, and a row list before
+    and after an add_vocab_file of a second vocab.  One JSON object per line; a result longer than G6B_LONG bytes is stored as
+    {"sha256", "len"} of its UTF-8 bytes in place of the text.  The gzip header carries no time stamp or file name, so a second
+    run writes the same bytes."""
+    import gzip
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import decode_tables as T
+    s = T.Shapes()
+    tmp = tempfile.mkdtemp()
+    vp, bp, vp2 = os.path.join(tmp, "v"), os.path.join(tmp, "b"), os.path.join(tmp, "v2")
+    open(vp, "wb").write(s.vocab); open(bp, "wb").write(T.BPE); open(vp2, "wb").write(T.second_vocab())
+
+    def build(**kw):
+        # what fromFile does (tokenize.py:261-267), with the keyword passed on to the second __init__
+        t = Tokenize()
+        t.vocab_file, t.bpe_file = vp, bp
+        t.__init__(**kw)
+        return t
+
+    def packed(text):
+        raw = text.encode("utf-8")
+        return text if len(raw) <= G6B_LONG else {"sha256": hashlib.sha256(raw).hexdigest(), "len": len(raw)}
+
+    def results(t, rows):
+        return [packed(t.decode(r)) for r in rows]
+    rows = [{"name": "table", "vocab_b64": base64.b64encode(s.vocab).decode(), "bpe_b64": base64.b64encode(T.BPE).decode(),
+             "second_vocab_b64": base64.b64encode(T.second_vocab()).decode(), "long": G6B_LONG}]
+    tok = Tokenize.fromFile(vp, bp)
+    for g in ("align", "trips", "nothing", "ids", "unk_rows"):
+        ids = getattr(s, g)
+        rows.append({"name": "default", "group": g, "unk_token": "<unk>", "construction": "Tokenize.fromFile(vocab, bpe)",
+                     "ids": ids, "result": results(tok, ids)})
+    for u in T.UNKS:
+        try:
+            t = build(unk_token=u)
+        except Exception as e:  # noqa: BLE001
+            rows.append({"name": "unk", "unk_token": u, "raises": type(e).__name__})
+            continue
+        rows.append({"name": "unk", "unk_token": u,
+                     "construction": "t = Tokenize(); t.vocab_file, t.bpe_file = vocab, bpe; t.__init__(unk_token=u)",
+                     "result": {g: results(t, getattr(s, g)) for g in ("ids", "unk_rows")}})
+    # add_vocab_file: `decoder` stays what __init__ made it (tokenize.py:40), `encoder` grows
+    tok = Tokenize.fromFile(vp, bp)
+    n_before = tok.vocab_size()
+    words = ["new0", T.plain(7), T.plain(5)]
+    enc_before = {w: tok.encode(w, False) for w in words}
+    tok2 = Tokenize.fromFile(vp, bp)
+    tok2.add_vocab_file(vp2)
+    lists = s.added_rows()
+    assert lists[:4] == [[i] for i in range(n_before, n_before + 4)] and tok2.vocab_size() == n_before + 3
+    rows.append({"name": "add_vocab_file", "ids": lists, "before": results(tok, lists), "after": results(tok2, lists),
+                 "vocab_size": [n_before, tok2.vocab_size()], "new_word_ids": {w: tok2.encoder[w] for w in ("new0", "new1@@", T.plain(7))},
+                 "encode_before": enc_before, "encode_after": {w: tok2.encode(w, False) for w in words}})
+    path = os.path.join(HERE, "g6b_decode_shapes.jsonl.gz")
+    with open(path, "wb") as f, gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0, compresslevel=9) as z:
+        for r in rows:
+            z.write((json.dumps(r, ensure_ascii=True) + "\n").encode("ascii"))
+    print("g6b_decode_shapes.jsonl.gz", len(rows), os.path.getsize(path), "bytes")
+
+
 # ------------------------------------------------------------------ G7
 def g7():
     from genz_tokenize import preprocess as P
@@ -423,7 +492,7 @@ def g7():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g7"]
+    which = sys.argv[1:] or ["g1", "g3", "g4", "g5", "g6", "g6b", "g7"]
     tok = Tokenize()
     if "g1" in which: g1(tok)
     if "g3" in which: g3(tok)
@@ -431,4 +500,5 @@ if __name__ == "__main__":
     if "g5" in which: g5(False)
     if "g5full" in which: g5(True)
     if "g6" in which: g6(tok)
+    if "g6b" in which: g6b()
     if "g7" in which: g7()
