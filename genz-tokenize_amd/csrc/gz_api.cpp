@@ -155,6 +155,7 @@ struct gz_ctx {
     std::string dec_unk;
     bool dec_unk_set = false;
     DBuf t_dec_entries, t_dec_bytes, w_dec_ids, w_dec_roff, w_dec_rb, w_dec_ooff, w_dec_out;
+    DBuf w_win_cnt, w_win_ids, w_win_roff, w_win_off, w_win_out, w_win_mask, w_win_meta;               // overlapping windows (gz_window_rows*)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_pp_in, w_pp_inoff, w_ppctl, w_pplen32, w_pplb;      // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
     // host path with copies overlapped (gz_encode_batch_csr): copy-in / copy-out streams, per-sub-batch events and buffers
@@ -1042,6 +1043,7 @@ try {
     for (auto& t2 : c->w_tiny) for (auto& t : t2) release(t);
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_pp_in, &c->w_pp_inoff, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_ids, &c->w_dec_roff, &c->w_dec_rb, &c->w_dec_ooff, &c->w_dec_out}) release(*b);
+    for (DBuf* b : {&c->w_win_cnt, &c->w_win_ids, &c->w_win_roff, &c->w_win_off, &c->w_win_out, &c->w_win_mask, &c->w_win_meta}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
     for (DBuf* b : {&c->t_merges, &c->t_symids, &c->t_bmp, &c->t_astral, &c->t_struct, &c->t_words2, &c->w_text, &c->w_toff, &c->w_pair,
@@ -2028,6 +2030,115 @@ try {
         HostPool pool(pool_threads(c, (size_t)total));
         if ((rc = copy_out(c, out, c->w_dec_out.p, (size_t)total, c->stream, &pool))) return rc;
     }
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+// ---- overlapping max_len windows ------------------------------------------------------------------------------------
+namespace {
+// the fill pass over win_off, enqueued on the context's stream; bos / eos / pad are the context's current special ids
+void window_fill(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
+                 int32_t skip_back, const int64_t* win_off_dev, int64_t n_win, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc,
+                 int32_t* win_start, int32_t* win_n_real)
+{
+    GzWinArgs A{ids_dev, row_off_dev, n_rows, win_off_dev, n_win, max_len, max_len - 2, max_len - 2 - stride, skip_front, skip_back,
+                c->dev.bos_id, c->dev.eos_id, c->dev.pad_id, out_ids, out_mask, win_doc, win_start, win_n_real};
+    gz_launch_window_fill(A, c->stream);
+}
+
+// Both passes on the context's stream, behind whatever it holds (an encode call's forked streams have rejoined it when that call
+// returns).  *total = windows of the batch.  out_ids == nullptr: the count pass only.
+int window_device_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
+                         int32_t skip_front, int32_t skip_back, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc, int32_t* win_start,
+                         int32_t* win_n_real, int64_t* win_off_dev, int64_t capacity, int64_t* total)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_win_cnt, (size_t)(n_rows + 1) * 8))) return rc;
+    const int32_t room = max_len - 2, step = room - stride;
+    gz_launch_window_count(row_off_dev, n_rows, room, step, skip_front + skip_back, (int64_t*)c->w_win_cnt.p, win_off_dev, c->stream);
+    *total = 0;
+    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
+    *h_total = 0;
+    if (n_rows > 0) HIPCHK(c, hipMemcpyAsync(h_total, win_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(c, hipMemsetAsync(win_off_dev, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *total = *h_total;
+    if (!out_ids) return GZ_OK;
+    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)*total, (long long)capacity);
+    window_fill(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, win_off_dev, *total, out_ids, out_mask, win_doc, win_start,
+                win_n_real);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+bool window_rule_ok(int32_t max_len, int32_t stride, int32_t skip_front, int32_t skip_back)
+{
+    return max_len >= 3 && stride >= 0 && stride <= max_len - 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1;
+}
+}  // namespace
+
+int gz_window_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
+                          int32_t skip_front, int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* win_doc_dev,
+                          int32_t* win_start_dev, int32_t* win_n_real_dev, int64_t* win_off_dev, int64_t capacity_windows, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !win_off_dev || !total_host || n_rows < 0 || capacity_windows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
+        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return window_device_locked(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, input_ids_dev, attention_mask_dev,
+                                win_doc_dev, win_start_dev, win_n_real_dev, win_off_dev, capacity_windows, total_host);
+} GZ_CATCH(c)
+
+int gz_window_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
+                   int32_t skip_back, int32_t* input_ids, int32_t* attention_mask, int32_t* win_doc, int32_t* win_start, int32_t* win_n_real,
+                   int64_t* win_off, int64_t capacity_windows, int64_t* total_host)
+try {
+    if (!c || !row_off || !win_off || !total_host || n_rows < 0 || capacity_windows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
+        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
+    const int64_t n_ids = row_off[n_rows] - row_off[0];
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(c, GZ_E_INVALID, "bad row offsets");
+    for (int64_t r = 0; r < n_rows; ++r) if (row_off[r + 1] < row_off[r]) return fail(c, GZ_E_INVALID, "row offsets must not decrease");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_win_ids, (size_t)(n_ids + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->w_win_roff, (size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_win_off, (size_t)(n_rows + 1) * 8))) return rc;
+    if (n_ids && (rc = copy_in(c, c->w_win_ids.p, ids + row_off[0], (size_t)n_ids * 4, c->stream))) return rc;
+    if ((rc = copy_in(c, c->w_win_roff.p, row_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    const int32_t* const ids_dev = (const int32_t*)c->w_win_ids.p - row_off[0];
+    const int64_t* const roff_dev = (const int64_t*)c->w_win_roff.p;
+    int64_t total = 0;
+    if ((rc = window_device_locked(c, ids_dev, roff_dev, n_rows, max_len, stride, skip_front, skip_back, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   (int64_t*)c->w_win_off.p, 0, &total))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, win_off, c->w_win_off.p, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_windows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)total, (long long)capacity_windows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len;
+    if ((rc = ensure(c, c->w_win_out, cells * 4))) return rc;
+    if (attention_mask && (rc = ensure(c, c->w_win_mask, cells * 4))) return rc;
+    if ((rc = ensure(c, c->w_win_meta, (size_t)total * 12))) return rc;
+    int32_t* const meta = (int32_t*)c->w_win_meta.p;
+    window_fill(c, ids_dev, roff_dev, n_rows, max_len, stride, skip_front, skip_back, (const int64_t*)c->w_win_off.p, total, (int32_t*)c->w_win_out.p,
+                attention_mask ? (int32_t*)c->w_win_mask.p : nullptr, win_doc ? meta : nullptr, win_start ? meta + total : nullptr,
+                win_n_real ? meta + 2 * total : nullptr);
+    {
+        HostPool pool(pool_threads(c, cells * 4));
+        if ((rc = copy_out(c, input_ids, c->w_win_out.p, cells * 4, c->stream, &pool))) return rc;
+        if (attention_mask && (rc = copy_out(c, attention_mask, c->w_win_mask.p, cells * 4, c->stream, &pool))) return rc;
+    }
+    if (win_doc && (rc = copy_out(c, win_doc, meta, (size_t)total * 4, c->stream))) return rc;
+    if (win_start && (rc = copy_out(c, win_start, meta + total, (size_t)total * 4, c->stream))) return rc;
+    if (win_n_real && (rc = copy_out(c, win_n_real, meta + 2 * total, (size_t)total * 4, c->stream))) return rc;
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
 } GZ_CATCH(c)

@@ -114,6 +114,20 @@ void gz_launch_bpe_word(const GzDeviceTables* T_dev, const uint8_t* word, int64_
 void gz_launch_decode(const GzDecTable& D, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int64_t* row_bytes,
                       int64_t* out_off, uint8_t* out, int64_t capacity, hipStream_t s);
 
+// overlapping max_len windows over ragged rows (gz_window.inc).  Count pass: n_win[n_rows] and their exclusive scan win_off[n_rows + 1].
+// Fill pass: the n_win = win_off[n_rows] window rows; out_mask, win_doc, win_start, win_n_real may be null.
+struct GzWinArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets)
+    const int64_t* win_off; int64_t n_win;
+    int32_t max_len, room, step, skip_front, skip_back;             // room = max_len - 2, step = room - stride
+    int32_t bos_id, eos_id, pad_id;
+    int32_t* out_ids; int32_t* out_mask;                            // [n_win, max_len]
+    int32_t* win_doc; int32_t* win_start; int32_t* win_n_real;      // [n_win]
+};
+void gz_launch_window_count(const int64_t* row_off, int64_t n_rows, int32_t room, int32_t step, int32_t skip, int64_t* n_win, int64_t* win_off,
+                            hipStream_t s);
+void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s);
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

@@ -689,6 +689,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_hot.inc"
 #include "gz_small.inc"
 #include "gz_decode.inc"
+#include "gz_window.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -740,6 +741,24 @@ void gz_launch_decode(const GzDecTable& D, const int32_t* ids, const int64_t* ro
         hipLaunchKernelGGL(gz_decode_kernel, dim3(grid), dim3(WAVE * 4), 0, s, D, ids, row_off, n_rows, (int64_t*)nullptr,
                            (const int64_t*)out_off, out, capacity);
     }
+}
+
+void gz_launch_window_count(const int64_t* row_off, int64_t n_rows, int32_t room, int32_t step, int32_t skip, int64_t* n_win, int64_t* win_off,
+                            hipStream_t s)
+{
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(gz_window_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, room, step, skip, n_win);
+    launch_scan64((const int64_t*)n_win, n_rows, win_off, s);
+}
+
+void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s)
+{
+    if (A.n_win <= 0) return;
+    const dim3 grid((unsigned)((A.n_win + 4 * WAVE - 1) / (4 * WAVE))), block(WAVE * 4);
+    // 16 bytes a lane where every row starts on a 16-byte boundary; one cell a lane otherwise
+    const bool wide = A.max_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask)) & 15) == 0;
+    if (wide) hipLaunchKernelGGL(gz_window_fill_kernel<4>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(gz_window_fill_kernel<1>, grid, block, 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

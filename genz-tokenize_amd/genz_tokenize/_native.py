@@ -46,6 +46,7 @@ SYMBOLS = [
     "gz_bm25_search_near", "gz_bm25_search_near_device", "gz_bm25_match_count_near", "gz_bm25_cover", "gz_bm25_cover_device",
     "gz_bm25_similar", "gz_bm25_prefix", "gz_bm25_term_bytes",
     "gz_bm25_search_groups", "gz_bm25_search_groups_device", "gz_bm25_match_count_groups",
+    "gz_window_rows", "gz_window_rows_device",
 ]
 
 _lib = None
@@ -99,6 +100,9 @@ def load_library():
     L.gz_decoder_snapshot.argtypes = [vp]
     L.gz_decode_batch.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp]
     L.gz_decode_batch_device.argtypes = [vp, vp, vp, i64, vp, i32, vp, i64, vp, P(i64)]
+    win = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, P(i64)]
+    L.gz_window_rows.argtypes = win
+    L.gz_window_rows_device.argtypes = win
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -495,6 +499,40 @@ class Context:
         self._check(self.lib.gz_decode_batch_device(self.handle, C.c_void_p(d_ids), C.c_void_p(d_row_off), n_rows,
                                                     C.cast(ub, C.c_void_p), len(unk), C.c_void_p(d_out) if d_out else None,
                                                     capacity, C.c_void_p(d_out_off), C.byref(total)))
+        return total.value
+
+    # ---- overlapping max_len windows -----------------------------------------------------------------------
+    def window_rows(self, ids: np.ndarray, row_off: np.ndarray, max_len: int, stride: int, framed: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict(input_ids [W, L], attention_mask [W, L], doc [W], start [W],
+        n_real [W], win_off int64 [n+1]) (gz_window_rows: a sizing call, then the windows)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, L, skip = len(row_off) - 1, int(max_len), 1 if framed else 0
+        win_off = np.zeros(n + 1, dtype=np.int64)
+        total = C.c_int64()
+        head = (self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), n, L, int(stride), skip, skip)
+        self._check(self.lib.gz_window_rows(*head, None, None, None, None, None, _ptr(win_off), 0, C.byref(total)))
+        W = total.value
+        out = dict(input_ids=np.empty((W, L), dtype=np.int32), attention_mask=np.empty((W, L), dtype=np.int32),
+                   doc=np.empty(W, dtype=np.int32), start=np.empty(W, dtype=np.int32), n_real=np.empty(W, dtype=np.int32), win_off=win_off)
+        if W:
+            self._check(self.lib.gz_window_rows(*head, _ptr(out["input_ids"]), _ptr(out["attention_mask"]), _ptr(out["doc"]),
+                                                _ptr(out["start"]), _ptr(out["n_real"]), _ptr(win_off), W, C.byref(total)))
+        return out
+
+    def window_rows_device(self, d_ids, d_row_off, n_rows, max_len, stride, skip_front, skip_back, d_input_ids, d_mask, d_doc, d_start,
+                           d_n_real, d_win_off, capacity) -> int:
+        """gz_window_rows_device: returns W.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = W."""
+        vp = C.c_void_p
+        total = C.c_int64()
+        rc = self.lib.gz_window_rows_device(self.handle, vp(d_ids) if d_ids else None, vp(d_row_off), n_rows, max_len, stride, skip_front,
+                                            skip_back, vp(d_input_ids) if d_input_ids else None, vp(d_mask) if d_mask else None,
+                                            vp(d_doc) if d_doc else None, vp(d_start) if d_start else None,
+                                            vp(d_n_real) if d_n_real else None, vp(d_win_off), capacity, C.byref(total))
+        if rc:
+            e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
+            e.total = total.value
+            raise e
         return total.value
 
     # ---- text pre-pass ----------------------------------------------------------------------------------

@@ -188,16 +188,7 @@ class Tokenize(object):
         """`decode` for many id lists at once, on the GPU (the reference has no batch form).
         `rows` is a sequence of integer sequences or a 2-D integer array; ids outside the int32 range decode to the
         unk token like any other unknown id."""
-        if isinstance(rows, np.ndarray) and rows.ndim == 2:
-            n, L = rows.shape
-            flat = rows.reshape(-1)
-            off = np.arange(n + 1, dtype=np.int64) * L
-        else:
-            rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
-            off = np.zeros(len(rows) + 1, dtype=np.int64)
-            if rows:
-                np.cumsum([len(r) for r in rows], out=off[1:])
-            flat = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        flat, off = self._flat_rows(rows)
         self._sync_tables()
         flat = np.asarray(flat)
         if flat.dtype != np.int32:
@@ -207,6 +198,18 @@ class Tokenize(object):
         data, out_off = self._ctx.decode(flat, off, self.unk_token.encode("utf-8", "surrogatepass"))
         raw = data.tobytes()
         return [raw[out_off[i]:out_off[i + 1]].decode("utf-8", "surrogatepass") for i in range(len(off) - 1)]
+
+    @staticmethod
+    def _flat_rows(rows):
+        """Sequences of ints, or a 2-D array -> (the rows back to back, int64 offsets [N+1])."""
+        if isinstance(rows, np.ndarray) and rows.ndim == 2:
+            n, L = rows.shape
+            return rows.reshape(-1), np.arange(n + 1, dtype=np.int64) * L
+        rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([len(r) for r in rows], out=off[1:])
+        return (np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)), off
 
     def get_atttention_mask(self, token):
         pad = self._special_ids()[0]
@@ -439,6 +442,125 @@ class Tokenize(object):
         finally:
             for d in bufs:
                 ctx.free(d)
+
+    # ---- overlapping max_len windows (long documents) ---------------------------------------------------------------
+    @staticmethod
+    def _window_rule(max_len, stride):
+        """(L, s) of a window call, or the refusal: L >= 3 (bos, a token, eos) and 0 <= s <= L - 3 (every window adds a token)."""
+        for name, v in (("max_len", max_len), ("stride", stride)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an int" % name)
+        L, s = int(max_len), int(stride)
+        if L < 3 or L >= 2 ** 31:
+            raise ValueError("windows need 3 <= max_len < 2**31 (bos, at least one token, eos)")
+        if not 0 <= s <= L - 3:
+            raise ValueError("stride must lie in [0, max_len - 3]: every window adds at least one new token")
+        return L, s
+
+    def window_rows(self, rows, max_len: int, stride: int = 0, framed: bool = True):
+        """Cut token rows into overlapping rows of `max_len`, on the GPU.  `rows` as `decode_batch` takes them; `framed=True`:
+        each row is an encode result and loses its first and last entry first, `False`: bare bodies.  With room = max_len - 2
+        and step = room - stride, window j of a body is [bos] + body[j*step : j*step + room] + [eos], padded to max_len; a body
+        that fits makes one window, the reference's own row (tokenize.py:141-152), and the last window is shorter, not shifted
+        back.  Returns numpy arrays: input_ids [W, L], attention_mask [W, L] (ids != pad), doc [W] (the source row), start [W]
+        (the window's first body position), n_real [W], win_off [N+1] (row r's windows are win_off[r]:win_off[r+1])."""
+        L, s = self._window_rule(max_len, stride)
+        flat, off = self._flat_rows(rows)
+        flat = np.asarray(flat)
+        if flat.dtype != np.int32:
+            if flat.dtype.kind not in "iu":
+                raise TypeError("window_rows() expects integer ids")
+            if flat.size and (int(flat.min()) < -(2 ** 31) or int(flat.max()) >= 2 ** 31):
+                raise ValueError("window_rows() expects ids that fit in int32")
+            flat = flat.astype(np.int32)
+        self._sync_tables()
+        return self._ctx.window_rows(flat, off, L, s, bool(framed))
+
+    def encode_windows(self, texts: Sequence[str], max_len: int, stride: int = 0, word_table: bool = True):
+        """`window_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, cut into windows there, and only the windows come back.  Returns the dict of `window_rows`; window 0 of every
+        text is `encode_batch(texts, max_len=max_len)`'s row.  Single texts only."""
+        L, s = self._window_rule(max_len, stride)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            return self._encode_windows_locked(texts, L, s, word_table, False)
+
+    def encode_windows_to_device(self, texts: Sequence[str], max_len: int, stride: int = 0):
+        """`encode_windows` whose [W, max_len] input_ids / attention_mask STAY in HBM as `handoff.DeviceArray`s
+        (`torch.from_dlpack(x)` is zero-copy, as with `encode_to_device`); doc, start, n_real and win_off are host arrays."""
+        L, s = self._window_rule(max_len, stride)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        with self._batch_lock:
+            return self._encode_windows_locked(texts, L, s, True, True)
+
+    def _encode_windows_locked(self, texts, L, s, word_table, to_device):
+        from .handoff import DeviceArray
+        ctx = self._ctx
+        t, to = _packing.pack_pinned(texts, self, ctx)
+        n = len(to) - 1
+        cap = (int(to[n] - to[0]) if n else 0) + 2 * n                 # a token takes a byte of text at least, plus the frame
+        bufs = []
+
+        def dev(nbytes):
+            d = ctx.alloc(max(int(nbytes), 1) + 64)
+            bufs.append(d)
+            return d
+        try:
+            d_t, d_to = dev(t.nbytes), dev(to.nbytes)
+            if t.nbytes:
+                ctx.h2d(d_t, np.ascontiguousarray(t))
+            ctx.h2d(d_to, np.ascontiguousarray(to))
+            d_ids, d_mask, d_ro, d_wo = dev(4 * cap), dev(4 * cap), dev(8 * (n + 1)), dev(8 * (n + 1))
+            if n:
+                # ragged rows, then the windows right behind them on the context's stream (no synchronisation in between)
+                ctx.encode_device(d_t, d_to, 0, 0, n, 0, _native.GZ_MAX_LEN_NONE | (0 if word_table else _native.GZ_NO_WORD_TABLE), cap,
+                                  d_ids, d_mask, d_row_off=d_ro)
+            else:
+                ctx.h2d(d_ro, np.zeros(1, dtype=np.int64))
+            W = ctx.window_rows_device(d_ids, d_ro, n, L, s, 1, 1, 0, 0, 0, 0, 0, d_wo, 0)
+            ctx.sync()                                                 # (what the encode call deferred is reported here)
+            cells = max(W * L, 1)
+            out = {k: DeviceArray(ctx, ctx.alloc(4 * cells), (W, L)) for k in ("input_ids", "attention_mask")}
+            d_meta = dev(12 * W)
+            ctx.window_rows_device(d_ids, d_ro, n, L, s, 1, 1, out["input_ids"].ptr, out["attention_mask"].ptr, d_meta, d_meta + 4 * W,
+                                   d_meta + 8 * W, d_wo, W)
+            meta = np.empty((3, W), dtype=np.int32)
+            win_off = np.zeros(n + 1, dtype=np.int64)
+            if W:
+                ctx.d2h(meta, d_meta)
+            ctx.d2h(win_off, d_wo)
+            if not to_device:
+                out = {k: v.numpy() for k, v in out.items()}           # (the DeviceArrays go with this frame)
+            out["doc"], out["start"], out["n_real"], out["win_off"] = meta[0], meta[1], meta[2], win_off
+            return out
+        finally:
+            for d in bufs:
+                ctx.free(d)
+
+    @staticmethod
+    def join_windows(result, stride: int):
+        """The bodies back from a window result (numpy only): (flat int32, row_off int64 [N+1]), body r =
+        flat[row_off[r]:row_off[r+1]].  Window 0 gives its whole chunk, every later window its chunk without the first
+        `stride` tokens, which the window before it holds already.  The same selection stitches per-token model outputs."""
+        ids, n_real, win_off = np.asarray(result["input_ids"]), np.asarray(result["n_real"]), np.asarray(result["win_off"])
+        W, s = len(n_real), int(stride)
+        first = np.zeros(W, dtype=bool)
+        first[win_off[:-1][win_off[:-1] < W]] = True
+        lo = np.where(first, 1, 1 + s)[:, None]                        # column of the window's first NEW token (column 0 is bos)
+        cols = np.arange(ids.shape[1] if ids.ndim == 2 else 0)[None, :]
+        keep = (cols >= lo) & (cols <= (n_real - 2)[:, None])          # the chunk is columns 1 .. n_real - 2
+        new = keep.sum(axis=1)
+        row_off = np.zeros(len(win_off), dtype=np.int64)
+        per_win = np.zeros(W + 1, dtype=np.int64)
+        np.cumsum(new, out=per_win[1:])
+        row_off[:] = per_win[win_off]
+        return ids[keep].astype(np.int32, copy=False), row_off
 
     @staticmethod
     def _shape(r, n):

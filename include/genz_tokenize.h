@@ -275,6 +275,44 @@ int  gz_decode_batch(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, in
 int  gz_decode_batch_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, const uint8_t *unk,
                             int32_t unk_len, uint8_t *out_dev, int64_t capacity, int64_t *out_off_dev, int64_t *total_host);
 
+/* ---- overlapping max_len windows for long documents ----------------------------------------------------------------
+ * Rows and masks of the reference are made by tokenize.py:141-152: a document longer than max_len keeps token[:max_len-1] + [eos]
+ * and loses the rest, a shorter one is padded (:141-146); attention_mask is ids != pad (:148-152).  These calls keep the rest: they cut ragged rows -- what an encode call
+ * with GZ_MAX_LEN_NONE leaves, or bare token lists -- into rows of max_len that overlap by `stride` tokens, each framed and
+ * padded like a document.  Single texts only.  With L = max_len >= 3, 0 <= stride <= L - 3, room = L - 2, step = room - stride
+ * and body = row r without its first skip_front and last skip_back entries (T = max(len - skip_front - skip_back, 0) tokens):
+ *     n_win   = 1 if T <= room else 1 + ceil((T - room) / step)
+ *     window j: start = j * step, chunk = body[start : min(start + room, T)]
+ *     row     = [bos] + chunk + [eos] + [pad] * (room - len(chunk)),  n_real = len(chunk) + 2,  mask = (row != pad)
+ *   The last window is shorter, not shifted back.  bos / eos / pad are the context's current special ids (gz_table_info).
+ *   Window 0 is the reference's own padded / truncated row; chunk_0 ++ chunk_1[stride:] ++ ... is the body; every later window
+ *   adds at least one token.
+ *   skip_front = skip_back = 1: rows of an encode call (their frame is dropped); 0: bare bodies.  Each is 0 or 1; rows are
+ *   shorter than 2^31 tokens.
+ *   ids / row_off          packed int32 rows as gz_decode_batch takes them: row r = ids[row_off[r] .. row_off[r+1])
+ *   input_ids, attention_mask  [W, max_len] int32;  win_doc / win_start / win_n_real  [W] int32: the source row, `start`, n_real
+ *   win_off [n_rows+1]     int64: row r's windows are win_off[r] .. win_off[r+1]; win_off[n_rows] = W
+ *   *total_host = W on GZ_OK and on GZ_E_CAPACITY.  input_ids == NULL sizes only (win_off and *total_host are filled).  When
+ *   W > capacity_windows the call returns GZ_E_CAPACITY: win_off is valid and nothing is written to the other outputs.
+ *   attention_mask, win_doc, win_start, win_n_real may each be NULL.  A max_len below 3 or a stride outside [0, max_len - 3] is
+ *   GZ_E_INVALID.
+ * gz_window_rows_device: every pointer but total_host is a DEVICE pointer; as in every *_device entry point the offsets are
+ *   ABSOLUTE from the base pointer and row_off_dev[0] need not be 0.  Ordering: both passes run on the context's stream, which
+ *   every stream an encode call forks has rejoined by the time that call returns -- a gz_encode_batch_device enqueued just
+ *   before on the same context (ragged layout, no gz_sync in between) has written ids_dev / row_off_dev before they are read
+ *   here, as with gz_decode_batch_device.  The call returns when the windows are complete; an error the encode call deferred
+ *   (GZ_E_CAPACITY) is still reported by gz_sync, and rows of such a call must not be windowed.
+ * gz_window_rows: host pointers; the rows go up through the library's pinned staging, the device form runs, only win_off and
+ *   the windows come back. */
+int  gz_window_rows(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows,
+                    int32_t max_len, int32_t stride, int32_t skip_front, int32_t skip_back,
+                    int32_t *input_ids, int32_t *attention_mask, int32_t *win_doc, int32_t *win_start,
+                    int32_t *win_n_real, int64_t *win_off, int64_t capacity_windows, int64_t *total_host);
+int  gz_window_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                           int32_t max_len, int32_t stride, int32_t skip_front, int32_t skip_back,
+                           int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *win_doc_dev, int32_t *win_start_dev,
+                           int32_t *win_n_real_dev, int64_t *win_off_dev, int64_t capacity_windows, int64_t *total_host);
+
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
  *   GZ_PP_UNICODE  convert_unicode      preprocess.py:16-36   base letter + combining tone mark -> precomposed letter
