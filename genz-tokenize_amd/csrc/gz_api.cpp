@@ -156,6 +156,7 @@ struct gz_ctx {
     bool dec_unk_set = false;
     DBuf t_dec_entries, t_dec_bytes, w_dec_ids, w_dec_roff, w_dec_rb, w_dec_ooff, w_dec_out;
     DBuf w_win_cnt, w_win_ids, w_win_roff, w_win_off, w_win_out, w_win_mask, w_win_meta;               // overlapping windows (gz_window_rows*)
+    DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol, w_pk_dlen, w_pk_roff, w_pk_ids, w_pk_inoff, w_pk_out[4];   // packed rows (gz_pack_rows*)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_pp_in, w_pp_inoff, w_ppctl, w_pplen32, w_pplb;      // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
     // host path with copies overlapped (gz_encode_batch_csr): copy-in / copy-out streams, per-sub-batch events and buffers
@@ -1044,6 +1045,8 @@ try {
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_pp_in, &c->w_pp_inoff, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_ids, &c->w_dec_roff, &c->w_dec_rb, &c->w_dec_ooff, &c->w_dec_out}) release(*b);
     for (DBuf* b : {&c->w_win_cnt, &c->w_win_ids, &c->w_win_roff, &c->w_win_off, &c->w_win_out, &c->w_win_mask, &c->w_win_meta}) release(*b);
+    for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol, &c->w_pk_dlen, &c->w_pk_roff, &c->w_pk_ids,
+                    &c->w_pk_inoff, &c->w_pk_out[0], &c->w_pk_out[1], &c->w_pk_out[2], &c->w_pk_out[3]}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
     for (DBuf* b : {&c->t_merges, &c->t_symids, &c->t_bmp, &c->t_astral, &c->t_struct, &c->t_words2, &c->w_text, &c->w_toff, &c->w_pair,
@@ -2139,6 +2142,129 @@ try {
     if (win_doc && (rc = copy_out(c, win_doc, meta, (size_t)total * 4, c->stream))) return rc;
     if (win_start && (rc = copy_out(c, win_start, meta + total, (size_t)total * 4, c->stream))) return rc;
     if (win_n_real && (rc = copy_out(c, win_n_real, meta + 2 * total, (size_t)total * 4, c->stream))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+// ---- short documents packed into rows of max_len ------------------------------------------------------------------------
+namespace {
+// The maps of a batch on the context's stream, behind whatever it holds: doc_len, seg_off, the row heads in pack_off, doc_row, doc_col.
+// A map the caller does not take lives in the context's workspace (pack_off is the caller's).  A gets the pointers the fill pass
+// needs; *total = R, read back from the device.  fill: the fill pass goes right behind the maps -- it takes R from device memory,
+// writes nothing when R exceeds A.capacity, and writes doc_col in place of the col pass -- so the host waits once, for everything.
+int pack_maps_locked(gz_ctx* c, GzPackArgs& A, int64_t* total, bool fill)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = A.n_rows;
+    int rc;
+    if (!A.seg_off) { if ((rc = ensure(c, c->w_pk_seg, (size_t)(n + 1) * 8))) return rc; A.seg_off = (int64_t*)c->w_pk_seg.p; }
+    if (!A.doc_row) { if ((rc = ensure(c, c->w_pk_drow, (size_t)(n + 1) * 4))) return rc; A.doc_row = (int32_t*)c->w_pk_drow.p; }
+    if (!A.doc_col) { if ((rc = ensure(c, c->w_pk_dcol, (size_t)(n + 1) * 4))) return rc; A.doc_col = (int32_t*)c->w_pk_dcol.p; }
+    const size_t tiles = (size_t)gz_pack_tiles(n), groups = (size_t)gz_pack_groups(n), K = (size_t)gz_pack_entries(A.max_len);
+    if ((rc = ensure(c, c->w_pk_len, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_jc, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_nxt, (size_t)(n + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->w_pk_jc2, (groups * K + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_tile, (tiles + 1) * 8))) return rc;
+    A.len64 = (int64_t*)c->w_pk_len.p; A.jc = (int32_t*)c->w_pk_jc.p; A.nxt = (int32_t*)c->w_pk_nxt.p; A.jc2 = (int32_t*)c->w_pk_jc2.p; A.tile = (int32_t*)c->w_pk_tile.p;
+    A.total = (int64_t*)c->w_pk_tile.p + tiles;
+    A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id; A.pad_id = c->dev.pad_id;
+    *total = 0;
+    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
+    *h_total = 0;
+    if (n > 0) {
+        gz_launch_pack_maps(A, !fill, c->stream);
+        if (fill) gz_launch_pack_fill(A, c->stream);
+        HIPCHK(c, hipMemcpyAsync(h_total, A.total, 8, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPCHK(c, hipMemsetAsync(A.pack_off, 0, 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(A.seg_off, 0, 8, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    *total = *h_total;
+    return GZ_OK;
+}
+
+const char* const kPackRule = "packed rows need max_len >= 3, skips of 0 or 1 and fewer than 2^31 - 4096 documents";
+bool pack_rule_ok(int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back)
+{
+    return max_len >= 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1 && n_rows < INT32_MAX - 4096;
+}
+}  // namespace
+
+int gz_pack_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t skip_front,
+                        int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* segment_ids_dev, int32_t* position_ids_dev,
+                        int32_t* doc_row_dev, int32_t* doc_col_dev, int32_t* doc_len_dev, int64_t* pack_off_dev, int64_t* seg_off_dev,
+                        int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !pack_off_dev || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    std::lock_guard<std::mutex> lk(c->mu);
+    GzPackArgs A{};
+    A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows; A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.doc_row = doc_row_dev; A.doc_col = doc_col_dev; A.doc_len = doc_len_dev; A.pack_off = pack_off_dev; A.seg_off = seg_off_dev;
+    A.capacity = capacity_rows;
+    A.out_ids = input_ids_dev; A.out_mask = attention_mask_dev; A.out_seg = segment_ids_dev; A.out_pos = position_ids_dev;
+    int rc;
+    if ((rc = pack_maps_locked(c, A, total_host, input_ids_dev != nullptr))) return rc;
+    if (!input_ids_dev || *total_host <= capacity_rows) return GZ_OK;
+    gz_launch_pack_col(A, c->stream);                                      // (the fill wrote nothing, doc_col included: the maps are valid all the same)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)*total_host, (long long)capacity_rows);
+} GZ_CATCH(c)
+
+int gz_pack_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back,
+                 int32_t* input_ids, int32_t* attention_mask, int32_t* segment_ids, int32_t* position_ids, int32_t* doc_row, int32_t* doc_col,
+                 int32_t* doc_len, int64_t* pack_off, int64_t* seg_off, int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off || !pack_off || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    const int64_t n_ids = row_off[n_rows] - row_off[0];
+    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(c, GZ_E_INVALID, "bad row offsets");
+    for (int64_t r = 0; r < n_rows; ++r) if (row_off[r + 1] < row_off[r]) return fail(c, GZ_E_INVALID, "row offsets must not decrease");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_pk_ids, (size_t)(n_ids + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->w_pk_inoff, (size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_roff, (size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_dlen, (size_t)(n_rows + 1) * 4))) return rc;
+    if (n_ids && (rc = copy_in(c, c->w_pk_ids.p, ids + row_off[0], (size_t)n_ids * 4, c->stream))) return rc;
+    if ((rc = copy_in(c, c->w_pk_inoff.p, row_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    GzPackArgs A{};
+    A.ids = (const int32_t*)c->w_pk_ids.p - row_off[0]; A.row_off = (const int64_t*)c->w_pk_inoff.p; A.n_rows = n_rows;
+    A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.doc_len = (int32_t*)c->w_pk_dlen.p; A.pack_off = (int64_t*)c->w_pk_roff.p;                  // (the other maps: the workspace's)
+    int64_t total = 0;
+    if ((rc = pack_maps_locked(c, A, &total, false))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, pack_off, A.pack_off, (size_t)(total + 1) * 8, c->stream))) return rc;
+    if (seg_off && (rc = copy_out(c, seg_off, A.seg_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (doc_row && (rc = copy_out(c, doc_row, A.doc_row, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_col && (rc = copy_out(c, doc_col, A.doc_col, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_len && (rc = copy_out(c, doc_len, A.doc_len, (size_t)n_rows * 4, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_rows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)total, (long long)capacity_rows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len;
+    int32_t* const host[4] = {input_ids, attention_mask, segment_ids, position_ids};
+    int32_t* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) { if ((rc = ensure(c, c->w_pk_out[k], cells * 4))) return rc; dev[k] = (int32_t*)c->w_pk_out[k].p; }
+    A.capacity = total;
+    A.out_ids = dev[0]; A.out_mask = dev[1]; A.out_seg = dev[2]; A.out_pos = dev[3];
+    gz_launch_pack_fill(A, c->stream);
+    {
+        HostPool pool(pool_threads(c, cells * 4));
+        for (int k = 0; k < 4; ++k)
+            if (host[k] && (rc = copy_out(c, host[k], dev[k], cells * 4, c->stream, &pool))) return rc;
+    }
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
 } GZ_CATCH(c)

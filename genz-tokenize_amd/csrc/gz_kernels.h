@@ -128,6 +128,31 @@ void gz_launch_window_count(const int64_t* row_off, int64_t n_rows, int32_t room
                             hipStream_t s);
 void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s);
 
+// short documents packed into rows of max_len (gz_packrows.inc).  Maps: doc_len, seg_off (its scan), the row heads row by row
+// (pack_off[0 .. R], R -> *total), doc_row, doc_col.  Fill: the R rows; out_mask, out_seg, out_pos may be null.
+constexpr int GZ_PACK_TILE = 1024;      // documents per tile of the break chain
+constexpr int GZ_PACK_GROUP = 16;       // tiles per group
+struct GzPackArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;     // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); n_rows < 2^31 - 4096
+    int32_t max_len, skip_front, skip_back;
+    int32_t bos_id, eos_id, pad_id;
+    int32_t* doc_row; int32_t* doc_col; int32_t* doc_len;           // [n_rows]; doc_len may be null
+    int64_t* pack_off; int64_t* seg_off;                            // [n_rows + 1] (R + 1 entries of pack_off are written)
+    // workspace of the maps: len64 [n_rows + 1], jc [2 n_rows], nxt [n_rows], jc2 [2 * groups * gz_pack_entries(max_len)], tile [2 * tiles], total [1]
+    int64_t* len64; int32_t* jc; int32_t* nxt; int32_t* jc2; int32_t* tile; int64_t* total;
+    int64_t capacity;                                               // rows the cell arrays hold: the fill writes nothing when *total exceeds it
+    int32_t* out_ids; int32_t* out_mask; int32_t* out_seg; int32_t* out_pos;     // [*total, max_len]
+};
+inline int64_t gz_pack_tiles(int64_t n_rows) { return (n_rows + GZ_PACK_TILE - 1) / GZ_PACK_TILE; }
+inline int64_t gz_pack_groups(int64_t n_rows) { return (gz_pack_tiles(n_rows) + GZ_PACK_GROUP - 1) / GZ_PACK_GROUP; }
+inline int32_t gz_pack_entries(int32_t max_len)                     // where a chain can enter a group: its first max_len / 2 documents
+{
+    return max_len / 2 < GZ_PACK_TILE * GZ_PACK_GROUP ? max_len / 2 : GZ_PACK_TILE * GZ_PACK_GROUP;
+}
+void gz_launch_pack_maps(const GzPackArgs& A, bool with_col /* false: a fill follows and writes doc_col */, hipStream_t s);
+void gz_launch_pack_col(const GzPackArgs& A, hipStream_t s);
+void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s);     // R = *A.total, read on the device
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

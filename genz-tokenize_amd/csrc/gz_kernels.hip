@@ -690,6 +690,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_small.inc"
 #include "gz_decode.inc"
 #include "gz_window.inc"
+#include "gz_packrows.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -759,6 +760,43 @@ void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s)
     const bool wide = A.max_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask)) & 15) == 0;
     if (wide) hipLaunchKernelGGL(gz_window_fill_kernel<4>, grid, block, 0, s, A);
     else hipLaunchKernelGGL(gz_window_fill_kernel<1>, grid, block, 0, s, A);
+}
+
+void gz_launch_pack_maps(const GzPackArgs& A, bool with_col, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    const int32_t n = (int32_t)A.n_rows, L = A.max_len, K = gz_pack_entries(L);
+    const unsigned per_doc = (unsigned)((A.n_rows + 255) / 256), tiles = (unsigned)gz_pack_tiles(A.n_rows), groups = (unsigned)gz_pack_groups(A.n_rows);
+    const unsigned hop_blocks = (unsigned)((K + 255) / 256);
+    int2* const jc = reinterpret_cast<int2*>(A.jc);
+    int2* const jc2 = reinterpret_cast<int2*>(A.jc2);
+    int2* const tile = reinterpret_cast<int2*>(A.tile);
+    hipLaunchKernelGGL(gz_pack_len_kernel, dim3(per_doc), dim3(256), 0, s, A.row_off, n, L - 2, A.skip_front + A.skip_back, A.len64, A.doc_len);
+    launch_scan64((const int64_t*)A.len64, A.n_rows, A.seg_off, s);
+    hipLaunchKernelGGL(gz_pack_tile_kernel, dim3(tiles), dim3(PK_B), 0, s, (const int64_t*)A.seg_off, n, L, jc, A.nxt);
+    hipLaunchKernelGGL(gz_pack_hop_kernel, dim3(groups * hop_blocks), dim3(256), 0, s, (const int2*)jc, n, K, (int32_t)hop_blocks, jc2);
+    hipLaunchKernelGGL(gz_pack_down_kernel, dim3((groups + 255) / 256), dim3(256), 0, s, (const int2*)jc, (const int2*)jc2, n, K,
+                       (int32_t)tiles, tile, A.pack_off, A.total);
+    hipLaunchKernelGGL(gz_pack_mark_kernel, dim3(tiles), dim3(PK_B), 0, s, (const int32_t*)A.nxt, n, (const int2*)tile, A.pack_off, A.doc_row);
+    if (with_col) gz_launch_pack_col(A, s);
+}
+
+void gz_launch_pack_col(const GzPackArgs& A, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    hipLaunchKernelGGL(gz_pack_col_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, (const int64_t*)A.seg_off,
+                       (const int64_t*)A.pack_off, (const int32_t*)A.doc_row, (int32_t)A.n_rows, A.doc_col);
+}
+
+void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    const dim3 grid((unsigned)((A.n_rows + PK_FD - 1) / PK_FD)), block(PK_FD);
+    // 16 bytes a thread where every row starts on a 16-byte boundary; one cell a thread otherwise
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask) | reinterpret_cast<uintptr_t>(A.out_seg) |
+                           reinterpret_cast<uintptr_t>(A.out_pos);
+    if (A.max_len % 4 == 0 && (bits & 15) == 0) hipLaunchKernelGGL(gz_pack_fill_kernel<4>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(gz_pack_fill_kernel<1>, grid, block, 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

@@ -47,6 +47,7 @@ SYMBOLS = [
     "gz_bm25_similar", "gz_bm25_prefix", "gz_bm25_term_bytes",
     "gz_bm25_search_groups", "gz_bm25_search_groups_device", "gz_bm25_match_count_groups",
     "gz_window_rows", "gz_window_rows_device",
+    "gz_pack_rows", "gz_pack_rows_device",
 ]
 
 _lib = None
@@ -103,6 +104,9 @@ def load_library():
     win = [vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, P(i64)]
     L.gz_window_rows.argtypes = win
     L.gz_window_rows_device.argtypes = win
+    pk = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)]
+    L.gz_pack_rows.argtypes = pk
+    L.gz_pack_rows_device.argtypes = pk
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -529,6 +533,41 @@ class Context:
                                             skip_back, vp(d_input_ids) if d_input_ids else None, vp(d_mask) if d_mask else None,
                                             vp(d_doc) if d_doc else None, vp(d_start) if d_start else None,
                                             vp(d_n_real) if d_n_real else None, vp(d_win_off), capacity, C.byref(total))
+        if rc:
+            e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
+            e.total = total.value
+            raise e
+        return total.value
+
+    # ---- short documents packed into rows of max_len ------------------------------------------------------
+    def pack_rows(self, ids: np.ndarray, row_off: np.ndarray, max_len: int, framed: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict(input_ids, attention_mask, segment_ids, position_ids [R, L],
+        doc_row, doc_col, doc_len [n], row_off int64 [R+1], seg_off int64 [n+1]) (gz_pack_rows: a sizing call, then the rows)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, L, skip = len(row_off) - 1, int(max_len), 1 if framed else 0
+        maps = dict(doc_row=np.empty(n, dtype=np.int32), doc_col=np.empty(n, dtype=np.int32), doc_len=np.empty(n, dtype=np.int32),
+                    row_off=np.zeros(n + 1, dtype=np.int64), seg_off=np.zeros(n + 1, dtype=np.int64))
+        total = C.c_int64()
+        head = (self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), n, L, skip, skip)
+        tail = tuple(_ptr(maps[k]) for k in ("doc_row", "doc_col", "doc_len", "row_off", "seg_off"))
+        self._check(self.lib.gz_pack_rows(*head, None, None, None, None, *tail, 0, C.byref(total)))
+        R = total.value
+        out = {k: np.empty((R, L), dtype=np.int32) for k in ("input_ids", "attention_mask", "segment_ids", "position_ids")}
+        if R:
+            self._check(self.lib.gz_pack_rows(*head, *[_ptr(v) for v in out.values()], *tail, R, C.byref(total)))
+        out.update(maps)
+        out["row_off"] = maps["row_off"][:R + 1].copy()
+        return out
+
+    def pack_rows_device(self, d_ids, d_row_off, n_rows, max_len, skip_front, skip_back, d_input_ids, d_mask, d_seg, d_pos, d_doc_row,
+                         d_doc_col, d_doc_len, d_pack_off, d_seg_off, capacity) -> int:
+        """gz_pack_rows_device: returns R.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = R."""
+        vp = C.c_void_p
+        opt = [vp(d) if d else None for d in (d_input_ids, d_mask, d_seg, d_pos, d_doc_row, d_doc_col, d_doc_len)]
+        total = C.c_int64()
+        rc = self.lib.gz_pack_rows_device(self.handle, vp(d_ids) if d_ids else None, vp(d_row_off), n_rows, max_len, skip_front, skip_back,
+                                          *opt, vp(d_pack_off), vp(d_seg_off) if d_seg_off else None, capacity, C.byref(total))
         if rc:
             e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
             e.total = total.value

@@ -562,6 +562,117 @@ class Tokenize(object):
         row_off[:] = per_win[win_off]
         return ids[keep].astype(np.int32, copy=False), row_off
 
+    # ---- short documents packed into rows of max_len ("sequence packing") -------------------------------------------
+    PACK_CELLS = ("input_ids", "attention_mask", "segment_ids", "position_ids")
+    PACK_MAPS = ("doc_row", "doc_col", "doc_len")
+
+    @staticmethod
+    def _pack_rule(max_len):
+        """L of a pack call, or the refusal: L >= 3 (bos, a token, eos)."""
+        if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)):
+            raise TypeError("max_len must be an int")
+        L = int(max_len)
+        if L < 3 or L >= 2 ** 31:
+            raise ValueError("packed rows need 3 <= max_len < 2**31 (bos, at least one token, eos)")
+        return L
+
+    def pack_rows(self, rows, max_len: int, framed: bool = True):
+        """Lay token rows back to back into rows of `max_len`, on the GPU.  `rows` as `window_rows` takes them (`framed=True`:
+        each row is an encode result and loses its first and last entry first, `False`: bare bodies).  Document r becomes
+        [bos] + body[:max_len-2] + [eos] -- the reference's own row without its padding (tokenize.py:141-146) -- and goes behind
+        the documents before it, or opens the next row when it does not fit (next-fit: the order is kept).  Returns numpy
+        arrays: input_ids, attention_mask (ids != pad), segment_ids (1 + the document's index within its row; 0 in the padding
+        tail only), position_ids (column - doc_col; 0 in the tail), all [R, L]; doc_row, doc_col, doc_len [N]; row_off int64
+        [R+1] (packed row i holds documents row_off[i]:row_off[i+1]); seg_off int64 [N+1] (the scan of doc_len: the cumulative
+        sequence lengths variable-length attention kernels take)."""
+        L = self._pack_rule(max_len)
+        flat, off = self._flat_rows(rows)
+        flat = np.asarray(flat)
+        if flat.dtype != np.int32:
+            if flat.dtype.kind not in "iu":
+                raise TypeError("pack_rows() expects integer ids")
+            if flat.size and (int(flat.min()) < -(2 ** 31) or int(flat.max()) >= 2 ** 31):
+                raise ValueError("pack_rows() expects ids that fit in int32")
+            flat = flat.astype(np.int32)
+        self._sync_tables()
+        return self._ctx.pack_rows(flat, off, L, bool(framed))
+
+    def encode_packs(self, texts: Sequence[str], max_len: int, word_table: bool = True):
+        """`pack_rows` over the texts: they are encoded without a length limit on the device, packed there, and only the packed
+        rows and the maps come back.  Segment r of the result is `tok(texts[r], max_len=max_len)["input_ids"]` without its
+        padding.  Single texts only."""
+        L = self._pack_rule(max_len)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            return self._encode_packs_locked(texts, L, word_table, False)
+
+    def encode_packs_to_device(self, texts: Sequence[str], max_len: int):
+        """`encode_packs` whose four [R, max_len] arrays STAY in HBM as `handoff.DeviceArray`s (`torch.from_dlpack(x)` is
+        zero-copy, as with `encode_to_device`); doc_row, doc_col, doc_len, row_off and seg_off are host arrays."""
+        L = self._pack_rule(max_len)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        with self._batch_lock:
+            return self._encode_packs_locked(texts, L, True, True)
+
+    def _encode_packs_locked(self, texts, L, word_table, to_device):
+        from .handoff import DeviceArray
+        ctx = self._ctx
+        t, to = _packing.pack_pinned(texts, self, ctx)
+        n = len(to) - 1
+        cap = (int(to[n] - to[0]) if n else 0) + 2 * n                 # a token takes a byte of text at least, plus the frame
+        bufs = []
+
+        def dev(nbytes):
+            d = ctx.alloc(max(int(nbytes), 1) + 64)
+            bufs.append(d)
+            return d
+        try:
+            d_t, d_to = dev(t.nbytes), dev(to.nbytes)
+            if t.nbytes:
+                ctx.h2d(d_t, np.ascontiguousarray(t))
+            ctx.h2d(d_to, np.ascontiguousarray(to))
+            d_ids, d_mask, d_ro = dev(4 * cap), dev(4 * cap), dev(8 * (n + 1))
+            d_maps, d_po, d_so = dev(12 * n), dev(8 * (n + 1)), dev(8 * (n + 1))
+            if n:
+                # ragged rows, then the packing right behind them on the context's stream (no synchronisation in between)
+                ctx.encode_device(d_t, d_to, 0, 0, n, 0, _native.GZ_MAX_LEN_NONE | (0 if word_table else _native.GZ_NO_WORD_TABLE), cap,
+                                  d_ids, d_mask, d_row_off=d_ro)
+            else:
+                ctx.h2d(d_ro, np.zeros(1, dtype=np.int64))
+            maps = (d_maps, d_maps + 4 * n, d_maps + 8 * n) if n else (0, 0, 0)
+            R = ctx.pack_rows_device(d_ids, d_ro, n, L, 1, 1, 0, 0, 0, 0, *maps, d_po, d_so, 0)
+            ctx.sync()                                                 # (what the encode call deferred is reported here)
+            cells = max(R * L, 1)
+            out = {k: DeviceArray(ctx, ctx.alloc(4 * cells), (R, L)) for k in self.PACK_CELLS}
+            ctx.pack_rows_device(d_ids, d_ro, n, L, 1, 1, *[out[k].ptr for k in self.PACK_CELLS], *maps, d_po, d_so, R)
+            meta = np.empty((3, n), dtype=np.int32)
+            row_off, seg_off = np.zeros(R + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+            if n:
+                ctx.d2h(meta, d_maps)
+            ctx.d2h(row_off, d_po)
+            ctx.d2h(seg_off, d_so)
+            if not to_device:
+                out = {k: v.numpy() for k, v in out.items()}           # (the DeviceArrays go with this frame)
+            out["doc_row"], out["doc_col"], out["doc_len"], out["row_off"], out["seg_off"] = meta[0], meta[1], meta[2], row_off, seg_off
+            return out
+        finally:
+            for d in bufs:
+                ctx.free(d)
+
+    @staticmethod
+    def unpack_rows(result):
+        """The segments back from a pack result (numpy only): (flat int32, row_off int64 [N+1]), segment r =
+        flat[row_off[r]:row_off[r+1]] = [bos] + body + [eos].  Segments lie in document order in the packed rows and the tail
+        of a row has segment id 0, so one selection does it; the same selection un-packs per-token model outputs."""
+        ids, seg = np.asarray(result["input_ids"]), np.asarray(result["segment_ids"])
+        return ids[seg != 0].astype(np.int32, copy=False), np.asarray(result["seg_off"], dtype=np.int64).copy()
+
     @staticmethod
     def _shape(r, n):
         if r["dense"]:

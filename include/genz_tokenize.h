@@ -313,6 +313,45 @@ int  gz_window_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *r
                            int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *win_doc_dev, int32_t *win_start_dev,
                            int32_t *win_n_real_dev, int64_t *win_off_dev, int64_t capacity_windows, int64_t *total_host);
 
+/* ---- short documents packed back to back into rows of max_len ("sequence packing") ------------------------------------
+ * A dense [N, max_len] batch of short documents is mostly padding.  These calls lay whole documents back to back into rows of
+ * max_len instead and say, cell by cell, which document a cell belongs to and where in it, so that attention can be made
+ * block-diagonal.  Single texts only.  With L = max_len >= 3 and body = row r without its first skip_front and last skip_back
+ * entries (T = max(len - skip_front - skip_back, 0) tokens; the skips are 0 or 1 as in gz_window_rows):
+ *     seg_r = [bos] + body[:min(T, L-2)] + [eos],   len_r = min(T, L-2) + 2      (2 <= len_r <= L)
+ *   seg_r is the reference's own row for that text without its padding (tokenize.py:141-146): a document longer than a row is
+ *   cut the reference's way (gz_window_rows keeps the rest; the two are not combined).
+ *   Next-fit, order kept: used = 0, row = 0; for r = 0 .. n_rows-1: if used + len_r > L then row += 1, used = 0;
+ *   doc_row[r] = row, doc_col[r] = used, used += len_r.  R = row + 1 (0 when n_rows = 0).  A document that fills its row exactly fits.
+ *   input_ids [R, L]      the segments of a row back to back, then the pad id
+ *   attention_mask [R, L] input_ids != pad (tokenize.py:148-152: a real token equal to the pad id gets 0)
+ *   segment_ids [R, L]    1 + the document's index within its row, by position; 0 in the padding tail only
+ *   position_ids [R, L]   column - doc_col inside a segment, 0 in the tail
+ *   doc_row, doc_col, doc_len [n_rows] int32
+ *   pack_off              int64: packed row i holds documents pack_off[i] .. pack_off[i+1].  R + 1 entries are written; the array
+ *                         must hold n_rows + 1 (R <= n_rows, and R is not known before the call)
+ *   seg_off [n_rows+1]    int64: the exclusive scan of doc_len (the cumulative sequence lengths of variable-length attention)
+ *   *total_host = R on GZ_OK and on GZ_E_CAPACITY.  input_ids == NULL sizes only: the five maps and *total_host are filled.  When
+ *   R > capacity_rows the call returns GZ_E_CAPACITY: the maps are valid and nothing is written to the four cell arrays.
+ *   attention_mask, segment_ids, position_ids, doc_row, doc_col, doc_len and seg_off may each be NULL.  max_len < 3, a skip
+ *   outside {0, 1} or n_rows >= 2^31 - 4096 is GZ_E_INVALID.
+ * gz_pack_rows_device: every pointer but total_host is a DEVICE pointer; offsets are ABSOLUTE from the base pointer and
+ *   row_off_dev[0] need not be 0.  Ordering: as gz_window_rows_device -- all passes run on the context's stream, behind a
+ *   gz_encode_batch_device (ragged layout) enqueued just before with no gz_sync in between.  The call returns when the rows
+ *   are complete.
+ * gz_pack_rows: host pointers; the rows go up through the library's pinned staging, the device form runs, the maps and the
+ *   packed rows come back. */
+int  gz_pack_rows(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows,
+                  int32_t max_len, int32_t skip_front, int32_t skip_back,
+                  int32_t *input_ids, int32_t *attention_mask, int32_t *segment_ids, int32_t *position_ids,
+                  int32_t *doc_row, int32_t *doc_col, int32_t *doc_len, int64_t *pack_off, int64_t *seg_off,
+                  int64_t capacity_rows, int64_t *total_host);
+int  gz_pack_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                         int32_t max_len, int32_t skip_front, int32_t skip_back,
+                         int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *segment_ids_dev, int32_t *position_ids_dev,
+                         int32_t *doc_row_dev, int32_t *doc_col_dev, int32_t *doc_len_dev, int64_t *pack_off_dev, int64_t *seg_off_dev,
+                         int64_t capacity_rows, int64_t *total_host);
+
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
  *   GZ_PP_UNICODE  convert_unicode      preprocess.py:16-36   base letter + combining tone mark -> precomposed letter
