@@ -154,9 +154,11 @@ struct gz_ctx {
     size_t dec_bytes_len = 0;
     std::string dec_unk;
     bool dec_unk_set = false;
+    DBuf t_dec_cont;                                                                                    // continuation bitmap of the decoder snapshot (gz_mask_rows*)
     DBuf t_dec_entries, t_dec_bytes, w_dec_ids, w_dec_roff, w_dec_rb, w_dec_ooff, w_dec_out;
     DBuf w_win_cnt, w_win_ids, w_win_roff, w_win_off, w_win_out, w_win_mask, w_win_meta;               // overlapping windows (gz_window_rows*)
     DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol, w_pk_dlen, w_pk_roff, w_pk_ids, w_pk_inoff, w_pk_out[4];   // packed rows (gz_pack_rows*)
+    DBuf w_mk_ids, w_mk_out, w_mk_lab, w_mk_cnt;                                                        // masked-LM rows (gz_mask_rows)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_pp_in, w_pp_inoff, w_ppctl, w_pplen32, w_pplb;      // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
     // host path with copies overlapped (gz_encode_batch_csr): copy-in / copy-out streams, per-sub-batch events and buffers
@@ -1043,10 +1045,11 @@ try {
     release(c->w_pick); release(c->w_rowoff32);
     for (auto& t2 : c->w_tiny) for (auto& t : t2) release(t);
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_pp_in, &c->w_pp_inoff, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
-    for (DBuf* b : {&c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_ids, &c->w_dec_roff, &c->w_dec_rb, &c->w_dec_ooff, &c->w_dec_out}) release(*b);
+    for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_ids, &c->w_dec_roff, &c->w_dec_rb, &c->w_dec_ooff, &c->w_dec_out}) release(*b);
     for (DBuf* b : {&c->w_win_cnt, &c->w_win_ids, &c->w_win_roff, &c->w_win_off, &c->w_win_out, &c->w_win_mask, &c->w_win_meta}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol, &c->w_pk_dlen, &c->w_pk_roff, &c->w_pk_ids,
                     &c->w_pk_inoff, &c->w_pk_out[0], &c->w_pk_out[1], &c->w_pk_out[2], &c->w_pk_out[3]}) release(*b);
+    for (DBuf* b : {&c->w_mk_ids, &c->w_mk_out, &c->w_mk_lab, &c->w_mk_cnt}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
     for (DBuf* b : {&c->t_merges, &c->t_symids, &c->t_bmp, &c->t_astral, &c->t_struct, &c->t_words2, &c->w_text, &c->w_toff, &c->w_pair,
@@ -1980,11 +1983,16 @@ try {
         bytes += w;
     }
     ent[(size_t)n_ids] = GzDecEntry{GZ_DEC_INLINE, {0u, 0u, 0u}};                  // (the unk string: set per call, dec_set_unk)
+    std::vector<uint32_t> cont((size_t)n_ids / 32 + 1, 0u);                       // which ids continue a word: one bit each (gz_mask_rows*)
+    for (int32_t id = 0; id < n_ids; ++id)
+        if (ent[(size_t)id].len_flags != GZ_DEC_ABSENT && (ent[(size_t)id].len_flags & GZ_DEC_ENDS_ATAT)) cont[(size_t)id >> 5] |= 1u << (id & 31);
     int rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure(c, c->t_dec_entries, ent.size() * sizeof(GzDecEntry)))) return rc;
     if ((rc = ensure(c, c->t_dec_bytes, bytes.size() + GZ_DEC_UNK_MAX + 16))) return rc;
+    if ((rc = ensure(c, c->t_dec_cont, cont.size() * 4))) return rc;
     if ((rc = copy_in(c, c->t_dec_entries.p, ent.data(), ent.size() * sizeof(GzDecEntry), c->stream))) return rc;
+    if ((rc = copy_in(c, c->t_dec_cont.p, cont.data(), cont.size() * 4, c->stream))) return rc;
     if (!bytes.empty() && (rc = copy_in(c, c->t_dec_bytes.p, bytes.data(), bytes.size(), c->stream))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->dec_n_ids = n_ids;
@@ -2265,6 +2273,102 @@ try {
         for (int k = 0; k < 4; ++k)
             if (host[k] && (rc = copy_out(c, host[k], dev[k], cells * 4, c->stream, &pool))) return rc;
     }
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+// ---- masked-LM inputs and labels over dense rows -------------------------------------------------------------------------
+namespace {
+struct MaskRule {
+    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_sel, t1, t2;
+    int32_t rand_lo, rand_hi, mask_id, whole_word, ignore_index;
+};
+const char* const kMaskRule = "masked rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, thresholds in "
+                              "[0, 2^32] with t1 <= t2, rand_lo < rand_hi and whole_word 0 or 1";
+bool mask_rule_ok(const MaskRule& M)
+{
+    constexpr uint64_t one = 1ull << 32;
+    if (M.row_len < 1 || M.n_rows < 0 || M.row_base < 0) return false;
+    const unsigned __int128 cells = ((unsigned __int128)M.row_base + (unsigned __int128)M.n_rows) * (unsigned __int128)M.row_len;
+    if (cells >> 63) return false;
+    return M.t_sel <= one && M.t1 <= one && M.t2 <= one && M.t1 <= M.t2 && M.rand_lo < M.rand_hi && (M.whole_word == 0 || M.whole_word == 1);
+}
+// the cell arrays and the counts are pairwise disjoint (the heads are read from neighbours' ORIGINAL ids); n_rows * row_len > 0
+bool mask_buffers_ok(const MaskRule& M, const int32_t* ids, const int32_t* out_ids, const int32_t* labels, const int32_t* n_chosen)
+{
+    if (!ids || !out_ids || !labels) return false;
+    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
+    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u;
+    const uintptr_t p[4] = {(uintptr_t)ids, (uintptr_t)out_ids, (uintptr_t)labels, (uintptr_t)n_chosen};
+    const uintptr_t n[4] = {cells, cells, cells, n_chosen ? (uintptr_t)M.n_rows * 4u : 0u};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (n[a] && n[b] && (p[a] >= p[b] ? p[a] - p[b] < n[b] : p[b] - p[a] < n[a])) return false;       // (differences: no end address to wrap)
+    return true;
+}
+// the one launch on the context's stream, behind whatever it holds
+void mask_launch(gz_ctx* c, const MaskRule& M, const int32_t* ids_dev, int32_t* out_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
+{
+    GzMaskArgs A{};
+    A.ids = ids_dev; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
+    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
+    A.t_sel = M.t_sel; A.t1 = M.t1; A.t2 = M.t2;
+    A.rand_lo = M.rand_lo; A.rand_span = (uint32_t)M.rand_hi - (uint32_t)M.rand_lo;
+    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word;
+    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
+    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
+    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
+    A.out_ids = out_dev; A.labels = labels_dev; A.n_chosen = n_chosen_dev;
+    gz_launch_mask(A, c->stream);
+}
+}  // namespace
+
+int gz_mask_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel,
+                        uint64_t t1, uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index,
+                        int32_t* input_ids_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
+    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
+    if (n_rows > 0 && !mask_buffers_ok(M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev))
+        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    mask_launch(c, M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_mask_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel, uint64_t t1,
+                 uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t* input_ids,
+                 int32_t* labels, int32_t* n_chosen)
+try {
+    if (!c) return GZ_E_INVALID;
+    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
+    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
+    if (n_rows > 0 && !mask_buffers_ok(M, ids, input_ids, labels, n_chosen))
+        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)n_rows * (size_t)row_len;
+    int rc;
+    if ((rc = ensure(c, c->w_mk_ids, cells * 4))) return rc;
+    if ((rc = ensure(c, c->w_mk_out, cells * 4))) return rc;
+    if ((rc = ensure(c, c->w_mk_lab, cells * 4))) return rc;
+    if (n_chosen && (rc = ensure(c, c->w_mk_cnt, (size_t)n_rows * 4))) return rc;
+    if ((rc = copy_in(c, c->w_mk_ids.p, ids, cells * 4, c->stream))) return rc;
+    mask_launch(c, M, (const int32_t*)c->w_mk_ids.p, (int32_t*)c->w_mk_out.p, (int32_t*)c->w_mk_lab.p, n_chosen ? (int32_t*)c->w_mk_cnt.p : nullptr);
+    {
+        HostPool pool(pool_threads(c, cells * 4));
+        if ((rc = copy_out(c, input_ids, c->w_mk_out.p, cells * 4, c->stream, &pool))) return rc;
+        if ((rc = copy_out(c, labels, c->w_mk_lab.p, cells * 4, c->stream, &pool))) return rc;
+    }
+    if (n_chosen && (rc = copy_out(c, n_chosen, c->w_mk_cnt.p, (size_t)n_rows * 4, c->stream))) return rc;
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
 } GZ_CATCH(c)

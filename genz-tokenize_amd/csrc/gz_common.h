@@ -80,6 +80,7 @@ struct GzOptions {
     int32_t dense_csr = 1;            // 1: a large dense single-text host call brings only the rows' real entries over the bus and pads them on the host; 0: the dense rows cross
     int32_t host_hints = 0;           // fresh output arrays of a large host call: bit 0 MADV_HUGEPAGE on them, bit 1 MADV_POPULATE_WRITE per piece before it is written
                                       // (0: neither -- on the GPU box 16 threads fill 2 GB of fresh numpy arrays in 27 ms without them, 29-31 ms with)
+    int32_t mask_lds = 1;             // masked-LM rows: 1 the continuation bitmap is staged in LDS by every workgroup (when it fits); 0: read from memory
     int32_t inject_bad_alloc = 0;     // test hook: k > 0 makes the k-th allocation site reached from now on throw std::bad_alloc (counts down to 0)
     int32_t bm25_hash_bits = 0;       // BM25 index build: k > 0 keeps only the low k bits of every word's 64-bit hash (forced collisions: results
                                       // must not change); 0 the whole hash

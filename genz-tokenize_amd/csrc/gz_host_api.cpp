@@ -41,6 +41,7 @@ int gz_option_set(GzOptions& o, const char* key, int64_t v)
         {"diag_guard", &GzOptions::diag_guard, nullptr, 0, 2}, {"diag_exact", &GzOptions::diag_exact, nullptr, 0, 1}, {"diag_fresh", &GzOptions::diag_fresh, nullptr, 0, 256},
         {"diag_fresh_only", &GzOptions::diag_fresh_only, nullptr, -1, 1 << 20}, {"host_threads", &GzOptions::host_threads, nullptr, 0, 256},
         {"dense_csr", &GzOptions::dense_csr, nullptr, 0, 1}, {"host_hints", &GzOptions::host_hints, nullptr, 0, 3}, {"inject_bad_alloc", &GzOptions::inject_bad_alloc, nullptr, 0, 1 << 30},
+        {"mask_lds", &GzOptions::mask_lds, nullptr, 0, 1},
         {"bm25_hash_bits", &GzOptions::bm25_hash_bits, nullptr, 0, 62},
         {"bm25_topk_chunk", &GzOptions::bm25_topk_chunk, nullptr, 1, 1 << 30}, {"bm25_topk_tile", &GzOptions::bm25_topk_tile, nullptr, 0, 4096},
         {"bm25_search_chunk", &GzOptions::bm25_search_chunk, nullptr, 1, 1 << 30},

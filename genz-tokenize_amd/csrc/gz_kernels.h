@@ -153,6 +153,24 @@ void gz_launch_pack_maps(const GzPackArgs& A, bool with_col /* false: a fill fol
 void gz_launch_pack_col(const GzPackArgs& A, hipStream_t s);
 void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s);     // R = *A.total, read on the device
 
+// masked-LM inputs and labels over dense rows (gz_mask.inc): one launch; ids, out_ids and labels are [n_rows, row_len] and disjoint
+constexpr int GZ_MASK_LDS_MAX_BYTES = 48 * 1024;      // the continuation bitmap goes to LDS up to this size (393 216 ids)
+struct GzMaskArgs {
+    const int32_t* ids; int64_t n_rows; int32_t row_len;            // n_rows >= 1, row_len >= 1
+    int64_t row_base;                                               // the global index of cell (r, c) is (row_base + r) * row_len + c, < 2^63
+    uint32_t key0, key1;                                            // the seed's low and high word
+    uint64_t t_sel, t1, t2;                                         // thresholds in [0, 2^32], t1 <= t2 (2^32: always)
+    int32_t rand_lo; uint32_t rand_span;                            // random replacements: rand_lo + mulhi32(x2, rand_span), rand_span = rand_hi - rand_lo >= 1
+    int32_t mask_id, ignore_index, whole_word;
+    int32_t pad_id, bos_id, eos_id;                                 // protected beside mask_id
+    const uint32_t* cont_bits; int32_t n_ids;                       // the decoder snapshot's continuation bitmap: bit id of word id / 32 set when the word ends in "@@"
+    int32_t bits_in_lds;                                            // 1: the LDS form is wanted (the launcher takes it when the bitmap fits: (n_ids + 31) / 32 words of dynamic LDS)
+    int32_t* out_ids; int32_t* labels;
+    int32_t* n_chosen;                                              // [n_rows], may be null
+    int32_t rows_per_wave;                                          // set by the launcher
+};
+void gz_launch_mask(GzMaskArgs A, hipStream_t s);
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

@@ -48,6 +48,7 @@ SYMBOLS = [
     "gz_bm25_search_groups", "gz_bm25_search_groups_device", "gz_bm25_match_count_groups",
     "gz_window_rows", "gz_window_rows_device",
     "gz_pack_rows", "gz_pack_rows_device",
+    "gz_mask_rows", "gz_mask_rows_device",
 ]
 
 _lib = None
@@ -107,6 +108,11 @@ def load_library():
     pk = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)]
     L.gz_pack_rows.argtypes = pk
     L.gz_pack_rows_device.argtypes = pk
+    if hasattr(L, "gz_mask_rows"):
+        u64 = C.c_uint64
+        mk = [vp, vp, i64, i32, i64, u64, u64, u64, u64, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.gz_mask_rows.argtypes = mk
+        L.gz_mask_rows_device.argtypes = mk
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -573,6 +579,23 @@ class Context:
             e.total = total.value
             raise e
         return total.value
+
+    # ---- masked-LM inputs and labels ------------------------------------------------------------------------
+    def mask_rows(self, ids: np.ndarray, rule, row_base: int = 0):
+        """ids int32 [R, L]; rule = (seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index) as gz_mask_rows takes
+        them -> dict(input_ids [R, L], labels [R, L], n_chosen [R])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        R, L = ids.shape
+        out = dict(input_ids=np.empty((R, L), dtype=np.int32), labels=np.empty((R, L), dtype=np.int32), n_chosen=np.empty(R, dtype=np.int32))
+        self._check(self.lib.gz_mask_rows(self.handle, _ptr(ids) if R else None, R, L, int(row_base), *rule,
+                                          *[_ptr(out[k]) if R else None for k in ("input_ids", "labels", "n_chosen")]))
+        return out
+
+    def mask_rows_device(self, d_ids, n_rows, row_len, row_base, rule, d_input_ids, d_labels, d_n_chosen):
+        """gz_mask_rows_device: every pointer a device address (0: NULL); `rule` as in mask_rows."""
+        vp = C.c_void_p
+        self._check(self.lib.gz_mask_rows_device(self.handle, vp(d_ids) if d_ids else None, n_rows, row_len, row_base, *rule,
+                                                 *[vp(d) if d else None for d in (d_input_ids, d_labels, d_n_chosen)]))
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

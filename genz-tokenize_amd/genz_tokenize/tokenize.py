@@ -673,6 +673,121 @@ class Tokenize(object):
         ids, seg = np.asarray(result["input_ids"]), np.asarray(result["segment_ids"])
         return ids[seg != 0].astype(np.int32, copy=False), np.asarray(result["seg_off"], dtype=np.int64).copy()
 
+    # ---- masked-LM inputs and labels, whole-word ---------------------------------------------------------------------
+    @staticmethod
+    def _mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index):
+        """The arguments of a mask call as integers -- (seed, t_sel, t1, t2, rand_lo, rand_hi (None: the vocabulary), whole_word,
+        ignore_index, row_base) -- or the refusal.  Thresholds are floor(x * 2**32): exact, a float times a power of two."""
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an int" % name)
+            if not lo <= int(v) < hi:
+                raise ValueError("%s must lie in [%d, %d)" % (name, lo, hi))
+            return int(v)
+
+        def share(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("%s must be a number" % name)
+            if not 0 <= v <= 1:                                        # (NaN fails here too)
+                raise ValueError("%s must lie in [0, 1]" % name)
+            return float(v)
+        p, mp, rp = share("p", p), share("mask_prob", mask_prob), share("random_prob", random_prob)
+        if mp + rp > 1:
+            raise ValueError("mask_prob + random_prob must not exceed 1")
+        if not isinstance(whole_word, (bool, np.bool_)):
+            raise TypeError("whole_word must be a bool")
+        one = 2 ** 32
+        t_sel, t1, t2 = int(p * one), int(mp * one), min(int((mp + rp) * one), one)
+        lo = hi = None
+        if random_ids is not None:
+            if not isinstance(random_ids, (tuple, list)) or len(random_ids) != 2:
+                raise TypeError("random_ids must be None or a pair (lo, hi)")
+            lo = integer("random_ids[0]", random_ids[0], -(2 ** 31), 2 ** 31)
+            hi = integer("random_ids[1]", random_ids[1], -(2 ** 31), 2 ** 31)
+            if lo >= hi:
+                raise ValueError("random_ids must be a non-empty range [lo, hi)")
+        return (integer("seed", seed, 0, 2 ** 64), t_sel, t1, t2, lo, hi, int(bool(whole_word)),
+                integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31), integer("row_base", row_base, 0, 2 ** 63))
+
+    def _mask_call(self, rule, R, L):
+        """(the nine arguments of gz_mask_rows behind row_base, row_base) once the tables are known"""
+        seed, t_sel, t1, t2, lo, hi, ww, ignore, base = rule
+        if (base + R) * L >= 2 ** 63:
+            raise ValueError("(row_base + rows) * row length must stay below 2**63")
+        self._sync_tables()
+        mask_id = self._special_ids()[3]                               # encoder[mask_token], looked up at call time
+        if mask_id < 0:
+            raise KeyError(self.mask_token)
+        if lo is None:
+            lo, hi = 5, self.vocab_size()                              # (the five specials hold ids 0 .. 4, tokenize.py:31-37)
+            if hi <= lo:
+                raise ValueError("the vocabulary holds nothing but the specials: give random_ids")
+        return (seed, t_sel, t1, t2, lo, hi, mask_id, ww, ignore), base
+
+    def mask_rows(self, input_ids, p=0.15, seed=0, whole_word=True, mask_prob=0.8, random_prob=0.1, random_ids=None, row_base=0,
+                  ignore_index=-100):
+        """Masked-LM inputs and labels from dense [R, L] rows (the input_ids of `encode_batch`, `encode_windows`, `encode_packs`),
+        on the GPU.  A cell that holds pad, bos, eos or <mask> is never touched.  Of the others a share `p` is chosen -- with
+        `whole_word=True` word by word: the pieces "xx@@ yy@@ zz" of a word go together, and words end at protected cells and at
+        the row's edge -- and a chosen cell becomes <mask> (share `mask_prob`), a random id from `random_ids` = (lo, hi), default
+        (5, vocab_size()) (share `random_prob`), or stays.  The draw is Philox4x32-10 keyed by `seed` over the cell's global
+        position (row_base + r) * L + c: the same seed gives the same cells whatever the batch is cut into
+        (`mask_rows(rows[a:b], row_base=a)` is `mask_rows(rows)[a:b]`); a new epoch is a new seed.  Returns numpy arrays:
+        input_ids [R, L], labels [R, L] (the original id where chosen, `ignore_index` elsewhere), n_chosen [R].  The attention
+        mask is the caller's and does not change."""
+        rule = self._mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index)
+        ids = np.asarray(input_ids)
+        if ids.dtype.kind not in "iu":
+            raise TypeError("mask_rows() expects integer ids")
+        if ids.ndim != 2 or ids.shape[1] < 1 or ids.shape[1] >= 2 ** 31:
+            raise ValueError("mask_rows() expects a 2-D array of rows, [R, L] with 1 <= L < 2**31")
+        if ids.dtype != np.int32:
+            if ids.size and (int(ids.min()) < -(2 ** 31) or int(ids.max()) >= 2 ** 31):
+                raise ValueError("mask_rows() expects ids that fit in int32")
+            ids = ids.astype(np.int32)
+        args, base = self._mask_call(rule, *ids.shape)
+        return self._ctx.mask_rows(ids, args, base)
+
+    def mask_rows_to_device(self, input_ids, p=0.15, seed=0, whole_word=True, mask_prob=0.8, random_prob=0.1, random_ids=None,
+                            row_base=0, ignore_index=-100):
+        """`mask_rows` over rows that are in HBM already and stay there: `input_ids` is a `handoff.DeviceArray` -- the input_ids of
+        `encode_to_device`, `encode_windows_to_device` or `encode_packs_to_device` -- and input_ids and labels come back as
+        `DeviceArray`s (`torch.from_dlpack(x)` is zero-copy); n_chosen is a host array.  The source rows are not changed."""
+        from .handoff import DeviceArray
+        rule = self._mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index)
+        if not isinstance(input_ids, DeviceArray):
+            raise TypeError("mask_rows_to_device() expects a handoff.DeviceArray")
+        if input_ids.dtype != np.int32:
+            raise TypeError("mask_rows_to_device() expects int32 ids")
+        if len(input_ids.shape) != 2 or input_ids.shape[1] < 1 or input_ids.shape[1] >= 2 ** 31:
+            raise ValueError("mask_rows_to_device() expects rows [R, L] with 1 <= L < 2**31")
+        if input_ids._ctx is not self._ctx:
+            raise ValueError("the rows belong to another Tokenize object's device context")
+        R, L = input_ids.shape
+        args, base = self._mask_call(rule, R, L)
+        ctx = self._ctx
+
+        def rows():                                                    # (an allocation nothing owns yet is freed when its DeviceArray fails)
+            d = ctx.alloc(4 * max(R * L, 1))
+            try:
+                return DeviceArray(ctx, d, (R, L))
+            except BaseException:
+                ctx.free(d)
+                raise
+        out = {"input_ids": rows()}
+        out["labels"] = rows()
+        n_chosen = np.zeros(R, dtype=np.int32)
+        d_cnt = ctx.alloc(4 * max(R, 1))
+        try:
+            ctx.mask_rows_device(input_ids.ptr if R else 0, R, L, base, args, out["input_ids"].ptr if R else 0,
+                                 out["labels"].ptr if R else 0, d_cnt if R else 0)
+            if R:
+                ctx.d2h(n_chosen, d_cnt)
+        finally:
+            ctx.free(d_cnt)
+        out["n_chosen"] = n_chosen
+        return out
+
     @staticmethod
     def _shape(r, n):
         if r["dense"]:

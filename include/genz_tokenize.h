@@ -240,6 +240,7 @@ int64_t gz_limit(int which);
  *   dense_csr (0..1; 1)        a large dense single-text gz_encode_batch brings only the rows' real entries over the bus and pads them
  *                              into the caller's arrays on the host; 0: the dense rows cross
  *   host_hints (0..3; 0)       fresh output arrays of a large host call: bit 0 MADV_HUGEPAGE on them, bit 1 MADV_POPULATE_WRITE per piece
+ *   mask_lds (0..1; 1)         masked-LM rows: the continuation bitmap is staged in LDS by every workgroup when it fits; 0: read from memory
  *   inject_bad_alloc (>= 0; 0) test hook: the k-th allocation site reached from now on throws std::bad_alloc (the call answers GZ_E_NOMEM)
  *   bm25_hash_bits (0..62; 0)  BM25 index builds keep only the low k bits of every word's hash (0: all of it)
  *   bm25_topk_chunk (1..2^30; 2^27)  BM25 top-k: doubles of score rows held in the context's workspace at a time (queries are
@@ -351,6 +352,45 @@ int  gz_pack_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row
                          int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *segment_ids_dev, int32_t *position_ids_dev,
                          int32_t *doc_row_dev, int32_t *doc_col_dev, int32_t *doc_len_dev, int64_t *pack_off_dev, int64_t *seg_off_dev,
                          int64_t capacity_rows, int64_t *total_host);
+
+/* ---- masked-LM inputs and labels over dense rows, whole-word ----------------------------------------------------------------
+ * The reference reserves <mask> as id 3 (tokenize.py:11, :35) and never produces it.  These calls take dense [n_rows, row_len]
+ * int32 rows -- the input_ids of an encode, window or pack call -- and make the inputs and labels of masked-language-model
+ * training: some cells are chosen, a chosen cell becomes mask_id, a random id or stays, and labels holds the original id where a
+ * cell was chosen.  With whole_word = 1 the pieces of a word ("xx@@ yy@@ zz") are chosen together.  The draw is counter-based: it
+ * depends on the seed and the cell's global position alone, so a batch masked in chunks, or on another GPU, gives the same cells.
+ *   PROTECTED cell   its id is the context's current pad, bos or eos id (gz_table_info) or mask_id: never chosen, passes through,
+ *                    label = ignore_index
+ *   CONTINUATION     an id of the decoder snapshot (gz_decoder_snapshot) whose word ends in the two bytes "@@"; an id outside the
+ *                    snapshot or absent from it is none (the unk fallback of decode is not used)
+ *   start(r, c)      the cell is not protected, and c == 0 or cell c-1 is protected or cell c-1 is no continuation: words never
+ *                    run across a row edge or a protected cell (a packed row's eos / bos pair separates its documents)
+ *   head(r, c)       of an unprotected cell: the largest c' <= c with start(r, c'); with whole_word = 0, c itself
+ *   g(r, c)          (row_base + r) * row_len + c, unsigned 64-bit
+ *   D(g)             Philox4x32-10, counter (g & 0xffffffff, g >> 32, 0, 0), key (seed & 0xffffffff, seed >> 32), multipliers
+ *                    0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85; outputs x0 .. x3
+ *   chosen(r, c)     the cell is unprotected and D(g(r, head(r, c))).x0 < t_sel
+ *   a chosen cell    a = D(g(r, c)).x1:  a < t1 -> mask_id;  else a < t2 -> rand_lo + mulhi32(D(g(r, c)).x2, rand_hi - rand_lo);
+ *                    else the id stays
+ *   input_ids [n_rows, row_len]  the replaced ids, everything else copied;  labels [n_rows, row_len]  the original id where chosen,
+ *   ignore_index elsewhere;  n_chosen [n_rows] int32 (may be NULL): chosen cells of the row.  The attention mask is the caller's.
+ *   t_sel, t1, t2 are integers in [0, 2^32] (2^32: always), t1 <= t2; seed is any 64-bit value (a new epoch is a new seed).
+ *   mask(rows[a:b], row_base = a) == mask(rows)[a:b].
+ *   GZ_E_INVALID: row_len < 1, n_rows < 0, row_base < 0, (row_base + n_rows) * row_len not below 2^63, a threshold above 2^32,
+ *   t1 > t2, rand_lo >= rand_hi, whole_word outside {0, 1}, ids / input_ids / labels NULL with n_rows > 0, or buffers that overlap
+ *   (heads are read from neighbours' original ids): nothing is written.  GZ_E_NOTABLES without a decoder snapshot.  n_rows == 0 is
+ *   GZ_OK and launches nothing.
+ * gz_mask_rows_device: every pointer is a DEVICE pointer.  Ordering: one launch on the context's stream, behind an encode, window
+ *   or pack call enqueued just before on the same context with no gz_sync in between.  The call returns when the rows are complete.
+ * gz_mask_rows: host pointers; the rows go up through the library's pinned staging, the device form runs, the three arrays come
+ *   back. */
+int  gz_mask_rows(gz_ctx *ctx, const int32_t *ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed,
+                  uint64_t t_sel, uint64_t t1, uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id,
+                  int32_t whole_word, int32_t ignore_index, int32_t *input_ids, int32_t *labels, int32_t *n_chosen);
+int  gz_mask_rows_device(gz_ctx *ctx, const int32_t *ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed,
+                         uint64_t t_sel, uint64_t t1, uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id,
+                         int32_t whole_word, int32_t ignore_index, int32_t *input_ids_dev, int32_t *labels_dev,
+                         int32_t *n_chosen_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
