@@ -159,6 +159,7 @@ struct gz_ctx {
     DBuf w_win_cnt, w_win_ids, w_win_roff, w_win_off, w_win_out, w_win_mask, w_win_meta;               // overlapping windows (gz_window_rows*)
     DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol, w_pk_dlen, w_pk_roff, w_pk_ids, w_pk_inoff, w_pk_out[4];   // packed rows (gz_pack_rows*)
     DBuf w_mk_ids, w_mk_out, w_mk_lab, w_mk_cnt;                                                        // masked-LM rows (gz_mask_rows)
+    DBuf w_if_ids, w_if_out, w_if_am, w_if_lab, w_if_dec, w_if_cnt;                                     // span-corruption rows (gz_infill_rows)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_pp_in, w_pp_inoff, w_ppctl, w_pplen32, w_pplb;      // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
     // host path with copies overlapped (gz_encode_batch_csr): copy-in / copy-out streams, per-sub-batch events and buffers
@@ -1050,6 +1051,7 @@ try {
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol, &c->w_pk_dlen, &c->w_pk_roff, &c->w_pk_ids,
                     &c->w_pk_inoff, &c->w_pk_out[0], &c->w_pk_out[1], &c->w_pk_out[2], &c->w_pk_out[3]}) release(*b);
     for (DBuf* b : {&c->w_mk_ids, &c->w_mk_out, &c->w_mk_lab, &c->w_mk_cnt}) release(*b);
+    for (DBuf* b : {&c->w_if_ids, &c->w_if_out, &c->w_if_am, &c->w_if_lab, &c->w_if_dec, &c->w_if_cnt}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
     for (DBuf* b : {&c->t_merges, &c->t_symids, &c->t_bmp, &c->t_astral, &c->t_struct, &c->t_words2, &c->w_text, &c->w_toff, &c->w_pair,
@@ -2369,6 +2371,129 @@ try {
         if ((rc = copy_out(c, labels, c->w_mk_lab.p, cells * 4, c->stream, &pool))) return rc;
     }
     if (n_chosen && (rc = copy_out(c, n_chosen, c->w_mk_cnt.p, (size_t)n_rows * 4, c->stream))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+// ---- span-corruption inputs and targets over dense rows -------------------------------------------------------------------
+namespace {
+struct InfillRule {
+    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_start; const uint64_t* len_t;
+    int32_t n_len, mask_id, whole_word, ignore_index, dec_width;
+};
+struct InfillBufs {
+    const int32_t* ids; int32_t* input_ids; int32_t* attention_mask; int32_t* labels; int32_t* decoder_input_ids;
+    int32_t* enc_len; int32_t* dec_len; int32_t* n_spans;
+};
+const char* const kInfillRule = "infill rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, dec_width >= 1, "
+                                "t_start in [0, 2^32], 1 <= n_len <= 16 with n_len - 1 non-decreasing thresholds in [0, 2^32] and whole_word 0 or 1";
+bool infill_rule_ok(const InfillRule& M)
+{
+    constexpr uint64_t one = 1ull << 32;
+    if (M.row_len < 1 || M.n_rows < 0 || M.row_base < 0 || M.dec_width < 1) return false;
+    const unsigned __int128 cells = ((unsigned __int128)M.row_base + (unsigned __int128)M.n_rows) * (unsigned __int128)M.row_len;
+    if (cells >> 63) return false;
+    if (M.t_start > one || M.n_len < 1 || M.n_len > 16 || (M.whole_word != 0 && M.whole_word != 1)) return false;
+    if (M.n_len > 1 && !M.len_t) return false;
+    for (int k = 0; k + 1 < M.n_len; ++k)
+        if (M.len_t[k] > one || (k > 0 && M.len_t[k] < M.len_t[k - 1])) return false;
+    return true;
+}
+// the eight arrays are pairwise disjoint (every cell is read from the ORIGINAL rows and written once); n_rows > 0
+bool infill_buffers_ok(const InfillRule& M, const InfillBufs& B)
+{
+    if (!B.ids || !B.input_ids || !B.labels) return false;
+    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
+    if ((uint64_t)M.n_rows * (uint64_t)M.dec_width > (uint64_t)(UINTPTR_MAX / 4)) return false;
+    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u, dec = (uintptr_t)M.n_rows * (uintptr_t)M.dec_width * 4u,
+                    cnt = (uintptr_t)M.n_rows * 4u;
+    const uintptr_t p[8] = {(uintptr_t)B.ids, (uintptr_t)B.input_ids, (uintptr_t)B.attention_mask, (uintptr_t)B.labels,
+                            (uintptr_t)B.decoder_input_ids, (uintptr_t)B.enc_len, (uintptr_t)B.dec_len, (uintptr_t)B.n_spans};
+    const uintptr_t n[8] = {cells, cells, cells, dec, dec, cnt, cnt, cnt};
+    for (int a = 0; a < 8; ++a)
+        for (int b = a + 1; b < 8; ++b)
+            if (p[a] && p[b] && (p[a] >= p[b] ? p[a] - p[b] < n[b] : p[b] - p[a] < n[a])) return false;       // (differences: no end address to wrap)
+    return true;
+}
+// the one launch on the context's stream, behind whatever it holds; every pointer of B a device pointer
+void infill_launch(gz_ctx* c, const InfillRule& M, const InfillBufs& B)
+{
+    GzInfillArgs A{};
+    A.ids = B.ids; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
+    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
+    A.t_start = M.t_start; A.n_len = M.n_len;
+    for (int k = 0; k < 15; ++k) A.len_t[k] = k + 1 < M.n_len ? M.len_t[k] : 1ull << 32;       // (len_t is a host pointer: its words travel in the arguments)
+    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word; A.dec_width = M.dec_width;
+    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
+    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
+    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
+    A.out_ids = B.input_ids; A.out_mask = B.attention_mask; A.labels = B.labels; A.dec_ids = B.decoder_input_ids;
+    A.enc_len = B.enc_len; A.dec_len = B.dec_len; A.n_spans = B.n_spans;
+    gz_launch_infill(A, c->stream);
+}
+}  // namespace
+
+int gz_infill_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
+                          const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
+                          int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* labels_dev, int32_t* decoder_input_ids_dev,
+                          int32_t* enc_len_dev, int32_t* dec_len_dev, int32_t* n_spans_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
+    const InfillBufs B{ids_dev, input_ids_dev, attention_mask_dev, labels_dev, decoder_input_ids_dev, enc_len_dev, dec_len_dev, n_spans_dev};
+    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
+    if (n_rows > 0 && !infill_buffers_ok(M, B))
+        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    infill_launch(c, M, B);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_infill_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
+                   const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
+                   int32_t* input_ids, int32_t* attention_mask, int32_t* labels, int32_t* decoder_input_ids, int32_t* enc_len, int32_t* dec_len,
+                   int32_t* n_spans)
+try {
+    if (!c) return GZ_E_INVALID;
+    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
+    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
+    if (n_rows > 0 && !infill_buffers_ok(M, InfillBufs{ids, input_ids, attention_mask, labels, decoder_input_ids, enc_len, dec_len, n_spans}))
+        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)n_rows * (size_t)row_len * 4, dec = (size_t)n_rows * (size_t)dec_width * 4, cnt = (size_t)n_rows * 4;
+    int32_t* const counts[3] = {enc_len, dec_len, n_spans};
+    const bool any_count = enc_len || dec_len || n_spans;
+    int rc;
+    if ((rc = ensure(c, c->w_if_ids, cells))) return rc;
+    if ((rc = ensure(c, c->w_if_out, cells))) return rc;
+    if (attention_mask && (rc = ensure(c, c->w_if_am, cells))) return rc;
+    if ((rc = ensure(c, c->w_if_lab, dec))) return rc;
+    if (decoder_input_ids && (rc = ensure(c, c->w_if_dec, dec))) return rc;
+    if (any_count && (rc = ensure(c, c->w_if_cnt, 3 * cnt))) return rc;
+    if ((rc = copy_in(c, c->w_if_ids.p, ids, cells, c->stream))) return rc;
+    InfillBufs B{(const int32_t*)c->w_if_ids.p, (int32_t*)c->w_if_out.p, attention_mask ? (int32_t*)c->w_if_am.p : nullptr, (int32_t*)c->w_if_lab.p,
+                 decoder_input_ids ? (int32_t*)c->w_if_dec.p : nullptr, nullptr, nullptr, nullptr};
+    int32_t** const slots[3] = {&B.enc_len, &B.dec_len, &B.n_spans};
+    for (int k = 0; k < 3; ++k)
+        if (counts[k]) *slots[k] = (int32_t*)c->w_if_cnt.p + (size_t)k * (size_t)n_rows;
+    infill_launch(c, M, B);
+    {
+        HostPool pool(pool_threads(c, cells));
+        if ((rc = copy_out(c, input_ids, c->w_if_out.p, cells, c->stream, &pool))) return rc;
+        if (attention_mask && (rc = copy_out(c, attention_mask, c->w_if_am.p, cells, c->stream, &pool))) return rc;
+        if ((rc = copy_out(c, labels, c->w_if_lab.p, dec, c->stream, &pool))) return rc;
+        if (decoder_input_ids && (rc = copy_out(c, decoder_input_ids, c->w_if_dec.p, dec, c->stream, &pool))) return rc;
+    }
+    for (int k = 0; k < 3; ++k)
+        if (counts[k] && (rc = copy_out(c, counts[k], *slots[k], cnt, c->stream))) return rc;
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
 } GZ_CATCH(c)

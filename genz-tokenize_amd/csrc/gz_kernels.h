@@ -171,6 +171,25 @@ struct GzMaskArgs {
 };
 void gz_launch_mask(GzMaskArgs A, hipStream_t s);
 
+// span-corruption inputs and targets over dense rows (gz_infill.inc): one launch; ids, out_ids and out_mask are [n_rows, row_len],
+// labels and dec_ids [n_rows, dec_width], the three counts [n_rows]; all disjoint
+struct GzInfillArgs {
+    const int32_t* ids; int64_t n_rows; int32_t row_len;            // n_rows >= 1, row_len >= 1
+    int64_t row_base;                                               // the global index of cell (r, c) is (row_base + r) * row_len + c, < 2^63
+    uint32_t key0, key1;                                            // the seed's low and high word
+    uint64_t t_start;                                               // a span begins at a start whose x0 is below it; in [0, 2^32] (2^32: always)
+    uint64_t len_t[15]; int32_t n_len;                              // len = 1 + #{k : x1 >= len_t[k]}; non-decreasing, in [0, 2^32]; words from n_len - 1 on hold 2^32; 1 <= n_len <= 16
+    int32_t mask_id, ignore_index, whole_word, dec_width;           // dec_width >= 1
+    int32_t pad_id, bos_id, eos_id;                                 // protected beside mask_id
+    const uint32_t* cont_bits; int32_t n_ids;                       // the continuation bitmap of GzMaskArgs
+    int32_t bits_in_lds;                                            // as in GzMaskArgs (the switch mask_lds)
+    int32_t* out_ids; int32_t* labels;
+    int32_t* out_mask; int32_t* dec_ids;                            // each may be null
+    int32_t* enc_len; int32_t* dec_len; int32_t* n_spans;           // [n_rows], each may be null
+    int32_t rows_per_wave;                                          // set by the launcher
+};
+void gz_launch_infill(GzInfillArgs A, hipStream_t s);
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

@@ -74,6 +74,25 @@ __device__ __forceinline__ int below(uint64_t m)
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// the draw of the row passes over dense rows (gz_mask.inc, gz_infill.inc)
+struct Philox3 { uint32_t x0, x1, x2; };
+
+// Philox4x32-10 (Salmon et al., SC'11), counter (g lo, g hi, 0, 0), key (k0, k1); x3 is not used by the rule
+__device__ __forceinline__ Philox3 mask_draw(uint64_t g, uint32_t k0, uint32_t k1)
+{
+    uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return Philox3{c0, c1, c2};
+}
+
+__device__ __forceinline__ void nt_store1(int32_t* p, int32_t v) { __builtin_nontemporal_store(v, p); }
+
 // exclusive prefix sum over the wave, all in DPP (no LDS traffic): Hillis-Steele inside each row of 16 lanes
 // (row_shr 1, 2, 4, 8), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3.
 __device__ __forceinline__ int wave_excl_sum(int v, int lane, int& total)
@@ -692,6 +711,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_window.inc"
 #include "gz_packrows.inc"
 #include "gz_mask.inc"
+#include "gz_infill.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -821,6 +841,23 @@ void gz_launch_mask(GzMaskArgs A, hipStream_t s)
     else if (wide) hipLaunchKernelGGL((gz_mask_kernel<4, false>), grid, block, 0, s, A);
     else if (lds) hipLaunchKernelGGL((gz_mask_kernel<1, true>), grid, block, lds, s, A);
     else hipLaunchKernelGGL((gz_mask_kernel<1, false>), grid, block, 0, s, A);
+}
+
+void gz_launch_infill(GzInfillArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    // the division of gz_launch_mask: about 4096 cells a wave, more rows a wave only where the grid would not hold the waves
+    int64_t rpw = A.row_len < 4096 ? 4096 / A.row_len : 1;
+    const int64_t max_waves = (int64_t)4 * 0x7FFFFFFF;
+    if ((A.n_rows + rpw - 1) / rpw > max_waves) rpw = (A.n_rows + max_waves - 1) / max_waves;
+    A.rows_per_wave = (int32_t)rpw;
+    const int64_t waves = (A.n_rows + rpw - 1) / rpw;
+    const dim3 grid((unsigned)((waves + 3) / 4)), block(WAVE * 4);
+    // the continuation bitmap in LDS: whole words only, and only while it fits
+    const size_t words = ((size_t)A.n_ids + 31) / 32;
+    if (!A.whole_word || words == 0 || words * 4 > (size_t)GZ_MASK_LDS_MAX_BYTES) A.bits_in_lds = 0;
+    if (A.bits_in_lds) hipLaunchKernelGGL((gz_infill_kernel<true>), grid, block, (unsigned)(words * 4), s, A);
+    else hipLaunchKernelGGL((gz_infill_kernel<false>), grid, block, 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

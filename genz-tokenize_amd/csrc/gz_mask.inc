@@ -23,28 +23,6 @@
 // Traffic per cell: 4 bytes in, 8 out (non-temporal: written once), one LDS read; the bitmap once a workgroup (about 16 K cells)
 // from L2; 10 Philox rounds = 20 32x32->64 multiplies.  Cell indices and g are 64-bit throughout.
 
-namespace {
-
-struct Philox3 { uint32_t x0, x1, x2; };
-
-// Philox4x32-10 (Salmon et al., SC'11), counter (g lo, g hi, 0, 0), key (k0, k1); x3 is not used by the rule
-__device__ __forceinline__ Philox3 mask_draw(uint64_t g, uint32_t k0, uint32_t k1)
-{
-    uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Philox3{c0, c1, c2};
-}
-
-__device__ __forceinline__ void nt_store1(int32_t* p, int32_t v) { __builtin_nontemporal_store(v, p); }
-
-}  // namespace
-
 // U cells per lane, load and store: 4 (rows and base pointers 16-byte aligned) or 1 (any L); LDS: the continuation bitmap is staged in LDS
 template <int U, bool LDS>
 __global__ __launch_bounds__(WAVE * 4) void gz_mask_kernel(GzMaskArgs A)

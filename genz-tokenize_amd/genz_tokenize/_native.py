@@ -49,6 +49,7 @@ SYMBOLS = [
     "gz_window_rows", "gz_window_rows_device",
     "gz_pack_rows", "gz_pack_rows_device",
     "gz_mask_rows", "gz_mask_rows_device",
+    "gz_infill_rows", "gz_infill_rows_device",
 ]
 
 _lib = None
@@ -113,6 +114,11 @@ def load_library():
         mk = [vp, vp, i64, i32, i64, u64, u64, u64, u64, i32, i32, i32, i32, i32, vp, vp, vp]
         L.gz_mask_rows.argtypes = mk
         L.gz_mask_rows_device.argtypes = mk
+    if hasattr(L, "gz_infill_rows"):
+        u64 = C.c_uint64
+        fi = [vp, vp, i64, i32, i64, u64, u64, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_infill_rows.argtypes = fi
+        L.gz_infill_rows_device.argtypes = fi
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -596,6 +602,40 @@ class Context:
         vp = C.c_void_p
         self._check(self.lib.gz_mask_rows_device(self.handle, vp(d_ids) if d_ids else None, n_rows, row_len, row_base, *rule,
                                                  *[vp(d) if d else None for d in (d_input_ids, d_labels, d_n_chosen)]))
+
+    # ---- span-corruption inputs and targets ------------------------------------------------------------------
+    @staticmethod
+    def _infill_args(rule):
+        """rule = (seed, t_start, len_t (n_len - 1 integers), n_len, mask_id, whole_word, ignore_index, dec_width) -> the eight
+        arguments of gz_infill_rows behind row_base, and the array that keeps len_t alive during the call"""
+        seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width = rule
+        arr = np.ascontiguousarray(list(len_t) + [0], dtype=np.uint64)          # (never empty: n_len == 1 reads none of it)
+        return (seed, t_start, _ptr(arr), n_len, mask_id, whole_word, ignore_index, dec_width), arr
+
+    def infill_rows(self, ids: np.ndarray, rule, row_base: int = 0):
+        """ids int32 [R, L]; rule as in _infill_args -> dict(input_ids [R, L], attention_mask [R, L], labels [R, W],
+        decoder_input_ids [R, W], enc_len [R], dec_len [R], n_spans [R])."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        R, L = ids.shape
+        W = rule[7]
+        out = dict(input_ids=np.empty((R, L), dtype=np.int32), attention_mask=np.empty((R, L), dtype=np.int32),
+                   labels=np.empty((R, W), dtype=np.int32), decoder_input_ids=np.empty((R, W), dtype=np.int32),
+                   enc_len=np.empty(R, dtype=np.int32), dec_len=np.empty(R, dtype=np.int32), n_spans=np.empty(R, dtype=np.int32))
+        args, keep = self._infill_args(rule)
+        self._check(self.lib.gz_infill_rows(self.handle, _ptr(ids) if R else None, R, L, int(row_base), *args,
+                                            *[_ptr(v) if R else None for v in out.values()]))
+        del keep
+        return out
+
+    def infill_rows_device(self, d_ids, n_rows, row_len, row_base, rule, d_input_ids, d_attention_mask, d_labels, d_decoder_input_ids,
+                           d_enc_len, d_dec_len, d_n_spans):
+        """gz_infill_rows_device: every pointer a device address (0: NULL); `rule` as in infill_rows (len_t stays on the host)."""
+        vp = C.c_void_p
+        args, keep = self._infill_args(rule)
+        self._check(self.lib.gz_infill_rows_device(self.handle, vp(d_ids) if d_ids else None, n_rows, row_len, row_base, *args,
+                                                   *[vp(d) if d else None for d in (d_input_ids, d_attention_mask, d_labels,
+                                                                                    d_decoder_input_ids, d_enc_len, d_dec_len, d_n_spans)]))
+        del keep
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

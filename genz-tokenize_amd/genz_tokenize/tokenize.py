@@ -12,6 +12,7 @@ that returns numpy arrays, which is what the GPU is for.
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 from typing import Dict, List, Optional, Sequence
@@ -786,6 +787,174 @@ class Tokenize(object):
         finally:
             ctx.free(d_cnt)
         out["n_chosen"] = n_chosen
+        return out
+
+    # ---- span-corruption inputs and targets for encoder-decoder models ----------------------------------------------
+    @staticmethod
+    def _infill_lengths(lengths, mean_span, max_span):
+        """P(len = 1 .. n_len) of a span's length in words: the law truncated at max_span and renormalised"""
+        if lengths == "fixed":
+            return [0.0] * (int(mean_span) - 1) + [1.0]
+        if lengths == "geometric":
+            r = 1.0 / mean_span
+            w = [r * (1.0 - r) ** (k - 1) for k in range(1, max_span + 1)]
+        else:                                                          # "poisson", without the zero-length spans
+            w = [math.exp(-mean_span) * mean_span ** k / math.factorial(k) for k in range(1, max_span + 1)]
+        total = sum(w)
+        return [x / total for x in w]
+
+    @staticmethod
+    def _infill_coverage(q, tail):
+        """1 - prod_k (1 - q P(len > k)): the probability that a word with at least n_len - 1 words before it in its row lies in
+        a span, when every word begins one with probability q"""
+        prod = 1.0
+        for t in tail:
+            prod *= 1.0 - q * t
+        return 1.0 - prod
+
+    @staticmethod
+    def _infill_start_share(p, tail):
+        """q with _infill_coverage(q, tail) == p, by bisection (the coverage rises from 0 at q = 0 to 1 at q = 1)"""
+        if p <= 0.0 or p >= 1.0:
+            return float(p)
+        lo, hi = 0.0, 1.0
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            if Tokenize._infill_coverage(mid, tail) < p:
+                lo = mid
+            else:
+                hi = mid
+        return hi
+
+    @staticmethod
+    def _infill_rule(p, mean_span, max_span, lengths, seed, whole_word, dec_len, row_base, ignore_index):
+        """The arguments of an infill call as integers -- (seed, t_start, len_t (n_len - 1 thresholds), n_len, whole_word,
+        ignore_index, dec_len (None: the row length), row_base) -- or the refusal.  t_start = floor(q * 2**32) with q solved from
+        the coverage formula; len_t[k] = floor(P(len <= k + 1) * 2**32), non-decreasing."""
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an int" % name)
+            if not lo <= int(v) < hi:
+                raise ValueError("%s must lie in [%d, %d)" % (name, lo, hi))
+            return int(v)
+
+        def number(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("%s must be a number" % name)
+            return float(v)
+        p = number("p", p)
+        if not 0 <= p <= 1:                                            # (NaN fails here too)
+            raise ValueError("p must lie in [0, 1]")
+        max_span = integer("max_span", max_span, 1, 17)
+        mean_span = number("mean_span", mean_span)
+        if not isinstance(lengths, str):
+            raise TypeError("lengths must be a str")
+        if lengths not in ("geometric", "poisson", "fixed"):
+            raise ValueError('lengths must be "geometric", "poisson" or "fixed"')
+        if not 1 <= mean_span <= max_span:                             # (NaN and infinities fail here)
+            raise ValueError("mean_span must lie in [1, max_span]")
+        if lengths == "fixed" and mean_span != int(mean_span):
+            raise ValueError('lengths="fixed" needs a whole mean_span')
+        if not isinstance(whole_word, (bool, np.bool_)):
+            raise TypeError("whole_word must be a bool")
+        if dec_len is not None:
+            dec_len = integer("dec_len", dec_len, 1, 2 ** 31)
+        seed = integer("seed", seed, 0, 2 ** 64)
+        ignore_index = integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31)
+        row_base = integer("row_base", row_base, 0, 2 ** 63)
+        one = 2 ** 32
+        pmf = Tokenize._infill_lengths(lengths, mean_span, max_span)
+        tail = [max(0.0, 1.0 - sum(pmf[:k])) if k else 1.0 for k in range(len(pmf))]
+        q = Tokenize._infill_start_share(p, tail)
+        len_t, acc, last = [], 0.0, 0
+        for k in range(len(pmf) - 1):
+            acc += pmf[k]
+            last = max(last, min(int(min(acc, 1.0) * one), one))
+            len_t.append(last)
+        return (seed, int(q * one), len_t, len(pmf), int(bool(whole_word)), ignore_index, dec_len, row_base)
+
+    def _infill_call(self, rule, R, L):
+        """(the rule of _native.Context.infill_rows, row_base) once the tables are known"""
+        seed, t_start, len_t, n_len, ww, ignore, dec_len, base = rule
+        if (base + R) * L >= 2 ** 63:
+            raise ValueError("(row_base + rows) * row length must stay below 2**63")
+        self._sync_tables()
+        mask_id = self._special_ids()[3]                               # encoder[mask_token], looked up at call time
+        if mask_id < 0:
+            raise KeyError(self.mask_token)
+        return (seed, t_start, len_t, n_len, mask_id, ww, ignore, L if dec_len is None else dec_len), base
+
+    def infill_rows(self, input_ids, p=0.15, mean_span=3.0, max_span=10, lengths="geometric", seed=0, whole_word=True, dec_len=None,
+                    row_base=0, ignore_index=-100):
+        """Span-corruption inputs and targets for an encoder-decoder model (the denoising objective of T5, MASS and
+        BART-infilling) from dense [R, L] rows, on the GPU.  Spans of whole words are chosen so that about a share `p` of the
+        tokens lies inside one: every word begins a span with probability q, and a span is 1 .. `max_span` (<= 16) words long
+        -- `lengths` = "geometric" (mean `mean_span` before truncation), "poisson" (lambda `mean_span`, no empty spans) or
+        "fixed" (`mean_span` words) --, the law truncated at `max_span` and renormalised; q is solved so that a word with
+        max_span - 1 words before it in its row is covered with probability exactly p, hence the realised share near a row's
+        start is lower.  Overlapping and touching spans merge.  Cells that hold pad, bos, eos or <mask> are never chosen and end
+        a run.  Each run collapses to ONE <mask> in the encoder row, pads drop out and the row closes up; the target is, run by
+        run, <mask> and the run's ids, closed by eos.  With `whole_word=False` every token is a word.  The draw is counter-based
+        as in `mask_rows` (`infill_rows(rows[a:b], row_base=a)` is `infill_rows(rows)[a:b]`; the same seed gives draws
+        correlated with `mask_rows`).  Returns numpy arrays: input_ids and attention_mask [R, L]; labels (target, then
+        `ignore_index`) and decoder_input_ids (bos + target shifted, then pad) [R, `dec_len`] (None: L); enc_len, dec_len and
+        n_spans [R] -- dec_len is the target's whole length, so `dec_len > labels.shape[1]` marks a clipped row.  BART's
+        full-sequence target is the row you passed in."""
+        rule = self._infill_rule(p, mean_span, max_span, lengths, seed, whole_word, dec_len, row_base, ignore_index)
+        ids = np.asarray(input_ids)
+        if ids.dtype.kind not in "iu":
+            raise TypeError("infill_rows() expects integer ids")
+        if ids.ndim != 2 or ids.shape[1] < 1 or ids.shape[1] >= 2 ** 31:
+            raise ValueError("infill_rows() expects a 2-D array of rows, [R, L] with 1 <= L < 2**31")
+        if ids.dtype != np.int32:
+            if ids.size and (int(ids.min()) < -(2 ** 31) or int(ids.max()) >= 2 ** 31):
+                raise ValueError("infill_rows() expects ids that fit in int32")
+            ids = ids.astype(np.int32)
+        args, base = self._infill_call(rule, *ids.shape)
+        return self._ctx.infill_rows(ids, args, base)
+
+    def infill_rows_to_device(self, input_ids, p=0.15, mean_span=3.0, max_span=10, lengths="geometric", seed=0, whole_word=True,
+                              dec_len=None, row_base=0, ignore_index=-100):
+        """`infill_rows` over rows that are in HBM already and stay there: `input_ids` is a `handoff.DeviceArray` -- the
+        input_ids of `encode_to_device`, `encode_windows_to_device` or `encode_packs_to_device` -- and input_ids,
+        attention_mask, labels and decoder_input_ids come back as `DeviceArray`s (`torch.from_dlpack(x)` is zero-copy);
+        enc_len, dec_len and n_spans are host arrays.  The source rows are not changed."""
+        from .handoff import DeviceArray
+        rule = self._infill_rule(p, mean_span, max_span, lengths, seed, whole_word, dec_len, row_base, ignore_index)
+        if not isinstance(input_ids, DeviceArray):
+            raise TypeError("infill_rows_to_device() expects a handoff.DeviceArray")
+        if input_ids.dtype != np.int32:
+            raise TypeError("infill_rows_to_device() expects int32 ids")
+        if len(input_ids.shape) != 2 or input_ids.shape[1] < 1 or input_ids.shape[1] >= 2 ** 31:
+            raise ValueError("infill_rows_to_device() expects rows [R, L] with 1 <= L < 2**31")
+        if input_ids._ctx is not self._ctx:
+            raise ValueError("the rows belong to another Tokenize object's device context")
+        R, L = input_ids.shape
+        args, base = self._infill_call(rule, R, L)
+        W = args[7]
+        ctx = self._ctx
+
+        def rows(width):                                               # (an allocation nothing owns yet is freed when its DeviceArray fails)
+            d = ctx.alloc(4 * max(R * width, 1))
+            try:
+                return DeviceArray(ctx, d, (R, width))
+            except BaseException:
+                ctx.free(d)
+                raise
+        out = {"input_ids": rows(L)}
+        out["attention_mask"] = rows(L)
+        out["labels"] = rows(W)
+        out["decoder_input_ids"] = rows(W)
+        counts = np.zeros((3, R), dtype=np.int32)
+        d_cnt = ctx.alloc(12 * max(R, 1))
+        try:
+            ctx.infill_rows_device(input_ids.ptr if R else 0, R, L, base, args, *[out[k].ptr if R else 0 for k in out],
+                                   *[d_cnt + 4 * R * k if R else 0 for k in range(3)])
+            if R:
+                ctx.d2h(counts, d_cnt)
+        finally:
+            ctx.free(d_cnt)
+        out["enc_len"], out["dec_len"], out["n_spans"] = counts[0], counts[1], counts[2]
         return out
 
     @staticmethod

@@ -392,6 +392,69 @@ int  gz_mask_rows_device(gz_ctx *ctx, const int32_t *ids_dev, int64_t n_rows, in
                          int32_t whole_word, int32_t ignore_index, int32_t *input_ids_dev, int32_t *labels_dev,
                          int32_t *n_chosen_dev);
 
+/* ---- span-corruption inputs and targets over dense rows, for encoder-decoder models -----------------------------------------
+ * The denoising objective of T5, MASS and BART-infilling: contiguous spans of whole words are chosen, each span collapses to ONE
+ * mask_id in the encoder row, and the decoder is taught to write the spans back.  The reference ships seq2seq models
+ * (models/base_model; DataCollection carries dec_input_ids beside input_ids) and reserves <mask> as id 3.  Unlike gz_mask_rows the
+ * pass makes every row SHORTER and emits a second, ragged sequence.  BART's full-sequence target needs no call: it is the
+ * caller's original row.
+ * Rows are dense [n_rows, row_len] int32; pad, bos and eos are the context's current ids (gz_table_info); mask_id is an argument.
+ * Taken from the mask rule above, unchanged:
+ *   PROTECTED        the cell's id is pad, bos, eos or mask_id
+ *   CONTINUATION     snapshot ids (gz_decoder_snapshot) whose word ends in "@@"; an id outside the snapshot is none
+ *   start(r, c), head(r, c)   as above; whole_word = 0 makes every unprotected cell its own head
+ *   g(r, c)          (row_base + r) * row_len + c, unsigned 64-bit
+ *   D(g)             Philox4x32-10 with the same counter, key and constants (0xD2511F53 / 0xCD9E8D57, 0x9E3779B9 / 0xBB67AE85).
+ *                    Only x0 and x1 are used here; the same seed gives draws correlated with gz_mask_rows, which is harmless
+ * New here:
+ *   n(r, c)          the number of starts in row r at columns <= c: the word ordinal of the cell.  It counts across protected cells
+ *   span at a start s = (r, c_s)   a span begins there when D(g(s)).x0 < t_start.  Its length in words is
+ *                    len(s) = 1 + #{k : D(g(s)).x1 >= len_t[k]}; len_t[0 .. n_len-2] are non-decreasing integers in [0, 2^32], so
+ *                    len lies in [1, n_len]; 1 <= n_len <= 16
+ *   chosen(r, c)     the cell is unprotected and some start s of row r begins a span with n(s) <= n(r, c) < n(s) + len(s).  A span
+ *                    may count across a protected cell: harmless, protected cells are never chosen and split runs anyway.
+ *                    Equivalent: with reach(s) = n(s) + len(s) at span starts and 0 elsewhere, and far(c) the running maximum of
+ *                    reach over columns <= c, a cell is chosen when it is unprotected and far(head(c)) > n(c)
+ *   run              a maximal stretch of consecutive columns of chosen cells; overlapping or touching spans merge into one run
+ *   E(r)             the encoder sequence, over columns in ascending order: a pad cell contributes nothing, wherever it stands; a
+ *                    non-pad cell that is not chosen contributes its id; the first cell of a run contributes mask_id; the other
+ *                    cells of a run contribute nothing
+ *   T(r)             the target: for each run in order, mask_id followed by the run's original ids; one eos closes the whole
+ *                    sequence.  Hence len(T) = n_chosen + n_spans + 1
+ * Outputs -- every cell is written exactly once and nothing is zeroed beforehand:
+ *   input_ids         [n_rows, row_len]    E, then pad
+ *   attention_mask    [n_rows, row_len]    1 over E, then 0
+ *   labels            [n_rows, dec_width]  T[:dec_width], then ignore_index
+ *   decoder_input_ids [n_rows, dec_width]  ([bos] + T[:-1])[:dec_width], then pad
+ *   enc_len           [n_rows] int32       len(E)
+ *   dec_len           [n_rows] int32       len(T) UNCLIPPED, so the caller sees an overflow of dec_width
+ *   n_spans           [n_rows] int32       the number of runs
+ *   attention_mask, decoder_input_ids and the three count arrays may each be NULL.  len(E) <= row_len always; len(T) can reach
+ *   row_len + 2 (nine unprotected cells, whole_word = 0, t_start = 2^32: len(T) = 11), so dec_width is an argument of its own
+ *   with a clipping rule: a cell of T at or beyond dec_width is dropped.  At p = 0.15 the mean len(T) is about row_len / 10.
+ *   infill(rows[a:b], row_base = a) == infill(rows)[a:b] on all seven outputs.
+ *   len_t is a HOST pointer in both forms (its words travel in the kernel arguments); NULL is allowed when n_len == 1.
+ *   GZ_E_INVALID: row_len < 1, n_rows < 0, row_base < 0, (row_base + n_rows) * row_len not below 2^63, dec_width < 1, t_start above
+ *   2^32, n_len outside [1, 16], len_t NULL with n_len > 1, a threshold above 2^32 or thresholds that decrease, whole_word outside
+ *   {0, 1}, ids / input_ids / labels NULL with n_rows > 0, or any two of the buffers overlapping: nothing is written.
+ *   GZ_E_NOTABLES without a decoder snapshot.  n_rows == 0 is GZ_OK and launches nothing.
+ * gz_infill_rows_device: every pointer but len_t is a DEVICE pointer.  Ordering: one launch on the context's stream, behind an
+ *   encode, window or pack call enqueued just before on the same context with no gz_sync in between.  The call returns when the
+ *   rows are complete.
+ * gz_infill_rows: host pointers; the rows go up through the library's pinned staging, the device form runs, the arrays that were
+ *   asked for come back.
+ * Not here: sentinel families (the vocabulary has one <mask>), zero-length insertions, sentence permutation, remapping the
+ *   segment_ids / position_ids of packed rows through the compaction (packed rows are rows: their eos bos pairs split runs). */
+int  gz_infill_rows(gz_ctx *ctx, const int32_t *ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed,
+                    uint64_t t_start, const uint64_t *len_t, int32_t n_len, int32_t mask_id, int32_t whole_word,
+                    int32_t ignore_index, int32_t dec_width, int32_t *input_ids, int32_t *attention_mask, int32_t *labels,
+                    int32_t *decoder_input_ids, int32_t *enc_len, int32_t *dec_len, int32_t *n_spans);
+int  gz_infill_rows_device(gz_ctx *ctx, const int32_t *ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed,
+                           uint64_t t_start, const uint64_t *len_t, int32_t n_len, int32_t mask_id, int32_t whole_word,
+                           int32_t ignore_index, int32_t dec_width, int32_t *input_ids_dev, int32_t *attention_mask_dev,
+                           int32_t *labels_dev, int32_t *decoder_input_ids_dev, int32_t *enc_len_dev, int32_t *dec_len_dev,
+                           int32_t *n_spans_dev);
+
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
  *   GZ_PP_UNICODE  convert_unicode      preprocess.py:16-36   base letter + combining tone mark -> precomposed letter
