@@ -2,6 +2,7 @@
 // No C++ exception leaves this file; there is no CPU fallback for any entry point that computes.
 #include "../../include/genz_tokenize.h"
 #include "gz_kernels.h"
+#include "gz_rowrules.h"
 
 #include <dlfcn.h>
 #include <cstdarg>
@@ -155,12 +156,11 @@ struct gz_ctx {
     std::string dec_unk;
     bool dec_unk_set = false;
     DBuf t_dec_cont;                                                                                    // continuation bitmap of the decoder snapshot (gz_mask_rows*)
-    DBuf t_dec_entries, t_dec_bytes, w_dec_ids, w_dec_roff, w_dec_rb, w_dec_ooff, w_dec_out;
-    DBuf w_win_cnt, w_win_ids, w_win_roff, w_win_off, w_win_out, w_win_mask, w_win_meta;               // overlapping windows (gz_window_rows*)
-    DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol, w_pk_dlen, w_pk_roff, w_pk_ids, w_pk_inoff, w_pk_out[4];   // packed rows (gz_pack_rows*)
-    DBuf w_mk_ids, w_mk_out, w_mk_lab, w_mk_cnt;                                                        // masked-LM rows (gz_mask_rows)
-    DBuf w_if_ids, w_if_out, w_if_am, w_if_lab, w_if_dec, w_if_cnt;                                     // span-corruption rows (gz_infill_rows)
-    DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_pp_in, w_pp_inoff, w_ppctl, w_pplen32, w_pplb;      // text pre-pass
+    DBuf t_dec_entries, t_dec_bytes, w_dec_rb;
+    DBuf w_win_cnt;                                                                                     // overlapping windows (gz_window_rows*)
+    DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol;              // packed rows (gz_pack_rows*)
+    DBuf w_rows_in, w_rows_off, w_rows_out[4], w_rows_small;      // staging of the host forms of the row calls and the pre-pass (gz_rows_api.inc: WORKSPACE)
+    DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_ppctl, w_pplen32, w_pplb;                             // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
     // host path with copies overlapped (gz_encode_batch_csr): copy-in / copy-out streams, per-sub-batch events and buffers
     hipStream_t s_in = nullptr, s_out = nullptr;
@@ -1045,13 +1045,10 @@ try {
     if (c->h_pick) hipHostFree(c->h_pick);
     release(c->w_pick); release(c->w_rowoff32);
     for (auto& t2 : c->w_tiny) for (auto& t : t2) release(t);
-    for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_pp_in, &c->w_pp_inoff, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
-    for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_ids, &c->w_dec_roff, &c->w_dec_rb, &c->w_dec_ooff, &c->w_dec_out}) release(*b);
-    for (DBuf* b : {&c->w_win_cnt, &c->w_win_ids, &c->w_win_roff, &c->w_win_off, &c->w_win_out, &c->w_win_mask, &c->w_win_meta}) release(*b);
-    for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol, &c->w_pk_dlen, &c->w_pk_roff, &c->w_pk_ids,
-                    &c->w_pk_inoff, &c->w_pk_out[0], &c->w_pk_out[1], &c->w_pk_out[2], &c->w_pk_out[3]}) release(*b);
-    for (DBuf* b : {&c->w_mk_ids, &c->w_mk_out, &c->w_mk_lab, &c->w_mk_cnt}) release(*b);
-    for (DBuf* b : {&c->w_if_ids, &c->w_if_out, &c->w_if_am, &c->w_if_lab, &c->w_if_dec, &c->w_if_cnt}) release(*b);
+    for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
+    for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
+    for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
+    for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
     for (DBuf* b : {&c->t_merges, &c->t_symids, &c->t_bmp, &c->t_astral, &c->t_struct, &c->t_words2, &c->w_text, &c->w_toff, &c->w_pair,
@@ -1899,604 +1896,7 @@ try {
     return GZ_OK;
 } GZ_CATCH(c)
 
-// ---- batch decode ----------------------------------------------------------------------------------------------------
-namespace {
-constexpr size_t GZ_DEC_UNK_MAX = 4096;
-
-uint32_t dec_flags(const std::string& w)
-{
-    uint32_t f = (uint32_t)w.size();
-    if (w.size() >= 2 && w[w.size() - 1] == '@' && w[w.size() - 2] == '@') f |= GZ_DEC_ENDS_ATAT;
-    if (w.find("@@ ") != std::string::npos) f |= GZ_DEC_INNER;
-    return f;
-}
-
-// the table entry of a word whose bytes are (or would be) at `off` of the byte arena
-GzDecEntry dec_entry_of(const std::string& w, size_t off)
-{
-    GzDecEntry e{dec_flags(w), {(uint32_t)off, 0u, 0u}};
-    if (w.size() <= 12 && !(e.len_flags & GZ_DEC_INNER)) {
-        e.len_flags |= GZ_DEC_INLINE;
-        e.w[0] = 0;
-        for (size_t k = 0; k < w.size(); ++k) e.w[k >> 2] |= (uint32_t)(uint8_t)w[k] << (8 * (k & 3));
-    }
-    return e;
-}
-
-int dec_set_unk(gz_ctx* c, const uint8_t* unk, int32_t unk_len)
-{
-    if (unk_len < 0 || (size_t)unk_len > GZ_DEC_UNK_MAX) return fail(c, GZ_E_LIMIT, "unk string longer than %zu bytes", GZ_DEC_UNK_MAX);
-    const std::string u((const char*)unk, (size_t)unk_len);
-    if (c->dec_unk_set && u == c->dec_unk) return GZ_OK;
-    int rcs;
-    if (unk_len && (rcs = copy_in(c, (uint8_t*)c->t_dec_bytes.p + c->dec_bytes_len, unk, (size_t)unk_len, c->stream))) return rcs;
-    const GzDecEntry e = dec_entry_of(u, c->dec_bytes_len);
-    if ((rcs = copy_in(c, (GzDecEntry*)c->t_dec_entries.p + c->dec_n_ids, &e, sizeof e, c->stream))) return rcs;
-    c->dec_unk = u;
-    c->dec_unk_set = true;
-    return GZ_OK;
-}
-
-// both passes; *total = bytes of the whole batch.  out_dev may be nullptr (sizes only).
-int decode_device_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, const uint8_t* unk,
-                         int32_t unk_len, uint8_t* out_dev, int64_t capacity, int64_t* out_off_dev, int64_t* total)
-{
-    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = dec_set_unk(c, unk, unk_len))) return rc;
-    if ((rc = ensure(c, c->w_dec_rb, (size_t)(n_rows + 1) * 8))) return rc;
-    GzDecTable D{(const GzDecEntry*)c->t_dec_entries.p, (const uint8_t*)c->t_dec_bytes.p, c->dec_n_ids};
-    gz_launch_decode(D, ids_dev, row_off_dev, n_rows, (int64_t*)c->w_dec_rb.p, out_off_dev, nullptr, 0, c->stream);
-    *total = 0;
-    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
-    *h_total = 0;
-    if (n_rows > 0) HIPCHK(c, hipMemcpyAsync(h_total, out_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    else HIPCHK(c, hipMemsetAsync(out_off_dev, 0, 8, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *total = *h_total;
-    if (!out_dev) return GZ_OK;
-    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "decode needs %lld bytes, capacity is %lld", (long long)*total, (long long)capacity);
-    gz_launch_decode(D, ids_dev, row_off_dev, n_rows, nullptr, out_off_dev, out_dev, capacity, c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-}
-}  // namespace
-
-int gz_decoder_snapshot(gz_ctx* c)
-try {
-    if (!c) return GZ_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    // {v: k for k, v in encoder.items()} (tokenize.py:40): the last word wins on an id collision
-    int32_t n_ids = 0;
-    for (int32_t id : c->host.enc_ids) if (id + 1 > n_ids) n_ids = id + 1;
-    std::vector<int64_t> last((size_t)n_ids, -1);
-    for (size_t i = 0; i < c->host.enc_ids.size(); ++i) if (c->host.enc_ids[i] >= 0) last[(size_t)c->host.enc_ids[i]] = (int64_t)i;
-    std::vector<GzDecEntry> ent((size_t)n_ids + 1, GzDecEntry{GZ_DEC_ABSENT, {0u, 0u, 0u}});
-    std::string bytes;
-    for (int32_t id = 0; id < n_ids; ++id) {
-        if (last[(size_t)id] < 0) continue;
-        const std::string& w = c->host.enc_words[(size_t)last[(size_t)id]];
-        if (w.size() > GZ_DEC_LEN_MASK || bytes.size() + w.size() > 0xFFFF0000ull) return fail(c, GZ_E_LIMIT, "vocabulary too large for the decoder arena");
-        ent[(size_t)id] = dec_entry_of(w, bytes.size());
-        bytes += w;
-    }
-    ent[(size_t)n_ids] = GzDecEntry{GZ_DEC_INLINE, {0u, 0u, 0u}};                  // (the unk string: set per call, dec_set_unk)
-    std::vector<uint32_t> cont((size_t)n_ids / 32 + 1, 0u);                       // which ids continue a word: one bit each (gz_mask_rows*)
-    for (int32_t id = 0; id < n_ids; ++id)
-        if (ent[(size_t)id].len_flags != GZ_DEC_ABSENT && (ent[(size_t)id].len_flags & GZ_DEC_ENDS_ATAT)) cont[(size_t)id >> 5] |= 1u << (id & 31);
-    int rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = ensure(c, c->t_dec_entries, ent.size() * sizeof(GzDecEntry)))) return rc;
-    if ((rc = ensure(c, c->t_dec_bytes, bytes.size() + GZ_DEC_UNK_MAX + 16))) return rc;
-    if ((rc = ensure(c, c->t_dec_cont, cont.size() * 4))) return rc;
-    if ((rc = copy_in(c, c->t_dec_entries.p, ent.data(), ent.size() * sizeof(GzDecEntry), c->stream))) return rc;
-    if ((rc = copy_in(c, c->t_dec_cont.p, cont.data(), cont.size() * 4, c->stream))) return rc;
-    if (!bytes.empty() && (rc = copy_in(c, c->t_dec_bytes.p, bytes.data(), bytes.size(), c->stream))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->dec_n_ids = n_ids;
-    c->dec_bytes_len = bytes.size();
-    c->dec_unk_set = false;
-    c->have_dec = true;
-    return GZ_OK;
-} GZ_CATCH(c)
-
-int gz_decode_batch_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, const uint8_t* unk,
-                           int32_t unk_len, uint8_t* out_dev, int64_t capacity, int64_t* out_off_dev, int64_t* total_host)
-try {
-    if (!c || !row_off_dev || !out_off_dev || !total_host || n_rows < 0 || (!unk && unk_len) || capacity < 0)
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return decode_device_locked(c, ids_dev, row_off_dev, n_rows, unk, unk_len, out_dev, capacity, out_off_dev, total_host);
-} GZ_CATCH(c)
-
-int gz_decode_batch(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, const uint8_t* unk, int32_t unk_len,
-                    uint8_t* out, int64_t capacity, int64_t* out_off)
-try {
-    if (!c || !row_off || !out_off || n_rows < 0 || (!unk && unk_len) || capacity < 0 || (capacity > 0 && !out))
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    const int64_t n_ids = row_off[n_rows] - row_off[0];
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(c, GZ_E_INVALID, "bad row offsets");
-    for (int64_t r = 0; r < n_rows; ++r) if (row_off[r + 1] < row_off[r]) return fail(c, GZ_E_INVALID, "row offsets must not decrease");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->w_dec_ids, (size_t)(n_ids + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->w_dec_roff, (size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_dec_ooff, (size_t)(n_rows + 1) * 8))) return rc;
-    if (n_ids && (rc = copy_in(c, c->w_dec_ids.p, ids + row_off[0], (size_t)n_ids * 4, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_dec_roff.p, row_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    int64_t total = 0;
-    if ((rc = decode_device_locked(c, (const int32_t*)c->w_dec_ids.p - row_off[0], (const int64_t*)c->w_dec_roff.p, n_rows, unk, unk_len, nullptr, 0,
-                                   (int64_t*)c->w_dec_ooff.p, &total))) return rc;
-    if ((rc = copy_out(c, out_off, c->w_dec_ooff.p, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    if (total > capacity) return fail(c, GZ_E_CAPACITY, "decode needs %lld bytes, capacity is %lld", (long long)total, (long long)capacity);
-    if (total == 0) return GZ_OK;
-    if ((rc = ensure(c, c->w_dec_out, (size_t)total))) return rc;
-    GzDecTable D{(const GzDecEntry*)c->t_dec_entries.p, (const uint8_t*)c->t_dec_bytes.p, c->dec_n_ids};
-    gz_launch_decode(D, (const int32_t*)c->w_dec_ids.p - row_off[0], (const int64_t*)c->w_dec_roff.p, n_rows, nullptr, (int64_t*)c->w_dec_ooff.p,
-                     (uint8_t*)c->w_dec_out.p, total, c->stream);
-    {
-        HostPool pool(pool_threads(c, (size_t)total));
-        if ((rc = copy_out(c, out, c->w_dec_out.p, (size_t)total, c->stream, &pool))) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-// ---- overlapping max_len windows ------------------------------------------------------------------------------------
-namespace {
-// the fill pass over win_off, enqueued on the context's stream; bos / eos / pad are the context's current special ids
-void window_fill(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
-                 int32_t skip_back, const int64_t* win_off_dev, int64_t n_win, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc,
-                 int32_t* win_start, int32_t* win_n_real)
-{
-    GzWinArgs A{ids_dev, row_off_dev, n_rows, win_off_dev, n_win, max_len, max_len - 2, max_len - 2 - stride, skip_front, skip_back,
-                c->dev.bos_id, c->dev.eos_id, c->dev.pad_id, out_ids, out_mask, win_doc, win_start, win_n_real};
-    gz_launch_window_fill(A, c->stream);
-}
-
-// Both passes on the context's stream, behind whatever it holds (an encode call's forked streams have rejoined it when that call
-// returns).  *total = windows of the batch.  out_ids == nullptr: the count pass only.
-int window_device_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
-                         int32_t skip_front, int32_t skip_back, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc, int32_t* win_start,
-                         int32_t* win_n_real, int64_t* win_off_dev, int64_t capacity, int64_t* total)
-{
-    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->w_win_cnt, (size_t)(n_rows + 1) * 8))) return rc;
-    const int32_t room = max_len - 2, step = room - stride;
-    gz_launch_window_count(row_off_dev, n_rows, room, step, skip_front + skip_back, (int64_t*)c->w_win_cnt.p, win_off_dev, c->stream);
-    *total = 0;
-    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
-    *h_total = 0;
-    if (n_rows > 0) HIPCHK(c, hipMemcpyAsync(h_total, win_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    else HIPCHK(c, hipMemsetAsync(win_off_dev, 0, 8, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *total = *h_total;
-    if (!out_ids) return GZ_OK;
-    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)*total, (long long)capacity);
-    window_fill(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, win_off_dev, *total, out_ids, out_mask, win_doc, win_start,
-                win_n_real);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-}
-
-bool window_rule_ok(int32_t max_len, int32_t stride, int32_t skip_front, int32_t skip_back)
-{
-    return max_len >= 3 && stride >= 0 && stride <= max_len - 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1;
-}
-}  // namespace
-
-int gz_window_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
-                          int32_t skip_front, int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* win_doc_dev,
-                          int32_t* win_start_dev, int32_t* win_n_real_dev, int64_t* win_off_dev, int64_t capacity_windows, int64_t* total_host)
-try {
-    if (!c || !row_off_dev || !win_off_dev || !total_host || n_rows < 0 || capacity_windows < 0)
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
-        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
-    std::lock_guard<std::mutex> lk(c->mu);
-    return window_device_locked(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, input_ids_dev, attention_mask_dev,
-                                win_doc_dev, win_start_dev, win_n_real_dev, win_off_dev, capacity_windows, total_host);
-} GZ_CATCH(c)
-
-int gz_window_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
-                   int32_t skip_back, int32_t* input_ids, int32_t* attention_mask, int32_t* win_doc, int32_t* win_start, int32_t* win_n_real,
-                   int64_t* win_off, int64_t capacity_windows, int64_t* total_host)
-try {
-    if (!c || !row_off || !win_off || !total_host || n_rows < 0 || capacity_windows < 0)
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
-        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
-    const int64_t n_ids = row_off[n_rows] - row_off[0];
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(c, GZ_E_INVALID, "bad row offsets");
-    for (int64_t r = 0; r < n_rows; ++r) if (row_off[r + 1] < row_off[r]) return fail(c, GZ_E_INVALID, "row offsets must not decrease");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->w_win_ids, (size_t)(n_ids + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->w_win_roff, (size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_win_off, (size_t)(n_rows + 1) * 8))) return rc;
-    if (n_ids && (rc = copy_in(c, c->w_win_ids.p, ids + row_off[0], (size_t)n_ids * 4, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_win_roff.p, row_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    const int32_t* const ids_dev = (const int32_t*)c->w_win_ids.p - row_off[0];
-    const int64_t* const roff_dev = (const int64_t*)c->w_win_roff.p;
-    int64_t total = 0;
-    if ((rc = window_device_locked(c, ids_dev, roff_dev, n_rows, max_len, stride, skip_front, skip_back, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   (int64_t*)c->w_win_off.p, 0, &total))) return rc;
-    *total_host = total;
-    if ((rc = copy_out(c, win_off, c->w_win_off.p, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    if (!input_ids) return GZ_OK;
-    if (total > capacity_windows)
-        return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)total, (long long)capacity_windows);
-    if (total == 0) return GZ_OK;
-    const size_t cells = (size_t)total * (size_t)max_len;
-    if ((rc = ensure(c, c->w_win_out, cells * 4))) return rc;
-    if (attention_mask && (rc = ensure(c, c->w_win_mask, cells * 4))) return rc;
-    if ((rc = ensure(c, c->w_win_meta, (size_t)total * 12))) return rc;
-    int32_t* const meta = (int32_t*)c->w_win_meta.p;
-    window_fill(c, ids_dev, roff_dev, n_rows, max_len, stride, skip_front, skip_back, (const int64_t*)c->w_win_off.p, total, (int32_t*)c->w_win_out.p,
-                attention_mask ? (int32_t*)c->w_win_mask.p : nullptr, win_doc ? meta : nullptr, win_start ? meta + total : nullptr,
-                win_n_real ? meta + 2 * total : nullptr);
-    {
-        HostPool pool(pool_threads(c, cells * 4));
-        if ((rc = copy_out(c, input_ids, c->w_win_out.p, cells * 4, c->stream, &pool))) return rc;
-        if (attention_mask && (rc = copy_out(c, attention_mask, c->w_win_mask.p, cells * 4, c->stream, &pool))) return rc;
-    }
-    if (win_doc && (rc = copy_out(c, win_doc, meta, (size_t)total * 4, c->stream))) return rc;
-    if (win_start && (rc = copy_out(c, win_start, meta + total, (size_t)total * 4, c->stream))) return rc;
-    if (win_n_real && (rc = copy_out(c, win_n_real, meta + 2 * total, (size_t)total * 4, c->stream))) return rc;
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-// ---- short documents packed into rows of max_len ------------------------------------------------------------------------
-namespace {
-// The maps of a batch on the context's stream, behind whatever it holds: doc_len, seg_off, the row heads in pack_off, doc_row, doc_col.
-// A map the caller does not take lives in the context's workspace (pack_off is the caller's).  A gets the pointers the fill pass
-// needs; *total = R, read back from the device.  fill: the fill pass goes right behind the maps -- it takes R from device memory,
-// writes nothing when R exceeds A.capacity, and writes doc_col in place of the col pass -- so the host waits once, for everything.
-int pack_maps_locked(gz_ctx* c, GzPackArgs& A, int64_t* total, bool fill)
-{
-    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = A.n_rows;
-    int rc;
-    if (!A.seg_off) { if ((rc = ensure(c, c->w_pk_seg, (size_t)(n + 1) * 8))) return rc; A.seg_off = (int64_t*)c->w_pk_seg.p; }
-    if (!A.doc_row) { if ((rc = ensure(c, c->w_pk_drow, (size_t)(n + 1) * 4))) return rc; A.doc_row = (int32_t*)c->w_pk_drow.p; }
-    if (!A.doc_col) { if ((rc = ensure(c, c->w_pk_dcol, (size_t)(n + 1) * 4))) return rc; A.doc_col = (int32_t*)c->w_pk_dcol.p; }
-    const size_t tiles = (size_t)gz_pack_tiles(n), groups = (size_t)gz_pack_groups(n), K = (size_t)gz_pack_entries(A.max_len);
-    if ((rc = ensure(c, c->w_pk_len, (size_t)(n + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_pk_jc, (size_t)(n + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_pk_nxt, (size_t)(n + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->w_pk_jc2, (groups * K + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_pk_tile, (tiles + 1) * 8))) return rc;
-    A.len64 = (int64_t*)c->w_pk_len.p; A.jc = (int32_t*)c->w_pk_jc.p; A.nxt = (int32_t*)c->w_pk_nxt.p; A.jc2 = (int32_t*)c->w_pk_jc2.p; A.tile = (int32_t*)c->w_pk_tile.p;
-    A.total = (int64_t*)c->w_pk_tile.p + tiles;
-    A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id; A.pad_id = c->dev.pad_id;
-    *total = 0;
-    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
-    *h_total = 0;
-    if (n > 0) {
-        gz_launch_pack_maps(A, !fill, c->stream);
-        if (fill) gz_launch_pack_fill(A, c->stream);
-        HIPCHK(c, hipMemcpyAsync(h_total, A.total, 8, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPCHK(c, hipMemsetAsync(A.pack_off, 0, 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(A.seg_off, 0, 8, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    *total = *h_total;
-    return GZ_OK;
-}
-
-const char* const kPackRule = "packed rows need max_len >= 3, skips of 0 or 1 and fewer than 2^31 - 4096 documents";
-bool pack_rule_ok(int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back)
-{
-    return max_len >= 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1 && n_rows < INT32_MAX - 4096;
-}
-}  // namespace
-
-int gz_pack_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t skip_front,
-                        int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* segment_ids_dev, int32_t* position_ids_dev,
-                        int32_t* doc_row_dev, int32_t* doc_col_dev, int32_t* doc_len_dev, int64_t* pack_off_dev, int64_t* seg_off_dev,
-                        int64_t capacity_rows, int64_t* total_host)
-try {
-    if (!c || !row_off_dev || !pack_off_dev || !total_host || n_rows < 0 || capacity_rows < 0)
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
-    std::lock_guard<std::mutex> lk(c->mu);
-    GzPackArgs A{};
-    A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows; A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
-    A.doc_row = doc_row_dev; A.doc_col = doc_col_dev; A.doc_len = doc_len_dev; A.pack_off = pack_off_dev; A.seg_off = seg_off_dev;
-    A.capacity = capacity_rows;
-    A.out_ids = input_ids_dev; A.out_mask = attention_mask_dev; A.out_seg = segment_ids_dev; A.out_pos = position_ids_dev;
-    int rc;
-    if ((rc = pack_maps_locked(c, A, total_host, input_ids_dev != nullptr))) return rc;
-    if (!input_ids_dev || *total_host <= capacity_rows) return GZ_OK;
-    gz_launch_pack_col(A, c->stream);                                      // (the fill wrote nothing, doc_col included: the maps are valid all the same)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)*total_host, (long long)capacity_rows);
-} GZ_CATCH(c)
-
-int gz_pack_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back,
-                 int32_t* input_ids, int32_t* attention_mask, int32_t* segment_ids, int32_t* position_ids, int32_t* doc_row, int32_t* doc_col,
-                 int32_t* doc_len, int64_t* pack_off, int64_t* seg_off, int64_t capacity_rows, int64_t* total_host)
-try {
-    if (!c || !row_off || !pack_off || !total_host || n_rows < 0 || capacity_rows < 0)
-        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
-    const int64_t n_ids = row_off[n_rows] - row_off[0];
-    if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(c, GZ_E_INVALID, "bad row offsets");
-    for (int64_t r = 0; r < n_rows; ++r) if (row_off[r + 1] < row_off[r]) return fail(c, GZ_E_INVALID, "row offsets must not decrease");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure(c, c->w_pk_ids, (size_t)(n_ids + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->w_pk_inoff, (size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_pk_roff, (size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->w_pk_dlen, (size_t)(n_rows + 1) * 4))) return rc;
-    if (n_ids && (rc = copy_in(c, c->w_pk_ids.p, ids + row_off[0], (size_t)n_ids * 4, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_pk_inoff.p, row_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    GzPackArgs A{};
-    A.ids = (const int32_t*)c->w_pk_ids.p - row_off[0]; A.row_off = (const int64_t*)c->w_pk_inoff.p; A.n_rows = n_rows;
-    A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
-    A.doc_len = (int32_t*)c->w_pk_dlen.p; A.pack_off = (int64_t*)c->w_pk_roff.p;                  // (the other maps: the workspace's)
-    int64_t total = 0;
-    if ((rc = pack_maps_locked(c, A, &total, false))) return rc;
-    *total_host = total;
-    if ((rc = copy_out(c, pack_off, A.pack_off, (size_t)(total + 1) * 8, c->stream))) return rc;
-    if (seg_off && (rc = copy_out(c, seg_off, A.seg_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
-    if (doc_row && (rc = copy_out(c, doc_row, A.doc_row, (size_t)n_rows * 4, c->stream))) return rc;
-    if (doc_col && (rc = copy_out(c, doc_col, A.doc_col, (size_t)n_rows * 4, c->stream))) return rc;
-    if (doc_len && (rc = copy_out(c, doc_len, A.doc_len, (size_t)n_rows * 4, c->stream))) return rc;
-    if (!input_ids) return GZ_OK;
-    if (total > capacity_rows)
-        return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)total, (long long)capacity_rows);
-    if (total == 0) return GZ_OK;
-    const size_t cells = (size_t)total * (size_t)max_len;
-    int32_t* const host[4] = {input_ids, attention_mask, segment_ids, position_ids};
-    int32_t* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; ++k)
-        if (host[k]) { if ((rc = ensure(c, c->w_pk_out[k], cells * 4))) return rc; dev[k] = (int32_t*)c->w_pk_out[k].p; }
-    A.capacity = total;
-    A.out_ids = dev[0]; A.out_mask = dev[1]; A.out_seg = dev[2]; A.out_pos = dev[3];
-    gz_launch_pack_fill(A, c->stream);
-    {
-        HostPool pool(pool_threads(c, cells * 4));
-        for (int k = 0; k < 4; ++k)
-            if (host[k] && (rc = copy_out(c, host[k], dev[k], cells * 4, c->stream, &pool))) return rc;
-    }
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-// ---- masked-LM inputs and labels over dense rows -------------------------------------------------------------------------
-namespace {
-struct MaskRule {
-    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_sel, t1, t2;
-    int32_t rand_lo, rand_hi, mask_id, whole_word, ignore_index;
-};
-const char* const kMaskRule = "masked rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, thresholds in "
-                              "[0, 2^32] with t1 <= t2, rand_lo < rand_hi and whole_word 0 or 1";
-bool mask_rule_ok(const MaskRule& M)
-{
-    constexpr uint64_t one = 1ull << 32;
-    if (M.row_len < 1 || M.n_rows < 0 || M.row_base < 0) return false;
-    const unsigned __int128 cells = ((unsigned __int128)M.row_base + (unsigned __int128)M.n_rows) * (unsigned __int128)M.row_len;
-    if (cells >> 63) return false;
-    return M.t_sel <= one && M.t1 <= one && M.t2 <= one && M.t1 <= M.t2 && M.rand_lo < M.rand_hi && (M.whole_word == 0 || M.whole_word == 1);
-}
-// the cell arrays and the counts are pairwise disjoint (the heads are read from neighbours' ORIGINAL ids); n_rows * row_len > 0
-bool mask_buffers_ok(const MaskRule& M, const int32_t* ids, const int32_t* out_ids, const int32_t* labels, const int32_t* n_chosen)
-{
-    if (!ids || !out_ids || !labels) return false;
-    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
-    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u;
-    const uintptr_t p[4] = {(uintptr_t)ids, (uintptr_t)out_ids, (uintptr_t)labels, (uintptr_t)n_chosen};
-    const uintptr_t n[4] = {cells, cells, cells, n_chosen ? (uintptr_t)M.n_rows * 4u : 0u};
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            if (n[a] && n[b] && (p[a] >= p[b] ? p[a] - p[b] < n[b] : p[b] - p[a] < n[a])) return false;       // (differences: no end address to wrap)
-    return true;
-}
-// the one launch on the context's stream, behind whatever it holds
-void mask_launch(gz_ctx* c, const MaskRule& M, const int32_t* ids_dev, int32_t* out_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
-{
-    GzMaskArgs A{};
-    A.ids = ids_dev; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
-    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
-    A.t_sel = M.t_sel; A.t1 = M.t1; A.t2 = M.t2;
-    A.rand_lo = M.rand_lo; A.rand_span = (uint32_t)M.rand_hi - (uint32_t)M.rand_lo;
-    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word;
-    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
-    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
-    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
-    A.out_ids = out_dev; A.labels = labels_dev; A.n_chosen = n_chosen_dev;
-    gz_launch_mask(A, c->stream);
-}
-}  // namespace
-
-int gz_mask_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel,
-                        uint64_t t1, uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index,
-                        int32_t* input_ids_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
-try {
-    if (!c) return GZ_E_INVALID;
-    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
-    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
-    if (n_rows > 0 && !mask_buffers_ok(M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev))
-        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
-    if (n_rows == 0) return GZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    mask_launch(c, M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-int gz_mask_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel, uint64_t t1,
-                 uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t* input_ids,
-                 int32_t* labels, int32_t* n_chosen)
-try {
-    if (!c) return GZ_E_INVALID;
-    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
-    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
-    if (n_rows > 0 && !mask_buffers_ok(M, ids, input_ids, labels, n_chosen))
-        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
-    if (n_rows == 0) return GZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t cells = (size_t)n_rows * (size_t)row_len;
-    int rc;
-    if ((rc = ensure(c, c->w_mk_ids, cells * 4))) return rc;
-    if ((rc = ensure(c, c->w_mk_out, cells * 4))) return rc;
-    if ((rc = ensure(c, c->w_mk_lab, cells * 4))) return rc;
-    if (n_chosen && (rc = ensure(c, c->w_mk_cnt, (size_t)n_rows * 4))) return rc;
-    if ((rc = copy_in(c, c->w_mk_ids.p, ids, cells * 4, c->stream))) return rc;
-    mask_launch(c, M, (const int32_t*)c->w_mk_ids.p, (int32_t*)c->w_mk_out.p, (int32_t*)c->w_mk_lab.p, n_chosen ? (int32_t*)c->w_mk_cnt.p : nullptr);
-    {
-        HostPool pool(pool_threads(c, cells * 4));
-        if ((rc = copy_out(c, input_ids, c->w_mk_out.p, cells * 4, c->stream, &pool))) return rc;
-        if ((rc = copy_out(c, labels, c->w_mk_lab.p, cells * 4, c->stream, &pool))) return rc;
-    }
-    if (n_chosen && (rc = copy_out(c, n_chosen, c->w_mk_cnt.p, (size_t)n_rows * 4, c->stream))) return rc;
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-// ---- span-corruption inputs and targets over dense rows -------------------------------------------------------------------
-namespace {
-struct InfillRule {
-    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_start; const uint64_t* len_t;
-    int32_t n_len, mask_id, whole_word, ignore_index, dec_width;
-};
-struct InfillBufs {
-    const int32_t* ids; int32_t* input_ids; int32_t* attention_mask; int32_t* labels; int32_t* decoder_input_ids;
-    int32_t* enc_len; int32_t* dec_len; int32_t* n_spans;
-};
-const char* const kInfillRule = "infill rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, dec_width >= 1, "
-                                "t_start in [0, 2^32], 1 <= n_len <= 16 with n_len - 1 non-decreasing thresholds in [0, 2^32] and whole_word 0 or 1";
-bool infill_rule_ok(const InfillRule& M)
-{
-    constexpr uint64_t one = 1ull << 32;
-    if (M.row_len < 1 || M.n_rows < 0 || M.row_base < 0 || M.dec_width < 1) return false;
-    const unsigned __int128 cells = ((unsigned __int128)M.row_base + (unsigned __int128)M.n_rows) * (unsigned __int128)M.row_len;
-    if (cells >> 63) return false;
-    if (M.t_start > one || M.n_len < 1 || M.n_len > 16 || (M.whole_word != 0 && M.whole_word != 1)) return false;
-    if (M.n_len > 1 && !M.len_t) return false;
-    for (int k = 0; k + 1 < M.n_len; ++k)
-        if (M.len_t[k] > one || (k > 0 && M.len_t[k] < M.len_t[k - 1])) return false;
-    return true;
-}
-// the eight arrays are pairwise disjoint (every cell is read from the ORIGINAL rows and written once); n_rows > 0
-bool infill_buffers_ok(const InfillRule& M, const InfillBufs& B)
-{
-    if (!B.ids || !B.input_ids || !B.labels) return false;
-    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
-    if ((uint64_t)M.n_rows * (uint64_t)M.dec_width > (uint64_t)(UINTPTR_MAX / 4)) return false;
-    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u, dec = (uintptr_t)M.n_rows * (uintptr_t)M.dec_width * 4u,
-                    cnt = (uintptr_t)M.n_rows * 4u;
-    const uintptr_t p[8] = {(uintptr_t)B.ids, (uintptr_t)B.input_ids, (uintptr_t)B.attention_mask, (uintptr_t)B.labels,
-                            (uintptr_t)B.decoder_input_ids, (uintptr_t)B.enc_len, (uintptr_t)B.dec_len, (uintptr_t)B.n_spans};
-    const uintptr_t n[8] = {cells, cells, cells, dec, dec, cnt, cnt, cnt};
-    for (int a = 0; a < 8; ++a)
-        for (int b = a + 1; b < 8; ++b)
-            if (p[a] && p[b] && (p[a] >= p[b] ? p[a] - p[b] < n[b] : p[b] - p[a] < n[a])) return false;       // (differences: no end address to wrap)
-    return true;
-}
-// the one launch on the context's stream, behind whatever it holds; every pointer of B a device pointer
-void infill_launch(gz_ctx* c, const InfillRule& M, const InfillBufs& B)
-{
-    GzInfillArgs A{};
-    A.ids = B.ids; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
-    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
-    A.t_start = M.t_start; A.n_len = M.n_len;
-    for (int k = 0; k < 15; ++k) A.len_t[k] = k + 1 < M.n_len ? M.len_t[k] : 1ull << 32;       // (len_t is a host pointer: its words travel in the arguments)
-    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word; A.dec_width = M.dec_width;
-    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
-    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
-    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
-    A.out_ids = B.input_ids; A.out_mask = B.attention_mask; A.labels = B.labels; A.dec_ids = B.decoder_input_ids;
-    A.enc_len = B.enc_len; A.dec_len = B.dec_len; A.n_spans = B.n_spans;
-    gz_launch_infill(A, c->stream);
-}
-}  // namespace
-
-int gz_infill_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
-                          const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
-                          int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* labels_dev, int32_t* decoder_input_ids_dev,
-                          int32_t* enc_len_dev, int32_t* dec_len_dev, int32_t* n_spans_dev)
-try {
-    if (!c) return GZ_E_INVALID;
-    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
-    const InfillBufs B{ids_dev, input_ids_dev, attention_mask_dev, labels_dev, decoder_input_ids_dev, enc_len_dev, dec_len_dev, n_spans_dev};
-    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
-    if (n_rows > 0 && !infill_buffers_ok(M, B))
-        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
-    if (n_rows == 0) return GZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    infill_launch(c, M, B);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
-
-int gz_infill_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
-                   const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
-                   int32_t* input_ids, int32_t* attention_mask, int32_t* labels, int32_t* decoder_input_ids, int32_t* enc_len, int32_t* dec_len,
-                   int32_t* n_spans)
-try {
-    if (!c) return GZ_E_INVALID;
-    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
-    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
-    if (n_rows > 0 && !infill_buffers_ok(M, InfillBufs{ids, input_ids, attention_mask, labels, decoder_input_ids, enc_len, dec_len, n_spans}))
-        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
-    if (n_rows == 0) return GZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t cells = (size_t)n_rows * (size_t)row_len * 4, dec = (size_t)n_rows * (size_t)dec_width * 4, cnt = (size_t)n_rows * 4;
-    int32_t* const counts[3] = {enc_len, dec_len, n_spans};
-    const bool any_count = enc_len || dec_len || n_spans;
-    int rc;
-    if ((rc = ensure(c, c->w_if_ids, cells))) return rc;
-    if ((rc = ensure(c, c->w_if_out, cells))) return rc;
-    if (attention_mask && (rc = ensure(c, c->w_if_am, cells))) return rc;
-    if ((rc = ensure(c, c->w_if_lab, dec))) return rc;
-    if (decoder_input_ids && (rc = ensure(c, c->w_if_dec, dec))) return rc;
-    if (any_count && (rc = ensure(c, c->w_if_cnt, 3 * cnt))) return rc;
-    if ((rc = copy_in(c, c->w_if_ids.p, ids, cells, c->stream))) return rc;
-    InfillBufs B{(const int32_t*)c->w_if_ids.p, (int32_t*)c->w_if_out.p, attention_mask ? (int32_t*)c->w_if_am.p : nullptr, (int32_t*)c->w_if_lab.p,
-                 decoder_input_ids ? (int32_t*)c->w_if_dec.p : nullptr, nullptr, nullptr, nullptr};
-    int32_t** const slots[3] = {&B.enc_len, &B.dec_len, &B.n_spans};
-    for (int k = 0; k < 3; ++k)
-        if (counts[k]) *slots[k] = (int32_t*)c->w_if_cnt.p + (size_t)k * (size_t)n_rows;
-    infill_launch(c, M, B);
-    {
-        HostPool pool(pool_threads(c, cells));
-        if ((rc = copy_out(c, input_ids, c->w_if_out.p, cells, c->stream, &pool))) return rc;
-        if (attention_mask && (rc = copy_out(c, attention_mask, c->w_if_am.p, cells, c->stream, &pool))) return rc;
-        if ((rc = copy_out(c, labels, c->w_if_lab.p, dec, c->stream, &pool))) return rc;
-        if (decoder_input_ids && (rc = copy_out(c, decoder_input_ids, c->w_if_dec.p, dec, c->stream, &pool))) return rc;
-    }
-    for (int k = 0; k < 3; ++k)
-        if (counts[k] && (rc = copy_out(c, counts[k], *slots[k], cnt, c->stream))) return rc;
-    HIPCHK(c, hipGetLastError());
-    return GZ_OK;
-} GZ_CATCH(c)
+#include "gz_rows_api.inc"
 
 // ---- text pre-pass ----------------------------------------------------------------------------------------------------
 namespace {
@@ -2572,12 +1972,7 @@ int preprocess_device_locked(gz_ctx* c, const int32_t* ops, int32_t n_ops, const
         in = A.out; in_len = A.out_len;
     }
     gz_launch_scan64(in_len, n_docs, out_off_dev, c->stream);
-    *total = 0;
-    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 320);       // (pinned scratch)
-    *h_total = 0;
-    if (n_docs > 0) HIPCHK(c, hipMemcpyAsync(h_total, out_off_dev + n_docs, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *total = *h_total;
+    if ((rc = read_total(c, n_docs > 0 ? out_off_dev + n_docs : nullptr, nullptr, total))) return rc;
     if (!out_dev) return GZ_OK;
     if (*total > capacity) return fail(c, GZ_E_CAPACITY, "pre-pass output needs %lld bytes, capacity is %lld", (long long)*total, (long long)capacity);
     gz_launch_pp_pack(in, off_dev, in_len, n_docs, out_dev, out_off_dev, c->stream);
@@ -2602,25 +1997,19 @@ int gz_preprocess_batch(gz_ctx* c, const int32_t* ops, int32_t n_ops, const uint
 try {
     if (!c || !ops || n_ops < 1 || n_ops > 16 || !text_off || !out_off || n_docs < 0 || capacity < 0 || (capacity > 0 && !out))
         return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
-    const int64_t nbytes = text_off[n_docs] - text_off[0];
-    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
-    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
+    RowsIn in{text, text_off, n_docs, 1};
     int rc;
-    if ((rc = ensure(c, c->w_pp_in, (size_t)nbytes + 16))) return rc;
-    if ((rc = ensure(c, c->w_pp_inoff, (size_t)(n_docs + 1) * 8))) return rc;
-    DBuf& fin = c->w_dec_out;                                       // final text (shared scratch with decode)
-    DBuf& fino = c->w_dec_ooff;
+    if ((rc = rows_check(c, in, kTextWords))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_docs + 1) * 8))) return rc;
+    const int64_t nbytes = in.n;
+    int64_t* const fino = (int64_t*)in.d_keep;                      // the final offsets; the final text: the first large output
+    DBuf& fin = c->w_rows_out[0];
     if ((rc = ensure(c, fin, (size_t)nbytes + 16))) return rc;
-    if ((rc = ensure(c, fino, (size_t)(n_docs + 1) * 8))) return rc;
-    if (nbytes && (rc = copy_in(c, c->w_pp_in.p, text + text_off[0], (size_t)nbytes, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_pp_inoff.p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
     int64_t total = 0;
-    if ((rc = preprocess_device_locked(c, ops, n_ops, (const uint8_t*)c->w_pp_in.p - text_off[0], (const int64_t*)c->w_pp_inoff.p, n_docs, nbytes,
-                                       (uint8_t*)fin.p, nbytes, (int64_t*)fino.p, &total))) return rc;
+    if ((rc = preprocess_device_locked(c, ops, n_ops, (const uint8_t*)in.d_payload, in.d_off, n_docs, nbytes, (uint8_t*)fin.p, nbytes, fino, &total))) return rc;
     HostPool pool(pool_threads(c, (size_t)total));
-    if ((rc = copy_out(c, out_off, fino.p, (size_t)(n_docs + 1) * 8, c->stream, &pool))) return rc;
+    if ((rc = copy_out(c, out_off, fino, (size_t)(n_docs + 1) * 8, c->stream, &pool))) return rc;
     if (total > capacity) return fail(c, GZ_E_CAPACITY, "pre-pass output needs %lld bytes, capacity is %lld", (long long)total, (long long)capacity);
     if (total && (rc = copy_out(c, out, fin.p, (size_t)total, c->stream, &pool))) return rc;
     return GZ_OK;

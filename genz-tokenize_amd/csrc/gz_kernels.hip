@@ -820,22 +820,30 @@ void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s)
     else hipLaunchKernelGGL(gz_pack_fill_kernel<1>, grid, block, 0, s, A);
 }
 
-void gz_launch_mask(GzMaskArgs A, hipStream_t s)
+// The division of the dense-row launches (masked rows, infill rows), written into A: about 4096 cells a wave (a long row: one wave a
+// row), more rows a wave only where the grid would not hold the waves; the continuation bitmap in LDS for whole words only, and only
+// while it fits (bits_in_lds is dropped otherwise).  *lds = bytes of dynamic LDS.
+template <class Args>
+static dim3 dense_division(Args& A, unsigned* lds)
 {
-    if (A.n_rows <= 0) return;
-    // about 4096 cells a wave (a long row: one wave a row); more rows a wave only where the grid would not hold the waves
     int64_t rpw = A.row_len < 4096 ? 4096 / A.row_len : 1;
     const int64_t max_waves = (int64_t)4 * 0x7FFFFFFF;
     if ((A.n_rows + rpw - 1) / rpw > max_waves) rpw = (A.n_rows + max_waves - 1) / max_waves;
     A.rows_per_wave = (int32_t)rpw;
     const int64_t waves = (A.n_rows + rpw - 1) / rpw;
-    const dim3 grid((unsigned)((waves + 3) / 4)), block(WAVE * 4);
-    // 16 bytes a lane where every row starts on a 16-byte boundary; one cell a lane otherwise
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(A.ids) | reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.labels);
-    // the continuation bitmap in LDS: whole words only, and only while it fits
     const size_t words = ((size_t)A.n_ids + 31) / 32;
     if (!A.whole_word || words == 0 || words * 4 > (size_t)GZ_MASK_LDS_MAX_BYTES) A.bits_in_lds = 0;
-    const unsigned lds = A.bits_in_lds ? (unsigned)(words * 4) : 0u;
+    *lds = A.bits_in_lds ? (unsigned)(words * 4) : 0u;
+    return dim3((unsigned)((waves + 3) / 4));
+}
+
+void gz_launch_mask(GzMaskArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    unsigned lds;
+    const dim3 grid = dense_division(A, &lds), block(WAVE * 4);
+    // 16 bytes a lane where every row starts on a 16-byte boundary; one cell a lane otherwise
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(A.ids) | reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.labels);
     const bool wide = A.row_len % 4 == 0 && (bits & 15) == 0;
     if (wide && lds) hipLaunchKernelGGL((gz_mask_kernel<4, true>), grid, block, lds, s, A);
     else if (wide) hipLaunchKernelGGL((gz_mask_kernel<4, false>), grid, block, 0, s, A);
@@ -846,17 +854,9 @@ void gz_launch_mask(GzMaskArgs A, hipStream_t s)
 void gz_launch_infill(GzInfillArgs A, hipStream_t s)
 {
     if (A.n_rows <= 0) return;
-    // the division of gz_launch_mask: about 4096 cells a wave, more rows a wave only where the grid would not hold the waves
-    int64_t rpw = A.row_len < 4096 ? 4096 / A.row_len : 1;
-    const int64_t max_waves = (int64_t)4 * 0x7FFFFFFF;
-    if ((A.n_rows + rpw - 1) / rpw > max_waves) rpw = (A.n_rows + max_waves - 1) / max_waves;
-    A.rows_per_wave = (int32_t)rpw;
-    const int64_t waves = (A.n_rows + rpw - 1) / rpw;
-    const dim3 grid((unsigned)((waves + 3) / 4)), block(WAVE * 4);
-    // the continuation bitmap in LDS: whole words only, and only while it fits
-    const size_t words = ((size_t)A.n_ids + 31) / 32;
-    if (!A.whole_word || words == 0 || words * 4 > (size_t)GZ_MASK_LDS_MAX_BYTES) A.bits_in_lds = 0;
-    if (A.bits_in_lds) hipLaunchKernelGGL((gz_infill_kernel<true>), grid, block, (unsigned)(words * 4), s, A);
+    unsigned lds;
+    const dim3 grid = dense_division(A, &lds), block(WAVE * 4);
+    if (lds) hipLaunchKernelGGL((gz_infill_kernel<true>), grid, block, lds, s, A);
     else hipLaunchKernelGGL((gz_infill_kernel<false>), grid, block, 0, s, A);
 }
 

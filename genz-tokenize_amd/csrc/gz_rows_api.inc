@@ -1,0 +1,607 @@
+// The row-shaping calls behind the C ABI: batch decode, overlapping windows, packed rows, masked-LM rows, span-corruption rows.
+// Included by gz_api.cpp behind gz_ctx, fail, HIPCHK, ensure and the copy helpers; the kernels are in gz_decode.inc, gz_window.inc,
+// gz_packrows.inc, gz_mask.inc and gz_infill.inc.  A call supplies its rule, its launch and its list of outputs; the row front
+// below does the rest of a host form (DESIGN.md, "the row front"); its rules without HIP in them are in gz_rowrules.h.
+// WORKSPACE: the host forms share w_rows_in, w_rows_off, w_rows_out[4] and w_rows_small.  That is sound because every use lies
+// inside c->mu and every access -- copy, kernel, memset -- is enqueued on c->stream: a later call's accesses are ordered behind an
+// earlier call's even where that one returned early.  A kernel's own scratch (w_win_cnt, the w_pk_* maps, w_dec_rb) is not shared.
+
+// ---- the row front -----------------------------------------------------------------------------------------------------
+namespace {
+// the wording of a CSR input's two refusals
+struct RowsWords { const char* bad; const char* decrease; };
+constexpr RowsWords kRowWords{"bad row offsets", "row offsets must not decrease"};
+constexpr RowsWords kTextWords{"bad text offsets", "text offsets must not decrease"};
+
+// A host CSR input (gz_rowrules.h) of `elem`-byte elements.  Two halves, because a refusal of the offsets comes before
+// GZ_E_NOTABLES and so before the lock: rows_check validates and sets n; rows_stage, under c->mu, copies payload and offsets in and
+// sets the device pointers -- d_payload is biased by off[0], so the absolute offsets index it as they index the caller's array --
+// and d_keep, `keep_bytes` of the offsets buffer that are the call's own (its output offsets: they live through both passes).
+struct RowsIn {
+    const void* payload; const int64_t* off; int64_t n_rows; size_t elem;
+    int64_t n = 0;
+    const void* d_payload = nullptr; const int64_t* d_off = nullptr; void* d_keep = nullptr;
+};
+int rows_check(gz_ctx* c, RowsIn& in, const RowsWords& w)
+{
+    switch (rows_offsets_check(in.payload, in.off, in.n_rows, &in.n)) {
+    case ROWS_BAD: return fail(c, GZ_E_INVALID, "%s", w.bad);
+    case ROWS_DECREASE: return fail(c, GZ_E_INVALID, "%s", w.decrease);
+    default: return GZ_OK;
+    }
+}
+int rows_stage(gz_ctx* c, RowsIn& in, size_t keep_bytes)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)in.n * in.elem, off_bytes = (size_t)(in.n_rows + 1) * 8;
+    int rc;
+    if ((rc = ensure(c, c->w_rows_in, bytes + 16))) return rc;             // (slack: the pre-pass reads 16 bytes at a time)
+    if ((rc = ensure(c, c->w_rows_off, off_bytes + keep_bytes))) return rc;
+    if (bytes && (rc = copy_in(c, c->w_rows_in.p, (const uint8_t*)in.payload + in.off[0] * (int64_t)in.elem, bytes, c->stream))) return rc;
+    if ((rc = copy_in(c, c->w_rows_off.p, in.off, off_bytes, c->stream))) return rc;
+    in.d_payload = (const uint8_t*)c->w_rows_in.p - in.off[0] * (int64_t)in.elem;
+    in.d_off = (const int64_t*)c->w_rows_off.p;
+    in.d_keep = (uint8_t*)c->w_rows_off.p + off_bytes;
+    return GZ_OK;
+}
+
+// The one scalar a two-pass call waits for: the int64 at `src` on the device after ONE hipStreamSynchronize of the context's stream.
+// src == nullptr (an empty batch: no kernel wrote a total): 0, and the offsets word at `zero`, if given, is cleared in its place.
+int read_total(gz_ctx* c, const int64_t* src, int64_t* zero, int64_t* total)
+{
+    *total = 0;
+    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
+    *h_total = 0;
+    if (src) HIPCHK(c, hipMemcpyAsync(h_total, src, 8, hipMemcpyDeviceToHost, c->stream));
+    else if (zero) HIPCHK(c, hipMemsetAsync(zero, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *total = *h_total;
+    return GZ_OK;
+}
+
+// The outputs of a host form, in the order they are copied out.  staged_ensure gives every entry the caller wants (host != null) a
+// place in the workspace -- the k-th large one w_rows_out[k], the small ones pieces of w_rows_small, 256 bytes apart at the least -- and leaves
+// dev null for the others; staged_copy_out brings them back: the large ones under one HostPool sized by the largest, then the small
+// ones on the caller's thread, then the check for a failed launch.
+struct StagedOut {
+    struct Entry { void* host; size_t bytes; bool large; void* dev; };
+    Entry e[8];
+    int n = 0;
+    void add(void* host, size_t bytes, bool large) { e[n++] = Entry{host, bytes, large, nullptr}; }
+    int32_t* dev(int k) const { return (int32_t*)e[k].dev; }
+};
+int staged_ensure(gz_ctx* c, StagedOut& S)
+{
+    int rc, k_large = 0;
+    size_t small = 0;
+    for (int k = 0; k < S.n; ++k) {
+        StagedOut::Entry& E = S.e[k];
+        if (!E.host) continue;
+        if (E.large) {
+            if ((rc = ensure(c, c->w_rows_out[k_large], E.bytes))) return rc;
+            E.dev = c->w_rows_out[k_large++].p;
+        } else small += (E.bytes + 255) & ~(size_t)255;
+    }
+    if (!small) return GZ_OK;
+    if ((rc = ensure(c, c->w_rows_small, small))) return rc;
+    uint8_t* at = (uint8_t*)c->w_rows_small.p;
+    for (int k = 0; k < S.n; ++k)
+        if (S.e[k].host && !S.e[k].large) { S.e[k].dev = at; at += (S.e[k].bytes + 255) & ~(size_t)255; }
+    return GZ_OK;
+}
+int staged_copy_out(gz_ctx* c, const StagedOut& S)
+{
+    int rc;
+    size_t largest = 0;
+    for (int k = 0; k < S.n; ++k) if (S.e[k].dev && S.e[k].large && S.e[k].bytes > largest) largest = S.e[k].bytes;
+    {
+        HostPool pool(pool_threads(c, largest));
+        for (int k = 0; k < S.n; ++k)
+            if (S.e[k].dev && S.e[k].large && (rc = copy_out(c, S.e[k].host, S.e[k].dev, S.e[k].bytes, c->stream, &pool))) return rc;
+    }
+    for (int k = 0; k < S.n; ++k)
+        if (S.e[k].dev && !S.e[k].large && (rc = copy_out(c, S.e[k].host, S.e[k].dev, S.e[k].bytes, c->stream))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+}  // namespace
+
+// ---- batch decode ----------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t GZ_DEC_UNK_MAX = 4096;
+
+uint32_t dec_flags(const std::string& w)
+{
+    uint32_t f = (uint32_t)w.size();
+    if (w.size() >= 2 && w[w.size() - 1] == '@' && w[w.size() - 2] == '@') f |= GZ_DEC_ENDS_ATAT;
+    if (w.find("@@ ") != std::string::npos) f |= GZ_DEC_INNER;
+    return f;
+}
+
+// the table entry of a word whose bytes are (or would be) at `off` of the byte arena
+GzDecEntry dec_entry_of(const std::string& w, size_t off)
+{
+    GzDecEntry e{dec_flags(w), {(uint32_t)off, 0u, 0u}};
+    if (w.size() <= 12 && !(e.len_flags & GZ_DEC_INNER)) {
+        e.len_flags |= GZ_DEC_INLINE;
+        e.w[0] = 0;
+        for (size_t k = 0; k < w.size(); ++k) e.w[k >> 2] |= (uint32_t)(uint8_t)w[k] << (8 * (k & 3));
+    }
+    return e;
+}
+
+int dec_set_unk(gz_ctx* c, const uint8_t* unk, int32_t unk_len)
+{
+    if (unk_len < 0 || (size_t)unk_len > GZ_DEC_UNK_MAX) return fail(c, GZ_E_LIMIT, "unk string longer than %zu bytes", GZ_DEC_UNK_MAX);
+    const std::string u((const char*)unk, (size_t)unk_len);
+    if (c->dec_unk_set && u == c->dec_unk) return GZ_OK;
+    int rcs;
+    if (unk_len && (rcs = copy_in(c, (uint8_t*)c->t_dec_bytes.p + c->dec_bytes_len, unk, (size_t)unk_len, c->stream))) return rcs;
+    const GzDecEntry e = dec_entry_of(u, c->dec_bytes_len);
+    if ((rcs = copy_in(c, (GzDecEntry*)c->t_dec_entries.p + c->dec_n_ids, &e, sizeof e, c->stream))) return rcs;
+    c->dec_unk = u;
+    c->dec_unk_set = true;
+    return GZ_OK;
+}
+
+// both passes; *total = bytes of the whole batch.  out_dev may be nullptr (sizes only).
+int decode_device_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, const uint8_t* unk,
+                         int32_t unk_len, uint8_t* out_dev, int64_t capacity, int64_t* out_off_dev, int64_t* total)
+{
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = dec_set_unk(c, unk, unk_len))) return rc;
+    if ((rc = ensure(c, c->w_dec_rb, (size_t)(n_rows + 1) * 8))) return rc;
+    GzDecTable D{(const GzDecEntry*)c->t_dec_entries.p, (const uint8_t*)c->t_dec_bytes.p, c->dec_n_ids};
+    gz_launch_decode(D, ids_dev, row_off_dev, n_rows, (int64_t*)c->w_dec_rb.p, out_off_dev, nullptr, 0, c->stream);
+    if ((rc = read_total(c, n_rows > 0 ? out_off_dev + n_rows : nullptr, out_off_dev, total))) return rc;
+    if (!out_dev) return GZ_OK;
+    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "decode needs %lld bytes, capacity is %lld", (long long)*total, (long long)capacity);
+    gz_launch_decode(D, ids_dev, row_off_dev, n_rows, nullptr, out_off_dev, out_dev, capacity, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_decoder_snapshot(gz_ctx* c)
+try {
+    if (!c) return GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    // {v: k for k, v in encoder.items()} (tokenize.py:40): the last word wins on an id collision
+    int32_t n_ids = 0;
+    for (int32_t id : c->host.enc_ids) if (id + 1 > n_ids) n_ids = id + 1;
+    std::vector<int64_t> last((size_t)n_ids, -1);
+    for (size_t i = 0; i < c->host.enc_ids.size(); ++i) if (c->host.enc_ids[i] >= 0) last[(size_t)c->host.enc_ids[i]] = (int64_t)i;
+    std::vector<GzDecEntry> ent((size_t)n_ids + 1, GzDecEntry{GZ_DEC_ABSENT, {0u, 0u, 0u}});
+    std::string bytes;
+    for (int32_t id = 0; id < n_ids; ++id) {
+        if (last[(size_t)id] < 0) continue;
+        const std::string& w = c->host.enc_words[(size_t)last[(size_t)id]];
+        if (w.size() > GZ_DEC_LEN_MASK || bytes.size() + w.size() > 0xFFFF0000ull) return fail(c, GZ_E_LIMIT, "vocabulary too large for the decoder arena");
+        ent[(size_t)id] = dec_entry_of(w, bytes.size());
+        bytes += w;
+    }
+    ent[(size_t)n_ids] = GzDecEntry{GZ_DEC_INLINE, {0u, 0u, 0u}};                  // (the unk string: set per call, dec_set_unk)
+    std::vector<uint32_t> cont((size_t)n_ids / 32 + 1, 0u);                       // which ids continue a word: one bit each (gz_mask_rows*)
+    for (int32_t id = 0; id < n_ids; ++id)
+        if (ent[(size_t)id].len_flags != GZ_DEC_ABSENT && (ent[(size_t)id].len_flags & GZ_DEC_ENDS_ATAT)) cont[(size_t)id >> 5] |= 1u << (id & 31);
+    int rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = ensure(c, c->t_dec_entries, ent.size() * sizeof(GzDecEntry)))) return rc;
+    if ((rc = ensure(c, c->t_dec_bytes, bytes.size() + GZ_DEC_UNK_MAX + 16))) return rc;
+    if ((rc = ensure(c, c->t_dec_cont, cont.size() * 4))) return rc;
+    if ((rc = copy_in(c, c->t_dec_entries.p, ent.data(), ent.size() * sizeof(GzDecEntry), c->stream))) return rc;
+    if ((rc = copy_in(c, c->t_dec_cont.p, cont.data(), cont.size() * 4, c->stream))) return rc;
+    if (!bytes.empty() && (rc = copy_in(c, c->t_dec_bytes.p, bytes.data(), bytes.size(), c->stream))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->dec_n_ids = n_ids;
+    c->dec_bytes_len = bytes.size();
+    c->dec_unk_set = false;
+    c->have_dec = true;
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_decode_batch_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, const uint8_t* unk,
+                           int32_t unk_len, uint8_t* out_dev, int64_t capacity, int64_t* out_off_dev, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !out_off_dev || !total_host || n_rows < 0 || (!unk && unk_len) || capacity < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return decode_device_locked(c, ids_dev, row_off_dev, n_rows, unk, unk_len, out_dev, capacity, out_off_dev, total_host);
+} GZ_CATCH(c)
+
+int gz_decode_batch(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, const uint8_t* unk, int32_t unk_len,
+                    uint8_t* out, int64_t capacity, int64_t* out_off)
+try {
+    if (!c || !row_off || !out_off || n_rows < 0 || (!unk && unk_len) || capacity < 0 || (capacity > 0 && !out))
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    RowsIn in{ids, row_off, n_rows, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;
+    const int32_t* const ids_dev = (const int32_t*)in.d_payload;
+    int64_t* const ooff = (int64_t*)in.d_keep;
+    int64_t total = 0;
+    if ((rc = decode_device_locked(c, ids_dev, in.d_off, n_rows, unk, unk_len, nullptr, 0, ooff, &total))) return rc;
+    if ((rc = copy_out(c, out_off, ooff, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (total > capacity) return fail(c, GZ_E_CAPACITY, "decode needs %lld bytes, capacity is %lld", (long long)total, (long long)capacity);
+    if (total == 0) return GZ_OK;
+    StagedOut S;
+    S.add(out, (size_t)total, true);
+    if ((rc = staged_ensure(c, S))) return rc;
+    GzDecTable D{(const GzDecEntry*)c->t_dec_entries.p, (const uint8_t*)c->t_dec_bytes.p, c->dec_n_ids};
+    gz_launch_decode(D, ids_dev, in.d_off, n_rows, nullptr, ooff, (uint8_t*)S.e[0].dev, total, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- overlapping max_len windows ------------------------------------------------------------------------------------
+namespace {
+// the fill pass over win_off, enqueued on the context's stream; bos / eos / pad are the context's current special ids
+void window_fill(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
+                 int32_t skip_back, const int64_t* win_off_dev, int64_t n_win, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc,
+                 int32_t* win_start, int32_t* win_n_real)
+{
+    GzWinArgs A{ids_dev, row_off_dev, n_rows, win_off_dev, n_win, max_len, max_len - 2, max_len - 2 - stride, skip_front, skip_back,
+                c->dev.bos_id, c->dev.eos_id, c->dev.pad_id, out_ids, out_mask, win_doc, win_start, win_n_real};
+    gz_launch_window_fill(A, c->stream);
+}
+
+// Both passes on the context's stream, behind whatever it holds (an encode call's forked streams have rejoined it when that call
+// returns).  *total = windows of the batch.  out_ids == nullptr: the count pass only.
+int window_device_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
+                         int32_t skip_front, int32_t skip_back, int32_t* out_ids, int32_t* out_mask, int32_t* win_doc, int32_t* win_start,
+                         int32_t* win_n_real, int64_t* win_off_dev, int64_t capacity, int64_t* total)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_win_cnt, (size_t)(n_rows + 1) * 8))) return rc;
+    const int32_t room = max_len - 2, step = room - stride;
+    gz_launch_window_count(row_off_dev, n_rows, room, step, skip_front + skip_back, (int64_t*)c->w_win_cnt.p, win_off_dev, c->stream);
+    if ((rc = read_total(c, n_rows > 0 ? win_off_dev + n_rows : nullptr, win_off_dev, total))) return rc;
+    if (!out_ids) return GZ_OK;
+    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)*total, (long long)capacity);
+    window_fill(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, win_off_dev, *total, out_ids, out_mask, win_doc, win_start,
+                win_n_real);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+bool window_rule_ok(int32_t max_len, int32_t stride, int32_t skip_front, int32_t skip_back)
+{
+    return max_len >= 3 && stride >= 0 && stride <= max_len - 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1;
+}
+}  // namespace
+
+int gz_window_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t stride,
+                          int32_t skip_front, int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* win_doc_dev,
+                          int32_t* win_start_dev, int32_t* win_n_real_dev, int64_t* win_off_dev, int64_t capacity_windows, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !win_off_dev || !total_host || n_rows < 0 || capacity_windows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
+        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
+    std::lock_guard<std::mutex> lk(c->mu);
+    return window_device_locked(c, ids_dev, row_off_dev, n_rows, max_len, stride, skip_front, skip_back, input_ids_dev, attention_mask_dev,
+                                win_doc_dev, win_start_dev, win_n_real_dev, win_off_dev, capacity_windows, total_host);
+} GZ_CATCH(c)
+
+int gz_window_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t stride, int32_t skip_front,
+                   int32_t skip_back, int32_t* input_ids, int32_t* attention_mask, int32_t* win_doc, int32_t* win_start, int32_t* win_n_real,
+                   int64_t* win_off, int64_t capacity_windows, int64_t* total_host)
+try {
+    if (!c || !row_off || !win_off || !total_host || n_rows < 0 || capacity_windows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!window_rule_ok(max_len, stride, skip_front, skip_back))
+        return fail(c, GZ_E_INVALID, "windows need max_len >= 3, 0 <= stride <= max_len - 3 and skips of 0 or 1");
+    RowsIn in{ids, row_off, n_rows, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;
+    const int32_t* const ids_dev = (const int32_t*)in.d_payload;
+    int64_t* const woff = (int64_t*)in.d_keep;
+    int64_t total = 0;
+    if ((rc = window_device_locked(c, ids_dev, in.d_off, n_rows, max_len, stride, skip_front, skip_back, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   woff, 0, &total))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, win_off, woff, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_windows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)total, (long long)capacity_windows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len * 4, per_win = (size_t)total * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(attention_mask, cells, true);
+    S.add(win_doc, per_win, false); S.add(win_start, per_win, false); S.add(win_n_real, per_win, false);
+    if ((rc = staged_ensure(c, S))) return rc;
+    window_fill(c, ids_dev, in.d_off, n_rows, max_len, stride, skip_front, skip_back, woff, total, S.dev(0), S.dev(1), S.dev(2), S.dev(3), S.dev(4));
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- short documents packed into rows of max_len ------------------------------------------------------------------------
+namespace {
+// The maps of a batch on the context's stream, behind whatever it holds: doc_len, seg_off, the row heads in pack_off, doc_row, doc_col.
+// A map the caller does not take lives in the context's workspace (pack_off is the caller's).  A gets the pointers the fill pass
+// needs; *total = R, read back from the device.  fill: the fill pass goes right behind the maps -- it takes R from device memory,
+// writes nothing when R exceeds A.capacity, and writes doc_col in place of the col pass -- so the host waits once, for everything.
+int pack_maps_locked(gz_ctx* c, GzPackArgs& A, int64_t* total, bool fill)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = A.n_rows;
+    int rc;
+    if (!A.seg_off) { if ((rc = ensure(c, c->w_pk_seg, (size_t)(n + 1) * 8))) return rc; A.seg_off = (int64_t*)c->w_pk_seg.p; }
+    if (!A.doc_row) { if ((rc = ensure(c, c->w_pk_drow, (size_t)(n + 1) * 4))) return rc; A.doc_row = (int32_t*)c->w_pk_drow.p; }
+    if (!A.doc_col) { if ((rc = ensure(c, c->w_pk_dcol, (size_t)(n + 1) * 4))) return rc; A.doc_col = (int32_t*)c->w_pk_dcol.p; }
+    const size_t tiles = (size_t)gz_pack_tiles(n), groups = (size_t)gz_pack_groups(n), K = (size_t)gz_pack_entries(A.max_len);
+    if ((rc = ensure(c, c->w_pk_len, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_jc, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_nxt, (size_t)(n + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->w_pk_jc2, (groups * K + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pk_tile, (tiles + 1) * 8))) return rc;
+    A.len64 = (int64_t*)c->w_pk_len.p; A.jc = (int32_t*)c->w_pk_jc.p; A.nxt = (int32_t*)c->w_pk_nxt.p; A.jc2 = (int32_t*)c->w_pk_jc2.p; A.tile = (int32_t*)c->w_pk_tile.p;
+    A.total = (int64_t*)c->w_pk_tile.p + tiles;
+    A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id; A.pad_id = c->dev.pad_id;
+    *total = 0;
+    if (n > 0) {
+        gz_launch_pack_maps(A, !fill, c->stream);
+        if (fill) gz_launch_pack_fill(A, c->stream);
+    } else HIPCHK(c, hipMemsetAsync(A.seg_off, 0, 8, c->stream));
+    if ((rc = read_total(c, n > 0 ? A.total : nullptr, A.pack_off, total))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+const char* const kPackRule = "packed rows need max_len >= 3, skips of 0 or 1 and fewer than 2^31 - 4096 documents";
+bool pack_rule_ok(int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back)
+{
+    return max_len >= 3 && skip_front >= 0 && skip_back >= 0 && skip_front <= 1 && skip_back <= 1 && n_rows < INT32_MAX - 4096;
+}
+}  // namespace
+
+int gz_pack_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t skip_front,
+                        int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* segment_ids_dev, int32_t* position_ids_dev,
+                        int32_t* doc_row_dev, int32_t* doc_col_dev, int32_t* doc_len_dev, int64_t* pack_off_dev, int64_t* seg_off_dev,
+                        int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !pack_off_dev || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    std::lock_guard<std::mutex> lk(c->mu);
+    GzPackArgs A{};
+    A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows; A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.doc_row = doc_row_dev; A.doc_col = doc_col_dev; A.doc_len = doc_len_dev; A.pack_off = pack_off_dev; A.seg_off = seg_off_dev;
+    A.capacity = capacity_rows;
+    A.out_ids = input_ids_dev; A.out_mask = attention_mask_dev; A.out_seg = segment_ids_dev; A.out_pos = position_ids_dev;
+    int rc;
+    if ((rc = pack_maps_locked(c, A, total_host, input_ids_dev != nullptr))) return rc;
+    if (!input_ids_dev || *total_host <= capacity_rows) return GZ_OK;
+    gz_launch_pack_col(A, c->stream);                                      // (the fill wrote nothing, doc_col included: the maps are valid all the same)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)*total_host, (long long)capacity_rows);
+} GZ_CATCH(c)
+
+int gz_pack_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back,
+                 int32_t* input_ids, int32_t* attention_mask, int32_t* segment_ids, int32_t* position_ids, int32_t* doc_row, int32_t* doc_col,
+                 int32_t* doc_len, int64_t* pack_off, int64_t* seg_off, int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off || !pack_off || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    RowsIn in{ids, row_off, n_rows, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 12))) return rc;              // kept through both passes: pack_off, then doc_len
+    GzPackArgs A{};
+    A.ids = (const int32_t*)in.d_payload; A.row_off = in.d_off; A.n_rows = n_rows;
+    A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.pack_off = (int64_t*)in.d_keep; A.doc_len = (int32_t*)(A.pack_off + n_rows + 1);          // (the other maps: the workspace's)
+    int64_t total = 0;
+    if ((rc = pack_maps_locked(c, A, &total, false))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, pack_off, A.pack_off, (size_t)(total + 1) * 8, c->stream))) return rc;
+    if (seg_off && (rc = copy_out(c, seg_off, A.seg_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (doc_row && (rc = copy_out(c, doc_row, A.doc_row, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_col && (rc = copy_out(c, doc_col, A.doc_col, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_len && (rc = copy_out(c, doc_len, A.doc_len, (size_t)n_rows * 4, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_rows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)total, (long long)capacity_rows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(attention_mask, cells, true); S.add(segment_ids, cells, true); S.add(position_ids, cells, true);
+    if ((rc = staged_ensure(c, S))) return rc;
+    A.capacity = total;
+    A.out_ids = S.dev(0); A.out_mask = S.dev(1); A.out_seg = S.dev(2); A.out_pos = S.dev(3);
+    gz_launch_pack_fill(A, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- masked-LM inputs and labels over dense rows -------------------------------------------------------------------------
+namespace {
+struct MaskRule {
+    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_sel, t1, t2;
+    int32_t rand_lo, rand_hi, mask_id, whole_word, ignore_index;
+};
+const char* const kMaskRule = "masked rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, thresholds in "
+                              "[0, 2^32] with t1 <= t2, rand_lo < rand_hi and whole_word 0 or 1";
+bool mask_rule_ok(const MaskRule& M)
+{
+    constexpr uint64_t one = 1ull << 32;
+    return dense_rule_ok(M.n_rows, M.row_len, M.row_base, M.whole_word) && M.t_sel <= one && M.t1 <= one && M.t2 <= one && M.t1 <= M.t2 &&
+           M.rand_lo < M.rand_hi;
+}
+// the cell arrays and the counts are pairwise disjoint (the heads are read from neighbours' ORIGINAL ids); n_rows * row_len > 0
+bool mask_buffers_ok(const MaskRule& M, const int32_t* ids, const int32_t* out_ids, const int32_t* labels, const int32_t* n_chosen)
+{
+    if (!ids || !out_ids || !labels) return false;
+    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
+    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u;
+    const Span s[4] = {span_of(ids, cells), span_of(out_ids, cells), span_of(labels, cells), span_of(n_chosen, (uintptr_t)M.n_rows * 4u)};
+    return disjoint(s, 4);
+}
+// the one launch on the context's stream, behind whatever it holds
+void mask_launch(gz_ctx* c, const MaskRule& M, const int32_t* ids_dev, int32_t* out_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
+{
+    GzMaskArgs A{};
+    A.ids = ids_dev; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
+    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
+    A.t_sel = M.t_sel; A.t1 = M.t1; A.t2 = M.t2;
+    A.rand_lo = M.rand_lo; A.rand_span = (uint32_t)M.rand_hi - (uint32_t)M.rand_lo;
+    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word;
+    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
+    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
+    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
+    A.out_ids = out_dev; A.labels = labels_dev; A.n_chosen = n_chosen_dev;
+    gz_launch_mask(A, c->stream);
+}
+}  // namespace
+
+int gz_mask_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel,
+                        uint64_t t1, uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index,
+                        int32_t* input_ids_dev, int32_t* labels_dev, int32_t* n_chosen_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
+    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
+    if (n_rows > 0 && !mask_buffers_ok(M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev))
+        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    mask_launch(c, M, ids_dev, input_ids_dev, labels_dev, n_chosen_dev);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_mask_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_sel, uint64_t t1,
+                 uint64_t t2, int32_t rand_lo, int32_t rand_hi, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t* input_ids,
+                 int32_t* labels, int32_t* n_chosen)
+try {
+    if (!c) return GZ_E_INVALID;
+    const MaskRule M{n_rows, row_len, row_base, seed, t_sel, t1, t2, rand_lo, rand_hi, mask_id, whole_word, ignore_index};
+    if (!mask_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kMaskRule);
+    if (n_rows > 0 && !mask_buffers_ok(M, ids, input_ids, labels, n_chosen))
+        return fail(c, GZ_E_INVALID, "masked rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)n_rows * (size_t)row_len * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(labels, cells, true); S.add(n_chosen, (size_t)n_rows * 4, false);
+    int rc;
+    if ((rc = ensure(c, c->w_rows_in, cells)) || (rc = copy_in(c, c->w_rows_in.p, ids, cells, c->stream)) || (rc = staged_ensure(c, S))) return rc;
+    mask_launch(c, M, (const int32_t*)c->w_rows_in.p, S.dev(0), S.dev(1), S.dev(2));
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- span-corruption inputs and targets over dense rows -------------------------------------------------------------------
+namespace {
+struct InfillRule {
+    int64_t n_rows; int32_t row_len; int64_t row_base; uint64_t seed, t_start; const uint64_t* len_t;
+    int32_t n_len, mask_id, whole_word, ignore_index, dec_width;
+};
+struct InfillBufs {
+    const int32_t* ids; int32_t* input_ids; int32_t* attention_mask; int32_t* labels; int32_t* decoder_input_ids;
+    int32_t* enc_len; int32_t* dec_len; int32_t* n_spans;
+};
+const char* const kInfillRule = "infill rows need row_len >= 1, n_rows >= 0, row_base >= 0, (row_base + n_rows) * row_len < 2^63, dec_width >= 1, "
+                                "t_start in [0, 2^32], 1 <= n_len <= 16 with n_len - 1 non-decreasing thresholds in [0, 2^32] and whole_word 0 or 1";
+bool infill_rule_ok(const InfillRule& M)
+{
+    constexpr uint64_t one = 1ull << 32;
+    if (!dense_rule_ok(M.n_rows, M.row_len, M.row_base, M.whole_word) || M.dec_width < 1) return false;
+    if (M.t_start > one || M.n_len < 1 || M.n_len > 16) return false;
+    if (M.n_len > 1 && !M.len_t) return false;
+    for (int k = 0; k + 1 < M.n_len; ++k)
+        if (M.len_t[k] > one || (k > 0 && M.len_t[k] < M.len_t[k - 1])) return false;
+    return true;
+}
+// the eight arrays are pairwise disjoint (every cell is read from the ORIGINAL rows and written once); n_rows > 0
+bool infill_buffers_ok(const InfillRule& M, const InfillBufs& B)
+{
+    if (!B.ids || !B.input_ids || !B.labels) return false;
+    if ((uint64_t)M.n_rows * (uint64_t)M.row_len > (uint64_t)(UINTPTR_MAX / 4)) return false;       // (the byte counts below do not wrap)
+    if ((uint64_t)M.n_rows * (uint64_t)M.dec_width > (uint64_t)(UINTPTR_MAX / 4)) return false;
+    const uintptr_t cells = (uintptr_t)M.n_rows * (uintptr_t)M.row_len * 4u, dec = (uintptr_t)M.n_rows * (uintptr_t)M.dec_width * 4u,
+                    cnt = (uintptr_t)M.n_rows * 4u;
+    const Span s[8] = {span_of(B.ids, cells), span_of(B.input_ids, cells), span_of(B.attention_mask, cells), span_of(B.labels, dec),
+                       span_of(B.decoder_input_ids, dec), span_of(B.enc_len, cnt), span_of(B.dec_len, cnt), span_of(B.n_spans, cnt)};
+    return disjoint(s, 8);
+}
+// the one launch on the context's stream, behind whatever it holds; every pointer of B a device pointer
+void infill_launch(gz_ctx* c, const InfillRule& M, const InfillBufs& B)
+{
+    GzInfillArgs A{};
+    A.ids = B.ids; A.n_rows = M.n_rows; A.row_len = M.row_len; A.row_base = M.row_base;
+    A.key0 = (uint32_t)M.seed; A.key1 = (uint32_t)(M.seed >> 32);
+    A.t_start = M.t_start; A.n_len = M.n_len;
+    for (int k = 0; k < 15; ++k) A.len_t[k] = k + 1 < M.n_len ? M.len_t[k] : 1ull << 32;       // (len_t is a host pointer: its words travel in the arguments)
+    A.mask_id = M.mask_id; A.ignore_index = M.ignore_index; A.whole_word = M.whole_word; A.dec_width = M.dec_width;
+    A.pad_id = c->dev.pad_id; A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id;
+    A.cont_bits = (const uint32_t*)c->t_dec_cont.p; A.n_ids = c->dec_n_ids;
+    A.bits_in_lds = c->opt.mask_lds;                                          // (the launcher drops it when the bitmap does not fit)
+    A.out_ids = B.input_ids; A.out_mask = B.attention_mask; A.labels = B.labels; A.dec_ids = B.decoder_input_ids;
+    A.enc_len = B.enc_len; A.dec_len = B.dec_len; A.n_spans = B.n_spans;
+    gz_launch_infill(A, c->stream);
+}
+}  // namespace
+
+int gz_infill_rows_device(gz_ctx* c, const int32_t* ids_dev, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
+                          const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
+                          int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* labels_dev, int32_t* decoder_input_ids_dev,
+                          int32_t* enc_len_dev, int32_t* dec_len_dev, int32_t* n_spans_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
+    const InfillBufs B{ids_dev, input_ids_dev, attention_mask_dev, labels_dev, decoder_input_ids_dev, enc_len_dev, dec_len_dev, n_spans_dev};
+    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
+    if (n_rows > 0 && !infill_buffers_ok(M, B))
+        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    infill_launch(c, M, B);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_infill_rows(gz_ctx* c, const int32_t* ids, int64_t n_rows, int32_t row_len, int64_t row_base, uint64_t seed, uint64_t t_start,
+                   const uint64_t* len_t, int32_t n_len, int32_t mask_id, int32_t whole_word, int32_t ignore_index, int32_t dec_width,
+                   int32_t* input_ids, int32_t* attention_mask, int32_t* labels, int32_t* decoder_input_ids, int32_t* enc_len, int32_t* dec_len,
+                   int32_t* n_spans)
+try {
+    if (!c) return GZ_E_INVALID;
+    const InfillRule M{n_rows, row_len, row_base, seed, t_start, len_t, n_len, mask_id, whole_word, ignore_index, dec_width};
+    if (!infill_rule_ok(M)) return fail(c, GZ_E_INVALID, "%s", kInfillRule);
+    if (n_rows > 0 && !infill_buffers_ok(M, InfillBufs{ids, input_ids, attention_mask, labels, decoder_input_ids, enc_len, dec_len, n_spans}))
+        return fail(c, GZ_E_INVALID, "infill rows need ids, input_ids and labels, and buffers that do not overlap");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_dec) return fail(c, GZ_E_NOTABLES, "gz_decoder_snapshot has not been called");
+    if (n_rows == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)n_rows * (size_t)row_len * 4, dec = (size_t)n_rows * (size_t)dec_width * 4, cnt = (size_t)n_rows * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(attention_mask, cells, true); S.add(labels, dec, true); S.add(decoder_input_ids, dec, true);
+    S.add(enc_len, cnt, false); S.add(dec_len, cnt, false); S.add(n_spans, cnt, false);
+    int rc;
+    if ((rc = ensure(c, c->w_rows_in, cells)) || (rc = copy_in(c, c->w_rows_in.p, ids, cells, c->stream)) || (rc = staged_ensure(c, S))) return rc;
+    infill_launch(c, M, InfillBufs{(const int32_t*)c->w_rows_in.p, S.dev(0), S.dev(1), S.dev(2), S.dev(3), S.dev(4), S.dev(5), S.dev(6)});
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+

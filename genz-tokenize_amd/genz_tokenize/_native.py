@@ -230,6 +230,11 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _dptrs(*ds):
+    """optional device addresses (0 or None: NULL), as one call passes them on: f(..., *_dptrs(d_a, d_b), ...)"""
+    return [C.c_void_p(d) if d else None for d in ds]
+
+
 def default_device() -> int:
     for k in ("GENZ_TOKENIZE_DEVICE", "LOCAL_RANK"):
         v = os.environ.get(k)
@@ -267,6 +272,16 @@ class Context:
         if rc < 0:
             raise GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
         return rc
+
+    def _call_total(self, fn, *args) -> int:
+        """fn(*args, &total) -> total; a GzError of the call carries `.total` (GZ_E_CAPACITY: what the batch needs)."""
+        total = C.c_int64()
+        rc = fn(*args, C.byref(total))
+        if rc:
+            e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
+            e.total = total.value
+            raise e
+        return total.value
 
     # ---- tables ------------------------------------------------------------------------------------------
     def load_tables(self, vocab: bytes, bpe: bytes, specials):
@@ -445,11 +460,8 @@ class Context:
         """Enqueue one call on device-resident buffers.  h_text_off / h_pair_off: optional host copies (int64 numpy) of
         the offsets; with them the library does not read the batch's byte sizes back from the device first."""
         vp = C.c_void_p
-        args = [self.handle, vp(d_text), vp(d_text_off), vp(d_pair) if d_pair else None,
-                vp(d_pair_off) if d_pair_off else None, n_docs, max_len, flags, capacity, vp(d_ids), vp(d_mask),
-                vp(d_tt) if d_tt else None, vp(d_seq) if d_seq else None, vp(d_row_off) if d_row_off else None,
-                vp(d_pair_len) if d_pair_len else None, vp(d_n_real) if d_n_real else None,
-                vp(d_status) if d_status else None]
+        args = [self.handle, vp(d_text), vp(d_text_off), *_dptrs(d_pair, d_pair_off), n_docs, max_len, flags, capacity, vp(d_ids), vp(d_mask),
+                *_dptrs(d_tt, d_seq, d_row_off, d_pair_len, d_n_real, d_status)]
         if h_text_off is not None:
             self._check(self.lib.gz_encode_batch_device_h(*args, _ptr(h_text_off), _ptr(h_pair_off)))
         else:
@@ -513,7 +525,7 @@ class Context:
         total = C.c_int64()
         ub = C.create_string_buffer(unk, len(unk))
         self._check(self.lib.gz_decode_batch_device(self.handle, C.c_void_p(d_ids), C.c_void_p(d_row_off), n_rows,
-                                                    C.cast(ub, C.c_void_p), len(unk), C.c_void_p(d_out) if d_out else None,
+                                                    C.cast(ub, C.c_void_p), len(unk), *_dptrs(d_out),
                                                     capacity, C.c_void_p(d_out_off), C.byref(total)))
         return total.value
 
@@ -539,17 +551,9 @@ class Context:
     def window_rows_device(self, d_ids, d_row_off, n_rows, max_len, stride, skip_front, skip_back, d_input_ids, d_mask, d_doc, d_start,
                            d_n_real, d_win_off, capacity) -> int:
         """gz_window_rows_device: returns W.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = W."""
-        vp = C.c_void_p
-        total = C.c_int64()
-        rc = self.lib.gz_window_rows_device(self.handle, vp(d_ids) if d_ids else None, vp(d_row_off), n_rows, max_len, stride, skip_front,
-                                            skip_back, vp(d_input_ids) if d_input_ids else None, vp(d_mask) if d_mask else None,
-                                            vp(d_doc) if d_doc else None, vp(d_start) if d_start else None,
-                                            vp(d_n_real) if d_n_real else None, vp(d_win_off), capacity, C.byref(total))
-        if rc:
-            e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
-            e.total = total.value
-            raise e
-        return total.value
+        return self._call_total(self.lib.gz_window_rows_device, self.handle, *_dptrs(d_ids), C.c_void_p(d_row_off), n_rows, max_len, stride,
+                                skip_front, skip_back, *_dptrs(d_input_ids, d_mask, d_doc, d_start, d_n_real),
+                                C.c_void_p(d_win_off), capacity)
 
     # ---- short documents packed into rows of max_len ------------------------------------------------------
     def pack_rows(self, ids: np.ndarray, row_off: np.ndarray, max_len: int, framed: bool):
@@ -575,16 +579,9 @@ class Context:
     def pack_rows_device(self, d_ids, d_row_off, n_rows, max_len, skip_front, skip_back, d_input_ids, d_mask, d_seg, d_pos, d_doc_row,
                          d_doc_col, d_doc_len, d_pack_off, d_seg_off, capacity) -> int:
         """gz_pack_rows_device: returns R.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = R."""
-        vp = C.c_void_p
-        opt = [vp(d) if d else None for d in (d_input_ids, d_mask, d_seg, d_pos, d_doc_row, d_doc_col, d_doc_len)]
-        total = C.c_int64()
-        rc = self.lib.gz_pack_rows_device(self.handle, vp(d_ids) if d_ids else None, vp(d_row_off), n_rows, max_len, skip_front, skip_back,
-                                          *opt, vp(d_pack_off), vp(d_seg_off) if d_seg_off else None, capacity, C.byref(total))
-        if rc:
-            e = GzError(rc, self.lib.gz_last_error(self.handle).decode("utf-8", "replace"))
-            e.total = total.value
-            raise e
-        return total.value
+        opt = _dptrs(d_input_ids, d_mask, d_seg, d_pos, d_doc_row, d_doc_col, d_doc_len)
+        return self._call_total(self.lib.gz_pack_rows_device, self.handle, *_dptrs(d_ids), C.c_void_p(d_row_off), n_rows, max_len, skip_front,
+                                skip_back, *opt, C.c_void_p(d_pack_off), *_dptrs(d_seg_off), capacity)
 
     # ---- masked-LM inputs and labels ------------------------------------------------------------------------
     def mask_rows(self, ids: np.ndarray, rule, row_base: int = 0):
@@ -599,9 +596,8 @@ class Context:
 
     def mask_rows_device(self, d_ids, n_rows, row_len, row_base, rule, d_input_ids, d_labels, d_n_chosen):
         """gz_mask_rows_device: every pointer a device address (0: NULL); `rule` as in mask_rows."""
-        vp = C.c_void_p
-        self._check(self.lib.gz_mask_rows_device(self.handle, vp(d_ids) if d_ids else None, n_rows, row_len, row_base, *rule,
-                                                 *[vp(d) if d else None for d in (d_input_ids, d_labels, d_n_chosen)]))
+        self._check(self.lib.gz_mask_rows_device(self.handle, *_dptrs(d_ids), n_rows, row_len, row_base, *rule,
+                                                 *_dptrs(d_input_ids, d_labels, d_n_chosen)))
 
     # ---- span-corruption inputs and targets ------------------------------------------------------------------
     @staticmethod
@@ -630,11 +626,10 @@ class Context:
     def infill_rows_device(self, d_ids, n_rows, row_len, row_base, rule, d_input_ids, d_attention_mask, d_labels, d_decoder_input_ids,
                            d_enc_len, d_dec_len, d_n_spans):
         """gz_infill_rows_device: every pointer a device address (0: NULL); `rule` as in infill_rows (len_t stays on the host)."""
-        vp = C.c_void_p
         args, keep = self._infill_args(rule)
-        self._check(self.lib.gz_infill_rows_device(self.handle, vp(d_ids) if d_ids else None, n_rows, row_len, row_base, *args,
-                                                   *[vp(d) if d else None for d in (d_input_ids, d_attention_mask, d_labels,
-                                                                                    d_decoder_input_ids, d_enc_len, d_dec_len, d_n_spans)]))
+        self._check(self.lib.gz_infill_rows_device(self.handle, *_dptrs(d_ids), n_rows, row_len, row_base, *args,
+                                                   *_dptrs(d_input_ids, d_attention_mask, d_labels, d_decoder_input_ids, d_enc_len, d_dec_len,
+                                                            d_n_spans)))
         del keep
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
@@ -655,7 +650,7 @@ class Context:
         ops = np.ascontiguousarray(ops, dtype=np.int32)
         total = C.c_int64()
         self._check(self.lib.gz_preprocess_batch_device(self.handle, _ptr(ops), len(ops), C.c_void_p(d_text), C.c_void_p(d_off),
-                                                        n_docs, text_bytes, C.c_void_p(d_out) if d_out else None, capacity,
+                                                        n_docs, text_bytes, *_dptrs(d_out), capacity,
                                                         C.c_void_p(d_out_off), C.byref(total)))
         return total.value
 
@@ -675,7 +670,7 @@ class Context:
 
     def bm25_build_device(self, d_text, d_off, n_docs: int, text_bytes: int, positions: bool = False) -> int:
         h = C.c_void_p()
-        args = [self.handle, C.c_void_p(d_text) if d_text else None, C.c_void_p(d_off), n_docs, text_bytes]
+        args = [self.handle, *_dptrs(d_text), C.c_void_p(d_off), n_docs, text_bytes]
         if positions:
             self._check(self.lib.gz_bm25_build_device_ex(*args, GZ_BM25_POSITIONS, C.byref(h)))
         else:
@@ -705,8 +700,7 @@ class Context:
         self._check(self.lib.gz_bm25_append(C.c_void_p(index), _ptr(text) if len(text) else None, _ptr(text_off), len(text_off) - 1))
 
     def bm25_append_device(self, index: int, d_text, d_off, n_docs: int, text_bytes: int) -> None:
-        self._check(self.lib.gz_bm25_append_device(C.c_void_p(index), C.c_void_p(d_text) if d_text else None,
-                                                   C.c_void_p(d_off) if d_off else None, n_docs, text_bytes))
+        self._check(self.lib.gz_bm25_append_device(C.c_void_p(index), *_dptrs(d_text, d_off), n_docs, text_bytes))
 
     def bm25_remove(self, index: int, ids: np.ndarray) -> None:
         """document ids (int64; any order, duplicates allowed) leave the index: afterwards it answers as one built over the
@@ -715,7 +709,7 @@ class Context:
         self._check(self.lib.gz_bm25_remove(C.c_void_p(index), _ptr(ids) if len(ids) else None, len(ids)))
 
     def bm25_remove_device(self, index: int, d_ids, n_ids: int) -> None:
-        self._check(self.lib.gz_bm25_remove_device(C.c_void_p(index), C.c_void_p(d_ids) if d_ids else None, n_ids))
+        self._check(self.lib.gz_bm25_remove_device(C.c_void_p(index), *_dptrs(d_ids), n_ids))
 
     def bm25_compact(self, index: int) -> None:
         """the index becomes the one a fresh build of its current documents gives, term ids and buffer sizes included.  On
@@ -1051,7 +1045,7 @@ class Context:
 
     def encode_emit_block(self, d_block, bits: int = 16):
         """Arms the next (dense) encode call to leave its exchange block in d_block as part of the call (0: disarm)."""
-        self._check(self.lib.gz_encode_emit_block(self.handle, C.c_void_p(d_block) if d_block else None, bits))
+        self._check(self.lib.gz_encode_emit_block(self.handle, *_dptrs(d_block), bits))
 
     def block_total(self, back: int = 0) -> int:
         """Waits for the encode call `back` calls ago; the number of entries of the block it emitted."""
@@ -1074,7 +1068,7 @@ class Context:
     def gather_rows(self, d_send, n_rows_local, row_len, d_recv, rows_per_rank, root=0):
         rpr = np.ascontiguousarray(rows_per_rank, dtype=np.int64)
         self._check(self.lib.gz_gather_rows(self.handle, C.c_void_p(d_send), n_rows_local, row_len,
-                                            C.c_void_p(d_recv) if d_recv else None, _ptr(rpr), root))
+                                            *_dptrs(d_recv), _ptr(rpr), root))
 
 
 class HostTables:

@@ -12,6 +12,7 @@ that returns numpy arrays, which is what the GPU is for.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import threading
@@ -39,6 +40,43 @@ def _require_str(x):
     if isinstance(x, (bytes, bytearray, memoryview)):
         raise TypeError("cannot use a string pattern on a bytes-like object")
     raise TypeError("expected string or bytes-like object")
+
+
+# ---- validators of the row-shaping calls (window_rows, pack_rows, mask_rows, infill_rows): the value, or the refusal ----
+def _integer(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s must be an int" % name)
+    if not lo <= int(v) < hi:
+        raise ValueError("%s must lie in [%d, %d)" % (name, lo, hi))
+    return int(v)
+
+
+def _number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError("%s must be a number" % name)
+    return float(v)
+
+
+def _share(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError("%s must be a number" % name)
+    if not 0 <= v <= 1:                                                # (NaN fails here too)
+        raise ValueError("%s must lie in [0, 1]" % name)
+    return float(v)
+
+
+def _int32_ids(name, a, dense=False):
+    """ids as an int32 array, refused in the words of the call `name`; dense: they are rows [R, L], not flat"""
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s() expects integer ids" % name)
+    if dense and (a.ndim != 2 or a.shape[1] < 1 or a.shape[1] >= 2 ** 31):
+        raise ValueError("%s() expects a 2-D array of rows, [R, L] with 1 <= L < 2**31" % name)
+    if a.dtype != np.int32:
+        if a.size and (int(a.min()) < -(2 ** 31) or int(a.max()) >= 2 ** 31):
+            raise ValueError("%s() expects ids that fit in int32" % name)
+        a = a.astype(np.int32)
+    return a
 
 
 class Tokenize(object):
@@ -467,13 +505,7 @@ class Tokenize(object):
         (the window's first body position), n_real [W], win_off [N+1] (row r's windows are win_off[r]:win_off[r+1])."""
         L, s = self._window_rule(max_len, stride)
         flat, off = self._flat_rows(rows)
-        flat = np.asarray(flat)
-        if flat.dtype != np.int32:
-            if flat.dtype.kind not in "iu":
-                raise TypeError("window_rows() expects integer ids")
-            if flat.size and (int(flat.min()) < -(2 ** 31) or int(flat.max()) >= 2 ** 31):
-                raise ValueError("window_rows() expects ids that fit in int32")
-            flat = flat.astype(np.int32)
+        flat = _int32_ids("window_rows", flat)
         self._sync_tables()
         return self._ctx.window_rows(flat, off, L, s, bool(framed))
 
@@ -500,8 +532,11 @@ class Tokenize(object):
         with self._batch_lock:
             return self._encode_windows_locked(texts, L, s, True, True)
 
-    def _encode_windows_locked(self, texts, L, s, word_table, to_device):
-        from .handoff import DeviceArray
+    @contextlib.contextmanager
+    def _encode_ragged_to_device(self, texts, word_table):
+        """The texts encoded without a length limit into HBM, enqueued on the context's stream and NOT synchronised, so that what
+        shapes the rows goes right behind it: yields (d_ids, d_row_off, n, dev) -- dev(nbytes) allocates more -- and frees every
+        allocation on exit."""
         ctx = self._ctx
         t, to = _packing.pack_pinned(texts, self, ctx)
         n = len(to) - 1
@@ -517,13 +552,22 @@ class Tokenize(object):
             if t.nbytes:
                 ctx.h2d(d_t, np.ascontiguousarray(t))
             ctx.h2d(d_to, np.ascontiguousarray(to))
-            d_ids, d_mask, d_ro, d_wo = dev(4 * cap), dev(4 * cap), dev(8 * (n + 1)), dev(8 * (n + 1))
+            d_ids, d_mask, d_ro = dev(4 * cap), dev(4 * cap), dev(8 * (n + 1))
             if n:
-                # ragged rows, then the windows right behind them on the context's stream (no synchronisation in between)
                 ctx.encode_device(d_t, d_to, 0, 0, n, 0, _native.GZ_MAX_LEN_NONE | (0 if word_table else _native.GZ_NO_WORD_TABLE), cap,
                                   d_ids, d_mask, d_row_off=d_ro)
             else:
                 ctx.h2d(d_ro, np.zeros(1, dtype=np.int64))
+            yield d_ids, d_ro, n, dev
+        finally:
+            for d in bufs:
+                ctx.free(d)
+
+    def _encode_windows_locked(self, texts, L, s, word_table, to_device):
+        from .handoff import DeviceArray
+        ctx = self._ctx
+        with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, n, dev):
+            d_wo = dev(8 * (n + 1))
             W = ctx.window_rows_device(d_ids, d_ro, n, L, s, 1, 1, 0, 0, 0, 0, 0, d_wo, 0)
             ctx.sync()                                                 # (what the encode call deferred is reported here)
             cells = max(W * L, 1)
@@ -540,9 +584,6 @@ class Tokenize(object):
                 out = {k: v.numpy() for k, v in out.items()}           # (the DeviceArrays go with this frame)
             out["doc"], out["start"], out["n_real"], out["win_off"] = meta[0], meta[1], meta[2], win_off
             return out
-        finally:
-            for d in bufs:
-                ctx.free(d)
 
     @staticmethod
     def join_windows(result, stride: int):
@@ -588,13 +629,7 @@ class Tokenize(object):
         sequence lengths variable-length attention kernels take)."""
         L = self._pack_rule(max_len)
         flat, off = self._flat_rows(rows)
-        flat = np.asarray(flat)
-        if flat.dtype != np.int32:
-            if flat.dtype.kind not in "iu":
-                raise TypeError("pack_rows() expects integer ids")
-            if flat.size and (int(flat.min()) < -(2 ** 31) or int(flat.max()) >= 2 ** 31):
-                raise ValueError("pack_rows() expects ids that fit in int32")
-            flat = flat.astype(np.int32)
+        flat = _int32_ids("pack_rows", flat)
         self._sync_tables()
         return self._ctx.pack_rows(flat, off, L, bool(framed))
 
@@ -624,28 +659,8 @@ class Tokenize(object):
     def _encode_packs_locked(self, texts, L, word_table, to_device):
         from .handoff import DeviceArray
         ctx = self._ctx
-        t, to = _packing.pack_pinned(texts, self, ctx)
-        n = len(to) - 1
-        cap = (int(to[n] - to[0]) if n else 0) + 2 * n                 # a token takes a byte of text at least, plus the frame
-        bufs = []
-
-        def dev(nbytes):
-            d = ctx.alloc(max(int(nbytes), 1) + 64)
-            bufs.append(d)
-            return d
-        try:
-            d_t, d_to = dev(t.nbytes), dev(to.nbytes)
-            if t.nbytes:
-                ctx.h2d(d_t, np.ascontiguousarray(t))
-            ctx.h2d(d_to, np.ascontiguousarray(to))
-            d_ids, d_mask, d_ro = dev(4 * cap), dev(4 * cap), dev(8 * (n + 1))
+        with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, n, dev):
             d_maps, d_po, d_so = dev(12 * n), dev(8 * (n + 1)), dev(8 * (n + 1))
-            if n:
-                # ragged rows, then the packing right behind them on the context's stream (no synchronisation in between)
-                ctx.encode_device(d_t, d_to, 0, 0, n, 0, _native.GZ_MAX_LEN_NONE | (0 if word_table else _native.GZ_NO_WORD_TABLE), cap,
-                                  d_ids, d_mask, d_row_off=d_ro)
-            else:
-                ctx.h2d(d_ro, np.zeros(1, dtype=np.int64))
             maps = (d_maps, d_maps + 4 * n, d_maps + 8 * n) if n else (0, 0, 0)
             R = ctx.pack_rows_device(d_ids, d_ro, n, L, 1, 1, 0, 0, 0, 0, *maps, d_po, d_so, 0)
             ctx.sync()                                                 # (what the encode call deferred is reported here)
@@ -662,9 +677,6 @@ class Tokenize(object):
                 out = {k: v.numpy() for k, v in out.items()}           # (the DeviceArrays go with this frame)
             out["doc_row"], out["doc_col"], out["doc_len"], out["row_off"], out["seg_off"] = meta[0], meta[1], meta[2], row_off, seg_off
             return out
-        finally:
-            for d in bufs:
-                ctx.free(d)
 
     @staticmethod
     def unpack_rows(result):
@@ -674,25 +686,46 @@ class Tokenize(object):
         ids, seg = np.asarray(result["input_ids"]), np.asarray(result["segment_ids"])
         return ids[seg != 0].astype(np.int32, copy=False), np.asarray(result["seg_off"], dtype=np.int64).copy()
 
+    # ---- what the dense-row calls (mask_rows*, infill_rows*) share ----------------------------------------------------
+    def _dense_prologue(self, base, R, L):
+        """mask_id, once the cell indices are known to fit and the tables are on the device"""
+        if (base + R) * L >= 2 ** 63:
+            raise ValueError("(row_base + rows) * row length must stay below 2**63")
+        self._sync_tables()
+        mask_id = self._special_ids()[3]                               # encoder[mask_token], looked up at call time
+        if mask_id < 0:
+            raise KeyError(self.mask_token)
+        return mask_id
+
+    def _device_rows(self, name, x):
+        """(R, L) of int32 rows in this object's HBM, refused in the words of the call `name`"""
+        from .handoff import DeviceArray
+        if not isinstance(x, DeviceArray):
+            raise TypeError("%s() expects a handoff.DeviceArray" % name)
+        if x.dtype != np.int32:
+            raise TypeError("%s() expects int32 ids" % name)
+        if len(x.shape) != 2 or x.shape[1] < 1 or x.shape[1] >= 2 ** 31:
+            raise ValueError("%s() expects rows [R, L] with 1 <= L < 2**31" % name)
+        if x._ctx is not self._ctx:
+            raise ValueError("the rows belong to another Tokenize object's device context")
+        return x.shape
+
+    def _owned_rows(self, R, width):
+        """a fresh [R, width] int32 DeviceArray (an allocation nothing owns yet is freed when its DeviceArray fails)"""
+        from .handoff import DeviceArray
+        d = self._ctx.alloc(4 * max(R * width, 1))
+        try:
+            return DeviceArray(self._ctx, d, (R, width))
+        except BaseException:
+            self._ctx.free(d)
+            raise
+
     # ---- masked-LM inputs and labels, whole-word ---------------------------------------------------------------------
     @staticmethod
     def _mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index):
         """The arguments of a mask call as integers -- (seed, t_sel, t1, t2, rand_lo, rand_hi (None: the vocabulary), whole_word,
         ignore_index, row_base) -- or the refusal.  Thresholds are floor(x * 2**32): exact, a float times a power of two."""
-        def integer(name, v, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError("%s must be an int" % name)
-            if not lo <= int(v) < hi:
-                raise ValueError("%s must lie in [%d, %d)" % (name, lo, hi))
-            return int(v)
-
-        def share(name, v):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise TypeError("%s must be a number" % name)
-            if not 0 <= v <= 1:                                        # (NaN fails here too)
-                raise ValueError("%s must lie in [0, 1]" % name)
-            return float(v)
-        p, mp, rp = share("p", p), share("mask_prob", mask_prob), share("random_prob", random_prob)
+        p, mp, rp = _share("p", p), _share("mask_prob", mask_prob), _share("random_prob", random_prob)
         if mp + rp > 1:
             raise ValueError("mask_prob + random_prob must not exceed 1")
         if not isinstance(whole_word, (bool, np.bool_)):
@@ -703,22 +736,17 @@ class Tokenize(object):
         if random_ids is not None:
             if not isinstance(random_ids, (tuple, list)) or len(random_ids) != 2:
                 raise TypeError("random_ids must be None or a pair (lo, hi)")
-            lo = integer("random_ids[0]", random_ids[0], -(2 ** 31), 2 ** 31)
-            hi = integer("random_ids[1]", random_ids[1], -(2 ** 31), 2 ** 31)
+            lo = _integer("random_ids[0]", random_ids[0], -(2 ** 31), 2 ** 31)
+            hi = _integer("random_ids[1]", random_ids[1], -(2 ** 31), 2 ** 31)
             if lo >= hi:
                 raise ValueError("random_ids must be a non-empty range [lo, hi)")
-        return (integer("seed", seed, 0, 2 ** 64), t_sel, t1, t2, lo, hi, int(bool(whole_word)),
-                integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31), integer("row_base", row_base, 0, 2 ** 63))
+        return (_integer("seed", seed, 0, 2 ** 64), t_sel, t1, t2, lo, hi, int(bool(whole_word)),
+                _integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31), _integer("row_base", row_base, 0, 2 ** 63))
 
     def _mask_call(self, rule, R, L):
         """(the nine arguments of gz_mask_rows behind row_base, row_base) once the tables are known"""
         seed, t_sel, t1, t2, lo, hi, ww, ignore, base = rule
-        if (base + R) * L >= 2 ** 63:
-            raise ValueError("(row_base + rows) * row length must stay below 2**63")
-        self._sync_tables()
-        mask_id = self._special_ids()[3]                               # encoder[mask_token], looked up at call time
-        if mask_id < 0:
-            raise KeyError(self.mask_token)
+        mask_id = self._dense_prologue(base, R, L)
         if lo is None:
             lo, hi = 5, self.vocab_size()                              # (the five specials hold ids 0 .. 4, tokenize.py:31-37)
             if hi <= lo:
@@ -737,15 +765,7 @@ class Tokenize(object):
         input_ids [R, L], labels [R, L] (the original id where chosen, `ignore_index` elsewhere), n_chosen [R].  The attention
         mask is the caller's and does not change."""
         rule = self._mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index)
-        ids = np.asarray(input_ids)
-        if ids.dtype.kind not in "iu":
-            raise TypeError("mask_rows() expects integer ids")
-        if ids.ndim != 2 or ids.shape[1] < 1 or ids.shape[1] >= 2 ** 31:
-            raise ValueError("mask_rows() expects a 2-D array of rows, [R, L] with 1 <= L < 2**31")
-        if ids.dtype != np.int32:
-            if ids.size and (int(ids.min()) < -(2 ** 31) or int(ids.max()) >= 2 ** 31):
-                raise ValueError("mask_rows() expects ids that fit in int32")
-            ids = ids.astype(np.int32)
+        ids = _int32_ids("mask_rows", input_ids, dense=True)
         args, base = self._mask_call(rule, *ids.shape)
         return self._ctx.mask_rows(ids, args, base)
 
@@ -754,29 +774,12 @@ class Tokenize(object):
         """`mask_rows` over rows that are in HBM already and stay there: `input_ids` is a `handoff.DeviceArray` -- the input_ids of
         `encode_to_device`, `encode_windows_to_device` or `encode_packs_to_device` -- and input_ids and labels come back as
         `DeviceArray`s (`torch.from_dlpack(x)` is zero-copy); n_chosen is a host array.  The source rows are not changed."""
-        from .handoff import DeviceArray
         rule = self._mask_rule(p, seed, whole_word, mask_prob, random_prob, random_ids, row_base, ignore_index)
-        if not isinstance(input_ids, DeviceArray):
-            raise TypeError("mask_rows_to_device() expects a handoff.DeviceArray")
-        if input_ids.dtype != np.int32:
-            raise TypeError("mask_rows_to_device() expects int32 ids")
-        if len(input_ids.shape) != 2 or input_ids.shape[1] < 1 or input_ids.shape[1] >= 2 ** 31:
-            raise ValueError("mask_rows_to_device() expects rows [R, L] with 1 <= L < 2**31")
-        if input_ids._ctx is not self._ctx:
-            raise ValueError("the rows belong to another Tokenize object's device context")
-        R, L = input_ids.shape
+        R, L = self._device_rows("mask_rows_to_device", input_ids)
         args, base = self._mask_call(rule, R, L)
         ctx = self._ctx
-
-        def rows():                                                    # (an allocation nothing owns yet is freed when its DeviceArray fails)
-            d = ctx.alloc(4 * max(R * L, 1))
-            try:
-                return DeviceArray(ctx, d, (R, L))
-            except BaseException:
-                ctx.free(d)
-                raise
-        out = {"input_ids": rows()}
-        out["labels"] = rows()
+        out = {"input_ids": self._owned_rows(R, L)}
+        out["labels"] = self._owned_rows(R, L)
         n_chosen = np.zeros(R, dtype=np.int32)
         d_cnt = ctx.alloc(4 * max(R, 1))
         try:
@@ -831,22 +834,11 @@ class Tokenize(object):
         """The arguments of an infill call as integers -- (seed, t_start, len_t (n_len - 1 thresholds), n_len, whole_word,
         ignore_index, dec_len (None: the row length), row_base) -- or the refusal.  t_start = floor(q * 2**32) with q solved from
         the coverage formula; len_t[k] = floor(P(len <= k + 1) * 2**32), non-decreasing."""
-        def integer(name, v, lo, hi):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError("%s must be an int" % name)
-            if not lo <= int(v) < hi:
-                raise ValueError("%s must lie in [%d, %d)" % (name, lo, hi))
-            return int(v)
-
-        def number(name, v):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-                raise TypeError("%s must be a number" % name)
-            return float(v)
-        p = number("p", p)
+        p = _number("p", p)
         if not 0 <= p <= 1:                                            # (NaN fails here too)
             raise ValueError("p must lie in [0, 1]")
-        max_span = integer("max_span", max_span, 1, 17)
-        mean_span = number("mean_span", mean_span)
+        max_span = _integer("max_span", max_span, 1, 17)
+        mean_span = _number("mean_span", mean_span)
         if not isinstance(lengths, str):
             raise TypeError("lengths must be a str")
         if lengths not in ("geometric", "poisson", "fixed"):
@@ -858,10 +850,10 @@ class Tokenize(object):
         if not isinstance(whole_word, (bool, np.bool_)):
             raise TypeError("whole_word must be a bool")
         if dec_len is not None:
-            dec_len = integer("dec_len", dec_len, 1, 2 ** 31)
-        seed = integer("seed", seed, 0, 2 ** 64)
-        ignore_index = integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31)
-        row_base = integer("row_base", row_base, 0, 2 ** 63)
+            dec_len = _integer("dec_len", dec_len, 1, 2 ** 31)
+        seed = _integer("seed", seed, 0, 2 ** 64)
+        ignore_index = _integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31)
+        row_base = _integer("row_base", row_base, 0, 2 ** 63)
         one = 2 ** 32
         pmf = Tokenize._infill_lengths(lengths, mean_span, max_span)
         tail = [max(0.0, 1.0 - sum(pmf[:k])) if k else 1.0 for k in range(len(pmf))]
@@ -876,12 +868,7 @@ class Tokenize(object):
     def _infill_call(self, rule, R, L):
         """(the rule of _native.Context.infill_rows, row_base) once the tables are known"""
         seed, t_start, len_t, n_len, ww, ignore, dec_len, base = rule
-        if (base + R) * L >= 2 ** 63:
-            raise ValueError("(row_base + rows) * row length must stay below 2**63")
-        self._sync_tables()
-        mask_id = self._special_ids()[3]                               # encoder[mask_token], looked up at call time
-        if mask_id < 0:
-            raise KeyError(self.mask_token)
+        mask_id = self._dense_prologue(base, R, L)
         return (seed, t_start, len_t, n_len, mask_id, ww, ignore, L if dec_len is None else dec_len), base
 
     def infill_rows(self, input_ids, p=0.15, mean_span=3.0, max_span=10, lengths="geometric", seed=0, whole_word=True, dec_len=None,
@@ -901,15 +888,7 @@ class Tokenize(object):
         n_spans [R] -- dec_len is the target's whole length, so `dec_len > labels.shape[1]` marks a clipped row.  BART's
         full-sequence target is the row you passed in."""
         rule = self._infill_rule(p, mean_span, max_span, lengths, seed, whole_word, dec_len, row_base, ignore_index)
-        ids = np.asarray(input_ids)
-        if ids.dtype.kind not in "iu":
-            raise TypeError("infill_rows() expects integer ids")
-        if ids.ndim != 2 or ids.shape[1] < 1 or ids.shape[1] >= 2 ** 31:
-            raise ValueError("infill_rows() expects a 2-D array of rows, [R, L] with 1 <= L < 2**31")
-        if ids.dtype != np.int32:
-            if ids.size and (int(ids.min()) < -(2 ** 31) or int(ids.max()) >= 2 ** 31):
-                raise ValueError("infill_rows() expects ids that fit in int32")
-            ids = ids.astype(np.int32)
+        ids = _int32_ids("infill_rows", input_ids, dense=True)
         args, base = self._infill_call(rule, *ids.shape)
         return self._ctx.infill_rows(ids, args, base)
 
@@ -919,32 +898,15 @@ class Tokenize(object):
         input_ids of `encode_to_device`, `encode_windows_to_device` or `encode_packs_to_device` -- and input_ids,
         attention_mask, labels and decoder_input_ids come back as `DeviceArray`s (`torch.from_dlpack(x)` is zero-copy);
         enc_len, dec_len and n_spans are host arrays.  The source rows are not changed."""
-        from .handoff import DeviceArray
         rule = self._infill_rule(p, mean_span, max_span, lengths, seed, whole_word, dec_len, row_base, ignore_index)
-        if not isinstance(input_ids, DeviceArray):
-            raise TypeError("infill_rows_to_device() expects a handoff.DeviceArray")
-        if input_ids.dtype != np.int32:
-            raise TypeError("infill_rows_to_device() expects int32 ids")
-        if len(input_ids.shape) != 2 or input_ids.shape[1] < 1 or input_ids.shape[1] >= 2 ** 31:
-            raise ValueError("infill_rows_to_device() expects rows [R, L] with 1 <= L < 2**31")
-        if input_ids._ctx is not self._ctx:
-            raise ValueError("the rows belong to another Tokenize object's device context")
-        R, L = input_ids.shape
+        R, L = self._device_rows("infill_rows_to_device", input_ids)
         args, base = self._infill_call(rule, R, L)
         W = args[7]
         ctx = self._ctx
-
-        def rows(width):                                               # (an allocation nothing owns yet is freed when its DeviceArray fails)
-            d = ctx.alloc(4 * max(R * width, 1))
-            try:
-                return DeviceArray(ctx, d, (R, width))
-            except BaseException:
-                ctx.free(d)
-                raise
-        out = {"input_ids": rows(L)}
-        out["attention_mask"] = rows(L)
-        out["labels"] = rows(W)
-        out["decoder_input_ids"] = rows(W)
+        out = {"input_ids": self._owned_rows(R, L)}
+        out["attention_mask"] = self._owned_rows(R, L)
+        out["labels"] = self._owned_rows(R, W)
+        out["decoder_input_ids"] = self._owned_rows(R, W)
         counts = np.zeros((3, R), dtype=np.int32)
         d_cnt = ctx.alloc(12 * max(R, 1))
         try:
