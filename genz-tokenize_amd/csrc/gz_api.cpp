@@ -159,6 +159,7 @@ struct gz_ctx {
     DBuf t_dec_entries, t_dec_bytes, w_dec_rb;
     DBuf w_win_cnt;                                                                                     // overlapping windows (gz_window_rows*)
     DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol;              // packed rows (gz_pack_rows*)
+    DBuf w_mh_cnt, w_mh_off, w_mh_keys, w_mh_reps, w_mh_aux;                                            // MinHash: piece counts and offsets; the band table, EMPTY bytes + counter (gz_minhash_*)
     DBuf w_rows_in, w_rows_off, w_rows_out[4], w_rows_small;      // staging of the host forms of the row calls and the pre-pass (gz_rows_api.inc: WORKSPACE)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_ppctl, w_pplen32, w_pplb;                             // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
@@ -1048,6 +1049,7 @@ try {
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
+    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux}) release(*b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);

@@ -190,6 +190,38 @@ struct GzInfillArgs {
 };
 void gz_launch_infill(GzInfillArgs A, hipStream_t s);
 
+// MinHash signatures of ragged rows and near-duplicate groups from signatures (gz_minhash.inc)
+constexpr int GZ_MINHASH_PIECE = 4096;      // shingle positions a wave takes: a row with more is split over waves (64 trips of 64)
+// Count pass: n_pieces[n_rows] = max(1, ceil(shingles / GZ_MINHASH_PIECE)), their exclusive scan piece_off[n_rows + 1], and
+// *too_long = 1 when a body holds 2^31 ids or more (cleared first).
+void gz_launch_minhash_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle, int64_t* n_pieces,
+                             int64_t* piece_off, uint32_t* too_long, hipStream_t s);
+struct GzMinhashArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31
+    int32_t skip_front, skip_back, shingle, num_perm;               // skips 0 or 1, 1 <= shingle <= 32, 1 <= num_perm <= 256
+    uint32_t seed_lo, seed_hi;
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    uint32_t* sig;                                                  // [n_rows, num_perm]
+    int32_t* n_shingles;                                            // [n_rows], may be null
+};
+void gz_launch_minhash_sig(GzMinhashArgs A, hipStream_t s);        // fills sig with 0xFFFFFFFF first when a row has more than one piece
+struct GzMinhashGroupArgs {
+    const uint32_t* sig; int64_t n_rows;                            // [n_rows, num_perm]; 1 <= n_rows < 2^31 - 4096
+    int32_t num_perm, bands, min_agree;                             // bands divides num_perm, 1 <= min_agree <= num_perm
+    int32_t* group;                                                 // [n_rows]: the labels, and the forest while the bands are linked
+    unsigned long long* keys; uint32_t* reps; uint64_t cap;         // the table: cap = gz_minhash_cap(n_rows) slots
+    uint8_t* empty;                                                 // [n_rows]
+    unsigned long long* n_groups;                                   // rows with group[d] == d
+};
+inline uint64_t gz_minhash_cap(int64_t n_rows)                      // a power of two, at least twice the rows (and at least 64)
+{
+    uint64_t cap = 64;
+    while (cap < 2 * (uint64_t)n_rows) cap <<= 1;
+    return cap;
+}
+void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s);     // init, then per band clear / insert / link, then flatten + count
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

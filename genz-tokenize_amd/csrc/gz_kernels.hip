@@ -712,6 +712,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_packrows.inc"
 #include "gz_mask.inc"
 #include "gz_infill.inc"
+#include "gz_minhash.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -858,6 +859,44 @@ void gz_launch_infill(GzInfillArgs A, hipStream_t s)
     const dim3 grid = dense_division(A, &lds), block(WAVE * 4);
     if (lds) hipLaunchKernelGGL((gz_infill_kernel<true>), grid, block, lds, s, A);
     else hipLaunchKernelGGL((gz_infill_kernel<false>), grid, block, 0, s, A);
+}
+
+void gz_launch_minhash_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle, int64_t* n_pieces,
+                             int64_t* piece_off, uint32_t* too_long, hipStream_t s)
+{
+    if (n_rows <= 0) return;
+    (void)hipMemsetAsync(too_long, 0, 4, s);
+    hipLaunchKernelGGL(gz_minhash_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back,
+                       shingle, n_pieces, too_long);
+    launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
+}
+
+void gz_launch_minhash_sig(GzMinhashArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    if (!A.one_each) (void)hipMemsetAsync(A.sig, 0xFF, (size_t)A.n_rows * (size_t)A.num_perm * 4, s);       // the pieces of a long row meet by atomicMin
+    const dim3 grid((unsigned)((A.n_pieces + 3) / 4)), block(WAVE * 4);
+    switch ((A.num_perm + WAVE - 1) / WAVE) {
+    case 1: hipLaunchKernelGGL(gz_minhash_sig_kernel<1>, grid, block, 0, s, A); break;
+    case 2: hipLaunchKernelGGL(gz_minhash_sig_kernel<2>, grid, block, 0, s, A); break;
+    case 3: hipLaunchKernelGGL(gz_minhash_sig_kernel<3>, grid, block, 0, s, A); break;
+    default: hipLaunchKernelGGL(gz_minhash_sig_kernel<4>, grid, block, 0, s, A); break;
+    }
+}
+
+void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    const dim3 grid((unsigned)((A.n_rows + 255) / 256)), block(256);
+    hipLaunchKernelGGL(gz_minhash_init_kernel, grid, block, 0, s, A);
+    for (int band = 0; band < A.bands; ++band) {
+        (void)hipMemsetAsync(A.keys, 0, (size_t)A.cap * 8, s);
+        (void)hipMemsetAsync(A.reps, 0xFF, (size_t)A.cap * 4, s);
+        hipLaunchKernelGGL(gz_minhash_insert_kernel, grid, block, 0, s, A, band);
+        hipLaunchKernelGGL(gz_minhash_link_kernel, grid, block, 0, s, A, band);
+    }
+    hipLaunchKernelGGL(gz_minhash_flatten_kernel, grid, block, 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

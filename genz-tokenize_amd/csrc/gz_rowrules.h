@@ -1,5 +1,6 @@
 // gz_rowrules.h -- the rules every row-shaping call shares, as plain host C++ (no HIP, no context: tests/test_row_rules.py compiles
-// this file alone): the check of a host CSR input, the dense-row rule and the pairwise-disjoint check of a call's arrays.
+// this file alone): the check of a host CSR input, the dense-row rule, the MinHash argument rules (tests/test_minhash_surface.py
+// compiles them alone too) and the pairwise-disjoint check of a call's arrays.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -22,6 +23,34 @@ inline bool dense_rule_ok(int64_t n_rows, int32_t row_len, int64_t row_base, int
     if (row_len < 1 || n_rows < 0 || row_base < 0 || (whole_word != 0 && whole_word != 1)) return false;
     const unsigned __int128 cells = ((unsigned __int128)row_base + (unsigned __int128)n_rows) * (unsigned __int128)row_len;
     return (cells >> 63) == 0;
+}
+
+// MinHash (gz_minhash_rows*, gz_minhash_groups*): the sentence of the first rule an argument list breaks, or nullptr.  Every refusal
+// has its own sentence; the order below is the order they are reported in.
+inline const char* minhash_rows_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle, int32_t num_perm)
+{
+    if (n_rows < 0) return "minhash rows need n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "minhash rows need skips of 0 or 1";
+    if (shingle < 1 || shingle > 32) return "minhash rows need a shingle width in 1..32";
+    if (num_perm < 1 || num_perm > 256) return "minhash rows need num_perm in 1..256";
+    return nullptr;
+}
+inline const char* minhash_groups_fault(int64_t n_rows, int32_t num_perm, int32_t bands, int32_t min_agree)
+{
+    if (n_rows < 0) return "minhash groups need n_rows >= 0";
+    if (n_rows >= (int64_t)INT32_MAX - 4096) return "minhash groups need fewer than 2^31 - 4096 rows";
+    if (num_perm < 1 || num_perm > 256) return "minhash groups need num_perm in 1..256";
+    if (bands < 1) return "minhash groups need bands >= 1";
+    if (num_perm % bands != 0) return "minhash groups need a number of bands that divides num_perm";
+    if (min_agree < 1 || min_agree > num_perm) return "minhash groups need min_agree in 1..num_perm";
+    return nullptr;
+}
+// the longest body of a host CSR input whose offsets passed rows_offsets_check: a body of 2^31 ids or more is refused (GZ_E_LIMIT)
+inline bool minhash_bodies_fit(const int64_t* off, int64_t n_rows, int32_t skip_front, int32_t skip_back)
+{
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (off[r + 1] - off[r] - skip_front - skip_back >= ((int64_t)1 << 31)) return false;
+    return true;
 }
 
 // An array of a call: where it starts and how many bytes the call touches.  ABSENT: a null address or zero bytes.  (The callers

@@ -1,10 +1,12 @@
-// The row-shaping calls behind the C ABI: batch decode, overlapping windows, packed rows, masked-LM rows, span-corruption rows.
+// The row-shaping calls behind the C ABI: batch decode, overlapping windows, packed rows, masked-LM rows, span-corruption rows,
+// MinHash signatures and groups.
 // Included by gz_api.cpp behind gz_ctx, fail, HIPCHK, ensure and the copy helpers; the kernels are in gz_decode.inc, gz_window.inc,
-// gz_packrows.inc, gz_mask.inc and gz_infill.inc.  A call supplies its rule, its launch and its list of outputs; the row front
+// gz_packrows.inc, gz_mask.inc, gz_infill.inc and gz_minhash.inc.  A call supplies its rule, its launch and its list of outputs; the row front
 // below does the rest of a host form (DESIGN.md, "the row front"); its rules without HIP in them are in gz_rowrules.h.
 // WORKSPACE: the host forms share w_rows_in, w_rows_off, w_rows_out[4] and w_rows_small.  That is sound because every use lies
 // inside c->mu and every access -- copy, kernel, memset -- is enqueued on c->stream: a later call's accesses are ordered behind an
-// earlier call's even where that one returned early.  A kernel's own scratch (w_win_cnt, the w_pk_* maps, w_dec_rb) is not shared.
+// earlier call's even where that one returned early.  A kernel's own scratch (w_win_cnt, the w_pk_* maps, w_dec_rb, the w_mh_* piece
+// counts, band table and EMPTY bytes) is not shared.
 
 // ---- the row front -----------------------------------------------------------------------------------------------------
 namespace {
@@ -603,5 +605,147 @@ try {
     if ((rc = ensure(c, c->w_rows_in, cells)) || (rc = copy_in(c, c->w_rows_in.p, ids, cells, c->stream)) || (rc = staged_ensure(c, S))) return rc;
     infill_launch(c, M, InfillBufs{(const int32_t*)c->w_rows_in.p, S.dev(0), S.dev(1), S.dev(2), S.dev(3), S.dev(4), S.dev(5), S.dev(6)});
     return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- near-duplicate documents by MinHash signatures ---------------------------------------------------------------------
+namespace {
+const char* const kMinhashRowsBuffers = "minhash rows need ids, row_off and signatures, and output arrays that overlap neither the input nor each other";
+const char* const kMinhashGroupsBuffers = "minhash groups need signatures, group and n_groups_host, and arrays that do not overlap";
+
+// n_rows > 0.  ids_bytes: what the call knows of the ids' extent (the host form: all of it; the device form: their first word)
+bool minhash_rows_buffers_ok(const void* ids, uintptr_t ids_bytes, const int64_t* row_off, int64_t n_rows, int32_t num_perm, const uint32_t* signatures,
+                             const int32_t* n_shingles)
+{
+    if (!row_off || !signatures) return false;
+    if ((uint64_t)n_rows > (uint64_t)(UINTPTR_MAX / 4 / 256)) return false;                              // (the byte counts below do not wrap)
+    const uintptr_t n = (uintptr_t)n_rows;
+    const Span s[4] = {span_of(ids, ids_bytes), span_of(row_off, (n + 1) * 8u), span_of(signatures, n * (uintptr_t)num_perm * 4u), span_of(n_shingles, n * 4u)};
+    return disjoint(s, 4);
+}
+
+// Both passes on the context's stream, behind whatever it holds; the caller waits for the signatures.  piece_off_dev: n_rows + 1 words
+// of the caller's.  Nothing is written to the outputs when a body is too long.  n_rows > 0.
+int minhash_rows_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                        int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t* sig_dev, int32_t* n_shingles_dev, int64_t* piece_off_dev)
+{
+    int rc;
+    if ((rc = ensure(c, c->w_mh_cnt, (size_t)(n_rows + 1) * 8 + 16))) return rc;
+    int64_t* const cnt = (int64_t*)c->w_mh_cnt.p;
+    uint32_t* const too_long = (uint32_t*)(cnt + n_rows + 1);
+    gz_launch_minhash_count(row_off_dev, n_rows, skip_front, skip_back, shingle, cnt, piece_off_dev, too_long, c->stream);
+    uint32_t* const h_long = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 352);       // (pinned scratch)
+    *h_long = 0;
+    HIPCHK(c, hipMemcpyAsync(h_long, too_long, 4, hipMemcpyDeviceToHost, c->stream));
+    int64_t n_pieces = 0;
+    if ((rc = read_total(c, piece_off_dev + n_rows, nullptr, &n_pieces))) return rc;
+    if (*h_long) return fail(c, GZ_E_LIMIT, "a row's body holds 2^31 ids or more: split the document");
+    GzMinhashArgs A{};
+    A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows;
+    A.skip_front = skip_front; A.skip_back = skip_back; A.shingle = shingle; A.num_perm = num_perm;
+    A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
+    A.piece_off = piece_off_dev; A.n_pieces = n_pieces;
+    A.sig = sig_dev; A.n_shingles = n_shingles_dev;
+    gz_launch_minhash_sig(A, c->stream);
+    return GZ_OK;
+}
+
+// All bands and the labels on the context's stream; *n_groups is read back, so the labels are complete on return.  n_rows > 0.
+int minhash_groups_locked(gz_ctx* c, const uint32_t* sig_dev, int64_t n_rows, int32_t num_perm, int32_t bands, int32_t min_agree, int32_t* group_dev,
+                          int64_t* n_groups)
+{
+    const uint64_t cap = gz_minhash_cap(n_rows);
+    int rc;
+    if ((rc = ensure(c, c->w_mh_keys, (size_t)cap * 8)) || (rc = ensure(c, c->w_mh_reps, (size_t)cap * 4)) ||
+        (rc = ensure(c, c->w_mh_aux, (size_t)n_rows + 16))) return rc;
+    GzMinhashGroupArgs A{};
+    A.sig = sig_dev; A.n_rows = n_rows; A.num_perm = num_perm; A.bands = bands; A.min_agree = min_agree;
+    A.group = group_dev;
+    A.keys = (unsigned long long*)c->w_mh_keys.p; A.reps = (uint32_t*)c->w_mh_reps.p; A.cap = cap;
+    A.n_groups = (unsigned long long*)c->w_mh_aux.p; A.empty = (uint8_t*)c->w_mh_aux.p + 8;
+    gz_launch_minhash_groups(A, c->stream);
+    if ((rc = read_total(c, (const int64_t*)A.n_groups, nullptr, n_groups))) return rc;
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_minhash_rows_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                           int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t* signatures_dev, int32_t* n_shingles_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = minhash_rows_fault(n_rows, skip_front, skip_back, shingle, num_perm)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (n_rows == 0) return GZ_OK;
+    if (!ids_dev || !minhash_rows_buffers_ok(ids_dev, 4, row_off_dev, n_rows, num_perm, signatures_dev, n_shingles_dev))
+        return fail(c, GZ_E_INVALID, "%s", kMinhashRowsBuffers);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_mh_off, (size_t)(n_rows + 1) * 8))) return rc;
+    if ((rc = minhash_rows_locked(c, ids_dev, row_off_dev, n_rows, skip_front, skip_back, shingle, num_perm, seed, signatures_dev, n_shingles_dev,
+                                  (int64_t*)c->w_mh_off.p))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_minhash_rows(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle,
+                    int32_t num_perm, uint64_t seed, uint32_t* signatures, int32_t* n_shingles)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = minhash_rows_fault(n_rows, skip_front, skip_back, shingle, num_perm)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (n_rows == 0) return GZ_OK;
+    if (!row_off || !signatures) return fail(c, GZ_E_INVALID, "%s", kMinhashRowsBuffers);
+    RowsIn in{ids, row_off, n_rows, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords))) return rc;
+    if (!minhash_rows_buffers_ok(in.n ? ids + row_off[0] : nullptr, (uintptr_t)in.n * 4u, row_off, n_rows, num_perm, signatures, n_shingles))
+        return fail(c, GZ_E_INVALID, "%s", kMinhashRowsBuffers);
+    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "a row's body holds 2^31 ids or more: split the document");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;                 // kept through both passes: piece_off
+    StagedOut S;
+    S.add(signatures, (size_t)n_rows * (size_t)num_perm * 4, true); S.add(n_shingles, (size_t)n_rows * 4, false);
+    if ((rc = staged_ensure(c, S))) return rc;
+    if ((rc = minhash_rows_locked(c, (const int32_t*)in.d_payload, in.d_off, n_rows, skip_front, skip_back, shingle, num_perm, seed,
+                                  (uint32_t*)S.e[0].dev, S.dev(1), (int64_t*)in.d_keep))) return rc;
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+int gz_minhash_groups_device(gz_ctx* c, const uint32_t* signatures_dev, int64_t n_rows, int32_t num_perm, int32_t bands, int32_t min_agree,
+                             int32_t* group_dev, int64_t* n_groups_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = minhash_groups_fault(n_rows, num_perm, bands, min_agree)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!n_groups_host) return fail(c, GZ_E_INVALID, "%s", kMinhashGroupsBuffers);
+    if (n_rows == 0) { *n_groups_host = 0; return GZ_OK; }
+    const Span s[2] = {span_of(signatures_dev, (uintptr_t)n_rows * (uintptr_t)num_perm * 4u), span_of(group_dev, (uintptr_t)n_rows * 4u)};
+    if (!signatures_dev || !group_dev || !disjoint(s, 2)) return fail(c, GZ_E_INVALID, "%s", kMinhashGroupsBuffers);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return minhash_groups_locked(c, signatures_dev, n_rows, num_perm, bands, min_agree, group_dev, n_groups_host);
+} GZ_CATCH(c)
+
+int gz_minhash_groups(gz_ctx* c, const uint32_t* signatures, int64_t n_rows, int32_t num_perm, int32_t bands, int32_t min_agree, int32_t* group,
+                      int64_t* n_groups_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = minhash_groups_fault(n_rows, num_perm, bands, min_agree)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!n_groups_host) return fail(c, GZ_E_INVALID, "%s", kMinhashGroupsBuffers);
+    if (n_rows == 0) { *n_groups_host = 0; return GZ_OK; }
+    const size_t sig_bytes = (size_t)n_rows * (size_t)num_perm * 4;
+    const Span s[3] = {span_of(signatures, sig_bytes), span_of(group, (uintptr_t)n_rows * 4u), span_of(n_groups_host, 8)};
+    if (!signatures || !group || !disjoint(s, 3)) return fail(c, GZ_E_INVALID, "%s", kMinhashGroupsBuffers);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    StagedOut S;
+    S.add(group, (size_t)n_rows * 4, true);
+    int rc;
+    if ((rc = ensure(c, c->w_rows_in, sig_bytes)) || (rc = copy_in(c, c->w_rows_in.p, signatures, sig_bytes, c->stream)) || (rc = staged_ensure(c, S)))
+        return rc;
+    int64_t n_groups = 0;
+    if ((rc = minhash_groups_locked(c, (const uint32_t*)c->w_rows_in.p, n_rows, num_perm, bands, min_agree, S.dev(0), &n_groups))) return rc;
+    if ((rc = staged_copy_out(c, S))) return rc;
+    *n_groups_host = n_groups;
+    return GZ_OK;
 } GZ_CATCH(c)
 

@@ -50,6 +50,7 @@ SYMBOLS = [
     "gz_pack_rows", "gz_pack_rows_device",
     "gz_mask_rows", "gz_mask_rows_device",
     "gz_infill_rows", "gz_infill_rows_device",
+    "gz_minhash_rows", "gz_minhash_rows_device", "gz_minhash_groups", "gz_minhash_groups_device",
 ]
 
 _lib = None
@@ -119,6 +120,14 @@ def load_library():
         fi = [vp, vp, i64, i32, i64, u64, u64, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.gz_infill_rows.argtypes = fi
         L.gz_infill_rows_device.argtypes = fi
+    if hasattr(L, "gz_minhash_rows"):
+        u64 = C.c_uint64
+        mh = [vp, vp, vp, i64, i32, i32, i32, i32, u64, vp, vp]
+        L.gz_minhash_rows.argtypes = mh
+        L.gz_minhash_rows_device.argtypes = mh
+        mg = [vp, vp, i64, i32, i32, i32, vp, P(i64)]
+        L.gz_minhash_groups.argtypes = mg
+        L.gz_minhash_groups_device.argtypes = mg
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -631,6 +640,36 @@ class Context:
                                                    *_dptrs(d_input_ids, d_attention_mask, d_labels, d_decoder_input_ids, d_enc_len, d_dec_len,
                                                             d_n_spans)))
         del keep
+
+    # ---- MinHash signatures and near-duplicate groups -------------------------------------------------------
+    def minhash_rows(self, ids: np.ndarray, row_off: np.ndarray, num_perm: int, shingle: int, seed: int, framed: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict(signatures uint32 [n, K], n_shingles int32 [n]) (gz_minhash_rows)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, K, skip = len(row_off) - 1, int(num_perm), 1 if framed else 0
+        out = dict(signatures=np.empty((n, K), dtype=np.uint32), n_shingles=np.empty(n, dtype=np.int32))
+        self._check(self.lib.gz_minhash_rows(self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip, int(shingle), K,
+                                             int(seed), *[_ptr(v) if n else None for v in out.values()]))
+        return out
+
+    def minhash_rows_device(self, d_ids, d_row_off, n_rows, skip_front, skip_back, shingle, num_perm, seed, d_signatures, d_n_shingles):
+        """gz_minhash_rows_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_minhash_rows_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, shingle, num_perm,
+                                                    seed, *_dptrs(d_signatures, d_n_shingles)))
+
+    def minhash_groups(self, signatures: np.ndarray, bands: int, min_agree: int):
+        """signatures uint32 [n, K] -> (group int32 [n], n_groups) (gz_minhash_groups)."""
+        sig = np.ascontiguousarray(signatures, dtype=np.uint32)
+        n, K = sig.shape
+        group = np.empty(n, dtype=np.int32)
+        total = self._call_total(self.lib.gz_minhash_groups, self.handle, _ptr(sig) if n else None, n, K, int(bands), int(min_agree),
+                                 _ptr(group) if n else None)
+        return group, total
+
+    def minhash_groups_device(self, d_signatures, n_rows, num_perm, bands, min_agree, d_group) -> int:
+        """gz_minhash_groups_device: signatures and group device addresses (0: NULL); returns n_groups."""
+        return self._call_total(self.lib.gz_minhash_groups_device, self.handle, *_dptrs(d_signatures), n_rows, num_perm, bands, min_agree,
+                                *_dptrs(d_group))
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

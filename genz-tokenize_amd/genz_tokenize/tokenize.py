@@ -919,6 +919,115 @@ class Tokenize(object):
         out["enc_len"], out["dec_len"], out["n_spans"] = counts[0], counts[1], counts[2]
         return out
 
+    # ---- near-duplicate documents by MinHash signatures --------------------------------------------------------------
+    @staticmethod
+    def _minhash_rule(num_perm=128, shingle=5, seed=0, bands=16, threshold=0.7, min_agree=None):
+        """The arguments of the MinHash calls as integers -- (num_perm, shingle, seed, bands, min_agree) -- or the refusal;
+        min_agree defaults to max(1, ceil(threshold * num_perm))."""
+        K = _integer("num_perm", num_perm, 1, 257)
+        w = _integer("shingle", shingle, 1, 33)
+        seed = _integer("seed", seed, 0, 2 ** 64)
+        B = _integer("bands", bands, 1, 257)
+        if K % B:
+            raise ValueError("bands must divide num_perm")
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise TypeError("threshold must be a number")
+        if not 0 < threshold <= 1:                                         # (NaN fails here too)
+            raise ValueError("threshold must lie in (0, 1]")
+        if min_agree is None:
+            m = max(1, int(math.ceil(float(threshold) * K)))
+        else:
+            m = _integer("min_agree", min_agree, 1, K + 1)
+        return K, w, seed, B, m
+
+    def minhash_rows(self, rows, num_perm=128, shingle=5, seed=0, framed=True):
+        """MinHash signatures of token rows, on the GPU.  `rows` as `decode_batch` / `window_rows` take them (`framed=True`: each
+        row loses its first and last entry first).  A body's shingles are its runs of `shingle` ids (the whole body when it is
+        shorter, none when it is empty), each hashed with MurmurHash3 over the ids; slot k of the signature is the minimum over
+        the shingles of fmix32(hash ^ c_k), the c_k drawn from `seed`, and 0xFFFFFFFF in every slot without shingles -- the
+        share of equal slots of two signatures estimates the Jaccard index of the two shingle sets.  A row's signature depends
+        on its own body alone: `minhash_rows(rows[a:b])` is `minhash_rows(rows)[a:b]`, and signatures of shards concatenate.
+        Returns numpy arrays: signatures uint32 [N, num_perm], n_shingles int32 [N]."""
+        K, w, seed, _, _ = self._minhash_rule(num_perm, shingle, seed, 1)                # (no bands here: one always divides)
+        flat, off = self._flat_rows(rows)
+        flat = _int32_ids("minhash_rows", flat)
+        return self._ctx.minhash_rows(flat, off, K, w, seed, bool(framed))
+
+    def encode_minhash(self, texts: Sequence[str], num_perm=128, shingle=5, seed=0, word_table=True):
+        """`minhash_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, the signatures are made there, and only they come back, uint32 [N, num_perm].  The rule is `minhash_rows`'s,
+        over the rows of `encode_batch(texts, max_len=None)` without their frame; `encode_minhash(texts[a:b])` is
+        `encode_minhash(texts)[a:b]`, and signatures of shards concatenate.  Single texts only."""
+        return self._encode_minhash(texts, num_perm, shingle, seed, word_table).numpy()
+
+    def encode_minhash_to_device(self, texts: Sequence[str], num_perm=128, shingle=5, seed=0):
+        """`encode_minhash` whose [N, num_perm] signatures STAY in HBM as a `handoff.DeviceArray` of dtype uint32, ready for
+        `minhash_groups`; the same rule, and the same slicing identity: signatures of shards concatenate."""
+        return self._encode_minhash(texts, num_perm, shingle, seed, True)
+
+    def _encode_minhash(self, texts, num_perm, shingle, seed, word_table):
+        from .handoff import DeviceArray
+        K, w, seed, _, _ = self._minhash_rule(num_perm, shingle, seed, 1)                # (no bands here: one always divides)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, n, dev):
+                d_sig = ctx.alloc(4 * max(n * K, 1))
+                try:
+                    sig = DeviceArray(ctx, d_sig, (n, K), dtype=np.uint32)
+                except BaseException:
+                    ctx.free(d_sig)
+                    raise
+                ctx.minhash_rows_device(d_ids, d_ro, n, 1, 1, w, K, seed, d_sig, 0)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+                return sig
+
+    def minhash_groups(self, signatures, bands=16, threshold=0.7, min_agree=None):
+        """Near-duplicate groups from MinHash signatures, on the GPU: `signatures` is a numpy uint32 [N, K] array or a
+        `handoff.DeviceArray` of this object (`encode_minhash_to_device`); signatures made in many batches are concatenated and
+        grouped once.  The K slots are cut into `bands` bands; in every band a row is compared with the SMALLEST row that has the
+        same band (and with no other: two rows that share a band only with a smaller third that resembles neither are not joined
+        through it), and the two are joined when they agree in at least `min_agree` slots, default max(1, ceil(threshold * K)).
+        A row whose slots are all 0xFFFFFFFF (an empty document) stays alone.  Returns group int32 [N] (the smallest row of the
+        row's group), keep bool [N] (group == arange(N): the rows to keep) and n_groups."""
+        from .handoff import DeviceArray
+        on_device = isinstance(signatures, DeviceArray)
+        sig = signatures if on_device else np.asarray(signatures)
+        if sig.dtype != np.uint32:
+            raise TypeError("minhash_groups() expects uint32 signatures")
+        if len(sig.shape) != 2 or not 1 <= sig.shape[1] <= 256:
+            raise ValueError("minhash_groups() expects signatures [N, K] with 1 <= K <= 256")
+        N, K = sig.shape
+        if N >= 2 ** 31 - 4096:
+            raise ValueError("minhash_groups() takes fewer than 2**31 - 4096 rows")
+        _, _, _, B, m = self._minhash_rule(K, 5, 0, bands, threshold, min_agree)
+        if on_device and sig._ctx is not self._ctx:
+            raise ValueError("the signatures belong to another Tokenize object's device context")
+        ctx = self._ctx
+        if not on_device:
+            group, total = ctx.minhash_groups(sig, B, m)
+        else:
+            group = np.zeros(N, dtype=np.int32)
+            d_group = ctx.alloc(4 * max(N, 1))
+            try:
+                total = ctx.minhash_groups_device(sig.ptr if N else 0, N, K, B, m, d_group if N else 0)
+                if N:
+                    ctx.d2h(group, d_group)
+            finally:
+                ctx.free(d_group)
+        return dict(group=group, keep=group == np.arange(N, dtype=np.int32), n_groups=int(total))
+
+    def near_duplicates(self, texts: Sequence[str], num_perm=128, shingle=5, seed=0, bands=16, threshold=0.7, min_agree=None,
+                        word_table=True):
+        """`encode_minhash_to_device` and `minhash_groups` together: the signatures never leave HBM.  Returns the dict of
+        `minhash_groups`; `texts[i]` for the i with keep[i] is the corpus without its near-duplicates."""
+        self._minhash_rule(num_perm, shingle, seed, bands, threshold, min_agree)
+        sig = self._encode_minhash(texts, num_perm, shingle, seed, word_table)
+        return self.minhash_groups(sig, bands, threshold, min_agree)
+
     @staticmethod
     def _shape(r, n):
         if r["dense"]:

@@ -455,6 +455,65 @@ int  gz_infill_rows_device(gz_ctx *ctx, const int32_t *ids_dev, int64_t n_rows, 
                            int32_t *labels_dev, int32_t *decoder_input_ids_dev, int32_t *enc_len_dev, int32_t *dec_len_dev,
                            int32_t *n_spans_dev);
 
+/* ---- near-duplicate documents by MinHash signatures ----------------------------------------------------------------------------
+ * A web corpus holds mirrors, re-posts and near-copies; every pretraining recipe removes them before it packs and masks.  Two passes:
+ * gz_minhash_rows* writes num_perm 32-bit minima over the hashes of every document's token shingles (its signature; the share of
+ * slots in which two signatures agree estimates the Jaccard index of the two shingle sets), gz_minhash_groups* turns a
+ * [n_rows, num_perm] signature matrix into one label a document, the smallest row of its near-duplicate group.  Both are pure
+ * functions of their arguments: signatures made in many batches or on many GPUs are concatenated and grouped once.  Neither needs
+ * the tables or the decoder snapshot.  All arithmetic is unsigned and wraps at 32 or 64 bits.
+ *   fmix32(x)        x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16
+ *   H(t[0..m))       MurmurHash3_x86_32, seed 0, over the m ids as little-endian 32-bit words (the bit pattern of the int32):
+ *                    h = 0;  per id:  k = t * 0xCC9E2D51;  k = rotl(k, 15);  k *= 0x1B873593;  h ^= k;  h = rotl(h, 13);
+ *                    h = h * 5 + 0xE6546B64;  then  h ^= 4 m;  h = fmix32(h)
+ *   c_k              fmix32(seed_lo ^ fmix32(seed_hi + 0x9E3779B9 * (k + 1))),  k = 0 .. num_perm - 1,  seed_lo = seed & 0xFFFFFFFF,
+ *                    seed_hi = seed >> 32
+ *   g_k(x)           fmix32(x ^ c_k): a bijection of the 32-bit values for every k
+ *   body of row r    ids[row_off[r] + skip_front .. row_off[r+1] - skip_back); the skips are 0 or 1 as in gz_window_rows; a row
+ *                    shorter than its skips has an empty body
+ *   shingles         of a body of n ids, width w = shingle:  n >= w: the n - w + 1 runs body[i .. i + w), each hashed with H;
+ *                    0 < n < w: ONE shingle, the whole body, H over n ids (the 4 m term keeps it apart from every run of w);
+ *                    n == 0: none.  n_shingles[r] is that count
+ *   signature        sig[r][k] = min over the shingles s of g_k(H(s)); 0xFFFFFFFF in every slot for a body without shingles.  A row
+ *                    all of whose slots are 0xFFFFFFFF is EMPTY to the second pass
+ *   band key         bands divides num_perm, rows_per_band = num_perm / bands; for band j of row d:
+ *                    z = 0x9E3779B97F4A7C15 * (j + 1);  for v in sig[d][j * rows_per_band .. (j + 1) * rows_per_band):
+ *                    z = (z ^ v) * 0xFF51AFD7ED558CCD;  z ^= z >> 32;   key = z | 1   (never 0)
+ *   rep_j(d)         the smallest non-EMPTY row with the same key in band j: d itself when there is none smaller
+ *   agree(a, b)      the number of slots in which the two signatures are equal
+ *   edges            d -- rep_j(d) for every band j with rep_j(d) != d and agree(d, rep_j(d)) >= min_agree
+ *   group[d]         the smallest row of d's connected component: d itself for a row without edges and for an EMPTY row;
+ *                    *n_groups_host = the number of rows with group[d] == d
+ *   Only the smallest member of a bucket is asked: two rows that share a bucket with a third, smaller one that resembles neither
+ *   are NOT joined through that band (another band usually joins them).
+ *   minhash(rows[a:b]) == minhash(rows)[a:b]: a row's signature depends on its body, shingle, num_perm and seed alone.
+ *   ids / row_off    packed int32 rows as gz_decode_batch takes them;  signatures [n_rows, num_perm] uint32, row-major;
+ *   n_shingles [n_rows] int32, may be NULL;  group [n_rows] int32.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched or written: n_rows < 0; a skip
+ *   outside {0, 1}; shingle outside 1..32; num_perm outside 1..256; bands < 1 or a bands that does not divide num_perm; min_agree
+ *   outside 1..num_perm; n_rows >= 2^31 - 4096 (the group calls); a NULL required array with n_rows > 0 (n_groups_host is always
+ *   required); output arrays that overlap the input or each other; bad or decreasing row offsets (the host form).  A body of 2^31
+ *   ids or more is GZ_E_LIMIT and nothing is written.  n_rows == 0 is GZ_OK, launches nothing and sets *n_groups_host = 0.
+ *   Workspace of the group calls: one band at a time goes through one open-addressing table of the smallest power of two of slots
+ *   that is at least 2 * n_rows, 12 bytes a slot -- 24 to 48 bytes a document --, plus one byte a document.
+ * gz_minhash_rows_device / gz_minhash_groups_device: every pointer but n_groups_host is a DEVICE pointer; offsets are ABSOLUTE
+ *   from the base pointer and row_off_dev[0] need not be 0.  Ordering: all passes run on the context's stream, behind a
+ *   gz_encode_batch_device (ragged layout) enqueued just before with no gz_sync in between.  The calls return when their outputs
+ *   are complete.
+ * gz_minhash_rows: / gz_minhash_groups: host pointers; the input goes up through the library's pinned staging, the device form
+ *   runs, the outputs come back.
+ * Not here: shingles over words or characters of the raw text, weighted MinHash, b-bit signatures, exact Jaccard verification of
+ *   candidates, a persistent index that takes appends, removing the duplicates from the rows (the caller filters). */
+int  gz_minhash_rows(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                     int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t *signatures, int32_t *n_shingles);
+int  gz_minhash_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, int32_t skip_front,
+                            int32_t skip_back, int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t *signatures_dev,
+                            int32_t *n_shingles_dev);
+int  gz_minhash_groups(gz_ctx *ctx, const uint32_t *signatures, int64_t n_rows, int32_t num_perm, int32_t bands, int32_t min_agree,
+                       int32_t *group, int64_t *n_groups_host);
+int  gz_minhash_groups_device(gz_ctx *ctx, const uint32_t *signatures_dev, int64_t n_rows, int32_t num_perm, int32_t bands,
+                              int32_t min_agree, int32_t *group_dev, int64_t *n_groups_host);
+
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
  *   GZ_PP_UNICODE  convert_unicode      preprocess.py:16-36   base letter + combining tone mark -> precomposed letter
