@@ -516,6 +516,14 @@ int sync_locked(gz_ctx* c)
     return GZ_OK;
 }
 
+// The word records kept for gz_word_token_counts belong to the LAST encode call: every entry point that encodes without going
+// through encode_device_locked (which starts from a fresh Pending) -- an empty batch, the CSR sub-batches -- lets go of them here.
+void drop_word_records(gz_ctx* c)
+{
+    c->pend.keep_words = false;
+    c->pend.subs.clear();
+}
+
 // One text (A or B) of a (sub-)batch: its per-call workspace in slot W, sized from the byte and document counts.
 // tb = first byte of the batch on the device, off = its [n_docs + 1] absolute offsets (device), Bt = its bytes.
 int setup_text(gz_ctx* c, gz_ctx::TextWs& W, DBuf& tiny, const uint8_t* tb, const int64_t* off, int64_t Bt, int64_t n_docs,
@@ -690,12 +698,12 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
             n_raw = (int32_t*)c->w_status.p;
         }
     }
-    p.keep_words = (flags & GZ_KEEP_WORDS) != 0;
+    const bool keep_words = (flags & GZ_KEEP_WORDS) != 0;      // (p.keep_words is set once the call is enqueued: a call that fails keeps nothing)
     {
         // Small batches run in ONE launch that cuts the work by documents (gz_small.inc): single texts or pairs whose
         // longest document fits a workgroup's LDS (ragged layouts: the unpadded rows go to the raw area, finalize follows as in
         // the big path).  The host needs the document sizes for that, so only calls that bring host offsets qualify.  The option small = 0 switches the path off (tests run the golden batches both ways).
-        if (c->opt.small && h_text_off && !p.keep_words && n_docs > 0 && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20)) {
+        if (c->opt.small && h_text_off && !keep_words && n_docs > 0 && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20)) {
             int64_t maxdoc = 0, maxpair = 0;
             for (int64_t d = 0; d < n_docs; ++d) {
                 const int64_t b = h_text_off[d + 1] - h_text_off[d]; if (b > maxdoc) maxdoc = b;
@@ -774,6 +782,7 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
     p.active = true;
     rc = enqueue(c);
     if (rc) p.active = false;
+    else p.keep_words = keep_words;
     return rc;
 }
 
@@ -1328,6 +1337,7 @@ static int csr_core(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int
     const bool dense_out = O.ids != nullptr;
     const int64_t tb = text_off[n_docs] - text_off[0];
     if (c->pend.active) { int rc0 = sync_locked(c); if (rc0) return rc0; }
+    drop_word_records(c);                                       // (the sub-batches below take tw[k & 1][0] for themselves)
     if (c->x_used) HIPCHK(c, hipStreamSynchronize(c->xstream));
     if (!c->s_in) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
@@ -1541,7 +1551,7 @@ static int encode_host_locked(gz_ctx* c, const uint8_t* text, const int64_t* tex
     const bool dense = is_dense(S);
     if (dense && capacity < n_docs * (int64_t)max_len) return fail(c, GZ_E_CAPACITY, "capacity < n_docs*max_len");
     if (!dense && !row_off) return fail(c, GZ_E_INVALID, "row_off is required for ragged layouts");
-    if (n_docs == 0) { if (row_off) row_off[0] = 0; return GZ_OK; }
+    if (n_docs == 0) { drop_word_records(c); if (row_off) row_off[0] = 0; return GZ_OK; }     // (an encode call like any other: the one before it is no longer the last)
 
     hipStream_t s = c->stream;
     {
@@ -1750,7 +1760,7 @@ try {
     for (int64_t i = 0; i < n_docs; ++i)
         if (text_off[i + 1] < text_off[i]) return fail(c, GZ_E_INVALID, "text_off is not non-decreasing at %lld", (long long)i);
     *total_out = 0;
-    if (n_docs == 0) return GZ_OK;
+    if (n_docs == 0) { drop_word_records(c); return GZ_OK; }
     if (text_off[n_docs] - text_off[0] > 0 && !text) return fail(c, GZ_E_INVALID, "text is NULL");
     CsrOut O;
     O.tokens = tokens; O.capacity = capacity; O.n_real = n_real;
@@ -1767,21 +1777,30 @@ try {
     const std::vector<GzAsmArgs>& subs = c->pend.subs;
     if (!c->pend.keep_words) return fail(c, GZ_E_INVALID, "the last encode call was not made with GZ_KEEP_WORDS");
     if (subs.empty() || which_text >= subs[0].n_texts) return fail(c, GZ_E_INVALID, "no encode call with that text to report on");
-    if (subs.size() > 2) return fail(c, GZ_E_INVALID, "word counts are kept for batches of fewer than 65536 documents only");
+    if (subs.size() > 2) return fail(c, GZ_E_INVALID, "word counts are kept for calls of at most two sub-batches (the switch sub_batches), this one had %zu: a third reuses the first one's workspace", subs.size());
+    // the word total of the whole call first: GZ_E_CAPACITY reports it, whichever sub-batch does not fit
+    uint32_t totals[2] = {0, 0};
+    int64_t all = 0;
+    for (size_t k = 0; k < subs.size(); ++k) {
+        const GzTextBufs& X = subs[k].X[which_text];
+        int rcs;                                                 // the scanned block counts end with the word total
+        if ((rcs = copy_out_small(c, &totals[k], X.blkcnt + X.nblk, 4, c->stream))) return rcs;
+        all += totals[k];
+    }
+    if (all > capacity) {
+        *n_words = all;
+        return fail(c, GZ_E_CAPACITY, "the batch has %lld words, capacity is %lld", (long long)all, (long long)capacity);
+    }
     int64_t wbase = 0, dbase = 0;
-    for (const GzAsmArgs& S : subs) {
+    for (size_t k = 0; k < subs.size(); ++k) {
+        const GzAsmArgs& S = subs[k];
         const GzTextBufs& X = S.X[which_text];
+        const uint32_t total = totals[k];
         int rcs;
         alloc_site(c);
         std::vector<uint32_t> dw((size_t)S.n_docs + 1);
         if ((rcs = copy_out(c, dw.data(), X.docw0, dw.size() * 4, c->stream))) return rcs;
-        uint32_t total = 0;                                      // the scanned block counts end with the word total
-        if ((rcs = copy_out_small(c, &total, X.blkcnt + X.nblk, 4, c->stream))) return rcs;
         for (int64_t d = 0; d < S.n_docs; ++d) doc_first[dbase + d] = wbase + dw[(size_t)d];
-        if (wbase + (int64_t)total > capacity) {
-            *n_words = wbase + total;
-            return fail(c, GZ_E_CAPACITY, "the batch has more than %lld words", (long long)capacity);
-        }
         if (total) {
             alloc_site(c);
             std::vector<uint32_t> wt(total);

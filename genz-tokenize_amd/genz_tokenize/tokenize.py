@@ -340,6 +340,8 @@ class Tokenize(object):
         """The 'offset' lists of the last batch call, from the per-word piece counts the device kept (GZ_KEEP_WORDS): per text
         [(0, 0)] + one 1-based (first, last) token span per word + (T+1, T+1) (tokenize.py:105, :111-117); in pair mode B's
         entries follow A's, each shifted by the NUMBER OF ENTRIES of A (tokenize.py:231-234: `len(offset)`, not tokens)."""
+        if n == 0:                                               # no texts: the device kept nothing, and is asked for nothing
+            return np.zeros((0, 2), dtype=np.int32), np.zeros(1, dtype=np.int64)
         def spans(which):
             counts, first = self._ctx.word_token_counts(which, n, 1 << 16)
             first = first.astype(np.int64)

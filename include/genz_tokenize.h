@@ -146,9 +146,12 @@ int  gz_sync(gz_ctx *ctx);
 
 /* Token count of every word of the LAST encode call (for `return_offset=True`, tokenize.py:105,111-117,225-244):
  * which_text 0 = text, 1 = pair text.  counts[w] = pieces of word w (words of all documents, in order),
- * doc_first[d] = index of document d's first word (n_docs+1 entries).  Returns GZ_E_CAPACITY (and *n_words)
- * when the batch has more than `capacity` words.  Valid until the next encode call on the context.  The encode call
- * must have been made with GZ_KEEP_WORDS (GZ_E_INVALID otherwise). */
+ * doc_first[d] = index of document d's first word (n_docs+1 entries, n_docs of that encode call), *n_words = words of
+ * the whole call.  When the call has more than `capacity` words: GZ_E_CAPACITY, *n_words holds the word total of the WHOLE
+ * call (all its sub-batches) -- a second call with that capacity fits -- and counts / doc_first are not written.
+ * Valid until the next encode call on the context, of any entry point and of any size: the last encode call must have been
+ * made with GZ_KEEP_WORDS and must not have been cut into more than two sub-batches (GZ_E_INVALID otherwise; nothing is
+ * written).  A host call with n_docs == 0 and every gz_encode_batch_csr call keep nothing. */
 int  gz_word_token_counts(gz_ctx *ctx, int which_text, int32_t *counts, int64_t capacity,
                           int64_t *doc_first, int64_t *n_words);
 
