@@ -958,6 +958,7 @@ static int install_word_tables(gz_ctx* c, const WordImages& W)
 
 
 #include "gz_bm25_api.inc"
+#include "gz_learn_api.inc"
 
 
 // =================================================================================================================

@@ -522,3 +522,30 @@ constexpr int GZ_NEAR_MAX = 64;           // == GZ_BM25_NEAR_MAX of the public h
 enum { GZ_BM25_SR_NEAR, GZ_BM25_NR_COVER };
 // rows: of the chunk (GZ_BM25_SR_NEAR)
 void gz_launch_bm25_near(int step, const GzBm25Near& A, int64_t rows, hipStream_t s);
+
+// BPE learner (gz_learn.inc): the counts of a word set on top of the BM25 build's word front, and the merge loop of gz_bpe_learn.
+// The words' symbols live in one flat array, word d = sym[woff[d] .. woff[d] + wlen[d]) (a merge shortens it in place, its slice
+// stays where it is); the pair table is open addressing, key = (left << 32 | right) + 1 (0: empty), cnt = n(left, right); nothing is
+// ever deleted, a count of 0 stays.
+struct GzLearnSlot { unsigned long long key; long long cnt; };
+struct GzLearn {
+    int32_t* sym; const uint32_t* woff; uint32_t* wlen; const long long* cw; int64_t n_words;
+    const uint32_t* longw; int64_t n_long;          // the words of more than GZ_LEARN_LANE_MAX initial symbols: a wave each
+    GzLearnSlot* tab; unsigned long long mask;
+    unsigned long long* ctl;                        // [0] best key, [1] best count, [2] keys in the table, [3] a probe found the table full
+    unsigned long long* part; int32_t n_part;       // [2 * n_part] the reduction's per-workgroup bests (key, count)
+    int32_t l, r, m;                                // the step: every l r becomes m
+    long long* hist;                                // [2 * n_symbols] count of (symbol, is the word's last position)
+};
+constexpr int GZ_LEARN_LANE_MAX = 64;
+enum { GZ_LEARN_PAIRS, GZ_LEARN_BEST, GZ_LEARN_APPLY, GZ_LEARN_HIST };
+void gz_launch_learn(int step, const GzLearn& L, hipStream_t s);
+// a table into a larger one (cleared by the caller): every key claims its own slot and takes its count along
+void gz_launch_learn_rehash(const GzLearnSlot* from, int64_t n_slots, const GzLearn& to, hipStream_t s);
+// The counts of a word set, behind GZ_BM25_FIRST and the scan of its flags: cnt[term of w] += weight[document of w] (1 without
+// weights); the representatives write tstart / tlen.  cnt holds GZ_BM25_DF_SHARDS * n_terms zeroed counters, the sums end up in its
+// first n_terms.  strict: a document that is not exactly one word raises ctl[1] bit 1.
+void gz_launch_wordset_count(const GzBm25Args& A, const long long* weight, long long* cnt, int64_t n_terms, int strict, hipStream_t s);
+// word t = tb[tstart[t] .. + tlen[t]) -> arena[toff[t] ..)
+void gz_launch_wordset_gather(const uint8_t* tb, const int64_t* tstart, const uint32_t* tlen, const uint32_t* toff, uint8_t* arena, int64_t n,
+                              hipStream_t s);

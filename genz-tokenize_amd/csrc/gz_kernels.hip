@@ -721,6 +721,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_groups.inc"
 #include "gz_snippet.inc"
 #include "gz_near.inc"
+#include "gz_learn.inc"
 
 // =================================================================================================================
 // launchers

@@ -51,6 +51,8 @@ SYMBOLS = [
     "gz_mask_rows", "gz_mask_rows_device",
     "gz_infill_rows", "gz_infill_rows_device",
     "gz_minhash_rows", "gz_minhash_rows_device", "gz_minhash_groups", "gz_minhash_groups_device",
+    "gz_wordset_build", "gz_wordset_build_device", "gz_wordset_from_counts", "gz_wordset_info", "gz_wordset_words", "gz_wordset_destroy",
+    "gz_bpe_learn", "gz_bpe_learn_result",
 ]
 
 _lib = None
@@ -128,6 +130,15 @@ def load_library():
         mg = [vp, vp, i64, i32, i32, i32, vp, P(i64)]
         L.gz_minhash_groups.argtypes = mg
         L.gz_minhash_groups_device.argtypes = mg
+    if hasattr(L, "gz_wordset_build"):
+        L.gz_wordset_build.argtypes = [vp, vp, vp, i64, P(vp)]
+        L.gz_wordset_build_device.argtypes = [vp, vp, vp, i64, i64, P(vp)]
+        L.gz_wordset_from_counts.argtypes = [vp, vp, vp, vp, i64, P(vp)]
+        L.gz_wordset_info.argtypes = [vp, P(i64), P(i64), P(i64)]
+        L.gz_wordset_words.argtypes = [vp, vp, vp, vp, i64]
+        L.gz_wordset_destroy.argtypes = [vp]; L.gz_wordset_destroy.restype = None
+        L.gz_bpe_learn.argtypes = [vp, i64, i64, vp]
+        L.gz_bpe_learn_result.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64]
     L.gz_preprocess_batch.argtypes = [vp, vp, i32, vp, vp, i64, vp, i64, vp]
     L.gz_preprocess_batch_device.argtypes = [vp, vp, i32, vp, vp, i64, i64, vp, i64, vp, P(i64)]
     L.gz_block_create.argtypes = [vp, vp, P(vp)]
@@ -215,7 +226,7 @@ def load_library():
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
-                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy"):
+                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -694,6 +705,60 @@ class Context:
         return total.value
 
     # ---- BM25 index (ranking.py) ----------------------------------------------------------------------------
+    # ---- learn: word sets and the BPE learner ---------------------------------------------------------------------------------
+    def wordset_build(self, text: np.ndarray, text_off: np.ndarray) -> int:
+        """gz_wordset_build: the distinct words of packed documents (uint8 text, int64 offsets [n + 1]) -> handle"""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        h = C.c_void_p()
+        self._check(self.lib.gz_wordset_build(self.handle, _ptr(text), _ptr(text_off), len(text_off) - 1, C.byref(h)))
+        return h.value
+
+    def wordset_build_device(self, d_text, d_off, n_docs: int, text_bytes: int) -> int:
+        h = C.c_void_p()
+        self._check(self.lib.gz_wordset_build_device(self.handle, *_dptrs(d_text, d_off), int(n_docs), int(text_bytes), C.byref(h)))
+        return h.value
+
+    def wordset_from_counts(self, words: np.ndarray, word_off: np.ndarray, counts: np.ndarray) -> int:
+        words = np.ascontiguousarray(words, dtype=np.uint8)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        h = C.c_void_p()
+        self._check(self.lib.gz_wordset_from_counts(self.handle, _ptr(words), _ptr(word_off), _ptr(counts), len(counts), C.byref(h)))
+        return h.value
+
+    def wordset_destroy(self, ws: int):
+        if ws and getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.gz_wordset_destroy(C.c_void_p(ws))
+
+    def wordset_info(self, ws: int):
+        """(distinct words, their bytes, the sum of the counts)"""
+        n, b, t = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.gz_wordset_info(C.c_void_p(ws), C.byref(n), C.byref(b), C.byref(t)))
+        return n.value, b.value, t.value
+
+    def wordset_words(self, ws: int):
+        """(bytes uint8, offsets int64 [n + 1], counts int64 [n]) of the distinct words, first-occurrence order"""
+        n, nb, _ = self.wordset_info(ws)
+        off = np.zeros(n + 1, dtype=np.int64)
+        cnt = np.zeros(n, dtype=np.int64)
+        data = np.zeros(nb, dtype=np.uint8)
+        self._check(self.lib.gz_wordset_words(C.c_void_p(ws), _ptr(off), _ptr(cnt), _ptr(data), nb))
+        return data, off, cnt
+
+    def bpe_learn(self, ws: int, n_merges: int, min_frequency: int):
+        """gz_bpe_learn + gz_bpe_learn_result -> (info [8], merge bytes, merge offsets, piece bytes, piece offsets, piece counts)"""
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.gz_bpe_learn(C.c_void_p(ws), int(n_merges), int(min_frequency), _ptr(info)))
+        m, mb, p, pb = int(info[0]), int(info[2]), int(info[3]), int(info[4])
+        moff = np.zeros(2 * m + 1, dtype=np.int64)
+        mbytes = np.zeros(mb, dtype=np.uint8)
+        poff = np.zeros(p + 1, dtype=np.int64)
+        pcnt = np.zeros(p, dtype=np.int64)
+        pbytes = np.zeros(pb, dtype=np.uint8)
+        self._check(self.lib.gz_bpe_learn_result(C.c_void_p(ws), _ptr(moff), _ptr(mbytes), mb, _ptr(poff), _ptr(pcnt), _ptr(pbytes), pb))
+        return info, mbytes, moff, pbytes, poff, pcnt
+
     def bm25_build(self, text: np.ndarray, text_off: np.ndarray, positions: bool = False) -> int:
         """packed UTF-8 + int64 offsets -> a gz_bm25 handle (int), owned by this context.  positions: a positional index
         (gz_bm25_build_ex with GZ_BM25_POSITIONS), which keeps every word's term id for phrase searches; else gz_bm25_build."""

@@ -253,6 +253,8 @@ int64_t gz_limit(int which);
  *                              are marked, scored and ranked a chunk at a time, one row at least; the chunk's bitmap words obey it too)
  *   bm25_vocab_chunk (1..2^30; 2^23)  BM25 vocabulary queries (gz_bm25_similar, gz_bm25_prefix): doubles of key rows held in the
  *                              context's workspace at a time (the words are compared and ranked a chunk at a time, one row at least)
+ *   learn_table_bits (0..30; 0)  gz_bpe_learn starts its pair table at 2^k slots, fills it again at twice the size while it proves
+ *                              too small and grows it no further than the load rule asks (0: sized from the word set)
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -516,6 +518,66 @@ int  gz_minhash_groups(gz_ctx *ctx, const uint32_t *signatures, int64_t n_rows, 
                        int32_t *group, int64_t *n_groups_host);
 int  gz_minhash_groups_device(gz_ctx *ctx, const uint32_t *signatures_dev, int64_t n_rows, int32_t num_perm, int32_t bands,
                               int32_t min_agree, int32_t *group_dev, int64_t *n_groups_host);
+
+/* ---- learn: BPE merges and a vocabulary from a corpus -------------------------------------------------------------------------
+ * gz_load_tables takes any codes and vocab file; these calls make the two from text.  Two passes: gz_wordset_* reduces a corpus to
+ * its distinct words with int64 counts, gz_bpe_learn runs the merge loop on such a word set.  No tables and no decoder snapshot
+ * are needed.  The reference has no learner: the rule is this library's, and it is pinned by CLOSURE -- the tokenizer loaded with
+ * the learnt files segments every training word exactly as the learner left it.
+ *   words            the str.split() words of every document: maximal runs of characters outside the 29 whitespace code points (the
+ *                    BM25 index's word rule; no '\n' is glued to a word).  The corpus is the multiset of its words: document order
+ *                    and boundaries have no other effect.  A word set lists the distinct words in first-occurrence order
+ *   symbols          byte strings.  A word is its code points, the last one with the four bytes "</w>" appended (a byte that starts
+ *                    no well-formed UTF-8 sequence is a symbol of its own).  The distinct initial strings, sorted by bytes ascending,
+ *                    get the ids 0, 1, 2, ...; a merged symbol's string is left + right and takes the next id -- unless a symbol
+ *                    with that string exists already, whose id it REUSES (strings decide, as in the tokenizer; this matters only when
+ *                    the text itself holds a literal "</w>")
+ *   n(l, r)          the sum over the words w of count(w) * #{ i : s_i = l, s_(i+1) = r }, every adjacent position, overlaps
+ *                    included: "a a a" counts (a, a) twice
+ *   a step           the best pair has the largest n; among equal counts the smallest (id_l, id_r) wins.  Learning stops after
+ *                    n_merges steps, when no pair is left, or when the best count is below min_frequency.  Else every occurrence of
+ *                    the pair is merged, left to right and non-overlapping, in every word: aaaa -> aa aa, aaaaa -> aa aa a
+ *   pieces           of every word's final segmentation: a piece that is not its word's last is written string + "@@", the last one
+ *                    without its final four bytes (finality belongs to the position); a piece's count is the sum of count(w) over
+ *                    its occurrences; pieces come largest count first, then by bytes ascending; a piece equal to one of the five
+ *                    default special strings (<pad> <s> </s> <mask> <unk>) is left out, since a vocab line would move its id
+ *   files            codes = "#version: 0.2\n" + "left right\n" per merge; vocab = "piece count\n" per piece
+ * gz_wordset_build / gz_wordset_build_device: the word set of n_docs packed documents (layout of gz_bm25_build /
+ *   gz_bm25_build_device: host pointers, or DEVICE pointers with ABSOLUTE offsets and text_bytes = the bytes from text_off_dev[0];
+ *   the device text is read where it lies).  gz_wordset_from_counts: the word set of n_words given words with counts[i] >= 1 -- the
+ *   way shards are merged: add the counts of equal words on the host, or pass them twice, they add up.  Every given word must be
+ *   exactly one word of the rule above (not empty, no whitespace): GZ_E_INVALID otherwise.  Bytes + documents stay below 2^32 and the
+ *   counts sum to less than 2^62 (GZ_E_LIMIT).
+ * gz_wordset_info: distinct words, their bytes, the sum of the counts (each may be NULL).  gz_wordset_words: word_off [n_words + 1],
+ *   counts [n_words], bytes (each may be NULL; GZ_E_CAPACITY when bytes_cap is too small, nothing is written then).
+ * gz_bpe_learn: runs the rule on the word set; 0 <= n_merges <= GZ_BPE_MERGES_MAX and min_frequency >= 1, else GZ_E_INVALID with
+ *   its own sentence before anything is launched.  GZ_E_LIMIT and nothing learnt: more than 2^31 - 1 symbol positions (the code
+ *   points of the distinct words), or counts times symbols summing to 2^62 or more -- no count can wrap.  info[8] = merges done,
+ *   symbols, bytes of the merge strings, pieces, bytes of the piece strings, slots of the pair table at the end, keys in it, times
+ *   the table was filled again or grown.  The result stays with the word set until the next gz_bpe_learn on it.
+ *   The pair table is open addressing over (l << 32 | r) with int64 counts; every count is an integer sum and the best pair a
+ *   function of the counts: the result does not depend on the order of the atomics.  A full table is GZ_E_LIMIT, never a dropped
+ *   count.  One 32-byte readback per merge.
+ * gz_bpe_learn_result: merge_off [2 * merges + 1] and merge_bytes: left and right string of every merge back to back, in learning
+ *   order; piece_off [pieces + 1], piece_count [pieces], piece_bytes: the pieces as the vocab file writes them, in its order.  Each
+ *   pointer may be NULL; GZ_E_CAPACITY when a byte buffer is too small (sizes: info[2], info[4]); GZ_E_INVALID before a
+ *   gz_bpe_learn has succeeded.
+ * A word set belongs to its context and is destroyed before it.
+ * Not here: unigram or WordPiece training, a character-coverage cut-off, learning over pre-tokenized ids, multi-GPU learning (shards
+ *   merge through their word sets). */
+#define GZ_BPE_MERGES_MAX (1 << 20)
+typedef struct gz_wordset gz_wordset;
+int  gz_wordset_build(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, gz_wordset **out);
+int  gz_wordset_build_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
+                             gz_wordset **out);
+int  gz_wordset_from_counts(gz_ctx *ctx, const uint8_t *words, const int64_t *word_off, const int64_t *counts, int64_t n_words,
+                            gz_wordset **out);
+int  gz_wordset_info(gz_wordset *ws, int64_t *n_words, int64_t *n_bytes, int64_t *total);
+int  gz_wordset_words(gz_wordset *ws, int64_t *word_off, int64_t *counts, uint8_t *bytes, int64_t bytes_cap);
+void gz_wordset_destroy(gz_wordset *ws);
+int  gz_bpe_learn(gz_wordset *ws, int64_t n_merges, int64_t min_frequency, int64_t info[8]);
+int  gz_bpe_learn_result(gz_wordset *ws, int64_t *merge_off, uint8_t *merge_bytes, int64_t merge_cap, int64_t *piece_off,
+                         int64_t *piece_count, uint8_t *piece_bytes, int64_t piece_cap);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
