@@ -106,7 +106,12 @@ struct gz_ctx {
         int t_slot = 0;                // timing: the call's pair of events in the ring
         bool chained = false;          // enqueued behind a call that has not been synchronised (its scan flag is kept)
         bool inputs_resident = false;  // the caller's device buffers are readable now (no copy of them is queued on the stream)
+        bool drop = false;             // a BPE-dropout call (gz_encode_dropout*): always the pipeline, the whole-word tables off, the merge stage of gz_dropout.inc
+        GzDrop dropv{};                // ... its threshold, seed and doc_base
+        int64_t drop_docs = 0;         // ... its documents (sub-batch k starts at document k * drop_docs / subs.size())
     } pend;
+    bool drop_on = false;          // set by the dropout entry points around encode_host_locked / encode_device_locked
+    GzDrop drop_req{};
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     // timed calls that were chained without a host sync in between: start / end of the main kernels of the last RING
     // (events are created on first use: an untimed context never pays for them)
@@ -409,9 +414,11 @@ int enqueue(gz_ctx* c)
     for (size_t k = 0; k < p.subs.size(); ++k) {
         hipStream_t sk = (k & 1) ? c->stream2 : s;
         const GzAsmArgs& S = p.subs[k];
+        GzDrop dk = p.dropv;                                     // (D continues across the cut into sub-batches)
+        dk.doc0 += (int64_t)k * p.drop_docs / (int64_t)p.subs.size();
         for (int tx = 0; tx < S.n_texts; ++tx)
             gz_launch_pipeline_text(c->opt, T, c->dev, S.X[tx], S.n_docs, p.use_words, (int32_t*)c->w_flags.p + 3, sk, c->side, c->ev_sf0[k & 1][tx], c->ev_sf[k & 1][tx], c->ev_sj[k & 1][tx],
-                                    p.inputs_resident ? c->ev_sb[k & 1][tx] : nullptr);
+                                    p.inputs_resident ? c->ev_sb[k & 1][tx] : nullptr, p.drop ? &dk : nullptr);
         if (p.ragged_direct) gz_launch_rows_ragged(T, S, 0, p.text_bytes, sk);      // the row lengths
         else gz_launch_assemble(c->opt, T, S, sk);
     }
@@ -644,6 +651,8 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
     p.chained = chained;
     p.inputs_resident = c->caller_buffers;
     p.timing = (flags & GZ_TIMING) != 0;
+    const bool drop = c->drop_on;
+    if (drop) { p.drop = true; p.dropv = c->drop_req; p.drop_docs = n_docs; }
 
     // Sub-batches: contiguous document ranges (dense layouts of large batches only).  Their byte positions are the
     // only thing the host needs to know about the offsets: one tiny kernel + one 8*(2*nsub+2)-byte copy.
@@ -678,7 +687,7 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
         if (dpw > GZ_MAX_DOCS_PER_WAVE) dpw = GZ_MAX_DOCS_PER_WAVE;
         if (c->opt.docs_per_wave >= 1 && c->opt.docs_per_wave <= GZ_MAX_DOCS_PER_WAVE) dpw = c->opt.docs_per_wave;
         docs_per_wave = (int)dpw;
-        p.use_words = use_words_flags(c, flags);
+        p.use_words = drop ? 0 : use_words_flags(c, flags);      // (a dropout call never consults the whole-word tables)
     }
     int32_t* raw = nullptr;
     int32_t* n_raw = n_real;
@@ -686,7 +695,7 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
     // places (gz_rowsr_kernel); pairs and the padded ragged shapes go through the raw area and the finalize kernel.  (The option
     // assemble < 3 keeps the raw-area path for these rows too: tests.)
     const bool direct_ok = !dense && !is_pair && !S.pad_mode && c->opt.assemble >= 3;
-    const bool maybe_small = c->opt.small && h_text_off && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20);
+    const bool maybe_small = c->opt.small && !drop && h_text_off && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20);
     if (!dense) {
         rc = ensure(c, c->w_rowlen, (size_t)(n_docs + 1) * 8); if (rc) return rc;
         if (!direct_ok || maybe_small) {
@@ -703,7 +712,7 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
         // Small batches run in ONE launch that cuts the work by documents (gz_small.inc): single texts or pairs whose
         // longest document fits a workgroup's LDS (ragged layouts: the unpadded rows go to the raw area, finalize follows as in
         // the big path).  The host needs the document sizes for that, so only calls that bring host offsets qualify.  The option small = 0 switches the path off (tests run the golden batches both ways).
-        if (c->opt.small && h_text_off && !keep_words && n_docs > 0 && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20)) {
+        if (c->opt.small && !drop && h_text_off && !keep_words && n_docs > 0 && n_docs <= (1 << 20) && text_bytes + pair_bytes <= (2ll << 20)) {
             int64_t maxdoc = 0, maxpair = 0;
             for (int64_t d = 0; d < n_docs; ++d) {
                 const int64_t b = h_text_off[d + 1] - h_text_off[d]; if (b > maxdoc) maxdoc = b;
@@ -1589,7 +1598,7 @@ static int encode_host_locked(gz_ctx* c, const uint8_t* text, const int64_t* tex
             // device-accessible; a README-sized call reads ~ 100 bytes over the bus and writes as few) -- two copies and their stream
             // round trips less per call.  Only when the one-launch kernel will take it (it touches its text once).
             // (not for ragged pairs: their row scan, finalize and pair kernels read the rows several times -- 60 -> 70 us over the bus)
-            const bool direct = c->opt.host_direct > 0 && c->opt.small && o_end <= (size_t)c->opt.host_direct && !(flags & GZ_KEEP_WORDS) && !(is_pair && !dense);
+            const bool direct = c->opt.host_direct > 0 && c->opt.small && !c->drop_on && o_end <= (size_t)c->opt.host_direct && !(flags & GZ_KEEP_WORDS) && !(is_pair && !dense);
             uint8_t* D = direct ? H : (uint8_t*)c->w_stage.p;
             std::memcpy(H, text_off, off_b);
             if (tbs) std::memcpy(H + in_text, text + text_off[0], (size_t)tbs);
@@ -1634,7 +1643,7 @@ static int encode_host_locked(gz_ctx* c, const uint8_t* text, const int64_t* tex
     // Large dense calls of single texts -- the batch form of Tokenize.__call__(text, max_len=L) -- bring only the rows' real
     // entries over the bus and pad them into the caller's arrays on host threads (csr_core); the switch dense_csr = 0, timed
     // calls, kept word records and the load-time whole-word build take the plain path below.
-    if (dense && !is_pair && c->opt.dense_csr && !(flags & (GZ_TIMING | GZ_KEEP_WORDS)) && !c->building_words) {
+    if (dense && !is_pair && c->opt.dense_csr && !(flags & (GZ_TIMING | GZ_KEEP_WORDS)) && !c->building_words && !c->drop_on) {
         CsrOut O;
         O.ids = input_ids; O.mask = attention_mask; O.n_real = n_real;
         int64_t total = 0;
@@ -1723,6 +1732,86 @@ try {
     HIPCHK(c, hipSetDevice(c->device));
     return encode_host_locked(c, text, text_off, pair, pair_off, n_docs, max_len, flags, capacity, input_ids,
                               attention_mask, token_type_ids, sequence_id, row_off, pair_len, n_real, status);
+} GZ_CATCH(c)
+
+// ---- BPE-dropout (include/genz_tokenize.h "BPE-dropout"; kernels: gz_dropout.inc) ---------------------------------------------
+// The three entry points check their own arguments, arm the context (drop_on / drop_req) and go through the encode functions above:
+// a dropout call is a single-text call that always takes the pipeline, with the whole-word tables off and its own merge stage.
+namespace {
+int drop_args(gz_ctx* c, uint32_t flags, uint64_t thr, int64_t doc_base, int64_t n_docs)
+{
+    if (flags & GZ_KEEP_WORDS) return fail(c, GZ_E_INVALID, "a dropout call keeps no word records (GZ_KEEP_WORDS)");
+    if (thr > (1ull << 32)) return fail(c, GZ_E_INVALID, "drop_threshold must lie in 0 .. 2^32");
+    if (doc_base < 0) return fail(c, GZ_E_INVALID, "doc_base must not be negative");
+    if (n_docs > 0 && doc_base > INT64_MAX - n_docs) return fail(c, GZ_E_INVALID, "doc_base + n_docs must stay below 2^63");
+    return GZ_OK;
+}
+struct DropArm {
+    gz_ctx* c;
+    DropArm(gz_ctx* c_, uint64_t thr, uint64_t seed, int64_t doc_base) : c(c_) { c->drop_on = true; c->drop_req = GzDrop{thr, seed, doc_base}; }
+    ~DropArm() { c->drop_on = false; }
+};
+}  // namespace
+
+int gz_encode_dropout(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, int32_t max_len, uint32_t flags, int64_t capacity,
+                      uint64_t drop_threshold, uint64_t seed, int64_t doc_base, int32_t* input_ids, int32_t* attention_mask, int64_t* row_off, int32_t* n_real)
+try {
+    if (!c) return GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = drop_args(c, flags, drop_threshold, doc_base, n_docs);
+    if (rc) return rc;
+    DropArm arm(c, drop_threshold, seed, doc_base);
+    return encode_host_locked(c, text, text_off, nullptr, nullptr, n_docs, max_len, flags & ~(uint32_t)GZ_NO_WORD_TABLE, capacity, input_ids, attention_mask,
+                              nullptr, nullptr, row_off, nullptr, n_real, nullptr);
+} GZ_CATCH(c)
+
+int gz_encode_dropout_device(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, int32_t max_len, uint32_t flags, int64_t capacity,
+                             uint64_t drop_threshold, uint64_t seed, int64_t doc_base, int32_t* input_ids, int32_t* attention_mask, int64_t* row_off,
+                             int32_t* n_real)
+try {
+    if (!c) return GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = drop_args(c, flags, drop_threshold, doc_base, n_docs);
+    if (rc) return rc;
+    DropArm arm(c, drop_threshold, seed, doc_base);
+    struct Flag { bool& f; explicit Flag(bool& x) : f(x) { f = true; } ~Flag() { f = false; } } caller(c->caller_buffers);
+    return encode_device_locked(c, text, text_off, nullptr, nullptr, n_docs, max_len, flags & ~(uint32_t)GZ_NO_WORD_TABLE, capacity, input_ids, attention_mask,
+                                nullptr, nullptr, row_off, nullptr, n_real, nullptr, nullptr, nullptr);
+} GZ_CATCH(c)
+
+int64_t gz_bpe_word_dropout(gz_ctx* c, const uint8_t* word, int64_t len, uint64_t drop_threshold, uint64_t seed, int64_t doc, int64_t word_index,
+                            int32_t* pieces, int64_t cap)
+try {
+    if (!c) return GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    if (len <= 0 || !word || !pieces || cap <= 0 || len > 0x3FFFFFFF) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (drop_threshold > (1ull << 32)) return fail(c, GZ_E_INVALID, "drop_threshold must lie in 0 .. 2^32");
+    if (doc < 0) return fail(c, GZ_E_INVALID, "doc must not be negative");
+    if (word_index < 0 || word_index > 0xFFFFFFFFll) return fail(c, GZ_E_INVALID, "word_index must lie in 0 .. 2^32 - 1");
+    if (c->pend.active) { int rc = sync_locked(c); if (rc) return rc; }
+    int rc;
+    if ((rc = ensure(c, c->w_word, (size_t)len + 16))) return rc;
+    if ((rc = ensure(c, c->w_wordout, (size_t)len * 4 + 16))) return rc;
+    if ((rc = ensure(c, c->w_arena, (size_t)len * 4 + 16))) return rc;
+    hipStream_t s = c->stream;
+    if ((rc = copy_in(c, c->w_word.p, word, (size_t)len, s))) return rc;
+    gz_launch_bpe_word_drop((const GzDeviceTables*)c->t_struct.p, (const uint8_t*)c->w_word.p, len, (uint32_t*)c->w_arena.p, (int32_t*)c->w_wordout.p,
+                            (int32_t)len, (int32_t*)c->w_flags.p + 2, GzDrop{drop_threshold, seed, doc}, (uint32_t)word_index, s);
+    HIPCHK(c, hipMemcpyAsync(c->h_flags + 2, (int32_t*)c->w_flags.p + 2, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    const int64_t n = c->h_flags[2];
+    if (n > cap) return fail(c, GZ_E_CAPACITY, "word has %lld pieces, capacity %lld", (long long)n, (long long)cap);
+    if ((rc = copy_out(c, pieces, c->w_wordout.p, (size_t)n * 4, s))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t v = (uint32_t)pieces[i];
+        if (v & GZ_SYM_UNKNOWN) pieces[i] = -(int32_t)(v & 0x1FFFFFu) - 1;
+    }
+    return n;
 } GZ_CATCH(c)
 
 int gz_host_alloc(gz_ctx* c, size_t bytes, void** ptr)

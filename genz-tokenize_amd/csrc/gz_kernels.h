@@ -76,6 +76,13 @@ struct GzAsmArgs {
     const int64_t* row_off; int64_t capacity; int32_t* error_flag;
 };
 
+// BPE-dropout (gz_dropout.inc): what the merge stage of a dropout call draws from
+struct GzDrop {
+    uint64_t thr;                // a candidate merge is skipped when its draw is below this (0 .. 2^32: 2^32 drops everything)
+    uint64_t seed;
+    int64_t doc0;                // global index D of the first document of the text the kernels see (doc_base + the sub-batch's first document)
+};
+
 // T_host: the host copy of the table descriptor (table sizes decide launch shapes)
 // side / ev_fork0 / ev_fork / ev_join (may be null): a second stream on which gz_docw0_kernel runs beside the word kernel and
 // the rare wide-word kernels beside the merge kernel
@@ -83,7 +90,10 @@ void gz_launch_pipeline_text(const GzOptions& O, const GzDeviceTables* T_dev, co
                              int32_t* long_flag /* device int, zeroed by the caller */, hipStream_t s,
                              hipStream_t side = nullptr, hipEvent_t ev_fork0 = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr,
                              hipEvent_t ev_brk = nullptr /* non-null: X.off is readable NOW (no copy of it is queued on s): the document-start
-                                                            bits are prepared on the side stream, under whatever s is still running */);
+                                                            bits are prepared on the side stream, under whatever s is still running */,
+                             const GzDrop* drop = nullptr /* non-null: a BPE-dropout call -- the merge stage is gz_dropout.inc's (use_words must be 0) */);
+void gz_launch_bpe_word_drop(const GzDeviceTables* T_dev, const uint8_t* word, int64_t nbytes, uint32_t* arena, int32_t* out, int32_t cap, int32_t* n_out,
+                             const GzDrop& R, uint32_t word_index, hipStream_t s);
 void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int nsub, int64_t* out /* 2*(nsub+1) */, hipStream_t s);
 void gz_launch_row_offsets(const int32_t* n_real, int64_t n_rows, uint32_t* off, hipStream_t s);
 // first (may be null): receives where each row's entries start (= off[r]): the second array of an exchange block

@@ -1545,9 +1545,12 @@ void gz_launch_expand(const void* compact, int bits, const uint32_t* first, cons
 void gz_launch_hot_words(const GzOptions& O, const GzDeviceTables* T, const GzDeviceTables& Th, const GzTextBufs& X, int use_words, hipStream_t s);
 void gz_launch_hot_pre(const GzDeviceTables* T, const GzDeviceTables& Th, const GzTextBufs& X, int use_words, hipStream_t s);
 void gz_launch_hot_miss(const GzOptions& O, const GzDeviceTables* T, const GzDeviceTables& Th, const GzTextBufs& X, int use_words, hipStream_t s);
+// (the merge stage of a BPE-dropout call: gz_dropout.inc)
+void gz_launch_drop_miss(const GzOptions& O, const GzDeviceTables* T, const GzDeviceTables& Th, const GzTextBufs& X, int64_t n_docs, const GzDrop& R, hipStream_t s);
+void gz_launch_drop_wide(const GzDeviceTables* T, const GzTextBufs& X, int64_t n_docs, const GzDrop& R, hipStream_t s);
 
 void gz_launch_pipeline_text(const GzOptions& O, const GzDeviceTables* T, const GzDeviceTables& Th, const GzTextBufs& X, int64_t n_docs, int use_words, int32_t* long_flag,
-                             hipStream_t s, hipStream_t side, hipEvent_t ev_fork0, hipEvent_t ev_fork, hipEvent_t ev_join, hipEvent_t ev_brk)
+                             hipStream_t s, hipStream_t side, hipEvent_t ev_fork0, hipEvent_t ev_fork, hipEvent_t ev_join, hipEvent_t ev_brk, const GzDrop* drop)
 {
     const int fork_side = O.side;                              // 0: everything on one stream (tests)
     bool par0 = false;
@@ -1587,7 +1590,8 @@ void gz_launch_pipeline_text(const GzOptions& O, const GzDeviceTables* T, const 
     // the first word of every document is only needed by the row kernel: it goes on the side stream, BESIDE THE WORD KERNEL (the
     // join before the row kernel covers it).  (Round 3 ran it with the wide-word kernels beside the merge kernel -- one fork
     // instead of two; the merge kernel is now shorter than those three together, and the row kernel waited for the side stream.)
-    par0 = fork_side && side && ev_fork0 && ev_fork && ev_join;
+    // (a dropout call's merge kernels look a word's document up in docw0: there it stays on the main stream, before them)
+    par0 = fork_side && side && ev_fork0 && ev_fork && ev_join && !drop;
     if (par0) {
         hipEventRecord(ev_fork0, s); hipStreamWaitEvent(side, ev_fork0, 0);
         hipLaunchKernelGGL(gz_docw0_kernel, dim3((unsigned)((n_docs + 1 + 255) / 256)), dim3(256), 0, side, X, n_docs);
@@ -1595,6 +1599,7 @@ void gz_launch_pipeline_text(const GzOptions& O, const GzDeviceTables* T, const 
     gz_launch_hot_words(O, T, Th, X, use_words, s);
     scan32(X.blkmiss, X.grpblk, 1);
     auto wide = [&](hipStream_t q) {
+        if (drop) { gz_launch_drop_wide(T, X, n_docs, *drop, q); return; }
         const int ldw = Th.pair_ph.nbuckets <= GZ_PH_LDS_BUCKETS ? 1 : 0;
         hipLaunchKernelGGL(gz_miss_wide_kernel, dim3(nb < 2048u ? nb : 2048u), dim3(WAVE * PWPB), ldw ? (size_t)Th.pair_ph.nbuckets * 2 : 0, q, T, X, long_flag, ldw);   // (grid-stride over the list)
         hipLaunchKernelGGL(gz_long_kernel, dim3(nb < 1024u ? nb : 1024u), dim3(WAVE * PWPB), 0, q, T, X, (const int32_t*)long_flag);
@@ -1608,7 +1613,8 @@ void gz_launch_pipeline_text(const GzOptions& O, const GzDeviceTables* T, const 
         wide(side);
         hipEventRecord(ev_join, side);
     }
-    gz_launch_hot_miss(O, T, Th, X, use_words, s);
+    if (drop) gz_launch_drop_miss(O, T, Th, X, n_docs, *drop, s);
+    else gz_launch_hot_miss(O, T, Th, X, use_words, s);
     if (par) hipStreamWaitEvent(s, ev_join, 0);
     else wide(s);
 }

@@ -53,6 +53,7 @@ SYMBOLS = [
     "gz_minhash_rows", "gz_minhash_rows_device", "gz_minhash_groups", "gz_minhash_groups_device",
     "gz_wordset_build", "gz_wordset_build_device", "gz_wordset_from_counts", "gz_wordset_info", "gz_wordset_words", "gz_wordset_destroy",
     "gz_bpe_learn", "gz_bpe_learn_result",
+    "gz_encode_dropout", "gz_encode_dropout_device", "gz_bpe_word_dropout",
 ]
 
 _lib = None
@@ -221,11 +222,17 @@ def load_library():
         L.gz_bm25_search_groups.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.gz_bm25_search_groups_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, i32, i64, i32, vp, vp, vp, vp, vp]
         L.gz_bm25_match_count_groups.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp]
+    if hasattr(L, "gz_encode_dropout"):
+        u64 = C.c_uint64
+        dr = [vp, vp, vp, i64, i32, u32, i64, u64, u64, i64, vp, vp, vp, vp]
+        L.gz_encode_dropout.argtypes = dr
+        L.gz_encode_dropout_device.argtypes = dr
+        L.gz_bpe_word_dropout.argtypes = [vp, vp, i64, u64, u64, i64, i64, vp, i64]; L.gz_bpe_word_dropout.restype = i64
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
-        if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
+        if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_bpe_word_dropout", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
                         "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
@@ -454,6 +461,53 @@ class Context:
         out = np.empty(cap, dtype=np.int32)
         buf = np.frombuffer(word, dtype=np.uint8)
         n = self.lib.gz_bpe_word(self.handle, _ptr(buf), len(word), _ptr(out), cap)
+        self._check(n)
+        return out[:n]
+
+    # ---- BPE-dropout ---------------------------------------------------------------------------------------------
+    def encode_dropout(self, text: np.ndarray, text_off: np.ndarray, max_len, padding, truncation, thr: int, seed: int, doc_base: int):
+        """gz_encode_dropout: the dict `encode` returns for single texts; thr = drop threshold (0 .. 2^32)."""
+        n = len(text_off) - 1
+        flags = (GZ_PADDING if padding else 0) | (GZ_TRUNCATION if truncation else 0)
+        ml = 0
+        if max_len is None:
+            flags |= GZ_MAX_LEN_NONE
+        else:
+            ml = int(max_len)
+            if not -2**31 <= ml < 2**31:
+                raise OverflowError("max_len does not fit in int32")
+        dense = bool(max_len is not None and padding and truncation and ml >= 1)
+        tb = int(text_off[-1] - text_off[0]) if n else 0
+        if dense:
+            cap = n * ml
+        else:
+            cap = tb + 2 * n
+            if max_len is not None and padding and ml > 0:
+                cap += n * ml
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        mask = np.empty(max(cap, 1), dtype=np.int32)
+        row_off = np.zeros(n + 1, dtype=np.int64)
+        n_real = np.zeros(max(n, 1), dtype=np.int32)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        self._check(self.lib.gz_encode_dropout(self.handle, _ptr(text), _ptr(text_off), n, ml, flags, cap, thr, seed, doc_base,
+                                               _ptr(ids), _ptr(mask), _ptr(row_off), _ptr(n_real)))
+        total = int(row_off[-1]) if n else 0
+        return dict(input_ids=ids[:total], attention_mask=mask[:total], row_off=row_off, n_real=n_real[:n],
+                    status=np.zeros(n, dtype=np.int32), dense=dense, max_len=ml)
+
+    def encode_dropout_device(self, d_text, d_text_off, n_docs, max_len, flags, capacity, thr, seed, doc_base, d_ids, d_mask,
+                              d_row_off=None, d_n_real=None):
+        """gz_encode_dropout_device: every pointer a device address (0 / None: NULL)."""
+        vp = C.c_void_p
+        self._check(self.lib.gz_encode_dropout_device(self.handle, vp(d_text), vp(d_text_off), n_docs, max_len, flags, capacity, thr, seed, doc_base,
+                                                      vp(d_ids), vp(d_mask), *_dptrs(d_row_off, d_n_real)))
+
+    def bpe_word_dropout(self, word: bytes, thr: int, seed: int, doc: int, word_index: int):
+        cap = len(word) + 1
+        out = np.empty(cap, dtype=np.int32)
+        buf = np.frombuffer(word, dtype=np.uint8)
+        n = self.lib.gz_bpe_word_dropout(self.handle, _ptr(buf), len(word), thr, seed, doc, word_index, _ptr(out), cap)
         self._check(n)
         return out[:n]
 

@@ -484,6 +484,101 @@ class Tokenize(object):
             for d in bufs:
                 ctx.free(d)
 
+    # ---- BPE-dropout (Provilkov et al., 2020): seeded segmentation noise --------------------------------------------------
+    @staticmethod
+    def _dropout_rule(p, seed, doc_base=0, word=0):
+        """(thr, seed, doc_base, word) of a dropout call, or the refusal.  thr = int(p * 2**32): a candidate merge is skipped when its
+        32-bit draw is below it (p = 1.0 drops everything)."""
+        thr = int(_share("p", p) * 2 ** 32)
+        return thr, _integer("seed", seed, 0, 2 ** 64), _integer("doc_base", doc_base, 0, 2 ** 63), _integer("word", word, 0, 2 ** 32)
+
+    def bpe_dropout(self, token, p, seed=0, doc=0, word=0):
+        """`bpe(token)` under BPE-dropout: the segmentation that word number `word` of document `doc` gets in an
+        `encode_dropout(..., p, seed)` call, in `bpe()`'s form."""
+        if not isinstance(token, str):
+            raise TypeError("bpe_dropout() expects str")
+        thr, seed, doc, word = self._dropout_rule(p, seed, doc, word)
+        if token == "":
+            raise IndexError("tuple index out of range")         # as bpe()
+        self._sync_tables()
+        pieces = self._ctx.bpe_word_dropout(token.encode("utf-8", "surrogatepass"), thr, seed, doc, word)
+        if len(pieces) == 1 and len(token) == 1:
+            return token
+        strs = []
+        for k, q in enumerate(pieces):
+            q = int(q)
+            if q >= 0:
+                strs.append(self._ctx.symbol(q))
+            else:
+                strs.append(chr(-q - 1) + ("</w>" if k == len(pieces) - 1 else ""))
+        return "@@ ".join(strs)[:-4]
+
+    def encode_dropout(self, texts: Sequence[str], p=0.1, seed=0, max_len: Optional[int] = None, padding: bool = True,
+                       truncation: bool = True, doc_base=0):
+        """`encode_batch` for single texts under BPE-dropout: while a word is segmented, each candidate merge is skipped with
+        probability `p`.  The draws depend on (seed, doc_base + i, the word's index in text i, the merge iteration, the position)
+        alone: the same call gives the same arrays, on any batch split, as long as `doc_base` says where the batch starts.
+        p = 0 gives `encode_batch`'s result, p = 1 every word as its code points.  The result has `encode_batch`'s form: dense
+        [N, max_len] with max_len, padding and truncation, else flat with `row_off` (which feeds window_rows / pack_rows /
+        minhash_rows / decode_batch as an encode result does)."""
+        thr, seed, doc_base, _ = self._dropout_rule(p, seed, doc_base)
+        texts = list(texts)
+        if doc_base + len(texts) > 2 ** 63 - 1:
+            raise ValueError("doc_base + len(texts) must stay below 2**63")
+        self._sync_tables()
+        tb, to = _pack(texts)
+        r = self._ctx.encode_dropout(tb, to, max_len, bool(padding), bool(truncation), thr, seed, doc_base)
+        return self._shape(r, len(texts))
+
+    def encode_dropout_packed(self, text_u8: np.ndarray, offsets: np.ndarray, p=0.1, seed=0, max_len: Optional[int] = None,
+                              padding: bool = True, truncation: bool = True, doc_base=0):
+        """`encode_dropout` on already packed UTF-8 (uint8 array + int64 offsets[N+1])."""
+        thr, seed, doc_base, _ = self._dropout_rule(p, seed, doc_base)
+        if doc_base + len(offsets) - 1 > 2 ** 63 - 1:
+            raise ValueError("doc_base + the number of documents must stay below 2**63")
+        self._sync_tables()
+        r = self._ctx.encode_dropout(text_u8, offsets, max_len, bool(padding), bool(truncation), thr, seed, doc_base)
+        return self._shape(r, len(offsets) - 1)
+
+    def encode_dropout_to_device(self, texts: Sequence[str], p, seed, max_len, doc_base=0):
+        """`encode_dropout` (padding=True, truncation=True) whose [N, max_len] int32 rows STAY in HBM, as `encode_to_device`:
+        input_ids and attention_mask as `handoff.DeviceArray`s, plus the host array n_real [N]."""
+        from .handoff import DeviceArray
+        thr, seed, doc_base, _ = self._dropout_rule(p, seed, doc_base)
+        if max_len is None or isinstance(max_len, bool) or int(max_len) < 1:
+            raise ValueError("encode_dropout_to_device needs max_len >= 1 (dense rows)")
+        L = int(max_len)
+        texts = list(texts)
+        if doc_base + len(texts) > 2 ** 63 - 1:
+            raise ValueError("doc_base + len(texts) must stay below 2**63")
+        self._sync_tables()
+        ctx = self._ctx
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            t, to = _packing.pack_pinned(texts, self, ctx)
+            n = len(to) - 1
+            bufs = []
+            try:
+                for a in (t, to):
+                    d = ctx.alloc(max(a.nbytes, 1) + 64)
+                    bufs.append(d)
+                    if a.nbytes:
+                        ctx.h2d(d, np.ascontiguousarray(a))
+                cells = max(n * L, 1)
+                out = {k: DeviceArray(ctx, ctx.alloc(4 * cells), (n, L)) for k in ("input_ids", "attention_mask")}
+                d_nr = ctx.alloc(4 * max(n, 1))
+                bufs.append(d_nr)
+                ctx.encode_dropout_device(bufs[0], bufs[1], n, L, _native.GZ_PADDING | _native.GZ_TRUNCATION, n * L, thr, seed, doc_base,
+                                          out["input_ids"].ptr, out["attention_mask"].ptr, None, d_nr)
+                ctx.sync()
+                nr = np.zeros(n, dtype=np.int32)
+                if n:
+                    ctx.d2h(nr, d_nr)
+                out["n_real"], out["status"] = nr, np.zeros(n, dtype=np.int32)
+                return out
+            finally:
+                for d in bufs:
+                    ctx.free(d)
+
     # ---- overlapping max_len windows (long documents) ---------------------------------------------------------------
     @staticmethod
     def _window_rule(max_len, stride):

@@ -162,6 +162,44 @@ int  gz_word_token_counts(gz_ctx *ctx, int which_text, int32_t *counts, int64_t 
 int64_t gz_bpe_word(gz_ctx *ctx, const uint8_t *word_utf8, int64_t len, int32_t *pieces, int64_t cap);
 int  gz_symbol_utf8(gz_ctx *ctx, int32_t symbol, const uint8_t **utf8, int32_t *len);
 
+/* ---- BPE-dropout (Provilkov et al., 2020): seeded, reproducible segmentation noise ----
+ * gz_encode_batch for single texts with ONE change: while a word is segmented, each candidate merge is skipped with probability
+ * p = drop_threshold / 2^32.  Words ("\S+\n?", the glued line feed included), initial symbols, ranks, the piece-to-id lookup,
+ * bos / eos framing, truncation and padding are those of the plain call.  The reference has no dropout: the rule is this one
+ * (tests/dropout_oracle.py states it in plain Python).
+ *
+ *   The draws of a word are a pure function of (seed, D, j, t, i): D = doc_base + d the global document index, j the index of the
+ *   word within its document, t the merge iteration, i the position in the word's current symbol list.
+ *     key(seed, D, j) = words 0, 1 of Philox4x32-10(counter (D lo, D hi, j, 0), key (seed lo, seed hi))
+ *     u(key, t, i)    = word (i & 3) of Philox4x32-10(counter (t, i >> 2, 0, 0), key)
+ *   (Philox4x32-10: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten rounds, as the masked-LM rows.)
+ *   A word of one symbol is its own piece.  Else, iteration t = 0, 1, ...: position i is LIVE when u(key, t, i) >= drop_threshold
+ *   and the pair (s[i], s[i+1]) is in the merge table; no live position: the word is finished; else the smallest rank among the live
+ *   positions is merged at every live position that holds it, left to right, never overlapping; t + 1 follows.
+ *   - a dropped occurrence of the chosen pair stays unmerged in that iteration (as in subword-nmt);
+ *   - an iteration merges at least once: at most n - 1 iterations for n symbols, no spins, no retries;
+ *   - drop_threshold 0 gives the plain call's result bit for bit, 2^32 gives every word as its code points;
+ *   - the whole-word tables are never consulted, at no threshold.
+ *
+ * gz_encode_dropout: host pointers, the outputs of gz_encode_batch for single texts (row_off for ragged layouts, n_real may be NULL).
+ * gz_encode_dropout_device: the same, every pointer a DEVICE pointer; errors that are only known once the kernels have run are
+ * reported by gz_sync, as for gz_encode_batch_device.
+ * flags: GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE and GZ_TIMING as on gz_encode_batch; GZ_NO_WORD_TABLE is accepted and has no
+ * effect; GZ_KEEP_WORDS: GZ_E_INVALID.  drop_threshold > 2^32, doc_base < 0, doc_base + n_docs past 2^63: GZ_E_INVALID.
+ * A dropout call always takes the batch pipeline (the switch `small` does not apply); where a call is cut into sub-batches (the switch
+ * sub_batches) D continues across the cut, so the result does not depend on the cut -- nor on how a corpus is split into calls, as
+ * long as doc_base says where each call's documents start.  It counts as an encode call for gz_word_token_counts and keeps nothing.
+ *
+ * gz_bpe_word_dropout: gz_bpe_word for word number word_index (0 .. 2^32 - 1) of document doc (>= 0), same outputs. */
+int  gz_encode_dropout(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, int32_t max_len, uint32_t flags,
+                       int64_t capacity, uint64_t drop_threshold, uint64_t seed, int64_t doc_base,
+                       int32_t *input_ids, int32_t *attention_mask, int64_t *row_off, int32_t *n_real);
+int  gz_encode_dropout_device(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, int32_t max_len, uint32_t flags,
+                              int64_t capacity, uint64_t drop_threshold, uint64_t seed, int64_t doc_base,
+                              int32_t *input_ids, int32_t *attention_mask, int64_t *row_off, int32_t *n_real);
+int64_t gz_bpe_word_dropout(gz_ctx *ctx, const uint8_t *word_utf8, int64_t len, uint64_t drop_threshold, uint64_t seed, int64_t doc,
+                            int64_t word_index, int32_t *pieces, int64_t cap);
+
 /* Host path with the copies overlapped (SURVEY.md 8(d) timing (ii); replaces a loop of Tokenize.__call__ with
  * max_len, padding=True, truncation=True over host strings, tokenize.py:184-259): the result comes back in CSR form --
  * n_real[d] = entries of row d after truncation (tokenize.py:141-146), and the rows' real entries back to back in
