@@ -187,6 +187,8 @@ struct gz_ctx {
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
     DBuf w_bm[72];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
+    DBuf w_ng_cnt, w_ng_aux;             // n-gram overlap: piece / position counts and their scans; the distinct counter, first_hit where the caller takes only first_ref
+    std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
 };
 
 namespace {
@@ -1028,6 +1030,8 @@ try {
     return GZ_OK;
 } GZ_CATCH(nullptr)
 
+namespace { void ngram_index_free(gz_ngram_index* ix); }                  // (gz_ngram_api.inc)
+
 void gz_destroy(gz_ctx* c)
 try {
     if (!c) return;
@@ -1037,6 +1041,8 @@ try {
     for (hipStream_t q : {c->stream, c->stream2, c->side, c->xstream, c->s_in, c->s_out}) if (q) hipStreamSynchronize(q);
     for (gz_bm25* ix : c->bm25_live) delete ix;
     c->bm25_live.clear();
+    for (gz_ngram_index* ix : c->ngram_live) ngram_index_free(ix);
+    c->ngram_live.clear();
     for (DBuf& b : c->w_bm) release(b);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -1068,7 +1074,7 @@ try {
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
-    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux}) release(*b);
+    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_cnt, &c->w_ng_aux}) release(*b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);
@@ -2008,6 +2014,7 @@ try {
 } GZ_CATCH(c)
 
 #include "gz_rows_api.inc"
+#include "gz_ngram_api.inc"
 
 // ---- text pre-pass ----------------------------------------------------------------------------------------------------
 namespace {

@@ -90,6 +90,8 @@ struct GzOptions {
     int32_t bm25_vocab_chunk = 1 << 23;  // BM25 vocabulary queries: doubles of key rows in the context's workspace at a time (one row at least; 2^23 = 64 MiB)
     int32_t learn_table_bits = 0;     // BPE learner: k > 0 starts the pair table at 2^k slots and grows it to the smallest size the load rule allows
                                       // (probe wrap-around, the refill of a table that proved too small, many growths: results must not change)
+    int32_t ngram_hash_bits = 0;      // n-gram index build (and the queries of that index): k > 0 keeps only the low k bits of every n-gram's 64-bit hash
+                                      // (almost every probe collides in start slot and tag: results must not change); 0 the whole hash
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

@@ -232,6 +232,35 @@ inline uint64_t gz_minhash_cap(int64_t n_rows)                      // a power o
 }
 void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s);     // init, then per band clear / insert / link, then flatten + count
 
+// exact token n-gram overlap against a held-out set (gz_ngram.inc)
+constexpr int GZ_NGRAM_PIECE = 4096;        // n-gram positions a wave takes: a row with more is split over waves (64 trips of 64)
+// Count pass: n_pieces[n_rows] = max(1, ceil(n-grams / GZ_NGRAM_PIECE)) and their exclusive scan piece_off[n_rows + 1]; n_pos[n_rows] =
+// n-grams and their scan pos_off[n_rows + 1] (both null or both given); rebased[n_rows + 1] = row_off - row_off[0] (may be null);
+// *too_long = 1 when a body holds 2^31 ids or more (cleared first).
+void gz_launch_ngram_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
+                           int64_t* piece_off, int64_t* n_pos, int64_t* pos_off, int64_t* rebased, uint32_t* too_long, hipStream_t s);
+struct GzNgramArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // the rows walked: row r = ids[row_off[r] .. row_off[r + 1]); bodies shorter than 2^31
+    int32_t skip_front, skip_back, n;                               // skips 0 or 1, 1 <= n <= 32
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    unsigned long long* table; uint64_t mask;                       // the index: slots - 1 (a power of two of slots, at least twice the positions)
+    uint64_t hmask;                                                 // hash bits kept (switch ngram_hash_bits)
+    const int32_t* ref_ids; const int64_t* ref_off; int64_t ref_rows;     // the index's id copy, its offsets from 0, its rows (< 2^31)
+    unsigned long long* n_distinct;                                 // build: successful claims are added
+    int32_t* n_grams; int32_t* n_hits; int32_t* n_covered; int32_t* first_hit; int32_t* first_ref;   // query: [n_rows], each may be null --
+                                                                    // but first_hit is needed where first_ref is given
+    uint8_t* covered;                                               // query: covered[k] belongs to ids[k]; may be null
+};
+inline uint64_t gz_ngram_slots(int64_t n_positions)                 // the smallest power of two that is at least twice the positions
+{
+    uint64_t cap = 1;
+    while (cap < 2 * (uint64_t)n_positions) cap <<= 1;
+    return cap;
+}
+void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s);          // into a cleared table
+void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s);           // presets the counts when a row has more than one piece; then resolves first_ref
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

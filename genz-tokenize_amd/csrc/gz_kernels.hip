@@ -714,6 +714,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_mask.inc"
 #include "gz_infill.inc"
 #include "gz_minhash.inc"
+#include "gz_ngram.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -899,6 +900,37 @@ void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s)
         hipLaunchKernelGGL(gz_minhash_link_kernel, grid, block, 0, s, A, band);
     }
     hipLaunchKernelGGL(gz_minhash_flatten_kernel, grid, block, 0, s, A);
+}
+
+void gz_launch_ngram_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
+                           int64_t* piece_off, int64_t* n_pos, int64_t* pos_off, int64_t* rebased, uint32_t* too_long, hipStream_t s)
+{
+    if (n_rows <= 0) return;
+    (void)hipMemsetAsync(too_long, 0, 4, s);
+    hipLaunchKernelGGL(gz_ngram_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back, n,
+                       n_pieces, n_pos, rebased, too_long);
+    launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
+    if (n_pos) launch_scan64((const int64_t*)n_pos, n_rows, pos_off, s);
+}
+
+void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    hipLaunchKernelGGL(gz_ngram_insert_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
+}
+
+void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    if (!A.one_each) {                                                               // the pieces of a long row meet by atomicAdd / atomicMin
+        if (A.n_hits) (void)hipMemsetAsync(A.n_hits, 0, (size_t)A.n_rows * 4, s);
+        if (A.n_covered) (void)hipMemsetAsync(A.n_covered, 0, (size_t)A.n_rows * 4, s);
+        if (A.first_hit) (void)hipMemsetAsync(A.first_hit, 0xFF, (size_t)A.n_rows * 4, s);
+    }
+    hipLaunchKernelGGL(gz_ngram_query_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
+    if (A.first_ref) hipLaunchKernelGGL(gz_ngram_resolve_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

@@ -1,6 +1,7 @@
 // gz_rowrules.h -- the rules every row-shaping call shares, as plain host C++ (no HIP, no context: tests/test_row_rules.py compiles
 // this file alone): the check of a host CSR input, the dense-row rule, the MinHash argument rules (tests/test_minhash_surface.py
-// compiles them alone too) and the pairwise-disjoint check of a call's arrays.
+// compiles them alone too), the n-gram overlap argument rules (tests/test_ngram_surface.py) and the pairwise-disjoint check of a
+// call's arrays.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -52,6 +53,27 @@ inline bool minhash_bodies_fit(const int64_t* off, int64_t n_rows, int32_t skip_
         if (off[r + 1] - off[r] - skip_front - skip_back >= ((int64_t)1 << 31)) return false;
     return true;
 }
+
+// n-gram overlap (gz_ngram_index_build*, gz_ngram_overlap*; tests/test_ngram_surface.py compiles these alone): the sentence of the first
+// rule an argument list breaks, or nullptr, in the order they are reported in.  first_ref is an int32 a query row: the reference rows
+// stay below 2^31.
+inline const char* ngram_build_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n)
+{
+    if (n_rows < 0) return "n-gram index needs n_rows >= 0";
+    if (n_rows > (int64_t)INT32_MAX) return "n-gram index needs fewer than 2^31 reference rows";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "n-gram index needs skips of 0 or 1";
+    if (n < 1 || n > 32) return "n-gram index needs a width n in 1..32";
+    return nullptr;
+}
+inline const char* ngram_overlap_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back)
+{
+    if (n_rows < 0) return "n-gram overlap needs n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "n-gram overlap needs skips of 0 or 1";
+    return nullptr;
+}
+// the reference ids an index takes: a slot holds position + 1 in 32 bits, so 2^32 - 1 ids or more are refused (GZ_E_LIMIT); so is a
+// body of 2^31 ids or more (minhash_bodies_fit)
+inline bool ngram_ids_fit(int64_t n_ids) { return n_ids >= 0 && (uint64_t)n_ids < 0xFFFFFFFFull; }
 
 // An array of a call: where it starts and how many bytes the call touches.  ABSENT: a null address or zero bytes.  (The callers
 // spelled this two ways, "zero bytes" for masked rows and "null address" for infill rows; with n_rows > 0 and row_len >= 1, which

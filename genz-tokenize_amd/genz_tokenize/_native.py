@@ -54,6 +54,8 @@ SYMBOLS = [
     "gz_wordset_build", "gz_wordset_build_device", "gz_wordset_from_counts", "gz_wordset_info", "gz_wordset_words", "gz_wordset_destroy",
     "gz_bpe_learn", "gz_bpe_learn_result",
     "gz_encode_dropout", "gz_encode_dropout_device", "gz_bpe_word_dropout",
+    "gz_ngram_index_build", "gz_ngram_index_build_device", "gz_ngram_index_info", "gz_ngram_index_destroy", "gz_ngram_overlap",
+    "gz_ngram_overlap_device",
 ]
 
 _lib = None
@@ -228,12 +230,21 @@ def load_library():
         L.gz_encode_dropout.argtypes = dr
         L.gz_encode_dropout_device.argtypes = dr
         L.gz_bpe_word_dropout.argtypes = [vp, vp, i64, u64, u64, i64, i64, vp, i64]; L.gz_bpe_word_dropout.restype = i64
+    if hasattr(L, "gz_ngram_index_build"):
+        nb = [vp, vp, vp, i64, i32, i32, i32, P(vp)]
+        L.gz_ngram_index_build.argtypes = nb
+        L.gz_ngram_index_build_device.argtypes = nb
+        L.gz_ngram_index_info.argtypes = [vp, vp]
+        L.gz_ngram_index_destroy.argtypes = [vp]; L.gz_ngram_index_destroy.restype = None
+        no = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.gz_ngram_overlap.argtypes = no
+        L.gz_ngram_overlap_device.argtypes = no
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_bpe_word_dropout", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
-                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy"):
+                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy", "gz_ngram_index_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -735,6 +746,54 @@ class Context:
         """gz_minhash_groups_device: signatures and group device addresses (0: NULL); returns n_groups."""
         return self._call_total(self.lib.gz_minhash_groups_device, self.handle, *_dptrs(d_signatures), n_rows, num_perm, bands, min_agree,
                                 *_dptrs(d_group))
+
+    # ---- exact token n-gram overlap against a held-out set -------------------------------------------------------
+    NGRAM_OUT = ("n_grams", "n_hits", "n_covered", "first_hit", "first_ref")
+
+    def ngram_index_build(self, ids: np.ndarray, row_off: np.ndarray, n: int, framed: bool) -> int:
+        """ids int32 (packed reference rows), row_off int64 [R+1] -> handle of an n-gram index (gz_ngram_index_build)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        R, skip = len(row_off) - 1, 1 if framed else 0
+        h = C.c_void_p()
+        self._check(self.lib.gz_ngram_index_build(self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), R, skip, skip, int(n), C.byref(h)))
+        return h.value
+
+    def ngram_index_build_device(self, d_ids, d_row_off, n_rows, skip_front, skip_back, n) -> int:
+        """gz_ngram_index_build_device: ids and offsets device addresses (0: NULL) -> handle."""
+        h = C.c_void_p()
+        self._check(self.lib.gz_ngram_index_build_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, n, C.byref(h)))
+        return h.value
+
+    def ngram_index_info(self, index: int):
+        """dict(n, n_rows, n_ids, n_grams, n_distinct, slots, device_bytes, context_bytes) (gz_ngram_index_info)"""
+        info = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.gz_ngram_index_info(C.c_void_p(index), _ptr(info)))
+        return dict(zip(("n", "n_rows", "n_ids", "n_grams", "n_distinct", "slots", "device_bytes", "context_bytes"), (int(v) for v in info)))
+
+    def ngram_index_destroy(self, index: int):
+        if index and getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.gz_ngram_index_destroy(C.c_void_p(index))
+
+    def ngram_overlap(self, index: int, ids: np.ndarray, row_off: np.ndarray, framed: bool, with_covered: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict of the five int32 [n] arrays, and `covered` uint8 when asked for
+        (gz_ngram_overlap)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        out = {k: np.empty(n, dtype=np.int32) for k in self.NGRAM_OUT}
+        covered = np.zeros(len(ids), dtype=np.uint8) if with_covered else None
+        self._check(self.lib.gz_ngram_overlap(self.handle, C.c_void_p(index), _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip,
+                                              *[_ptr(v) if n else None for v in out.values()], _ptr(covered) if with_covered and len(ids) else None))
+        if with_covered:
+            out["covered"] = covered
+        return out
+
+    def ngram_overlap_device(self, index: int, d_ids, d_row_off, n_rows, skip_front, skip_back, d_n_grams, d_n_hits, d_n_covered, d_first_hit,
+                             d_first_ref, d_covered):
+        """gz_ngram_overlap_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_ngram_overlap_device(self.handle, C.c_void_p(index), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
+                                                     *_dptrs(d_n_grams, d_n_hits, d_n_covered, d_first_hit, d_first_ref, d_covered)))
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

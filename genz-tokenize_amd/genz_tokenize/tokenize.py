@@ -16,6 +16,7 @@ import contextlib
 import math
 import os
 import threading
+import weakref
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -77,6 +78,47 @@ def _int32_ids(name, a, dense=False):
             raise ValueError("%s() expects ids that fit in int32" % name)
         a = a.astype(np.int32)
     return a
+
+
+class NgramIndex(object):
+    """The token n-grams of a held-out set, resident in HBM (`Tokenize.ngram_index`, `Tokenize.encode_ngram_index`): what
+    `ngram_overlap_rows`, `encode_ngram_overlap` and `decontaminate` of the SAME Tokenize object query.  It owns a copy of the
+    reference ids.  `close()` (or leaving a `with` block, or garbage collection) frees the device memory; a closed index is
+    refused.  Properties: n, n_rows (reference rows), n_ids (reference ids), n_grams (n-gram positions), n_distinct (distinct
+    n-grams) and device_bytes."""
+
+    def __init__(self, ctx, handle):
+        self._ctx = ctx
+        self._handle = handle
+        self._info = ctx.ngram_index_info(handle)
+        # (the finalizer holds the context: the index is freed before it)
+        self._finalizer = weakref.finalize(self, ctx.ngram_index_destroy, handle)
+
+    n = property(lambda self: self._info["n"])
+    n_rows = property(lambda self: self._info["n_rows"])
+    n_ids = property(lambda self: self._info["n_ids"])
+    n_grams = property(lambda self: self._info["n_grams"])
+    n_distinct = property(lambda self: self._info["n_distinct"])
+    device_bytes = property(lambda self: self._info["device_bytes"])
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def close(self):
+        if self._handle is not None:
+            self._handle = None
+            self._finalizer()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __repr__(self):
+        return "NgramIndex(n=%d, n_rows=%d, n_distinct=%d%s)" % (self.n, self.n_rows, self.n_distinct, ", closed" if self.closed else "")
 
 
 class Tokenize(object):
@@ -1124,6 +1166,118 @@ class Tokenize(object):
         self._minhash_rule(num_perm, shingle, seed, bands, threshold, min_agree)
         sig = self._encode_minhash(texts, num_perm, shingle, seed, word_table)
         return self.minhash_groups(sig, bands, threshold, min_agree)
+
+    # ---- exact token n-gram overlap against a held-out set ("decontamination") ---------------------------------------------
+    @staticmethod
+    def _ngram_rule(n=13):
+        """The width of the n-gram calls as an integer, or the refusal."""
+        return _integer("n", n, 1, 33)
+
+    @staticmethod
+    def _ngram_rows(name, rows):
+        """`rows` as (flat int32, int64 offsets), or the refusal: ids that are not integers (a float is not cut to one here), or
+        that do not fit int32"""
+        if not (isinstance(rows, np.ndarray) and rows.ndim == 2):
+            rows = [np.asarray(r) for r in rows]
+            for r in rows:
+                if r.size and r.dtype.kind not in "iu":
+                    raise TypeError("%s() expects integer ids" % name)
+        flat, off = Tokenize._flat_rows(rows)
+        return _int32_ids(name, flat), off
+
+    def _ngram_index_of(self, index):
+        """The live handle of `index`, or the refusal: not an NgramIndex, closed, or of another Tokenize object."""
+        if not isinstance(index, NgramIndex):
+            raise TypeError("index must be an NgramIndex (Tokenize.ngram_index, Tokenize.encode_ngram_index)")
+        if index.closed:
+            raise ValueError("the NgramIndex is closed")
+        if index._ctx is not self._ctx:
+            raise ValueError("the NgramIndex belongs to another Tokenize object's device context")
+        return index._handle
+
+    def ngram_index(self, rows, n=13, framed=True):
+        """An `NgramIndex` of the token n-grams of held-out `rows` (benchmark questions, test splits, canaries), built on the GPU and
+        resident in HBM.  `rows` as `decode_batch` / `window_rows` take them (`framed=True`: each row loses its first and last
+        entry first).  The n-grams of a body are its runs of `n` ids, 1 <= n <= 32; a body shorter than `n` has none.  The index
+        owns a copy of the ids.  To find out which benchmark items leaked rather than which documents, swap the roles: index a
+        corpus shard and query the benchmark."""
+        n = self._ngram_rule(n)
+        flat, off = self._ngram_rows("ngram_index", rows)
+        return NgramIndex(self._ctx, self._ctx.ngram_index_build(flat, off, n, bool(framed)))
+
+    def encode_ngram_index(self, texts: Sequence[str], n=13, word_table=True):
+        """`ngram_index` over the whole token sequence of every text: the texts are encoded without a length limit on the device
+        and the index is built there, over the rows of `encode_batch(texts, max_len=None)` without their frame.  Single texts
+        only.  Swap the roles -- index a corpus shard, query the benchmark -- to learn which benchmark items leaked."""
+        n = self._ngram_rule(n)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, R, dev):
+                handle = ctx.ngram_index_build_device(d_ids, d_ro, R, 1, 1, n)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+        return NgramIndex(ctx, handle)
+
+    def ngram_overlap_rows(self, rows, index, framed=True, return_covered=False):
+        """Exact n-gram overlap of token `rows` with the held-out set of `index`, on the GPU.  Per row, with body q of m ids and
+        n = index.n: n_grams = max(0, m - n + 1); n_hits = the positions i whose n-gram q[i:i+n] is in the index; n_covered = the
+        body tokens that lie inside some such n-gram; first_hit = the smallest such i (-1: none); first_ref = the smallest
+        reference row that holds that n-gram (-1: none); body_len = m.  Everything is exact -- a hash decides where to look, never
+        whether two n-grams are equal.  A row's outputs depend on its own body and the index alone:
+        `ngram_overlap_rows(rows[a:b])` is `ngram_overlap_rows(rows)[a:b]`, and results of shards concatenate.
+        Returns a dict of numpy int32 [N] arrays; with `return_covered` also `covered`, uint8 over the rows back to back (1 on
+        covered body tokens, 0 elsewhere, the frame cells included) and `row_off` int64 [N+1]."""
+        handle = self._ngram_index_of(index)
+        flat, off = self._ngram_rows("ngram_overlap_rows", rows)
+        out = self._ctx.ngram_overlap(handle, flat, off, bool(framed), bool(return_covered))
+        skip = 2 if framed else 0
+        out["body_len"] = np.maximum(np.diff(off) - skip, 0).astype(np.int32)
+        if return_covered:
+            out["row_off"] = off
+        return out
+
+    def encode_ngram_overlap(self, texts: Sequence[str], index, word_table=True):
+        """`ngram_overlap_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, queried there, and only the per-document arrays come back -- n_grams, n_hits, n_covered, first_hit, first_ref
+        and body_len, int32 [N].  The rule is `ngram_overlap_rows`'s over the rows of `encode_batch(texts, max_len=None)`
+        without their frame; `encode_ngram_overlap(texts[a:b])` is `encode_ngram_overlap(texts)[a:b]`, and results of
+        shards concatenate.  Single texts only."""
+        handle = self._ngram_index_of(index)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        names = _native.Context.NGRAM_OUT
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, N, dev):
+                d_out = dev(4 * len(names) * max(N, 1))
+                ctx.ngram_overlap_device(handle, d_ids, d_ro, N, 1, 1, *[d_out + 4 * N * k if N else 0 for k in range(len(names))], 0)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+                host = np.empty((len(names), N), dtype=np.int32)
+                row_off = np.zeros(N + 1, dtype=np.int64)
+                if N:
+                    ctx.d2h(host, d_out)
+                ctx.d2h(row_off, d_ro)
+        out = {k: host[i] for i, k in enumerate(names)}
+        out["body_len"] = np.maximum(np.diff(row_off) - 2, 0).astype(np.int32)
+        return out
+
+    def decontaminate(self, texts: Sequence[str], index, max_fraction=0.0):
+        """`encode_ngram_overlap` plus the decision every recipe takes from it: fraction = n_covered / max(body_len, 1) (float64,
+        the share of a document's tokens inside n-grams of the held-out set) and keep = n_covered <= max_fraction * body_len
+        (bool [N]); `max_fraction` is a number in [0, 1], and 0 keeps exactly the documents without a hit.  `texts[i]` for the i
+        with keep[i] is the corpus without its contaminated documents.  To learn which benchmark items leaked, swap the roles:
+        index a corpus shard and query the benchmark."""
+        f = _share("max_fraction", max_fraction)
+        out = self.encode_ngram_overlap(texts, index)
+        covered, body = out["n_covered"].astype(np.float64), out["body_len"].astype(np.float64)
+        out["fraction"] = covered / np.maximum(body, 1.0)
+        out["keep"] = covered <= f * body
+        return out
 
     @staticmethod
     def _shape(r, n):

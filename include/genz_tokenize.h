@@ -293,6 +293,8 @@ int64_t gz_limit(int which);
  *                              context's workspace at a time (the words are compared and ranked a chunk at a time, one row at least)
  *   learn_table_bits (0..30; 0)  gz_bpe_learn starts its pair table at 2^k slots, fills it again at twice the size while it proves
  *                              too small and grows it no further than the load rule asks (0: sized from the word set)
+ *   ngram_hash_bits (0..32; 0)  gz_ngram_index_build* and the queries of that index keep only the low k bits of every n-gram's hash
+ *                              (0: all of it); with k = 1 almost every probe collides in start slot and tag: results must not change
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -616,6 +618,77 @@ void gz_wordset_destroy(gz_wordset *ws);
 int  gz_bpe_learn(gz_wordset *ws, int64_t n_merges, int64_t min_frequency, int64_t info[8]);
 int  gz_bpe_learn_result(gz_wordset *ws, int64_t *merge_off, uint8_t *merge_bytes, int64_t merge_cap, int64_t *piece_off,
                          int64_t *piece_count, uint8_t *piece_bytes, int64_t piece_cap);
+
+/* ---- token n-gram overlap against a held-out set ("decontamination") ------------------------------------------------------------
+ * Between deduplication and packing a pretraining recipe finds the training documents that share token n-grams with a held-out set
+ * -- benchmark questions, test splits, canaries -- and how much of each document is affected (GPT-3: 13-grams; PaLM: 8-grams;
+ * Llama-2: the share of tokens covered by matching 10-grams).  An INDEX of the held-out rows' n-grams lives in device memory; a
+ * query probes it once per token position.  Everything is exact: a hash decides where to look, never whether two n-grams are equal.
+ * Neither call needs the tables or the decoder snapshot.  To find which benchmark items leaked, swap the roles: index a corpus shard
+ * and query the benchmark.
+ *   body of row r    ids[row_off[r] + skip_front .. row_off[r+1] - skip_back); the skips are 0 or 1 as in gz_window_rows; a row
+ *                    shorter than its skips has an empty body
+ *   n-grams          of a body of m ids, width n in 1..32: the max(0, m - n + 1) runs body[i .. i + n).  A body shorter than n has
+ *                    NONE (unlike the one short shingle of gz_minhash_rows: a shorter run is not evidence of leakage)
+ *   index            S = the set of all n-grams of all reference bodies; first(g) = the smallest reference row that holds g.  The
+ *                    index owns a copy of the reference ids: the caller's buffers may be freed after the build.  An index with S
+ *                    empty (no rows, or every body shorter than n) is legal
+ *   query, row r     with body q of m ids:  n_grams[r] = max(0, m - n + 1);  hit(i) = q[i .. i + n) is in S;
+ *                    n_hits[r] = the number of i with hit(i);
+ *                    n_covered[r] = the number of body positions t for which some i has hit(i) and i <= t < i + n;
+ *                    first_hit[r] = the smallest i with hit(i), -1 when there is none;
+ *                    first_ref[r] = first(q[first_hit .. first_hit + n)), -1 when there is no hit;
+ *                    covered (optional) = one uint8 per id of the input, covered[k] belongs to ids[k] for k in
+ *                    [row_off[0], row_off[n_rows]): 1 on covered body positions, 0 elsewhere, the skipped frame cells included
+ *   overlap(rows[a:b]) == overlap(rows)[a:b]: a row's outputs depend on its own body and the index alone; shards concatenate.
+ *   The outputs are a pure function of (reference rows, n, query rows): not of launch geometry, scheduling or the hash.
+ *   hash             two MurmurHash3_x86_32 streams over the n ids (little-endian 32-bit words), seeds 0 and 0x9E3779B9:
+ *                    per id  k = t * 0xCC9E2D51;  k = rotl(k, 15);  k *= 0x1B873593;  and for both streams  h ^= k;  h = rotl(h, 13);
+ *                    h = h * 5 + 0xE6546B64;  then each  h ^= 4 n;  h = fmix32(h);   h64 = H_0 << 32 | H_0x9E3779B9, cut to its low
+ *                    ngram_hash_bits bits when that switch is set;  tag = h64 >> 32;  start slot = h64 & (slots - 1)
+ *   table            open addressing, linear probing, slots = the smallest power of two that is at least twice the reference n-gram
+ *                    positions (never more than half full), 8 bytes a slot: tag << 32 | (position + 1), position = the global
+ *                    index of the n-gram's first id in the index's id copy; 0 = free.  Insert: 64-bit compare-and-swap on a free
+ *                    slot; on a taken slot with an equal tag the n ids at the occupant's position are compared with the inserter's:
+ *                    equal -- the slot is lowered to the inserter's position by a 64-bit atomic minimum (equal tags: the packed
+ *                    order is the position order) and the insert is done; else the next slot.  Every occurrence of an n-gram ends
+ *                    in one slot, which holds its smallest position; first(g) is the row of that position (a binary search in the
+ *                    reference offsets): membership and first do not depend on the order of the inserts
+ *   memory           the index: 4 bytes a reference id, 8 bytes a reference row, 8 bytes a slot -- 20 to 36 bytes a reference token
+ *                    with one position a token; workspace of a build or a query: 16 to 32 bytes a row
+ *   ids / row_off    packed int32 rows as gz_decode_batch takes them;  the five per-row outputs int32 [n_rows], each may be NULL;
+ *                    covered uint8, may be NULL.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched or written: n_rows < 0; 2^31 reference
+ *   rows or more; a skip outside {0, 1}; n outside 1..32; a NULL index or out handle; NULL ids or row_off with n_rows > 0; output
+ *   arrays that overlap the input or each other; bad or decreasing row offsets (the host form); an index of another context.
+ *   GZ_E_LIMIT and nothing built or written: reference ids that total 2^32 - 1 or more (a slot holds position + 1 in 32 bits: shard the
+ *   held-out set), or a body of 2^31 ids or more.  n_rows == 0 is GZ_OK and launches nothing (a build then gives the empty index).
+ * gz_ngram_index_build: host pointers; the rows go up through the library's pinned staging.  gz_ngram_index_build_device: DEVICE
+ *   pointers; offsets are ABSOLUTE from the base pointer and row_off_dev[0] need not be 0.  Ordering: every pass runs on the
+ *   context's stream, behind a gz_encode_batch_device (ragged layout) enqueued just before with no gz_sync in between.  The index
+ *   is complete on return.
+ * gz_ngram_index_info: info[8] = n, reference rows, reference ids, n-gram positions, distinct n-grams, table slots, device bytes of
+ *   this index, device bytes of all live n-gram indexes of its context.
+ * gz_ngram_index_destroy: frees the index (NULL is fine).  An index belongs to its context and is destroyed before it; gz_destroy
+ *   frees what is left.
+ * gz_ngram_overlap: host pointers, the outputs come back.  gz_ngram_overlap_device: every pointer a DEVICE pointer, offsets ABSOLUTE
+ *   as above, same ordering; the call returns when its outputs are complete.  Both use the index's n; the skips are the call's own.
+ * Not here: appending to a live index, saving and loading one, multi-GPU indexes (shards query one replicated index), removing or
+ *   splitting the contaminated spans, text or character n-grams, exact whole-document deduplication, approximate (Bloom) tables,
+ *   per-reference-row "seen" marks. */
+typedef struct gz_ngram_index gz_ngram_index;
+int  gz_ngram_index_build(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                          int32_t n, gz_ngram_index **out);
+int  gz_ngram_index_build_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, int32_t skip_front,
+                                 int32_t skip_back, int32_t n, gz_ngram_index **out);
+int  gz_ngram_index_info(gz_ngram_index *index, int64_t info[8]);
+void gz_ngram_index_destroy(gz_ngram_index *index);
+int  gz_ngram_overlap(gz_ctx *ctx, gz_ngram_index *index, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front,
+                      int32_t skip_back, int32_t *n_grams, int32_t *n_hits, int32_t *n_covered, int32_t *first_hit, int32_t *first_ref,
+                      uint8_t *covered);
+int  gz_ngram_overlap_device(gz_ctx *ctx, gz_ngram_index *index, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                             int32_t skip_front, int32_t skip_back, int32_t *n_grams_dev, int32_t *n_hits_dev, int32_t *n_covered_dev,
+                             int32_t *first_hit_dev, int32_t *first_ref_dev, uint8_t *covered_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
