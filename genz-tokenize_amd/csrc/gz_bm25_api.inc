@@ -1,6 +1,9 @@
 // The BM25 index behind the C ABI: the index, its workspace and the host code of every gz_bm25_* call, then the entry points.
 // Included by gz_api.cpp behind gz_ctx, fail, HIPCHK, ensure and the copy helpers; the kernels are in gz_bm25.inc, gz_topk.inc,
 // gz_vocab.inc, gz_search.inc, gz_groups.inc, gz_snippet.inc and gz_near.inc.
+// A build, an append and a word set (gz_learn_api.inc) begin with the same word front -- count, scan, words, hash, de-duplication
+// rounds, first, scan: bm_front_count and bm_front_words, the only callers of those kernels.  What the host and the device forms of
+// their entry points repeat is in bm_host_offsets, bm_upload, bm_read_off0 and bm_hmask.
 // What changes a live index -- append, remove, compact -- has one shape: a core in three phases (A: workspace and tails only, B: every
 // remaining allocation, through bm_stage and its size rule, C: one commit() that nothing below can undo), run by bm25_change, which
 // owns the lock, the stage-before-drain order and the dropping of the derived lists.  The searches have theirs in bm25_search_entry.
@@ -91,6 +94,114 @@ int bm_read_u32(gz_ctx* c, const uint32_t* src, int64_t& v)
     return rc;
 }
 
+// ---- what the entry points of the host and the device forms share ---------------------------------------------------------------
+// a host form's packed offsets: n + 1 of them that do not decrease, over bytes that are there
+int bm_host_offsets(gz_ctx* c, const uint8_t* text, const int64_t* off, int64_t n)
+{
+    const int64_t nbytes = off[n] - off[0];
+    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
+    for (int64_t d = 0; d < n; ++d) if (off[d + 1] < off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
+    return GZ_OK;
+}
+
+// a host form's text and offsets on the device: the nbytes from off[0] on into `text_buf`, the n + 1 offsets into the workspace
+int bm_upload(gz_ctx* c, DBuf& text_buf, const uint8_t* text, const int64_t* off, int64_t n, int64_t nbytes)
+{
+    DBuf& o = c->w_bm[BMW_OFF];
+    int rc;
+    if ((rc = bm_alloc(c, text_buf, (size_t)nbytes + 16)) || (rc = bm_alloc(c, o, (size_t)(n + 1) * 8))) return rc;
+    if (nbytes && (rc = copy_in(c, text_buf.p, text + off[0], (size_t)nbytes, c->stream))) return rc;
+    return copy_in(c, o.p, off, (size_t)(n + 1) * 8, c->stream);
+}
+
+// a device form's first offset, read back: the base of its text
+int bm_read_off0(gz_ctx* c, const int64_t* off_dev, int64_t& off0)
+{
+    const int rc = copy_out_small(c, &off0, off_dev, 8, c->stream);
+    return rc ? rc : off0 < 0 ? fail(c, GZ_E_INVALID, "negative text offset") : GZ_OK;
+}
+
+// the word hashes' mask: the whole hash but its top bit, or the low bits the switch bm25_hash_bits leaves (forced collisions)
+unsigned long long bm_hmask(const gz_ctx* c)
+{
+    const int bits = c->opt.bm25_hash_bits;
+    return bits > 0 ? (1ull << bits) - 1ull : ~0ull >> 1;
+}
+
+// ---- the word front: what a build, an append and a word set (gz_learn_api.inc) begin with ----------------------------------------
+// Count, scan, words, hash, de-duplication rounds, first, scan: one function per host round trip that sizes the next buffers, both
+// on the GzBm25Args the caller has begun to fill.  Workspace only: whatever else the kernels write is the caller's, so an append
+// keeps its rule (tails beyond the counts).
+//
+// The documents' words are counted into A.wcnt (the caller's: fieldLens, their staged tail, a buffer of a word set) and scanned
+// into woff; A.n_words = W.  The caller has set tb, off, n_docs, lo, hi, obase, hmask and the bases.  `whose` opens the refusal of
+// offsets that decrease or leave [lo, hi].
+int bm_front_count(gz_ctx* c, GzBm25Args& A, const char* whose, int64_t& W)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t N = A.n_docs, text_bytes = A.hi - A.lo, wmax = (text_bytes + N) / 2 + 1;
+    int rc;
+    if ((rc = bm_alloc(c, w[BMW_WOFF], (size_t)(N + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
+        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((N > wmax ? N : wmax) / 4096 + 2) * 4)))
+        return rc;
+    A.ctl = (uint32_t*)w[BMW_CTL].p; A.woff = (uint32_t*)w[BMW_WOFF].p;
+    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.wcnt, N, A.woff))) return rc;
+    int64_t bad = 0;
+    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + N, W))) return rc;
+    if (bad) return fail(c, GZ_E_INVALID, "%s offsets decrease or leave the %lld bytes of text", whose, (long long)text_bytes);
+    A.n_words = W;
+    return GZ_OK;
+}
+
+// The words' byte ranges and hashes, then the distinct ones among them: rep, flag and its scan; T = the words that are the first
+// of their bytes.  Where the kernels are to write term ids, the caller has set A.term (and a build A.ptab, which they leave alone).
+// known (an append; A.ttab, tmask, tstart and tlen are the live term table's): the words that are terms already leave first, and
+// T counts the new terms.  The de-duplication table has load <= 3/4 of the words that enter the first round.
+int bm_front_words(gz_ctx* c, GzBm25Args& A, bool known, int64_t& T)
+{
+    hipStream_t s = c->stream;
+    DBuf* w = c->w_bm;
+    const int64_t W = A.n_words;
+    const size_t w1 = (size_t)W + 1;
+    int rc;
+    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) ||
+        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)))
+        return rc;
+    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
+    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
+    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
+    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
+    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
+    const uint32_t* list = nullptr;                           // (no list: every word)
+    int64_t n = W;
+    if (known) {
+        list = (const uint32_t*)w[BMW_LIST1].p;
+        gz_launch_bm25(GZ_BM25_KNOWN, A, nullptr, 0, (uint32_t*)w[BMW_LIST1].p, s);
+        if ((rc = bm_read_u32(c, A.ctl, n))) return rc;
+    }
+    const uint64_t slots = bm_pow2((uint64_t)n + (uint64_t)n / 3 + 16);
+    if ((rc = bm_alloc(c, w[BMW_DTAB], slots * 16))) return rc;
+    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = slots - 1;
+    // each round settles at least the word that wins each slot, so the rounds end; with the whole hash there is one
+    for (int64_t k = 0; n > 0; ++k) {
+        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
+        HIPCHK(c, hipMemsetAsync(A.dtab, 0, slots * 16, s));
+        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
+        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, n, nullptr, s);
+        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, n, next, s);
+        if ((rc = bm_read_u32(c, A.ctl, n))) return rc;
+        list = next;
+    }
+    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
+    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
+    return bm_read_u32(c, A.scan + W, T);
+}
+
 // The build after the text is in ix->text: off_dev = the documents' absolute offsets (device), text_bytes = bytes from off[0].
 // Four host round trips: the word count, each de-duplication round's leftovers (one round unless hashes collide), the term count
 // and the entry count size the next buffers.
@@ -105,58 +216,22 @@ int bm25_build_core(gz_ctx* c, gz_bm25* ix, const int64_t* off_dev, int64_t text
     A.tb = (const uint8_t*)ix->text.p - ix->off0;
     A.off = off_dev; A.n_docs = N; A.lo = ix->off0; A.hi = ix->off0 + text_bytes;
     ix->text_bytes = text_bytes;
-    const int bits = c->opt.bm25_hash_bits;
-    ix->hmask = A.hmask = bits > 0 ? (1ull << bits) - 1ull : ~0ull >> 1;
-    const int64_t wmax = (text_bytes + N) / 2 + 1;
-    if ((rc = bm_alloc(c, ix->dl, (size_t)N * 4)) || (rc = bm_alloc(c, ix->sig, (size_t)N * 32)) || (rc = bm_alloc(c, ix->eoff, (size_t)(N + 1) * 4)) ||
-        (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(N + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
-        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((N > wmax ? N : wmax) / 4096 + 2) * 4)))
+    ix->hmask = A.hmask = bm_hmask(c);
+    if ((rc = bm_alloc(c, ix->dl, (size_t)N * 4)) || (rc = bm_alloc(c, ix->sig, (size_t)N * 32)) || (rc = bm_alloc(c, ix->eoff, (size_t)(N + 1) * 4)))
         return rc;
-    A.ctl = (uint32_t*)w[BMW_CTL].p; A.wcnt = (uint32_t*)ix->dl.p; A.woff = (uint32_t*)w[BMW_WOFF].p;
-    A.sig = (unsigned long long*)ix->sig.p; A.eoff = (uint32_t*)ix->eoff.p;
-    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
+    A.wcnt = (uint32_t*)ix->dl.p; A.sig = (unsigned long long*)ix->sig.p; A.eoff = (uint32_t*)ix->eoff.p;
     if (N) HIPCHK(c, hipMemsetAsync(A.sig, 0, (size_t)N * 32, s));
-    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.wcnt, N, A.woff))) return rc;
-    int64_t bad = 0, W = 0;
-    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + N, W))) return rc;
-    if (bad) return fail(c, GZ_E_INVALID, "BM25 index: document offsets decrease or leave the %lld bytes of text", (long long)text_bytes);
-    ix->n_words = A.n_words = W;
-
-    // ---- words, their hashes, the de-duplication rounds
-    const size_t w1 = (size_t)W + 1;
-    const uint64_t slots = bm_pow2((uint64_t)W + (uint64_t)W / 3 + 16);           // load <= 3/4 in the de-duplication and pair tables
-    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) || (rc = bm_alloc(c, w[BMW_DTAB], slots * 16)) ||
-        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)) ||
-        (rc = bm_alloc(c, pos ? ix->seq : w[BMW_TERM], pos ? (size_t)W * 4 : w1 * 4)) || (rc = bm_alloc(c, ix->ptab, slots * 16)))
+    int64_t W = 0, T = 0;
+    if ((rc = bm_front_count(c, A, "BM25 index: document", W))) return rc;
+    ix->n_words = W;
+    const uint64_t slots = bm_pow2((uint64_t)W + (uint64_t)W / 3 + 16);           // load <= 3/4 in the pair table
+    if ((rc = bm_alloc(c, pos ? ix->seq : w[BMW_TERM], pos ? (size_t)W * 4 : ((size_t)W + 1) * 4)) || (rc = bm_alloc(c, ix->ptab, slots * 16)))
         return rc;
-    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
-    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
-    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = slots - 1;
-    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
     A.term = (uint32_t*)(pos ? ix->seq : w[BMW_TERM]).p;     // (a positional index owns the words' term ids: they are its seq)
     A.ptab = (GzBm25Slot*)ix->ptab.p; A.pmask = ix->pmask = slots - 1;
-    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
-    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
-    // each round settles at least the word that wins each slot, so the rounds end; with the whole hash there is one
-    const uint32_t* list = nullptr;
-    for (int64_t n = W, k = 0; n > 0; ++k) {
-        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
-        HIPCHK(c, hipMemsetAsync(A.dtab, 0, slots * 16, s));
-        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
-        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, n, nullptr, s);
-        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, n, next, s);
-        if ((rc = bm_read_u32(c, A.ctl, n))) return rc;
-        list = next;
-    }
+    if ((rc = bm_front_words(c, A, false, T))) return rc;
 
-    // ---- term ids, term table, pairs, df, signatures, entries
-    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
-    int64_t T = 0;
-    if ((rc = bm_read_u32(c, A.scan + W, T))) return rc;
+    // ---- term table, pairs, df, signatures, entries
     ix->n_terms = ix->n_live = T;
     const uint64_t tslots = bm_pow2(2 * (uint64_t)T + 16);
     if ((rc = bm_alloc(c, ix->tstart, (size_t)T * 8)) || (rc = bm_alloc(c, ix->tlen, (size_t)T * 4)) || (rc = bm_alloc(c, ix->df, (size_t)T * 4)) ||
@@ -236,13 +311,10 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     const int64_t N0 = ix->n_docs, T0 = ix->n_terms, E0 = ix->n_ent, used = ix->text_bytes, W0 = ix->n_words;
     const bool pos = (ix->flags & GZ_BM25_POSITIONS) != 0;
     int rc;
-    // ---- phase A: text, word boundaries, known terms, de-duplication of the rest
+    // ---- phase A: the text, then the word front with the known terms taken out
     void* p_text = nullptr; void* p_dl = nullptr;
-    const int64_t wmax = (add + n) / 2 + 1;
     auto grow = [&](DBuf& live, size_t keep, size_t need, void** p) { return bm_stage(c, st, live, keep, need, BmSize::Grow, p); };
-    if ((rc = grow(ix->text, (size_t)used, (size_t)(used + add) + 16, &p_text)) || (rc = grow(ix->dl, (size_t)N0 * 4, (size_t)(N0 + n) * 4, &p_dl)) ||
-        (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(n + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
-        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((n > wmax ? n : wmax) / 4096 + 2) * 4)))
+    if ((rc = grow(ix->text, (size_t)used, (size_t)(used + add) + 16, &p_text)) || (rc = grow(ix->dl, (size_t)N0 * 4, (size_t)(N0 + n) * 4, &p_dl)))
         return rc;
     if (add && text_host && (rc = copy_in(c, (uint8_t*)p_text + used, text_host, (size_t)add, s))) return rc;
     if (add && text_dev) HIPCHK(c, hipMemcpyAsync((uint8_t*)p_text + used, text_dev, (size_t)add, hipMemcpyDeviceToDevice, s));
@@ -251,51 +323,16 @@ int bm25_append_core(gz_ctx* c, gz_bm25* ix, BmStage& st, const uint8_t* text_ho
     A.off = off_dev; A.n_docs = n; A.lo = ix->off0 + used; A.hi = A.lo + add; A.obase = A.lo - batch_off0;
     A.hmask = ix->hmask;                                     // (the index's own: the switch's value of today does not enter)
     A.doc_base = (uint32_t)N0; A.term_base = (uint32_t)T0; A.ent_base = (uint32_t)E0;
-    A.ctl = (uint32_t*)w[BMW_CTL].p; A.wcnt = (uint32_t*)p_dl + N0; A.woff = (uint32_t*)w[BMW_WOFF].p;
-    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
-    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.wcnt, n, A.woff))) return rc;
-    int64_t bad = 0, W = 0;
-    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + n, W))) return rc;
-    if (bad) return fail(c, GZ_E_INVALID, "BM25 append: document offsets decrease or leave the %lld bytes of text", (long long)add);
-    A.n_words = W;
-    const size_t w1 = (size_t)W + 1;
-    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)))
-        return rc;
+    A.wcnt = (uint32_t*)p_dl + N0;
+    int64_t W = 0, Tn = 0;
+    if ((rc = bm_front_count(c, A, "BM25 append: document", W))) return rc;
     // the batch's term ids: workspace, or -- a positional index -- the tail of seq behind the index's own words
     void* p_seq = nullptr;
-    if (pos ? (rc = grow(ix->seq, (size_t)W0 * 4, (size_t)(W0 + W) * 4, &p_seq)) : (rc = bm_alloc(c, w[BMW_TERM], w1 * 4))) return rc;
-    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
-    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
-    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
+    if (pos ? (rc = grow(ix->seq, (size_t)W0 * 4, (size_t)(W0 + W) * 4, &p_seq)) : (rc = bm_alloc(c, w[BMW_TERM], ((size_t)W + 1) * 4))) return rc;
     A.term = pos ? (uint32_t*)p_seq + W0 : (uint32_t*)w[BMW_TERM].p;
     A.tstart = (int64_t*)ix->tstart.p; A.tlen = (uint32_t*)ix->tlen.p;          // (read only in this phase)
     A.ttab = (GzBm25Slot*)ix->ttab.p; A.tmask = ix->tmask;
-    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
-    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
-    const uint32_t* list = (const uint32_t*)w[BMW_LIST1].p;
-    gz_launch_bm25(GZ_BM25_KNOWN, A, nullptr, 0, (uint32_t*)w[BMW_LIST1].p, s);
-    int64_t U = 0;
-    if ((rc = bm_read_u32(c, A.ctl, U))) return rc;
-    const uint64_t dslots = bm_pow2((uint64_t)U + (uint64_t)U / 3 + 16);
-    if ((rc = bm_alloc(c, w[BMW_DTAB], dslots * 16))) return rc;
-    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = dslots - 1;
-    for (int64_t m = U, k = 0; m > 0; ++k) {
-        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
-        HIPCHK(c, hipMemsetAsync(A.dtab, 0, dslots * 16, s));
-        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
-        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, m, nullptr, s);
-        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, m, next, s);
-        if ((rc = bm_read_u32(c, A.ctl, m))) return rc;
-        list = next;
-    }
-    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
-    int64_t Tn = 0;
-    if ((rc = bm_read_u32(c, A.scan + W, Tn))) return rc;
+    if ((rc = bm_front_words(c, A, true, Tn))) return rc;
 
     // ---- phase B: room for the new terms, pairs, rows and entries (W bounds the new pairs and entries: their count is known
     // only once the pair table has been written)
@@ -1468,20 +1505,17 @@ try {
     if (!c || !out || !text_off || n_docs < 0) return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
     *out = nullptr;
     if (flags & ~GZ_BM25_POSITIONS) return fail(c, GZ_E_INVALID, "BM25 build flags 0x%x: only GZ_BM25_POSITIONS is defined", (unsigned)flags);
+    int rc;
+    if ((rc = bm_host_offsets(c, text, text_off, n_docs))) return rc;
     const int64_t nbytes = text_off[n_docs] - text_off[0];
-    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
-    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
     if ((rc = bm_limits(c, nbytes, n_docs))) return rc;
     alloc_site(c);
     std::unique_ptr<gz_bm25> ix(new gz_bm25());
     BmDrain drain{c};
     ix->c = c; ix->n_docs = n_docs; ix->off0 = text_off[0]; ix->flags = flags;
-    if ((rc = bm_alloc(c, ix->text, (size_t)nbytes + 16)) || (rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
-    if (nbytes && (rc = copy_in(c, ix->text.p, text + text_off[0], (size_t)nbytes, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
+    if ((rc = bm_upload(c, ix->text, text, text_off, n_docs, nbytes))) return rc;
     if ((rc = bm25_build_core(c, ix.get(), (const int64_t*)c->w_bm[BMW_OFF].p, nbytes)) || (rc = bm25_build_finish(c, ix.get()))) return rc;
     return bm_adopt(c, ix, out);
 } GZ_CATCH(c)
@@ -1501,8 +1535,7 @@ try {
     std::unique_ptr<gz_bm25> ix(new gz_bm25());
     BmDrain drain{c};
     int64_t off0 = 0;
-    if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
-    if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+    if ((rc = bm_read_off0(c, text_off_dev, off0))) return rc;
     ix->c = c; ix->n_docs = n_docs; ix->off0 = off0; ix->flags = flags;
     if ((rc = bm_alloc(c, ix->text, (size_t)text_bytes + 16))) return rc;
     if (text_bytes) HIPCHK(c, hipMemcpyAsync(ix->text.p, text_dev + off0, (size_t)text_bytes, hipMemcpyDeviceToDevice, c->stream));
@@ -1516,9 +1549,8 @@ try {
     gz_ctx* c = ix->c;
     if (n_docs < 0 || (n_docs > 0 && !text_off)) return fail(c, GZ_E_INVALID, "bad arguments");
     if (n_docs == 0) return GZ_OK;
+    if (int rc = bm_host_offsets(c, text, text_off, n_docs)) return rc;
     const int64_t nbytes = text_off[n_docs] - text_off[0];
-    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
-    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
     return bm25_change(ix, [&](BmStage& st) -> int {             // (the offsets through the workspace, then as the device form)
         DBuf& off = c->w_bm[BMW_OFF];
         int rc;
@@ -1540,8 +1572,7 @@ try {
         if ((rc = bm_limits(c, ix->text_bytes + text_bytes, ix->n_docs + n_docs))) return rc;     // (before anything is read)
         if (!text_off_dev || (text_bytes > 0 && !text_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
         int64_t off0 = 0;
-        if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
-        if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+        if ((rc = bm_read_off0(c, text_off_dev, off0))) return rc;
         return bm25_append_core(c, ix, st, nullptr, text_bytes ? text_dev + off0 : nullptr, text_off_dev, off0, n_docs, text_bytes);
     });
 } GZ_CATCH(ix ? ix->c : nullptr)

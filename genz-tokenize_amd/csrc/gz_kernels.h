@@ -562,7 +562,8 @@ enum { GZ_BM25_SR_NEAR, GZ_BM25_NR_COVER };
 // rows: of the chunk (GZ_BM25_SR_NEAR)
 void gz_launch_bm25_near(int step, const GzBm25Near& A, int64_t rows, hipStream_t s);
 
-// BPE learner (gz_learn.inc): the counts of a word set on top of the BM25 build's word front, and the merge loop of gz_bpe_learn.
+// BPE learner (gz_learn.inc): the counts of a word set on top of the word front it shares with the BM25 build and append (host side:
+// bm_front_count and bm_front_words in gz_bm25_api.inc, the only callers of those kernels), and the merge loop of gz_bpe_learn.
 // The words' symbols live in one flat array, word d = sym[woff[d] .. woff[d] + wlen[d]) (a merge shortens it in place, its slice
 // stays where it is); the pair table is open addressing, key = (left << 32 | right) + 1 (0: empty), cnt = n(left, right); nothing is
 // ever deleted, a count of 0 stays.

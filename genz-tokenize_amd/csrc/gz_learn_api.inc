@@ -1,11 +1,12 @@
 // The word sets and the BPE learner behind the C ABI (gz_wordset_*, gz_bpe_learn*).  Included by gz_api.cpp behind gz_bm25_api.inc,
-// whose workspace (BMW_*), bm_alloc, bm_scan, bm_read_u32, bm_limits and BmDrain it shares; the kernels are in gz_learn.inc, the host
-// rules in gz_learn_host.h.
+// whose workspace (BMW_*), word front (bm_front_count, bm_front_words), entry-point helpers, bm_alloc, bm_scan, bm_read_u32, bm_limits
+// and BmDrain it shares; the kernels are in gz_learn.inc, the host rules in gz_learn_host.h.
 //
 // A word set lives on the host once it is built: the distinct words' bytes in first-occurrence order, their offsets and int64
-// counts.  The build is the BM25 build's word front -- count, scan, words, hash, de-duplication rounds, first, scan -- followed by
-// one counting kernel and a gather; nothing of a BM25 index is made.  The counts form runs the same front with every given word as
-// a document of its own and its count as the document's weight: words given twice add up.
+// counts.  The build calls the word front the BM25 build and append call -- count, scan, words, hash, de-duplication rounds, first,
+// scan: there is one copy of it, in gz_bm25_api.inc -- and follows it with one counting kernel and a gather; nothing of a BM25 index
+// is made.  The counts form runs the same front with every given word as a document of its own and its count as the document's
+// weight: words given twice add up.
 //
 // gz_bpe_learn: the host numbers the initial symbols and interns the merged ones (gz_learn_host.h), the device holds the words'
 // symbols and the pair table.  Per step: the arg-best reduction, ONE small readback (the best key and count, the keys in the
@@ -42,54 +43,17 @@ int wordset_core(gz_ctx* c, gz_wordset* ws, LnBufs& B, const uint8_t* tb, const 
                  const long long* weight, bool strict)
 {
     hipStream_t s = c->stream;
-    DBuf* w = c->w_bm;
     int rc;
+    // ---- the word front (gz_bm25_api.inc) on counters of the word set's own; no term ids, no table of an index
     GzBm25Args A{};
     A.tb = tb; A.off = off_dev; A.n_docs = N; A.lo = lo; A.hi = lo + text_bytes;
-    const int bits = c->opt.bm25_hash_bits;
-    A.hmask = bits > 0 ? (1ull << bits) - 1ull : ~0ull >> 1;
-    const int64_t wmax = (text_bytes + N) / 2 + 1;
-    if ((rc = bm_alloc(c, B.b[0], (size_t)N * 4)) || (rc = bm_alloc(c, w[BMW_WOFF], (size_t)(N + 1) * 4)) || (rc = bm_alloc(c, w[BMW_CTL], 64)) ||
-        (rc = bm_alloc(c, w[BMW_BSUM], (size_t)((N > wmax ? N : wmax) / 4096 + 2) * 4)))
-        return rc;
-    A.ctl = (uint32_t*)w[BMW_CTL].p; A.wcnt = (uint32_t*)B.b[0].p; A.woff = (uint32_t*)w[BMW_WOFF].p;
-    HIPCHK(c, hipMemsetAsync(A.ctl, 0, 64, s));
-    gz_launch_bm25(GZ_BM25_COUNT, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.wcnt, N, A.woff))) return rc;
-    int64_t bad = 0, W = 0;
-    if ((rc = bm_read_u32(c, A.ctl + 1, bad)) || (rc = bm_read_u32(c, A.woff + N, W))) return rc;
-    if (bad) return fail(c, GZ_E_INVALID, "word set: offsets decrease or leave the %lld bytes of text", (long long)text_bytes);
+    A.hmask = bm_hmask(c);
+    if ((rc = bm_alloc(c, B.b[0], (size_t)N * 4))) return rc;
+    A.wcnt = (uint32_t*)B.b[0].p;
+    int64_t W = 0, T = 0, bad = 0;
+    if ((rc = bm_front_count(c, A, "word set:", W))) return rc;
     if (strict && W != N) return fail(c, GZ_E_INVALID, "word set: %lld words were given, they split into %lld", (long long)N, (long long)W);
-    A.n_words = W;
-
-    // ---- words, their hashes, the de-duplication rounds (bm25_build_core's)
-    const size_t w1 = (size_t)W + 1;
-    const uint64_t slots = bm_pow2((uint64_t)W + (uint64_t)W / 3 + 16);
-    if ((rc = bm_alloc(c, w[BMW_WSTART], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WEND], w1 * 8)) || (rc = bm_alloc(c, w[BMW_WDOC], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_HASH], w1 * 8)) || (rc = bm_alloc(c, w[BMW_REP], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SLOT], w1 * 4)) ||
-        (rc = bm_alloc(c, w[BMW_LIST0], w1 * 4)) || (rc = bm_alloc(c, w[BMW_LIST1], w1 * 4)) || (rc = bm_alloc(c, w[BMW_DTAB], slots * 16)) ||
-        (rc = bm_alloc(c, w[BMW_FLAG], w1 * 4)) || (rc = bm_alloc(c, w[BMW_SCAN], w1 * 4)))
-        return rc;
-    A.wstart = (int64_t*)w[BMW_WSTART].p; A.wend = (int64_t*)w[BMW_WEND].p; A.wdoc = (uint32_t*)w[BMW_WDOC].p;
-    A.whash = (unsigned long long*)w[BMW_HASH].p; A.rep = (uint32_t*)w[BMW_REP].p; A.wslot = (uint32_t*)w[BMW_SLOT].p;
-    A.dtab = (GzBm25Slot*)w[BMW_DTAB].p; A.dmask = slots - 1;
-    A.flag = (uint32_t*)w[BMW_FLAG].p; A.scan = (uint32_t*)w[BMW_SCAN].p;
-    gz_launch_bm25(GZ_BM25_WORDS, A, nullptr, 0, nullptr, s);
-    gz_launch_bm25(GZ_BM25_HASH, A, nullptr, 0, nullptr, s);
-    const uint32_t* list = nullptr;
-    for (int64_t n = W, k = 0; n > 0; ++k) {
-        uint32_t* next = (uint32_t*)w[BMW_LIST0 + (k & 1)].p;
-        HIPCHK(c, hipMemsetAsync(A.dtab, 0, slots * 16, s));
-        HIPCHK(c, hipMemsetAsync(A.ctl, 0, 4, s));
-        gz_launch_bm25(GZ_BM25_DEDUP_INS, A, list, n, nullptr, s);
-        gz_launch_bm25(GZ_BM25_DEDUP_RES, A, list, n, next, s);
-        if ((rc = bm_read_u32(c, A.ctl, n))) return rc;
-        list = next;
-    }
-    gz_launch_bm25(GZ_BM25_FIRST, A, nullptr, 0, nullptr, s);
-    if ((rc = bm_scan(c, A.flag, W, A.scan))) return rc;
-    int64_t T = 0;
-    if ((rc = bm_read_u32(c, A.scan + W, T))) return rc;
+    if ((rc = bm_front_words(c, A, false, T))) return rc;
 
     // ---- the counts, the distinct words' byte ranges, their bytes
     const size_t t1 = (size_t)T + 1;
@@ -258,21 +222,18 @@ int gz_wordset_build(gz_ctx* c, const uint8_t* text, const int64_t* text_off, in
 try {
     if (!c || !out || !text_off || n_docs < 0) return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
     *out = nullptr;
+    int rc;
+    if ((rc = bm_host_offsets(c, text, text_off, n_docs))) return rc;
     const int64_t nbytes = text_off[n_docs] - text_off[0];
-    if (nbytes < 0 || (nbytes > 0 && !text)) return fail(c, GZ_E_INVALID, "bad text offsets");
-    for (int64_t d = 0; d < n_docs; ++d) if (text_off[d + 1] < text_off[d]) return fail(c, GZ_E_INVALID, "text offsets must not decrease");
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
     if ((rc = bm_limits(c, nbytes, n_docs))) return rc;
     alloc_site(c);
     std::unique_ptr<gz_wordset> ws(new gz_wordset());
     ws->c = c;
     LnBufs B;
     BmDrain drain{c};
-    if ((rc = bm_alloc(c, B.b[6], (size_t)nbytes + 16)) || (rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_docs + 1) * 8))) return rc;
-    if (nbytes && (rc = copy_in(c, B.b[6].p, text + text_off[0], (size_t)nbytes, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, text_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
+    if ((rc = bm_upload(c, B.b[6], text, text_off, n_docs, nbytes))) return rc;
     if ((rc = wordset_core(c, ws.get(), B, (const uint8_t*)B.b[6].p - text_off[0], (const int64_t*)c->w_bm[BMW_OFF].p, n_docs, text_off[0], nbytes,
                            nullptr, false)))
         return rc;
@@ -294,8 +255,7 @@ try {
     LnBufs B;
     BmDrain drain{c};
     int64_t off0 = 0;
-    if ((rc = copy_out_small(c, &off0, text_off_dev, 8, c->stream))) return rc;
-    if (off0 < 0) return fail(c, GZ_E_INVALID, "negative text offset");
+    if ((rc = bm_read_off0(c, text_off_dev, off0))) return rc;
     // (the caller's text is read where it lies: nothing of it is kept)
     if ((rc = wordset_core(c, ws.get(), B, text_dev, text_off_dev, n_docs, off0, text_bytes, nullptr, false))) return rc;
     return wordset_adopt(c, ws, out);
@@ -323,12 +283,9 @@ try {
     ws->c = c;
     LnBufs B;
     BmDrain drain{c};
-    if ((rc = bm_alloc(c, B.b[6], (size_t)nbytes + 16)) || (rc = bm_alloc(c, B.b[7], (size_t)n_words * 8)) ||
-        (rc = bm_alloc(c, c->w_bm[BMW_OFF], (size_t)(n_words + 1) * 8)))
+    if ((rc = bm_upload(c, B.b[6], words, word_off, n_words, nbytes)) || (rc = bm_alloc(c, B.b[7], (size_t)n_words * 8)) ||
+        (rc = copy_in(c, B.b[7].p, counts, (size_t)n_words * 8, c->stream)))
         return rc;
-    if (nbytes && (rc = copy_in(c, B.b[6].p, words + word_off[0], (size_t)nbytes, c->stream))) return rc;
-    if ((rc = copy_in(c, B.b[7].p, counts, (size_t)n_words * 8, c->stream))) return rc;
-    if ((rc = copy_in(c, c->w_bm[BMW_OFF].p, word_off, (size_t)(n_words + 1) * 8, c->stream))) return rc;
     if ((rc = wordset_core(c, ws.get(), B, (const uint8_t*)B.b[6].p - word_off[0], (const int64_t*)c->w_bm[BMW_OFF].p, n_words, word_off[0], nbytes,
                            (const long long*)B.b[7].p, true)))
         return rc;
