@@ -261,6 +261,47 @@ inline uint64_t gz_ngram_slots(int64_t n_positions)                 // the small
 void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s);          // into a cleared table
 void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s);           // presets the counts when a row has more than one piece; then resolves first_ref
 
+// word spans, word ids and aligned labels (gz_align.inc)
+constexpr int64_t GZ_SPAN_BLOCK = 4096;                            // bytes of packed text per block of the span kernels
+inline int64_t gz_span_blocks(int64_t text_bytes) { return (text_bytes + GZ_SPAN_BLOCK - 1) / GZ_SPAN_BLOCK; }
+struct GzSpanArgs {
+    const uint8_t* text; const int64_t* text_off; int64_t n_docs;   // document d = text[text_off[d] .. text_off[d + 1]) (absolute offsets)
+    int64_t B;                                                      // text_off[n_docs] - text_off[0]
+    int32_t unit;                                                   // 0 code points, 1 bytes
+    uint32_t* brk;                                                  // B / 32 + 4 words: the launcher clears them, then one bit a document start
+    uint32_t* gran;                                                 // 256 * blocks words: (starts | leads << 16) before a granule, inside its block
+    int64_t* blk_s; int64_t* blk_l;                                 // [blocks] starts / leads of a block
+    int64_t* base_s; int64_t* base_l;                               // [blocks + 1] their exclusive scans
+    int64_t* lead0;                                                 // [n_docs + 1] leads before a document's first byte
+    int64_t* blk_doc;                                               // [blocks + 1] the document of a block's first byte; [blocks] = n_docs - 1
+    uint32_t* too_long;                                             // set when a document holds 2^31 bytes or more (cleared first)
+    int64_t* word_off;                                              // [n_docs + 1] out
+    int32_t* span; int64_t n_words;                                 // write pass: [n_words, 2] out, n_words = word_off[n_docs]
+};
+void gz_launch_span_count(const GzSpanArgs& A, hipStream_t s);      // everything but span: word_off, lead0 and the scans the write pass reads
+void gz_launch_span_write(const GzSpanArgs& A, hipStream_t s);
+struct GzAlignArgs {
+    const uint32_t* tok_off;                                        // [n_words + 1] exclusive scan of the piece counts, from 0, wrapping
+    int32_t rows_per_block;                                         // set by the launcher
+    const int64_t* word_off; int64_t n_docs, n_words;               // absolute; n_words = word_off[n_docs] - word_off[0]
+    const int32_t* row_doc; const int32_t* row_start; int64_t n_rows;     // each may be null: row r is document r / start 0
+    int32_t max_len;
+    const int32_t* word_labels;                                     // indexed as counts (absolute); needed where labels is given
+    int32_t continuation; const int32_t* cont_map; int32_t n_map; int32_t ignore_index;
+    int32_t* word_ids; int32_t* labels; int32_t* n_real;            // [n_rows, max_len] x 2, [n_rows]; each may be null
+};
+void gz_launch_align_scan(const int32_t* counts, const int64_t* word_off, int64_t n_words, uint32_t* tok_off /* n_words + 1 */, hipStream_t s);
+void gz_launch_align_rows(GzAlignArgs A, hipStream_t s);
+struct GzSpanLabArgs {
+    const int32_t* span; const int64_t* word_off; int64_t n_docs, n_words;      // span[word_off[d] .. word_off[d + 1]) are document d's words (absolute)
+    const int32_t* marks; const int64_t* mark_off; int64_t n_marks;             // marks[mark_off[d] .. mark_off[d + 1]) are its marks (absolute)
+    int32_t scheme, outside;                                        // 0 plain, 1 BIO
+    uint32_t* owner;                                                // [n_words] scratch, from 0; needed where word_labels is given
+    int32_t* word_labels;                                           // indexed as span (absolute); may be null
+    int32_t* mark_words;                                            // [n_marks, 2] from 0; may be null
+};
+void gz_launch_span_labels(const GzSpanLabArgs& A, hipStream_t s);
+
 // text pre-pass (gz_preproc.inc): one filter over documents that sit in the slots of a packed text
 struct GzPpArgs {
     const uint8_t* in; const int64_t* in_off;   // slot of document d = in[in_off[d] - in_off[0] ... (in_abs: see below)

@@ -705,6 +705,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 }
 
 #include "gz_pipeline.inc"
+#include "gz_align.inc"
 #include "gz_hot.inc"
 #include "gz_dropout.inc"
 #include "gz_small.inc"
@@ -951,6 +952,64 @@ void gz_launch_preprocess(const GzPpArgs& A, int pass, hipStream_t s)
 void gz_launch_scan64(const int64_t* len, int64_t n, int64_t* out_off /* n+1 */, hipStream_t s)
 {
     launch_scan64(len, n, out_off, s);
+}
+
+void gz_launch_span_count(const GzSpanArgs& A, hipStream_t s)
+{
+    static_assert(AL_BLK == GZ_SPAN_BLOCK, "gz_kernels.h and gz_align.inc disagree");
+    const int64_t nblk = gz_span_blocks(A.B);
+    (void)hipMemsetAsync(A.brk, 0, (size_t)(A.B / 32 + 4) * 4, s);
+    (void)hipMemsetAsync(A.too_long, 0, 4, s);
+    if (A.n_docs > 1) hipLaunchKernelGGL(gz_brk_kernel, dim3((unsigned)((A.n_docs + 255) / 256)), dim3(256), 0, s, A.text_off, A.n_docs, A.brk);
+    if (nblk > 0) hipLaunchKernelGGL(gz_span_scan_kernel, dim3((unsigned)nblk), dim3(256), 0, s, A);
+    launch_scan64((const int64_t*)A.blk_s, nblk, A.base_s, s);
+    launch_scan64((const int64_t*)A.blk_l, nblk, A.base_l, s);
+    hipLaunchKernelGGL(gz_span_doc_kernel, dim3((unsigned)(A.n_docs / 256 + 1)), dim3(256), 0, s, A);
+}
+
+void gz_launch_span_write(const GzSpanArgs& A, hipStream_t s)
+{
+    const int64_t nblk = gz_span_blocks(A.B);
+    if (nblk <= 0 || A.n_words <= 0 || A.n_docs <= 0) return;
+    hipLaunchKernelGGL(gz_span_write_kernel, dim3((unsigned)nblk), dim3(256), 0, s, A);
+}
+
+void gz_launch_align_scan(const int32_t* counts, const int64_t* word_off, int64_t n_words, uint32_t* tok_off, hipStream_t s)
+{
+    hipLaunchKernelGGL(gz_align_scan_local_kernel, dim3((unsigned)(n_words / SC32 + 1)), dim3(1024), 0, s, counts, word_off, n_words, tok_off);
+    hipLaunchKernelGGL(gz_scan32x_bases_kernel, dim3(1), dim3(1024), 0, s, tok_off, n_words);
+    hipLaunchKernelGGL(gz_scan32x_add_kernel, dim3((unsigned)(n_words / 256 + 1)), dim3(256), 0, s, tok_off, n_words);
+}
+
+void gz_launch_align_rows(GzAlignArgs A, hipStream_t s)
+{
+    const int64_t cells = A.n_rows * (int64_t)A.max_len;
+    if (cells <= 0) return;
+    if (A.max_len <= AL_LMAX) {
+        // about 2 048 cells a block, 8 rows at the least: rows_per_block * ceil(max_len / 32) <= AL_BITS either way
+        const int rb = 2048 / A.max_len;
+        A.rows_per_block = rb < 8 ? 8 : rb > AL_RMAX ? AL_RMAX : rb;
+        const int64_t blocks = (A.n_rows + A.rows_per_block - 1) / A.rows_per_block;
+        if (blocks <= 0x7FFFFFFF) {
+            // 16 bytes a lane where every row starts on a 16-byte boundary; one cell a lane otherwise
+            const bool wide = A.max_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(A.word_ids) | reinterpret_cast<uintptr_t>(A.labels)) & 15) == 0;
+            if (wide) hipLaunchKernelGGL(gz_align_rows_lds_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, A);
+            else hipLaunchKernelGGL(gz_align_rows_lds_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, A);
+            return;
+        }
+    }
+    const int64_t blocks = (cells + 255) / 256;
+    hipLaunchKernelGGL(gz_align_rows_kernel, dim3((unsigned)(blocks < (1 << 22) ? blocks : (1 << 22))), dim3(256), 0, s, A);
+}
+
+void gz_launch_span_labels(const GzSpanLabArgs& A, hipStream_t s)
+{
+    if (A.n_docs <= 0) return;
+    if (A.word_labels && A.n_words > 0) (void)hipMemsetAsync(A.owner, 0xFF, (size_t)A.n_words * 4, s);
+    if (A.n_marks > 0) hipLaunchKernelGGL(gz_spanlab_mark_kernel, dim3((unsigned)((A.n_marks + 255) / 256)), dim3(256), 0, s, A);
+    if (!A.word_labels || A.n_words <= 0) return;
+    hipLaunchKernelGGL(gz_spanlab_word_kernel, dim3((unsigned)((A.n_words + 255) / 256)), dim3(256), 0, s, A);
+    if (A.scheme) hipLaunchKernelGGL(gz_spanlab_first_kernel, dim3((unsigned)((A.n_docs + 255) / 256)), dim3(256), 0, s, A);
 }
 
 void gz_launch_preprocess_fused(const GzPpFusedArgs& A, hipStream_t s)

@@ -75,6 +75,54 @@ inline const char* ngram_overlap_fault(int64_t n_rows, int32_t skip_front, int32
 // body of 2^31 ids or more (minhash_bodies_fit)
 inline bool ngram_ids_fit(int64_t n_ids) { return n_ids >= 0 && (uint64_t)n_ids < 0xFFFFFFFFull; }
 
+// Word spans, aligned rows, span labels (gz_word_spans*, gz_align_rows*, gz_span_labels*; tests/test_align_surface.py compiles these
+// alone): the sentence of the first rule broken, or nullptr, in the order they are reported in.  The *_data_fault rules read the
+// caller's arrays, so only the host forms can apply them; the device forms trust what they cannot read.
+inline const char* word_spans_fault(int64_t n_docs, int32_t unit, int64_t capacity_words)
+{
+    if (n_docs < 0) return "word spans need n_docs >= 0";
+    if (unit != 0 && unit != 1) return "word spans need unit 0 (code points) or 1 (bytes)";
+    if (capacity_words < 0) return "word spans need capacity_words >= 0";
+    return nullptr;
+}
+inline const char* align_rows_fault(int64_t n_docs, int64_t n_rows, bool have_row_doc, int32_t max_len, int32_t continuation, bool have_map,
+                                    int32_t n_map, bool want_labels, bool have_word_labels)
+{
+    if (n_docs < 0 || n_rows < 0) return "aligned rows need n_docs >= 0 and n_rows >= 0";
+    if (max_len < 3) return "aligned rows need max_len >= 3";
+    if (!have_row_doc && n_rows != n_docs) return "aligned rows without row_doc need n_rows == n_docs";
+    if (continuation < 0 || continuation > 2) return "aligned rows need continuation 0 (ignore), 1 (same) or 2 (map)";
+    if (n_map < 0) return "aligned rows need n_map >= 0";
+    if (continuation == 2 && (!have_map || n_map < 1)) return "aligned rows in map mode need a cont_map of at least one entry";
+    if (want_labels && !have_word_labels) return "aligned rows need word_labels where labels are asked for";
+    if ((uint64_t)n_rows > (uint64_t)(INT64_MAX / 4) / (uint64_t)max_len) return "aligned rows need n_rows * max_len * 4 below 2^63";
+    return nullptr;
+}
+// counts: the n counts of the batch (already at its first word); row_doc / row_start may be null
+inline const char* align_data_fault(const int32_t* counts, int64_t n, const int32_t* row_doc, const int32_t* row_start, int64_t n_rows, int64_t n_docs)
+{
+    for (int64_t i = 0; i < n; ++i) if (counts[i] < 1) return "aligned rows: a word's piece count is below 1";
+    if (row_doc) for (int64_t r = 0; r < n_rows; ++r) if (row_doc[r] < 0 || (int64_t)row_doc[r] >= n_docs) return "aligned rows: a row_doc lies outside [0, n_docs)";
+    if (row_start) for (int64_t r = 0; r < n_rows; ++r) if (row_start[r] < 0) return "aligned rows: a row_start is negative";
+    return nullptr;
+}
+inline const char* span_labels_fault(int64_t n_docs, int32_t scheme)
+{
+    if (n_docs < 0) return "span labels need n_docs >= 0";
+    if (scheme != 0 && scheme != 1) return "span labels need scheme 0 (plain) or 1 (BIO)";
+    return nullptr;
+}
+// marks: the n_marks (begin, end, label) triples of the batch (already at its first mark).  BIO writes 2 * label + 2.
+inline const char* span_labels_data_fault(const int32_t* marks, int64_t n_marks, int32_t scheme)
+{
+    if (scheme != 1) return nullptr;
+    for (int64_t m = 0; m < n_marks; ++m) {
+        if (marks[3 * m + 2] < 0) return "span labels under BIO need labels >= 0";
+        if (marks[3 * m + 2] >= (1 << 30) - 1) return "span labels under BIO need labels below 2^30 - 1";
+    }
+    return nullptr;
+}
+
 // An array of a call: where it starts and how many bytes the call touches.  ABSENT: a null address or zero bytes.  (The callers
 // spelled this two ways, "zero bytes" for masked rows and "null address" for infill rows; with n_rows > 0 and row_len >= 1, which
 // both have checked by then, every array that is given has bytes and every array with bytes that is left out is null: one rule.)

@@ -749,3 +749,225 @@ try {
     return GZ_OK;
 } GZ_CATCH(c)
 
+// ---- word spans, word ids and aligned labels (gz_align.inc) ---------------------------------------------------------------
+namespace {
+constexpr RowsWords kWordWords{"bad word offsets", "word offsets must not decrease"};
+constexpr RowsWords kMarkWords{"bad mark offsets", "mark offsets must not decrease"};
+const char* const kSpanDocLimit = "a document holds 2^31 bytes or more: split it";
+const char* const kSpanWordLimit = "the batch holds 2^31 words or more: split it";
+// c->w_al: the span kernels' scans, the align call's token scan, the owners of span labels, and the staged inputs of the host forms
+enum { ALW_BRK, ALW_GRAN, ALW_BLKS, ALW_BLKL, ALW_BASES, ALW_BASEL, ALW_LEAD0, ALW_BLKDOC, ALW_TOK, ALW_OWNER, ALW_IN0, ALW_IN1, ALW_IN2, ALW_IN3 };
+
+// a host array the row front does not carry: `bytes` of it into w_al[k]; *dev = its device copy (nullptr for a null array)
+int align_stage_bytes(gz_ctx* c, int k, const void* host, size_t bytes, const void** dev)
+{
+    *dev = nullptr;
+    if (!host) return GZ_OK;
+    int rc;
+    if ((rc = ensure(c, c->w_al[k], bytes ? bytes : 16))) return rc;
+    if (bytes && (rc = copy_in(c, c->w_al[k].p, host, bytes, c->stream))) return rc;
+    *dev = c->w_al[k].p;
+    return GZ_OK;
+}
+int align_stage(gz_ctx* c, int k, const int32_t* host, size_t bytes, const int32_t** dev) { return align_stage_bytes(c, k, host, bytes, (const void**)dev); }
+int align_stage64(gz_ctx* c, int k, const int64_t* host, size_t bytes, const int64_t** dev) { return align_stage_bytes(c, k, host, bytes, (const void**)dev); }
+
+// The count pass on the context's stream, behind whatever it holds: A.text, text_off, n_docs, B, unit and word_off are the caller's,
+// the scans are the workspace's.  *total = W, read back from the device (the one wait of the pass); the limits are checked there.
+int span_count_locked(gz_ctx* c, GzSpanArgs& A, int64_t* total)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nblk = (size_t)gz_span_blocks(A.B);
+    int rc;
+    if ((rc = ensure(c, c->w_al[ALW_BRK], (size_t)(A.B / 32 + 4) * 4)) || (rc = ensure(c, c->w_al[ALW_GRAN], (nblk * 256 + 1) * 4)) ||
+        (rc = ensure(c, c->w_al[ALW_BLKS], (nblk + 1) * 8)) || (rc = ensure(c, c->w_al[ALW_BLKL], (nblk + 1) * 8)) ||
+        (rc = ensure(c, c->w_al[ALW_BASES], (nblk + 2) * 8)) || (rc = ensure(c, c->w_al[ALW_BASEL], (nblk + 2) * 8)) ||
+        (rc = ensure(c, c->w_al[ALW_LEAD0], (size_t)(A.n_docs + 2) * 8)) || (rc = ensure(c, c->w_al[ALW_BLKDOC], (nblk + 2) * 8))) return rc;
+    A.brk = (uint32_t*)c->w_al[ALW_BRK].p; A.gran = (uint32_t*)c->w_al[ALW_GRAN].p;
+    A.blk_s = (int64_t*)c->w_al[ALW_BLKS].p; A.blk_l = (int64_t*)c->w_al[ALW_BLKL].p;
+    A.base_s = (int64_t*)c->w_al[ALW_BASES].p; A.base_l = (int64_t*)c->w_al[ALW_BASEL].p;
+    A.lead0 = (int64_t*)c->w_al[ALW_LEAD0].p; A.blk_doc = (int64_t*)c->w_al[ALW_BLKDOC].p;
+    A.too_long = (uint32_t*)(A.lead0 + A.n_docs + 1);
+    A.span = nullptr; A.n_words = 0;
+    gz_launch_span_count(A, c->stream);
+    uint32_t* const h_long = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 360);       // (pinned scratch)
+    *h_long = 0;
+    HIPCHK(c, hipMemcpyAsync(h_long, A.too_long, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = read_total(c, A.word_off + A.n_docs, nullptr, total))) return rc;
+    HIPCHK(c, hipGetLastError());
+    if (*h_long) return fail(c, GZ_E_LIMIT, "%s", kSpanDocLimit);
+    if (*total >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_word_spans_device(gz_ctx* c, const uint8_t* text_dev, const int64_t* text_off_dev, int64_t n_docs, int64_t text_bytes, int32_t unit,
+                         int32_t* span_dev, int64_t* word_off_dev, int64_t capacity_words, int64_t* total_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = word_spans_fault(n_docs, unit, capacity_words)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!text_off_dev || !word_off_dev || !total_host || text_bytes < 0 || (text_bytes > 0 && !text_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    GzSpanArgs A{};
+    A.text = text_dev; A.text_off = text_off_dev; A.n_docs = n_docs; A.B = text_bytes; A.unit = unit; A.word_off = word_off_dev;
+    int rc;
+    if ((rc = span_count_locked(c, A, total_host))) return rc;
+    if (!span_dev) return GZ_OK;
+    if (*total_host > capacity_words)
+        return fail(c, GZ_E_CAPACITY, "the batch has %lld words, capacity is %lld", (long long)*total_host, (long long)capacity_words);
+    A.span = span_dev; A.n_words = *total_host;
+    gz_launch_span_write(A, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_word_spans(gz_ctx* c, const uint8_t* text, const int64_t* text_off, int64_t n_docs, int32_t unit, int32_t* span, int64_t* word_off,
+                  int64_t capacity_words, int64_t* total_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = word_spans_fault(n_docs, unit, capacity_words)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!text_off || !word_off || !total_host) return fail(c, GZ_E_INVALID, "bad arguments");
+    RowsIn in{text, text_off, n_docs, 1};
+    int rc;
+    if ((rc = rows_check(c, in, kTextWords))) return rc;
+    if (!minhash_bodies_fit(text_off, n_docs, 0, 0)) return fail(c, GZ_E_LIMIT, "%s", kSpanDocLimit);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_docs + 1) * 8))) return rc;                  // kept through both passes: word_off
+    GzSpanArgs A{};
+    A.text = (const uint8_t*)in.d_payload; A.text_off = in.d_off; A.n_docs = n_docs; A.B = in.n; A.unit = unit; A.word_off = (int64_t*)in.d_keep;
+    int64_t total = 0;
+    if ((rc = span_count_locked(c, A, &total))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, word_off, A.word_off, (size_t)(n_docs + 1) * 8, c->stream))) return rc;
+    if (!span) return GZ_OK;
+    if (total > capacity_words) return fail(c, GZ_E_CAPACITY, "the batch has %lld words, capacity is %lld", (long long)total, (long long)capacity_words);
+    if (total == 0) return GZ_OK;
+    StagedOut S;
+    S.add(span, (size_t)total * 8, true);
+    if ((rc = staged_ensure(c, S))) return rc;
+    A.span = S.dev(0); A.n_words = total;
+    gz_launch_span_write(A, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+namespace {
+// the token scan and the one launch on the context's stream; every pointer of A a device pointer, A.tok_off is set here
+int align_launch_locked(gz_ctx* c, GzAlignArgs& A, const int32_t* counts_dev)
+{
+    int rc;
+    if ((rc = ensure(c, c->w_al[ALW_TOK], (size_t)(A.n_words + 2) * 4))) return rc;
+    gz_launch_align_scan(counts_dev, A.word_off, A.n_words, (uint32_t*)c->w_al[ALW_TOK].p, c->stream);
+    A.tok_off = (const uint32_t*)c->w_al[ALW_TOK].p;
+    gz_launch_align_rows(A, c->stream);
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_align_rows_device(gz_ctx* c, const int32_t* counts_dev, const int64_t* word_off_dev, int64_t n_docs, int64_t n_words, const int32_t* row_doc_dev,
+                         const int32_t* row_start_dev, int64_t n_rows, int32_t max_len, const int32_t* word_labels_dev, int32_t continuation,
+                         const int32_t* cont_map_dev, int32_t n_map, int32_t ignore_index, int32_t* word_ids_dev, int32_t* labels_dev, int32_t* n_real_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = align_rows_fault(n_docs, n_rows, row_doc_dev != nullptr, max_len, continuation, cont_map_dev != nullptr, n_map,
+                                           labels_dev != nullptr, word_labels_dev != nullptr)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off_dev || n_words < 0 || (n_words > 0 && !counts_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_words >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_rows == 0 || (!word_ids_dev && !labels_dev && !n_real_dev)) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    GzAlignArgs A{};
+    A.word_off = word_off_dev; A.n_docs = n_docs; A.n_words = n_words; A.row_doc = row_doc_dev; A.row_start = row_start_dev; A.n_rows = n_rows;
+    A.max_len = max_len; A.word_labels = word_labels_dev; A.continuation = continuation; A.cont_map = cont_map_dev; A.n_map = n_map;
+    A.ignore_index = ignore_index; A.word_ids = word_ids_dev; A.labels = labels_dev; A.n_real = n_real_dev;
+    int rc;
+    if ((rc = align_launch_locked(c, A, counts_dev))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_align_rows(gz_ctx* c, const int32_t* counts, const int64_t* word_off, int64_t n_docs, const int32_t* row_doc, const int32_t* row_start,
+                  int64_t n_rows, int32_t max_len, const int32_t* word_labels, int32_t continuation, const int32_t* cont_map, int32_t n_map,
+                  int32_t ignore_index, int32_t* word_ids, int32_t* labels, int32_t* n_real)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = align_rows_fault(n_docs, n_rows, row_doc != nullptr, max_len, continuation, cont_map != nullptr, n_map, labels != nullptr,
+                                           word_labels != nullptr)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off) return fail(c, GZ_E_INVALID, "bad arguments");
+    RowsIn in{counts, word_off, n_docs, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kWordWords))) return rc;
+    if (in.n >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    if (const char* why = align_data_fault(in.n ? counts + word_off[0] : nullptr, in.n, row_doc, row_start, n_rows, n_docs))
+        return fail(c, GZ_E_INVALID, "%s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_rows == 0 || (!word_ids && !labels && !n_real)) return GZ_OK;
+    if ((rc = rows_stage(c, in, 0))) return rc;
+    GzAlignArgs A{};
+    A.word_off = in.d_off; A.n_docs = n_docs; A.n_words = in.n; A.n_rows = n_rows; A.max_len = max_len;
+    A.continuation = continuation; A.n_map = n_map; A.ignore_index = ignore_index;
+    const int32_t* wl = nullptr;
+    if ((rc = align_stage(c, ALW_IN0, row_doc, (size_t)n_rows * 4, &A.row_doc)) || (rc = align_stage(c, ALW_IN1, row_start, (size_t)n_rows * 4, &A.row_start)) ||
+        (rc = align_stage(c, ALW_IN2, labels && word_labels ? word_labels + word_off[0] : nullptr, (size_t)in.n * 4, &wl)) ||
+        (rc = align_stage(c, ALW_IN3, continuation == 2 ? cont_map : nullptr, (size_t)n_map * 4, &A.cont_map))) return rc;
+    A.word_labels = wl ? wl - word_off[0] : nullptr;                          // (biased: indexed as the caller's array)
+    const size_t cells = (size_t)n_rows * (size_t)max_len * 4;
+    StagedOut S;
+    S.add(word_ids, cells, true); S.add(labels, cells, true); S.add(n_real, (size_t)n_rows * 4, false);
+    if ((rc = staged_ensure(c, S))) return rc;
+    A.word_ids = S.dev(0); A.labels = S.dev(1); A.n_real = S.dev(2);
+    if ((rc = align_launch_locked(c, A, (const int32_t*)in.d_payload))) return rc;
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+int gz_span_labels_device(gz_ctx* c, const int32_t* span_dev, const int64_t* word_off_dev, int64_t n_docs, int64_t n_words, const int32_t* marks_dev,
+                          const int64_t* mark_off_dev, int64_t n_marks, int32_t scheme, int32_t outside, int32_t* word_labels_dev, int32_t* mark_words_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = span_labels_fault(n_docs, scheme)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off_dev || !mark_off_dev || n_words < 0 || n_marks < 0 || (n_words > 0 && !span_dev) || (n_marks > 0 && !marks_dev))
+        return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_words >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    if (n_marks >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "span labels take fewer than 2^31 marks");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_docs == 0 || (!word_labels_dev && !mark_words_dev)) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->w_al[ALW_OWNER], (size_t)(n_words + 1) * 4))) return rc;
+    GzSpanLabArgs A{span_dev, word_off_dev, n_docs, n_words, marks_dev, mark_off_dev, n_marks, scheme, outside,
+                    word_labels_dev ? (uint32_t*)c->w_al[ALW_OWNER].p : nullptr, word_labels_dev, mark_words_dev};
+    gz_launch_span_labels(A, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_span_labels(gz_ctx* c, const int32_t* span, const int64_t* word_off, int64_t n_docs, const int32_t* marks, const int64_t* mark_off, int32_t scheme,
+                   int32_t outside, int32_t* word_labels, int32_t* mark_words)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = span_labels_fault(n_docs, scheme)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off || !mark_off) return fail(c, GZ_E_INVALID, "bad arguments");
+    RowsIn in{span, word_off, n_docs, 8}, mk{marks, mark_off, n_docs, 12};
+    int rc;
+    if ((rc = rows_check(c, in, kWordWords)) || (rc = rows_check(c, mk, kMarkWords))) return rc;
+    if (in.n >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    if (mk.n >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "span labels take fewer than 2^31 marks");
+    if (const char* why = span_labels_data_fault(mk.n ? marks + 3 * mark_off[0] : nullptr, mk.n, scheme)) return fail(c, GZ_E_INVALID, "%s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_docs == 0) return GZ_OK;
+    if ((rc = rows_stage(c, in, 0))) return rc;
+    const int32_t* marks_dev = nullptr;
+    const int64_t* moff_dev = nullptr;
+    if ((rc = align_stage(c, ALW_IN0, mk.n ? marks + 3 * mark_off[0] : nullptr, (size_t)mk.n * 12, &marks_dev)) ||
+        (rc = align_stage64(c, ALW_IN1, mark_off, (size_t)(n_docs + 1) * 8, &moff_dev)) || (rc = ensure(c, c->w_al[ALW_OWNER], (size_t)(in.n + 1) * 4))) return rc;
+    StagedOut S;
+    S.add(in.n ? word_labels : nullptr, (size_t)in.n * 4, true); S.add(mk.n ? mark_words : nullptr, (size_t)mk.n * 8, true);
+    if (!S.e[0].host && !S.e[1].host) return GZ_OK;
+    if ((rc = staged_ensure(c, S))) return rc;
+    GzSpanLabArgs A{(const int32_t*)in.d_payload, in.d_off, n_docs, in.n, marks_dev ? marks_dev - 3 * mark_off[0] : nullptr, moff_dev, mk.n, scheme, outside,
+                    S.dev(0) ? (uint32_t*)c->w_al[ALW_OWNER].p : nullptr, S.dev(0) ? S.dev(0) - word_off[0] : nullptr, S.dev(1)};
+    gz_launch_span_labels(A, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)

@@ -56,6 +56,7 @@ SYMBOLS = [
     "gz_encode_dropout", "gz_encode_dropout_device", "gz_bpe_word_dropout",
     "gz_ngram_index_build", "gz_ngram_index_build_device", "gz_ngram_index_info", "gz_ngram_index_destroy", "gz_ngram_overlap",
     "gz_ngram_overlap_device",
+    "gz_word_spans", "gz_word_spans_device", "gz_align_rows", "gz_align_rows_device", "gz_span_labels", "gz_span_labels_device",
 ]
 
 _lib = None
@@ -239,6 +240,13 @@ def load_library():
         no = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
         L.gz_ngram_overlap.argtypes = no
         L.gz_ngram_overlap_device.argtypes = no
+    if hasattr(L, "gz_word_spans"):
+        L.gz_word_spans.argtypes = [vp, vp, vp, i64, i32, vp, vp, i64, P(i64)]
+        L.gz_word_spans_device.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, i64, P(i64)]
+        L.gz_align_rows.argtypes = [vp, vp, vp, i64, vp, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp, vp]
+        L.gz_align_rows_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp, vp]
+        L.gz_span_labels.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
+        L.gz_span_labels_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, i32, vp, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -794,6 +802,73 @@ class Context:
         """gz_ngram_overlap_device: every pointer a device address (0: NULL)."""
         self._check(self.lib.gz_ngram_overlap_device(self.handle, C.c_void_p(index), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
                                                      *_dptrs(d_n_grams, d_n_hits, d_n_covered, d_first_hit, d_first_ref, d_covered)))
+
+    # ---- word spans, word ids and aligned labels ----------------------------------------------------------------
+    def word_spans(self, text: np.ndarray, text_off: np.ndarray, unit: int):
+        """packed UTF-8, int64 offsets [n+1] -> (span int32 [W, 2], word_off int64 [n+1]) (gz_word_spans: a sizing call, then the spans)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        n = len(text_off) - 1
+        word_off = np.zeros(n + 1, dtype=np.int64)
+        total = C.c_int64()
+        head = (self.handle, _ptr(text) if len(text) else None, _ptr(text_off), n, int(unit))
+        self._check(self.lib.gz_word_spans(*head, None, _ptr(word_off), 0, C.byref(total)))
+        W = total.value
+        span = np.empty((W, 2), dtype=np.int32)
+        if W:
+            self._check(self.lib.gz_word_spans(*head, _ptr(span), _ptr(word_off), W, C.byref(total)))
+        return span, word_off
+
+    def word_spans_device(self, d_text, d_text_off, n_docs, text_bytes, unit, d_span, d_word_off, capacity) -> int:
+        """gz_word_spans_device: returns W.  d_span == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = W."""
+        return self._call_total(self.lib.gz_word_spans_device, self.handle, *_dptrs(d_text), C.c_void_p(d_text_off), n_docs, text_bytes, unit,
+                                *_dptrs(d_span), C.c_void_p(d_word_off), capacity)
+
+    def align_rows(self, counts, word_off, max_len, word_labels, row_doc, row_start, continuation, cont_map, ignore_index, want=(True, True, True)):
+        """counts int32 [W], word_off int64 [n+1] (+ optional int32 arrays) -> dict(word_ids [R, L], labels [R, L] when word_labels is given,
+        n_real [R]) (gz_align_rows).  want: which of (word_ids, labels, n_real) to take."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        n, L = len(word_off) - 1, int(max_len)
+        R = n if row_doc is None else len(row_doc)
+        out = {}
+        if want[0]:
+            out["word_ids"] = np.empty((R, L), dtype=np.int32)
+        if want[1] and word_labels is not None:
+            out["labels"] = np.empty((R, L), dtype=np.int32)
+        if want[2]:
+            out["n_real"] = np.empty(R, dtype=np.int32)
+        self._check(self.lib.gz_align_rows(self.handle, _ptr(counts) if len(counts) else None, _ptr(word_off), n, _ptr(row_doc), _ptr(row_start), R, L,
+                                           _ptr(word_labels), int(continuation), _ptr(cont_map), 0 if cont_map is None else len(cont_map),
+                                           int(ignore_index), _ptr(out.get("word_ids")), _ptr(out.get("labels")), _ptr(out.get("n_real"))))
+        return out
+
+    def align_rows_device(self, d_counts, d_word_off, n_docs, n_words, d_row_doc, d_row_start, n_rows, max_len, d_word_labels, continuation, d_cont_map,
+                          n_map, ignore_index, d_word_ids, d_labels, d_n_real):
+        """gz_align_rows_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_align_rows_device(self.handle, *_dptrs(d_counts), C.c_void_p(d_word_off), n_docs, n_words, *_dptrs(d_row_doc, d_row_start),
+                                                  n_rows, max_len, *_dptrs(d_word_labels), continuation, *_dptrs(d_cont_map), n_map, ignore_index,
+                                                  *_dptrs(d_word_ids, d_labels, d_n_real)))
+
+    def span_labels(self, span, word_off, marks, mark_off, scheme: int, outside: int):
+        """span int32 [W, 2], word_off int64 [n+1], marks int32 [S, 3], mark_off int64 [n+1] -> (word_labels int32 [W], mark_words int32 [S, 2])
+        (gz_span_labels)."""
+        span = np.ascontiguousarray(span, dtype=np.int32)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        marks = np.ascontiguousarray(marks, dtype=np.int32)
+        mark_off = np.ascontiguousarray(mark_off, dtype=np.int64)
+        n = len(word_off) - 1
+        word_labels = np.empty(len(span), dtype=np.int32)
+        mark_words = np.empty((len(marks), 2), dtype=np.int32)
+        self._check(self.lib.gz_span_labels(self.handle, _ptr(span) if len(span) else None, _ptr(word_off), n, _ptr(marks) if len(marks) else None,
+                                            _ptr(mark_off), int(scheme), int(outside), _ptr(word_labels) if len(span) else None,
+                                            _ptr(mark_words) if len(marks) else None))
+        return word_labels, mark_words
+
+    def span_labels_device(self, d_span, d_word_off, n_docs, n_words, d_marks, d_mark_off, n_marks, scheme, outside, d_word_labels, d_mark_words):
+        """gz_span_labels_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_span_labels_device(self.handle, *_dptrs(d_span), C.c_void_p(d_word_off), n_docs, n_words, *_dptrs(d_marks),
+                                                   C.c_void_p(d_mark_off), n_marks, scheme, outside, *_dptrs(d_word_labels, d_mark_words)))
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

@@ -743,6 +743,203 @@ class Tokenize(object):
         row_off[:] = per_win[win_off]
         return ids[keep].astype(np.int32, copy=False), row_off
 
+    # ---- align: word spans, word ids and token labels (token classification) ---------------------------------------------
+    ALIGN_UNITS = {"char": 0, "byte": 1}
+    ALIGN_SCHEMES = {"plain": 0, "bio": 1}
+    ALIGN_CONTINUATIONS = {"ignore": 0, "same": 1, "bio": 2}
+
+    @staticmethod
+    def _align_choice(name, v, table):
+        if not isinstance(v, str):
+            raise TypeError("%s must be a str" % name)
+        if v not in table:
+            raise ValueError("%s must be one of %s" % (name, ", ".join(repr(k) for k in table)))
+        return table[v]
+
+    @staticmethod
+    def _align_offsets(call, name, off, total=None):
+        """int64 offsets [N+1] from 0, not decreasing (and ending at `total`), or the refusal in the words of `call`"""
+        off = np.asarray(off)
+        if off.dtype.kind not in "iu":
+            raise TypeError("%s() expects integer %s" % (call, name))
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError("%s() expects %s as a 1-D array of N + 1 entries" % (call, name))
+        off = off.astype(np.int64)
+        if off[0] != 0 or (len(off) > 1 and bool(np.any(np.diff(off) < 0))):
+            raise ValueError("%s() expects %s that start at 0 and do not decrease" % (call, name))
+        if total is not None and int(off[-1]) != total:
+            raise ValueError("%s() expects %s that end at %d, the number of entries they index" % (call, name, total))
+        return np.ascontiguousarray(off)
+
+    @staticmethod
+    def _align_vector(call, name, a, length=None):
+        a = _int32_ids(call, a)
+        if a.ndim != 1 or (length is not None and len(a) != length):
+            raise ValueError("%s() expects %s as a 1-D array%s" % (call, name, "" if length is None else " of %d entries" % length))
+        return np.ascontiguousarray(a)
+
+    @classmethod
+    def _align_continuation(cls, continuation, word_labels):
+        """(mode, map or None) of `continuation`: a name, or an integer array that is the map itself"""
+        if isinstance(continuation, str):
+            mode = cls._align_choice("continuation", continuation, cls.ALIGN_CONTINUATIONS)
+            if mode != 2:
+                return mode, None
+            top = int(word_labels.max()) + 1 if word_labels is not None and len(word_labels) else 1
+            v = np.arange(max(top, 1), dtype=np.int32)
+            return 2, np.ascontiguousarray(np.where(v % 2 == 1, v + 1, v).astype(np.int32))      # B-x = 2l + 1 -> I-x = 2l + 2
+        cont_map = cls._align_vector("align_rows", "a continuation map", continuation)
+        if len(cont_map) < 1:
+            raise ValueError("align_rows() expects a continuation map of at least one entry")
+        return 2, cont_map
+
+    def word_spans(self, texts: Sequence[str], unit: str = "char"):
+        """Where every word of every text stands: (span int32 [W, 2], word_off int64 [N+1]).  span[j] is the [begin, end) of the
+        `\\S+` part of word j in its own text -- `str` indices with unit="char", UTF-8 bytes with "byte" -- and text i's words are
+        span[word_off[i]:word_off[i+1]], the words `encode_batch(..., return_offset=True)` reports on.  Computed on the GPU."""
+        u = self._align_choice("unit", unit, self.ALIGN_UNITS)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        tb, to = _pack(texts)
+        return self._ctx.word_spans(tb, to, u)
+
+    def align_rows(self, counts, word_off, max_len: int, word_labels=None, row_doc=None, row_start=None, continuation="ignore",
+                   ignore_index: int = -100):
+        """The word of every cell of [R, max_len] rows, and its label, on the GPU.  counts [W] / word_off [N+1]: the per-word piece
+        counts of an encode call.  Row r holds body tokens row_start[r] .. of document row_doc[r] behind a bos (row_doc None: row r
+        is document r; row_start None: 0, the reference's own row; `doc` / `start` of `window_rows` give its windows).  Returns
+        word_ids [R, L] (-1 on bos, eos, pad), n_real [R] and, with word_labels [W], labels [R, L]: a word's first piece carries its
+        label, a later piece `ignore_index` ("ignore"), the same label ("same"), the I- label of a B- label 2l+1 -> 2l+2 ("bio"),
+        or map[label] where `continuation` is an integer array; specials and padding carry `ignore_index`."""
+        L = _integer("max_len", max_len, 3, 2 ** 31)
+        ig = _integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31)
+        counts = self._align_vector("align_rows", "counts", counts)
+        word_off = self._align_offsets("align_rows", "word_off", word_off, len(counts))
+        n = len(word_off) - 1
+        if len(counts) and int(counts.min()) < 1:
+            raise ValueError("align_rows() expects piece counts of at least 1")
+        if word_labels is not None:
+            word_labels = self._align_vector("align_rows", "word_labels", word_labels, len(counts))
+        if row_doc is not None:
+            row_doc = self._align_vector("align_rows", "row_doc", row_doc)
+            if len(row_doc) and (int(row_doc.min()) < 0 or int(row_doc.max()) >= n):
+                raise ValueError("align_rows() expects row_doc inside [0, %d)" % n)
+        if row_start is not None:
+            row_start = self._align_vector("align_rows", "row_start", row_start, n if row_doc is None else len(row_doc))
+            if len(row_start) and int(row_start.min()) < 0:
+                raise ValueError("align_rows() expects row_start >= 0")
+        mode, cont_map = self._align_continuation(continuation, word_labels)
+        return self._ctx.align_rows(counts, word_off, L, word_labels, row_doc, row_start, mode, cont_map, ig)
+
+    @classmethod
+    def _align_marks(cls, marks, n):
+        """(marks int32 [S, 3], mark_off int64 [N+1]) of a list of (begin, end, label) lists per document, or of that pair itself"""
+        if isinstance(marks, tuple) and len(marks) == 2 and isinstance(marks[0], np.ndarray) and marks[0].ndim == 2:
+            arr = _int32_ids("span_labels", marks[0])
+            if arr.ndim != 2 or arr.shape[1] != 3:
+                raise ValueError("span_labels() expects marks as an [S, 3] array of (begin, end, label)")
+            return np.ascontiguousarray(arr), cls._align_offsets("span_labels", "mark_off", marks[1], len(arr))
+        per_doc = list(marks)
+        if len(per_doc) != n:
+            raise ValueError("span_labels() expects one list of marks per document: %d documents, %d lists" % (n, len(per_doc)))
+        flat, off = [], np.zeros(n + 1, dtype=np.int64)
+        for d, ms in enumerate(per_doc):
+            for m in ms:
+                if len(m) != 3:
+                    raise ValueError("span_labels() expects marks of (begin, end, label)")
+                flat.append([_integer("a mark's " + k, v, -(2 ** 31), 2 ** 31) for k, v in zip(("begin", "end", "label"), m)])
+            off[d + 1] = len(flat)
+        return np.asarray(flat, dtype=np.int32).reshape(len(flat), 3), off
+
+    def span_labels(self, span, word_off, marks, scheme: str = "bio", outside: int = 0):
+        """Word labels from annotated character spans, on the GPU.  span / word_off of `word_spans`; marks: per document a list of
+        (begin, end, label) in the unit of the spans, in any order, or (array [S, 3], mark_off [N+1]).  A mark owns the words it
+        overlaps (touching is not overlapping); where marks overlap the one given first wins.  scheme="plain": a word gets its
+        mark's label, else `outside`; "bio" (labels >= 0): 0 outside, 2*label+1 on a mark's first owned word, 2*label+2 after it.
+        Returns (word_labels int32 [W], mark_words int32 [S, 2]: the [first, last+1) words of its document a mark overlaps, or -1)."""
+        sc = self._align_choice("scheme", scheme, self.ALIGN_SCHEMES)
+        out = _integer("outside", outside, -(2 ** 31), 2 ** 31)
+        span = _int32_ids("span_labels", span)
+        if span.ndim != 2 or span.shape[1] != 2:
+            raise ValueError("span_labels() expects span as a [W, 2] array")
+        word_off = self._align_offsets("span_labels", "word_off", word_off, len(span))
+        arr, mark_off = self._align_marks(marks, len(word_off) - 1)
+        if len(mark_off) != len(word_off):
+            raise ValueError("span_labels() expects mark_off and word_off over the same documents")
+        if sc == 1 and len(arr) and (int(arr[:, 2].min()) < 0 or int(arr[:, 2].max()) >= 2 ** 30 - 1):
+            raise ValueError("span_labels() with scheme='bio' expects labels in [0, 2**30 - 1)")
+        return self._ctx.span_labels(np.ascontiguousarray(span), word_off, arr, mark_off, sc, out)
+
+    def encode_aligned(self, texts: Sequence[str], max_len: int, word_labels=None, marks=None, stride: Optional[int] = None,
+                       continuation="ignore", scheme: str = "bio", ignore_index: int = -100, unit: str = "char", word_table: bool = True):
+        """Rows for token classification in one call: the texts encoded, and every cell's word and label beside them.
+        stride None: one row a text, cut the reference's way (`encode_batch(texts, max_len=max_len)`'s rows); an int: every text
+        whole, in `encode_windows`'s overlapping windows.  word_labels: one label per word of the batch (the words of
+        `word_spans`), or marks: annotated spans as `span_labels` takes them (not both).  Returns input_ids, attention_mask,
+        word_ids [R, L], labels [R, L] (when labels or marks are given), n_real [R], word_off [N+1], word_span [W, 2],
+        word_tokens [W] (pieces per word) and, with a stride, doc, start, win_off of the windows.  Single texts only."""
+        L = _integer("max_len", max_len, 3, 2 ** 31)
+        s = None
+        if stride is not None:
+            L, s = self._window_rule(max_len, stride)
+        if word_labels is not None and marks is not None:
+            raise ValueError("encode_aligned() takes word_labels or marks, not both")
+        u = self._align_choice("unit", unit, self.ALIGN_UNITS)
+        sc = self._align_choice("scheme", scheme, self.ALIGN_SCHEMES)
+        ig = _integer("ignore_index", ignore_index, -(2 ** 31), 2 ** 31)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        if word_labels is not None:
+            word_labels = self._align_vector("encode_aligned", "word_labels", word_labels)
+        if not isinstance(continuation, str):
+            self._align_continuation(continuation, None)                  # (refused here, before any device call)
+        else:
+            self._align_choice("continuation", continuation, self.ALIGN_CONTINUATIONS)
+        if marks is not None:
+            marks = self._align_marks(marks, len(texts))
+            if len(marks[1]) != len(texts) + 1:
+                raise ValueError("encode_aligned() expects marks over the same documents as texts")
+        n = len(texts)
+        self._sync_tables()
+        with self._batch_lock:
+            tb, to = _pack(texts)
+            flags = (0 if word_table else _native.GZ_NO_WORD_TABLE) | _native.GZ_KEEP_WORDS
+            if s is None:
+                r = self._shape(self._ctx.encode(tb, to, None, None, L, True, True, flags), n)
+            else:
+                r = self._ctx.encode(tb, to, None, None, None, False, False, flags)
+            if n:
+                counts, word_off = self._ctx.word_token_counts(0, n, 1 << 16)
+            else:
+                counts, word_off = np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64)
+            counts = np.ascontiguousarray(counts)
+            span, span_off = self._ctx.word_spans(tb, to, u)
+            if not np.array_equal(span_off, word_off):
+                raise RuntimeError("encode_aligned(): the word spans and the piece counts disagree on the words of the batch")
+            if word_labels is not None and len(word_labels) != len(counts):
+                raise ValueError("encode_aligned() expects one word label per word: %d words, %d labels" % (len(counts), len(word_labels)))
+            out = {}
+            if marks is not None:
+                if sc == 1 and len(marks[0]) and (int(marks[0][:, 2].min()) < 0 or int(marks[0][:, 2].max()) >= 2 ** 30 - 1):
+                    raise ValueError("encode_aligned() with scheme='bio' expects labels in [0, 2**30 - 1)")
+                word_labels, out["mark_words"] = self._ctx.span_labels(span, word_off, marks[0], marks[1], sc, 0)
+            mode, cont_map = self._align_continuation(continuation, word_labels)
+            if s is None:
+                out["input_ids"], out["attention_mask"] = r["input_ids"], r["attention_mask"]
+                row_doc = row_start = None
+            else:
+                w = self._ctx.window_rows(r["input_ids"], r["row_off"], L, s, True)
+                out["input_ids"], out["attention_mask"] = w["input_ids"], w["attention_mask"]
+                out["doc"], out["start"], out["win_off"] = w["doc"], w["start"], w["win_off"]
+                row_doc, row_start = w["doc"], w["start"]
+            out.update(self._ctx.align_rows(counts, word_off, L, word_labels, row_doc, row_start, mode, cont_map, ig))
+            out["word_off"], out["word_span"], out["word_tokens"] = word_off, span, counts
+            if word_labels is not None:
+                out["word_labels"] = word_labels
+            return out
+
     # ---- short documents packed into rows of max_len ("sequence packing") -------------------------------------------
     PACK_CELLS = ("input_ids", "attention_mask", "segment_ids", "position_ids")
     PACK_MAPS = ("doc_row", "doc_col", "doc_len")

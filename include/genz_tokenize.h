@@ -690,6 +690,74 @@ int  gz_ngram_overlap_device(gz_ctx *ctx, gz_ngram_index *index, const int32_t *
                              int32_t skip_front, int32_t skip_back, int32_t *n_grams_dev, int32_t *n_hits_dev, int32_t *n_covered_dev,
                              int32_t *first_hit_dev, int32_t *first_ref_dev, uint8_t *covered_dev);
 
+/* ---- align: word spans, word ids and aligned token labels ("token classification") --------------------------------------------
+ * The reference's return_offset says which tokens belong to which word (tokenize.py:105-117); a tagger over word-segmented text
+ * (NER, POS) also needs where each word stands in its text, the word of every cell of a row, and labels [N, max_len] made from word
+ * labels or from annotated character spans.  Three calls, single texts only, every output an exact integer.
+ * Definitions:
+ *   words of a document   the matches of \S+\n? over the document, Unicode whitespace as str.isspace (what the encoder splits on);
+ *                         a document boundary ends a word.  Document d has W_d words.
+ *   per-word quantities   word j has c_j >= 1 pieces (gz_word_token_counts); C_j = the exclusive scan of c within the document;
+ *                         T_d = the sum of c_j.
+ *   row geometry          a row is (doc, start) with room = max_len - 2.  Its chunk is the body tokens start .. min(start + room,
+ *                         T_doc) - 1, empty when start >= T_doc.  Cell 0 is bos, cells 1..n the chunk, cell n + 1 eos, the rest pad.
+ *                         start = 0 is the reference's padded / truncated row (tokenize.py:141-146); (win_doc, win_start) of
+ *                         gz_window_rows are its windows.
+ * gz_word_spans / gz_word_spans_device: where each word stands.  text / text_off [n_docs + 1] as gz_wordset_build[_device] takes
+ *   them (the device form: ABSOLUTE offsets and text_bytes = the bytes from text_off_dev[0]; text_off_dev[0] need not be 0).
+ *   unit: 0 code points (Python str indices), 1 bytes.
+ *   span [W, 2] int32     [begin, end) of the \S+ part of every word, relative to its document's start.  The glued line feed is not
+ *                         inside: the word ends with one exactly when the character at `end` is "\n".
+ *   word_off [n_docs + 1] int64: the index of every document's first word; word_off[n_docs] = W.
+ *   A code point index is the number of bytes that are not 10xxxxxx since the document's start: exact for Python strings encoded
+ *   with surrogatepass (lone surrogates and 4-byte characters included); for bytes that are not UTF-8 the byte unit is exact and the
+ *   code point unit is that count.  Nothing leaves its document.
+ *   *total_host = W on GZ_OK and on GZ_E_CAPACITY.  span == NULL sizes only (word_off and *total_host are filled).  W >
+ *   capacity_words is GZ_E_CAPACITY: word_off is valid and span is untouched.  A document of 2^31 bytes or more, or W >= 2^31,
+ *   is GZ_E_LIMIT.  For structurally valid UTF-8 word_off equals doc_first of gz_word_token_counts on the same batch.
+ * gz_align_rows / gz_align_rows_device: word ids and labels, cell by cell.
+ *   counts [W] int32, word_off [n_docs + 1] int64: exactly what gz_word_token_counts returns.  row_doc, row_start [n_rows] int32:
+ *   row_doc == NULL means row r is document r and n_rows == n_docs; row_start == NULL means every start is 0.  max_len >= 3.
+ *   word_labels [W] int32 (optional), indexed as counts.  continuation: 0 ignore, 1 same, 2 map (cont_map [n_map] int32).
+ *   word_ids, labels [n_rows, max_len] int32, n_real [n_rows] int32; each may be NULL; labels requires word_labels.
+ *     chunk cell holding body token t: word_ids = the j with C_j <= t < C_{j+1};  bos, eos, pad: word_ids = -1, labels = ignore_index
+ *     label of a chunk cell: the first piece (t == C_j) carries word_labels[j]; a later piece carries ignore_index (ignore),
+ *     word_labels[j] (same), or (map) cont_map[v] for 0 <= v < n_map, else v unchanged, with v = word_labels[j].
+ *   The rule is per token, not per row: a window that begins inside a word begins with a continuation cell.  n_real = chunk length + 2.
+ *   The host form refuses (GZ_E_INVALID, each with its own sentence): a count below 1, decreasing offsets, a row_doc outside
+ *   [0, n_docs), a negative row_start, max_len < 3, labels without word_labels, map mode without a map.  The device form takes
+ *   n_words = word_off_dev[n_docs] - word_off_dev[0] as an argument and trusts what it cannot read: counts, offsets, row_doc and
+ *   row_start are the caller's promise (offsets and documents out of range are clamped into the arrays, a negative start reads as 0).
+ * gz_span_labels / gz_span_labels_device: word labels from character annotations.
+ *   span, word_off of gz_word_spans.  marks [S, 3] int32: (begin, end, label) in the same unit, grouped by document with mark_off
+ *   [n_docs + 1] int64, in any order within a document.  scheme: 0 plain, 1 BIO.
+ *   word_labels [W] int32; mark_words [S, 2] int32: the doc-relative [first word, last word + 1) a mark overlaps, or (-1, -1).
+ *   Either may be NULL.  A mark with end <= begin overlaps nothing; otherwise it overlaps word [b, e) iff begin < e and b < end
+ *   (touching is not overlapping; a mark over whitespace only, or past the document's end, overlaps nothing).  A word's owner is
+ *   the SMALLEST MARK INDEX among the marks overlapping it.  plain: the owner's label, else `outside`.  BIO (labels >= 0): outside is
+ *   0; 2 * label + 1 when the previous word of the document has a different owner or there is none, else 2 * label + 2 -- a mark whose
+ *   first word was taken by an earlier mark still begins with a B.  The host form refuses a negative label under BIO and bad offsets;
+ *   the device form takes n_words and n_marks and trusts what it cannot read.
+ * Ordering: every pass runs on the context's stream; the calls return when their outputs are complete.
+ * Not here: sentence pairs; character spans of sub-word pieces (an unk piece has no length in the tables); a device form of
+ *   gz_word_token_counts; IOBES and other schemes; an encode call that aligns on the device in one go. */
+int  gz_word_spans(gz_ctx *ctx, const uint8_t *text, const int64_t *text_off, int64_t n_docs, int32_t unit, int32_t *span,
+                   int64_t *word_off, int64_t capacity_words, int64_t *total_host);
+int  gz_word_spans_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs, int64_t text_bytes,
+                          int32_t unit, int32_t *span_dev, int64_t *word_off_dev, int64_t capacity_words, int64_t *total_host);
+int  gz_align_rows(gz_ctx *ctx, const int32_t *counts, const int64_t *word_off, int64_t n_docs, const int32_t *row_doc,
+                   const int32_t *row_start, int64_t n_rows, int32_t max_len, const int32_t *word_labels, int32_t continuation,
+                   const int32_t *cont_map, int32_t n_map, int32_t ignore_index, int32_t *word_ids, int32_t *labels, int32_t *n_real);
+int  gz_align_rows_device(gz_ctx *ctx, const int32_t *counts_dev, const int64_t *word_off_dev, int64_t n_docs, int64_t n_words,
+                          const int32_t *row_doc_dev, const int32_t *row_start_dev, int64_t n_rows, int32_t max_len,
+                          const int32_t *word_labels_dev, int32_t continuation, const int32_t *cont_map_dev, int32_t n_map,
+                          int32_t ignore_index, int32_t *word_ids_dev, int32_t *labels_dev, int32_t *n_real_dev);
+int  gz_span_labels(gz_ctx *ctx, const int32_t *span, const int64_t *word_off, int64_t n_docs, const int32_t *marks,
+                    const int64_t *mark_off, int32_t scheme, int32_t outside, int32_t *word_labels, int32_t *mark_words);
+int  gz_span_labels_device(gz_ctx *ctx, const int32_t *span_dev, const int64_t *word_off_dev, int64_t n_docs, int64_t n_words,
+                           const int32_t *marks_dev, const int64_t *mark_off_dev, int64_t n_marks, int32_t scheme, int32_t outside,
+                           int32_t *word_labels_dev, int32_t *mark_words_dev);
+
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
  *   GZ_PP_UNICODE  convert_unicode      preprocess.py:16-36   base letter + combining tone mark -> precomposed letter
