@@ -189,6 +189,7 @@ struct gz_ctx {
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_ng_cnt, w_ng_aux;             // n-gram overlap: piece / position counts and their scans; the distinct counter, first_hit where the caller takes only first_ref
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
+    DBuf w_rp_cnt, w_rp_tab, w_rp_top;   // n-gram repeats: piece counts, their scan and the position total; the table with its counts; top cells of long rows
     DBuf w_al[16];                       // word spans, aligned rows, span labels: scans, scratch and staged inputs (gz_rows_api.inc, ALW_*)
 };
 
@@ -1075,7 +1076,7 @@ try {
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
-    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_cnt, &c->w_ng_aux}) release(*b);
+    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_cnt, &c->w_ng_aux, &c->w_rp_cnt, &c->w_rp_tab, &c->w_rp_top}) release(*b);
     for (auto& b : c->w_al) release(b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
@@ -2017,6 +2018,7 @@ try {
 
 #include "gz_rows_api.inc"
 #include "gz_ngram_api.inc"
+#include "gz_repeat_api.inc"
 
 // ---- text pre-pass ----------------------------------------------------------------------------------------------------
 namespace {

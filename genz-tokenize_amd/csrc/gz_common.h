@@ -92,6 +92,8 @@ struct GzOptions {
                                       // (probe wrap-around, the refill of a table that proved too small, many growths: results must not change)
     int32_t ngram_hash_bits = 0;      // n-gram index build (and the queries of that index): k > 0 keeps only the low k bits of every n-gram's 64-bit hash
                                       // (almost every probe collides in start slot and tag: results must not change); 0 the whole hash
+    int32_t repeat_hash_bits = 0;     // n-gram repeats: k > 0 keeps only the low k bits of every (row, n-gram) hash (the same forced collisions,
+                                      // between rows too: results must not change); 0 the whole hash
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

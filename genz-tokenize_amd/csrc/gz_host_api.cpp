@@ -48,6 +48,7 @@ int gz_option_set(GzOptions& o, const char* key, int64_t v)
         {"bm25_vocab_chunk", &GzOptions::bm25_vocab_chunk, nullptr, 1, 1 << 30},
         {"learn_table_bits", &GzOptions::learn_table_bits, nullptr, 0, 30},
         {"ngram_hash_bits", &GzOptions::ngram_hash_bits, nullptr, 0, 32},
+        {"repeat_hash_bits", &GzOptions::repeat_hash_bits, nullptr, 0, 32},
     };
     for (const Key& k : keys)
         if (std::strcmp(k.name, key) == 0) {

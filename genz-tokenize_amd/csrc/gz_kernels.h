@@ -261,6 +261,27 @@ inline uint64_t gz_ngram_slots(int64_t n_positions)                 // the small
 void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s);          // into a cleared table
 void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s);           // presets the counts when a row has more than one piece; then resolves first_ref
 
+// n-gram repetition inside a document (gz_repeat.inc); pieces of GZ_NGRAM_PIECE positions at the call's smallest width
+// Count pass: n_pieces[n_rows] at width n and their exclusive scan piece_off[n_rows + 1]; *n_pos = the n-gram positions of all rows;
+// *too_long = 1 when a body holds 2^31 ids or more (both cleared first).
+void gz_launch_repeat_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
+                            int64_t* piece_off, unsigned long long* n_pos, uint32_t* too_long, hipStream_t s);
+struct GzRepeatArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31
+    int64_t off0;                                                   // row_off[0]: a slot's position counts from here (fewer than 2^32 - 1 ids behind it)
+    int32_t skip_front, skip_back, n, k;                            // skips 0 or 1; this launch's width, 1 <= n <= 32, and its index in the caller's list
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // n_pieces == n_rows, piece p is row p
+    unsigned long long* table; uint32_t* count; uint64_t mask;      // slots - 1 (a power of two of slots, at least twice the positions at the smallest width)
+    uint64_t hmask;                                                 // hash bits kept (switch repeat_hash_bits)
+    unsigned long long* top;                                        // [n_rows] where a row has several pieces and a top output is asked for, else null
+    int32_t* n_grams; int32_t* n_distinct; int32_t* n_repeated; int32_t* n_covered; int32_t* top_count; int32_t* top_pos;   // this width's
+                                                                    // [n_rows], each may be null
+    uint16_t* covered;                                              // covered[i] belongs to ids[i]; may be null
+};
+// One width: clears the table and the counts, presets the add / max cells where a row has several pieces, inserts, queries, unpacks.
+void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s);
+
 // word spans, word ids and aligned labels (gz_align.inc)
 constexpr int64_t GZ_SPAN_BLOCK = 4096;                            // bytes of packed text per block of the span kernels
 inline int64_t gz_span_blocks(int64_t text_bytes) { return (text_bytes + GZ_SPAN_BLOCK - 1) / GZ_SPAN_BLOCK; }

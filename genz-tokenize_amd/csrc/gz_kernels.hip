@@ -716,6 +716,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_infill.inc"
 #include "gz_minhash.inc"
 #include "gz_ngram.inc"
+#include "gz_repeat.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_topk.inc"
@@ -932,6 +933,34 @@ void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s)
     }
     hipLaunchKernelGGL(gz_ngram_query_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
     if (A.first_ref) hipLaunchKernelGGL(gz_ngram_resolve_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
+}
+
+void gz_launch_repeat_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
+                            int64_t* piece_off, unsigned long long* n_pos, uint32_t* too_long, hipStream_t s)
+{
+    if (n_rows <= 0) return;
+    (void)hipMemsetAsync(n_pos, 0, 8, s);
+    (void)hipMemsetAsync(too_long, 0, 4, s);
+    hipLaunchKernelGGL(gz_repeat_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back, n,
+                       n_pieces, n_pos, too_long);
+    launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
+}
+
+void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    (void)hipMemsetAsync(A.table, 0, (size_t)(A.mask + 1) * 12, s);                  // (the counts lie behind the slots: one clear)
+    if (!A.one_each) {                                                               // the pieces of a long row meet by atomicAdd / atomicMax
+        if (A.n_distinct) (void)hipMemsetAsync(A.n_distinct, 0, (size_t)A.n_rows * 4, s);
+        if (A.n_repeated) (void)hipMemsetAsync(A.n_repeated, 0, (size_t)A.n_rows * 4, s);
+        if (A.n_covered) (void)hipMemsetAsync(A.n_covered, 0, (size_t)A.n_rows * 4, s);
+        if (A.top) (void)hipMemsetAsync(A.top, 0, (size_t)A.n_rows * 8, s);
+    }
+    const dim3 grid((unsigned)((A.n_pieces + 3) / 4)), block(WAVE * 4);
+    hipLaunchKernelGGL(gz_repeat_insert_kernel, grid, block, 0, s, A);
+    hipLaunchKernelGGL(gz_repeat_query_kernel, grid, block, 0, s, A);
+    if (A.top) hipLaunchKernelGGL(gz_repeat_top_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

@@ -112,7 +112,9 @@ __global__ __launch_bounds__(256) void gz_ngram_count_kernel(const int64_t* __re
 }
 
 // the wave's piece p: its row (the last row with piece_off[r] <= p; every row has a piece) and which of the row's pieces it is
-__device__ __forceinline__ int64_t ng_piece_row(const GzNgramArgs& A, int64_t p, int64_t* j, int64_t* n_pc)
+// (Args: GzNgramArgs, or GzRepeatArgs of gz_repeat.inc -- their one_each, n_rows and piece_off)
+template <class Args>
+__device__ __forceinline__ int64_t ng_piece_row(const Args& A, int64_t p, int64_t* j, int64_t* n_pc)
 {
     if (A.one_each) { *j = 0; *n_pc = 1; return p; }
     int64_t lo = 0, hi = p < A.n_rows - 1 ? p : A.n_rows - 1;

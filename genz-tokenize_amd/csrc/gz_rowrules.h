@@ -1,7 +1,7 @@
 // gz_rowrules.h -- the rules every row-shaping call shares, as plain host C++ (no HIP, no context: tests/test_row_rules.py compiles
 // this file alone): the check of a host CSR input, the dense-row rule, the MinHash argument rules (tests/test_minhash_surface.py
-// compiles them alone too), the n-gram overlap argument rules (tests/test_ngram_surface.py) and the pairwise-disjoint check of a
-// call's arrays.
+// compiles them alone too), the n-gram overlap argument rules (tests/test_ngram_surface.py), the n-gram repeats argument rules
+// (tests/test_repeat_surface.py) and the pairwise-disjoint check of a call's arrays.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -74,6 +74,24 @@ inline const char* ngram_overlap_fault(int64_t n_rows, int32_t skip_front, int32
 // the reference ids an index takes: a slot holds position + 1 in 32 bits, so 2^32 - 1 ids or more are refused (GZ_E_LIMIT); so is a
 // body of 2^31 ids or more (minhash_bodies_fit)
 inline bool ngram_ids_fit(int64_t n_ids) { return n_ids >= 0 && (uint64_t)n_ids < 0xFFFFFFFFull; }
+
+// n-gram repeats (gz_ngram_repeats*; tests/test_repeat_surface.py compiles this alone): the sentence of the first rule an argument
+// list breaks, or nullptr, in the order they are reported in.  The ids of a call obey ngram_ids_fit (a slot holds position + 1 in 32
+// bits) and its bodies minhash_bodies_fit.
+inline const char* repeat_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, const int32_t* widths, int32_t n_widths)
+{
+    if (n_rows < 0) return "n-gram repeats need n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "n-gram repeats need skips of 0 or 1";
+    if (n_widths < 1 || n_widths > 16) return "n-gram repeats need 1..16 widths";
+    if (!widths) return "n-gram repeats need the widths";
+    uint64_t seen = 0;                                                 // bit n: width n stands earlier in the list
+    for (int32_t k = 0; k < n_widths; ++k) {
+        if (widths[k] < 1 || widths[k] > 32) return "n-gram repeats need every width in 1..32";
+        if (seen >> widths[k] & 1u) return "n-gram repeats need distinct widths";
+        seen |= (uint64_t)1 << widths[k];
+    }
+    return nullptr;
+}
 
 // Word spans, aligned rows, span labels (gz_word_spans*, gz_align_rows*, gz_span_labels*; tests/test_align_surface.py compiles these
 // alone): the sentence of the first rule broken, or nullptr, in the order they are reported in.  The *_data_fault rules read the

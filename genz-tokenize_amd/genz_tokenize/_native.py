@@ -57,6 +57,7 @@ SYMBOLS = [
     "gz_ngram_index_build", "gz_ngram_index_build_device", "gz_ngram_index_info", "gz_ngram_index_destroy", "gz_ngram_overlap",
     "gz_ngram_overlap_device",
     "gz_word_spans", "gz_word_spans_device", "gz_align_rows", "gz_align_rows_device", "gz_span_labels", "gz_span_labels_device",
+    "gz_ngram_repeats", "gz_ngram_repeats_device",
 ]
 
 _lib = None
@@ -247,6 +248,10 @@ def load_library():
         L.gz_align_rows_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, vp, i32, vp, i32, i32, vp, vp, vp]
         L.gz_span_labels.argtypes = [vp, vp, vp, i64, vp, vp, i32, i32, vp, vp]
         L.gz_span_labels_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, i32, i32, vp, vp]
+    if hasattr(L, "gz_ngram_repeats"):
+        nr = [vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_ngram_repeats.argtypes = nr
+        L.gz_ngram_repeats_device.argtypes = nr
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -802,6 +807,31 @@ class Context:
         """gz_ngram_overlap_device: every pointer a device address (0: NULL)."""
         self._check(self.lib.gz_ngram_overlap_device(self.handle, C.c_void_p(index), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
                                                      *_dptrs(d_n_grams, d_n_hits, d_n_covered, d_first_hit, d_first_ref, d_covered)))
+
+    # ---- n-gram repetition inside a document -----------------------------------------------------------------------
+    REPEAT_OUT = ("n_grams", "n_distinct", "n_repeated", "n_covered", "top_count", "top_pos")
+
+    def ngram_repeats(self, ids: np.ndarray, row_off: np.ndarray, widths, framed: bool, with_covered: bool):
+        """ids int32 (packed rows), row_off int64 [n+1], widths a sequence of ints -> dict of the six int32 [K, n] arrays, and
+        `covered` uint16 when asked for (gz_ngram_repeats)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        out = {k: np.empty((len(w), n), dtype=np.int32) for k in self.REPEAT_OUT}
+        covered = np.zeros(len(ids), dtype=np.uint16) if with_covered else None
+        self._check(self.lib.gz_ngram_repeats(self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip, _ptr(w), len(w),
+                                              *[_ptr(v) if n else None for v in out.values()], _ptr(covered) if with_covered and len(ids) else None))
+        if with_covered:
+            out["covered"] = covered
+        return out
+
+    def ngram_repeats_device(self, d_ids, d_row_off, n_rows, skip_front, skip_back, widths, d_n_grams, d_n_distinct, d_n_repeated, d_n_covered,
+                             d_top_count, d_top_pos, d_covered):
+        """gz_ngram_repeats_device: ids, offsets and outputs device addresses (0: NULL); widths a sequence of ints on the host."""
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        self._check(self.lib.gz_ngram_repeats_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, _ptr(w), len(w),
+                                                     *_dptrs(d_n_grams, d_n_distinct, d_n_repeated, d_n_covered, d_top_count, d_top_pos, d_covered)))
 
     # ---- word spans, word ids and aligned labels ----------------------------------------------------------------
     def word_spans(self, text: np.ndarray, text_off: np.ndarray, unit: int):

@@ -1476,6 +1476,117 @@ class Tokenize(object):
         out["keep"] = covered <= f * body
         return out
 
+    # ---- n-gram repetition inside a document ("quality filtering") -----------------------------------------------------------
+    REPEAT_WIDTHS = (2, 3, 4, 5, 6, 7, 8, 9, 10)
+    REPEAT_TOP_MAX = {2: 0.20, 3: 0.18, 4: 0.16}
+    REPEAT_DUP_MAX = {5: 0.15, 6: 0.14, 7: 0.13, 8: 0.12, 9: 0.11, 10: 0.10}
+
+    @staticmethod
+    def _repeat_rule(widths=REPEAT_WIDTHS):
+        """The widths of the repetition calls as a tuple of ints, or the refusal: 1..16 distinct integers, each in 1..32."""
+        if isinstance(widths, (str, bytes)) or not hasattr(widths, "__iter__"):
+            raise TypeError("widths must be a sequence of ints")
+        w = tuple(_integer("a width", v, 1, 33) for v in widths)
+        if not 1 <= len(w) <= 16:
+            raise ValueError("widths must hold 1 to 16 entries")
+        if len(set(w)) != len(w):
+            raise ValueError("widths must be distinct")
+        return w
+
+    @staticmethod
+    def _repeat_bounds(name, bounds):
+        """{width: largest share kept} of `repetition_filter` as {int: float}, or the refusal"""
+        if not isinstance(bounds, dict):
+            raise TypeError("%s must be a dict {n: share}" % name)
+        return {_integer("a width of %s" % name, n, 1, 33): _share("a share of %s" % name, v) for n, v in bounds.items()}
+
+    @staticmethod
+    def _repeat_decide(out, top_max, dup_max):
+        """The shares and the decision of `repetition_filter` from the counts of `encode_repetition`, added to `out`."""
+        at = {n: k for k, n in enumerate(out["widths"])}
+        body = np.maximum(out["body_len"].astype(np.float64), 1.0)
+        out["top_fraction"] = {n: n * out["top_count"][at[n]].astype(np.float64) / body for n in top_max}
+        out["dup_fraction"] = {n: out["n_covered"][at[n]].astype(np.float64) / body for n in dup_max}
+        keep = np.ones(len(body), dtype=bool)
+        for n, bound in top_max.items():
+            keep &= out["top_fraction"][n] <= bound
+        for n, bound in dup_max.items():
+            keep &= out["dup_fraction"][n] <= bound
+        out["keep"] = keep
+        return out
+
+    def repetition_rows(self, rows, widths=REPEAT_WIDTHS, framed=True, return_covered=False):
+        """How much token `rows` repeat THEMSELVES, on the GPU: the counts behind the repetition rule of Gopher (Rae et al., 2021,
+        table A1).  `rows` as `ngram_overlap_rows` takes them (`framed=True`: each row loses its first and last entry first);
+        `widths`: 1..16 distinct ints in 1..32, in any order.  Per row with body q of m ids and per width n = widths[k], with c(g)
+        the number of positions whose n-gram is g (occurrences may overlap) and first(g) the smallest of them:
+        n_grams = G = max(0, m - n + 1); n_distinct = the different n-grams (G - n_distinct: the later occurrences);
+        n_repeated = the positions i with c(q[i:i+n]) >= 2, the first occurrence too; n_covered = the body tokens inside some
+        repeated n-gram, each once; top_count = max c(g) (0: no n-gram); top_pos = first(g) of the most frequent n-gram, among
+        equal counts the smallest (-1: no n-gram).  Everything is exact -- a hash decides where to look, never whether two
+        n-grams are equal, nor whether they stand in the same row.  A row's outputs depend on its own body and the widths alone,
+        never on another row: `repetition_rows(rows[a:b])` is `repetition_rows(rows)[:, a:b]`, and results of shards concatenate.
+        Rows of any integer ids are legal: the word-id sequences of `BM25(..., positions=True).term_sequences()` give Gopher's
+        word n-grams.
+        Returns a dict of numpy int32 [K, N] arrays plus body_len int32 [N] and `widths` (the tuple); with `return_covered` also
+        `covered`, uint16 over the rows back to back (bit k: the token is covered at widths[k]; 0 on the frame cells) and
+        `row_off` int64 [N+1]."""
+        w = self._repeat_rule(widths)
+        flat, off = self._ngram_rows("repetition_rows", rows)
+        out = self._ctx.ngram_repeats(flat, off, w, bool(framed), bool(return_covered))
+        skip = 2 if framed else 0
+        out["body_len"] = np.maximum(np.diff(off) - skip, 0).astype(np.int32)
+        out["widths"] = w
+        if return_covered:
+            out["row_off"] = off
+        return out
+
+    def encode_repetition(self, texts: Sequence[str], widths=REPEAT_WIDTHS, word_table=True):
+        """`repetition_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, counted there, and only the per-document arrays come back -- n_grams, n_distinct, n_repeated, n_covered,
+        top_count and top_pos, int32 [K, N], body_len int32 [N] and `widths`.  The rule is `repetition_rows`'s over the rows of
+        `encode_batch(texts, max_len=None)` without their frame; `encode_repetition(texts[a:b])` is
+        `encode_repetition(texts)[:, a:b]`, and results of shards concatenate.  Single texts only."""
+        w = self._repeat_rule(widths)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        names = _native.Context.REPEAT_OUT
+        K = len(w)
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, N, dev):
+                d_out = dev(4 * len(names) * K * max(N, 1))
+                ctx.ngram_repeats_device(d_ids, d_ro, N, 1, 1, w, *[d_out + 4 * K * N * i if N else 0 for i in range(len(names))], 0)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+                host = np.empty((len(names), K, N), dtype=np.int32)
+                row_off = np.zeros(N + 1, dtype=np.int64)
+                if N:
+                    ctx.d2h(host, d_out)
+                ctx.d2h(row_off, d_ro)
+        out = {k: host[i] for i, k in enumerate(names)}
+        out["body_len"] = np.maximum(np.diff(row_off) - 2, 0).astype(np.int32)
+        out["widths"] = w
+        return out
+
+    def repetition_filter(self, texts: Sequence[str], top_max=None, dup_max=None):
+        """`encode_repetition` plus the decision of the Gopher repetition rule.  `top_max` {n: share} bounds the share of a
+        document inside its most frequent n-gram, top_fraction[n] = n * top_count / max(body_len, 1); `dup_max` {n: share} bounds
+        the share inside n-grams that occur more than once, dup_fraction[n] = n_covered / max(body_len, 1); both float64 [N] in
+        dicts keyed by n.  keep (bool [N]): every fraction is at or under its bound; `texts[i]` for the i with keep[i] is the
+        corpus without its repetitive documents.  The defaults, top_max = {2: 0.20, 3: 0.18, 4: 0.16} and dup_max = {5: 0.15,
+        6: 0.14, 7: 0.13, 8: 0.12, 9: 0.11, 10: 0.10}, are Gopher's thresholds: they were stated for CHARACTER shares of WORD
+        n-grams and are applied here to TOKEN shares of token n-grams, so a caller tunes them (a document of fewer than n / bound
+        tokens passes a top bound only without an n-gram: filter very short documents by length).  The call runs
+        `encode_repetition` over the union of the widths; an empty dict for either is legal, both empty is refused."""
+        top = self._repeat_bounds("top_max", self.REPEAT_TOP_MAX if top_max is None else top_max)
+        dup = self._repeat_bounds("dup_max", self.REPEAT_DUP_MAX if dup_max is None else dup_max)
+        if not top and not dup:
+            raise ValueError("repetition_filter() needs a bound in top_max or dup_max")
+        out = self.encode_repetition(texts, self._repeat_rule(sorted(set(top) | set(dup))))
+        return self._repeat_decide(out, top, dup)
+
     @staticmethod
     def _shape(r, n):
         if r["dense"]:

@@ -295,6 +295,8 @@ int64_t gz_limit(int which);
  *                              too small and grows it no further than the load rule asks (0: sized from the word set)
  *   ngram_hash_bits (0..32; 0)  gz_ngram_index_build* and the queries of that index keep only the low k bits of every n-gram's hash
  *                              (0: all of it); with k = 1 almost every probe collides in start slot and tag: results must not change
+ *   repeat_hash_bits (0..32; 0)  gz_ngram_repeats* keep only the low k bits of every (row, n-gram) hash (0: all of it); with k = 1 almost
+ *                              every probe collides in start slot and tag, between rows too: results must not change
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -757,6 +759,74 @@ int  gz_span_labels(gz_ctx *ctx, const int32_t *span, const int64_t *word_off, i
 int  gz_span_labels_device(gz_ctx *ctx, const int32_t *span_dev, const int64_t *word_off_dev, int64_t n_docs, int64_t n_words,
                            const int32_t *marks_dev, const int64_t *mark_off_dev, int64_t n_marks, int32_t scheme, int32_t outside,
                            int32_t *word_labels_dev, int32_t *mark_words_dev);
+
+/* ---- repeats: n-gram repetition inside a document ("quality filtering") ---------------------------------------------------------------
+ * Beside deduplication and decontamination a pretraining recipe drops documents that repeat themselves: boiler-plate, menu spam,
+ * "aaaa aaaa aaaa" pages, degenerate generations.  The rule of Gopher (Rae et al., 2021, table A1), taken over by MassiveText,
+ * RefinedWeb and FineWeb, asks for the share of a document inside its MOST FREQUENT n-gram (n = 2..4) and inside n-grams that occur
+ * MORE THAN ONCE (n = 5..10).  One call answers both for up to 16 widths.  It compares a document with itself: gz_minhash_rows compares
+ * documents with each other, and an n-gram index is one set for all rows that does not count.  Neither form needs the tables or the
+ * decoder snapshot.
+ *   body of row r    q = ids[row_off[r] + skip_front .. row_off[r+1] - skip_back), m ids; the skips are 0 or 1 exactly as in
+ *                    gz_minhash_rows and gz_ngram_overlap; a row shorter than its skips has an empty body
+ *   widths           a list of 1..16 distinct integers, each in 1..32, in the caller's order; k indexes it
+ *   n-grams          for width n the G = max(0, m - n + 1) runs q[i:i+n].  A body shorter than n has none.  c(g) = the number of
+ *                    positions whose n-gram is g; occurrences may overlap, so [5, 5, 5] holds (5, 5) twice.  first(g) = the smallest
+ *                    such position.
+ *   per row r and width k, all int32 and laid out [K, N] (K = n_widths, N = n_rows; entry k * N + r):
+ *     n_grams[k, r]    = G
+ *     n_distinct[k, r] = the number of different n-grams.  G - n_distinct is then the number of later occurrences, which is what some
+ *                        implementations of the Gopher rule count
+ *     n_repeated[k, r] = the positions i with c(q[i:i+n]) >= 2.  The first occurrence counts too.
+ *     n_covered[k, r]  = the body tokens t with some repeated position i, i <= t < i + n.  Each token counts once.
+ *     top_count[k, r]  = max c(g), or 0 when G == 0
+ *     top_pos[k, r]    = first(g) of the n-gram with the largest count; among equal counts it is the one with the smallest first.
+ *                        -1 when G == 0
+ *   covered (optional) one uint16 per id of the input in the input's own layout: covered[i] belongs to ids[i] for i in
+ *                    [row_off[0], row_off[n_rows]).  Bit k is set when the token is covered at widths[k].  0 on frame cells.
+ *   repetition(rows[a:b]) == repetition(rows)[:, a:b]: a row's outputs depend on its own body and widths alone, never on another
+ *   row, even an identical neighbour; shards concatenate.  The outputs are a pure function of (rows, widths): not of launch geometry,
+ *   scheduling or the hash.  A hash decides where to look, never whether two n-grams are equal, nor whether they stand in the same row.
+ *   table            one table a call, allocated once and cleared per width: open addressing, linear probing, slots = the smallest
+ *                    power of two that is at least twice the call's n-gram positions at the smallest width (never more than half
+ *                    full).  A slot has two parts: 8 bytes, tag << 32 | (position + 1), position = the global index of the n-gram's
+ *                    first id in the caller's flat ids relative to row_off[0], 0 = free; and 4 bytes in a parallel array, the
+ *                    occurrence count.  The key of a slot is (row, n-gram).  Insert: 64-bit compare-and-swap on a free slot; on a
+ *                    taken slot whose tag agrees the occupant is the same key only if its position lies inside this row's n-gram
+ *                    positions AND the n ids are equal: then the slot is lowered to the smaller position by a 64-bit atomic minimum;
+ *                    otherwise the next slot.  Then the count of the slot the occurrence ended in is incremented.  A slot once taken
+ *                    holds one key for good, so every occurrence of a key ends in the same slot, whatever the order.  Query: every
+ *                    position probes and reads (first, c); the row's top is the maximum of c << 32 | (0xFFFFFFFF - first); coverage
+ *                    comes from the ballot of the repeated positions as gz_ngram_overlap derives it from its hits.  All
+ *                    order-dependent state is an integer minimum, maximum or sum.
+ *   hash             the 64-bit hash of gz_ngram_index_build over the n ids, then the row mixed in:  h64 ^= mix(r),
+ *                    mix(r): x = r + 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ *                    x ^ x >> 31 (the finalizer of splitmix64);  h64 is cut to its low repeat_hash_bits bits when that switch is set;
+ *                    tag = h64 >> 32;  start slot = h64 & (slots - 1).  Correctness does not depend on it.
+ *   memory           workspace of the context, kept between calls: 12 bytes a slot -- 24 to 48 bytes a token with one position a
+ *                    token -- plus 16 bytes a row for piece counts and their scan, plus 8 bytes a row where a body has more than
+ *                    4096 n-grams and top_count or top_pos is asked for
+ *   ids / row_off    packed int32 rows as gz_decode_batch takes them (any integers: word ids give word n-grams); widths on the HOST
+ *                    in both forms; every output pointer may be NULL.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error, before anything is launched and with the outputs untouched: n_rows < 0;
+ *   a skip outside {0, 1}; n_widths outside 1..16; NULL widths; a width outside 1..32; a repeated width; NULL ids or row_off with
+ *   n_rows > 0; bad or decreasing row offsets (the host form); output arrays that overlap the input or each other.
+ *   GZ_E_LIMIT and nothing written: a body of 2^31 ids or more, or 2^32 - 1 ids or more in the call (a slot holds position + 1 in 32
+ *   bits: shard the rows).  n_rows == 0 is GZ_OK and touches nothing.
+ * gz_ngram_repeats: host pointers; the rows go up through the library's pinned staging and the outputs come back.
+ * gz_ngram_repeats_device: ids, row_off and the outputs DEVICE pointers; offsets are ABSOLUTE from the base pointer and row_off_dev[0]
+ *   need not be 0.  Ordering: every pass runs on the context's stream, behind a gz_encode_batch_device (ragged layout) enqueued just
+ *   before with no gz_sync in between; the call returns when its outputs are complete.
+ * Not here: character weighting of the shares, line and paragraph duplicates and the other Gopher heuristics (word lengths, symbol
+ *   ratios, stop words), which work on text; a table in LDS for short rows; removing the repeated spans (the caller reads covered);
+ *   repetition across documents (gz_minhash_rows, gz_ngram_index_build); multi-GPU forms (shards concatenate). */
+int  gz_ngram_repeats(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                      const int32_t *widths, int32_t n_widths, int32_t *n_grams, int32_t *n_distinct, int32_t *n_repeated,
+                      int32_t *n_covered, int32_t *top_count, int32_t *top_pos, uint16_t *covered);
+int  gz_ngram_repeats_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, int32_t skip_front,
+                             int32_t skip_back, const int32_t *widths, int32_t n_widths, int32_t *n_grams_dev, int32_t *n_distinct_dev,
+                             int32_t *n_repeated_dev, int32_t *n_covered_dev, int32_t *top_count_dev, int32_t *top_pos_dev,
+                             uint16_t *covered_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
