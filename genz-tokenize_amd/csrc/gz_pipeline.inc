@@ -188,9 +188,10 @@ __global__ void gz_brk_kernel(const int64_t* off, int64_t n_docs, uint32_t* brk3
 // -----------------------------------------------------------------------------------------------------------------
 // Two forms per tile, chosen by the wave (both exact for structurally valid UTF-8):
 //   fast     the tile holds no control character other than the space, no byte that could lead a multi-byte whitespace
-//            character (C2, E2 and above; 9A, the second byte of U+1680) and nothing carried in from the tile before: then the
-//            whitespace of the tile is exactly its bytes below 0x21, a word starts at every other byte that follows one (or a
-//            document start) -- a third of the instructions of the general form, and what running text takes nearly always;
+//            character (C2, E2 and above; 9A, the second byte of U+1680, also as the first byte BEHIND a tile that ends in E1)
+//            and nothing carried in from the tile before: then the whitespace of the tile is exactly its bytes below 0x21, a
+//            word starts at every other byte that follows one (or a document start) -- a third of the instructions of the
+//            general form, and what running text takes nearly always;
 //   general  classify_stream(): every Unicode whitespace code point, "\n" and friends included.
 __global__ __launch_bounds__(WAVE * PWPB) void gz_classify_kernel(GzTextBufs X)
 {
@@ -212,7 +213,8 @@ __global__ __launch_bounds__(WAVE * PWPB) void gz_classify_kernel(GzTextBufs X)
     }
     int count = 0;
     // one tile: its 16 bytes per lane (w) and its document-start bits (brk16) -> start / end bits, the running word count
-    auto tile = [&](int t, const uint32_t (&w)[4], uint32_t brk16) {
+    // (nx0: the first byte behind the tile, wave-uniform; a space behind the text)
+    auto tile = [&](int t, const uint32_t (&w)[4], uint32_t brk16, uint32_t nx0) {
         const int64_t pos = p0 + (int64_t)t * TILE;
         // bytes below 0x21 (ASCII), and what would send the tile to the general form
         uint32_t lt[4], odd = 0;
@@ -225,6 +227,9 @@ __global__ __launch_bounds__(WAVE * PWPB) void gz_classify_kernel(GzTextBufs X)
                  | (x & (x7o - 0x62626262u) & H)                                  // a byte >= 0xE2
                  | ((tc - 0x01010101u) & ~tc & H) | ((t9 - 0x01010101u) & ~t9 & H);
         }
+        // E1 in the tile's last byte with 9A behind it (U+1680 = E1 9A 80 cut 1|2 by the tile edge): the 9A is the next tile's, so
+        // nothing above sees it -- and the general form must run HERE, for the end bit at the E1 and the carry into the next tile
+        if (lane == WAVE - 1 && (w[3] >> 24) == 0xE1u && nx0 == 0x9Au) odd |= H;
         uint32_t st16, en16;
         uint32_t has_nl = 0;                               // (wave-uniform) the tile may hold a line feed: only the general form can see one
         if (carry == 0 && wballot(odd != 0) == 0) {
@@ -259,15 +264,17 @@ __global__ __launch_bounds__(WAVE * PWPB) void gz_classify_kernel(GzTextBufs X)
             w[t][0] = v.x; w[t][1] = v.y; w[t][2] = v.z; w[t][3] = v.w;
             brk16[t] = X.brk[((p0 + t * TILE) >> 4) + lane];
         }
+        const uint32_t nxb = tb[p0 + PBLK];                   // (inside the text: p0 + PBLK + 16 <= B)
 #pragma unroll
-        for (int t = 0; t < PBLK / TILE; ++t) tile(t, w[t], brk16[t]);
+        for (int t = 0; t < PBLK / TILE; ++t)
+            tile(t, w[t], brk16[t], t + 1 < PBLK / TILE ? (uint32_t)__builtin_amdgcn_readfirstlane((int)w[t + 1 < PBLK / TILE ? t + 1 : t][0]) & 0xFFu : nxb);
     } else {
         for (int t = 0; t < PBLK / TILE; ++t) {
             const int64_t pos = p0 + (int64_t)t * TILE;
             if (pos > B) break;                               // position B itself can still hold a word end
             uint32_t w[4];
             load16(tb, pos + 16 * lane, B, w);
-            tile(t, w, X.brk[(pos >> 4) + lane]);
+            tile(t, w, X.brk[(pos >> 4) + lane], pos + TILE < B ? (uint32_t)tb[pos + TILE] : 0x20u);
         }
     }
     if (lane == 0) X.blkcnt[blk] = (uint32_t)count;
