@@ -191,6 +191,7 @@ struct gz_ctx {
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_rp_cnt, w_rp_tab, w_rp_top;   // n-gram repeats: piece counts, their scan and the position total; the table with its counts; top cells of long rows
     DBuf w_al[16];                       // word spans, aligned rows, span labels: scans, scratch and staged inputs (gz_rows_api.inc, ALW_*)
+    DBuf w_pw_cnt, w_pw_tok;             // pair windows: window counts and q of every pair; span tokens: the counts as 64-bit words and their scan
 };
 
 namespace {
@@ -1078,6 +1079,7 @@ try {
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
     for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_cnt, &c->w_ng_aux, &c->w_rp_cnt, &c->w_rp_tab, &c->w_rp_top}) release(*b);
     for (auto& b : c->w_al) release(b);
+    for (DBuf* b : {&c->w_pw_cnt, &c->w_pw_tok}) release(*b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     for (DBuf* b : {&c->t_pair8, &c->t_pair_disp, &c->t_words0p, &c->t_word0_disp, &c->t_pair_hot, &c->t_word_hot}) release(*b);

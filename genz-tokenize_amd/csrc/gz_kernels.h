@@ -138,6 +138,32 @@ void gz_launch_window_count(const int64_t* row_off, int64_t n_rows, int32_t room
                             hipStream_t s);
 void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s);
 
+// question-context windows with answer positions (gz_pairwin.inc).  Count pass: n_win[n_rows], pair_q[n_rows] and the exclusive scan
+// win_off[n_rows + 1].  Fill pass: the n_win = win_off[n_rows] window rows; every output but out_ids may be null.
+struct GzPairWinArgs {
+    const int32_t* q_ids; const int64_t* q_off; int64_t n_q;        // question row i = q_ids[q_off[i] .. q_off[i + 1]) (absolute offsets)
+    const int32_t* c_ids; const int64_t* c_off; int64_t n_rows;     // context row r likewise: pair r
+    const int32_t* q_row;                                           // [n_rows] the question of pair r; null: question r
+    const int32_t* ans;                                             // [n_rows, 2] body positions [a0, a1); may be null
+    const int64_t* win_off; int64_t n_win;
+    int32_t* pair_q;                                                // [n_rows] q of every pair: written by the count pass, read by the fill pass
+    int32_t max_len, stride, max_q, skip_front, skip_back;
+    int32_t bos_id, eos_id, pad_id;
+    int32_t* out_ids; int32_t* out_mask; int32_t* out_type;         // [n_win, max_len]
+    int32_t* win_pair; int32_t* win_start; int32_t* win_n_real; int32_t* win_q_len;      // [n_win]
+    int32_t* start_pos; int32_t* end_pos; int32_t* has_answer;      // [n_win]; written where ans is given
+};
+void gz_launch_pairwin_count(const GzPairWinArgs& A, int64_t* n_win, int64_t* win_off, hipStream_t s);
+void gz_launch_pairwin_fill(const GzPairWinArgs& A, hipStream_t s);
+// word ranges -> body-token ranges (gz_pairwin.inc): cnt64 [n_words + 1] and tok_off [n_words + 2] are scratch
+struct GzSpanTokArgs {
+    const int64_t* word_off; int64_t n_docs, n_words;               // absolute; n_words = word_off[n_docs] - word_off[0]
+    const int32_t* mark_words; const int64_t* mark_off; int64_t n_marks;      // mark_words [n_marks, 2] from 0; mark_off absolute
+    const int64_t* tok_off;                                         // [n_words + 1] exclusive scan of the counts, from 0
+    int32_t* out;                                                   // [n_marks, 2] from 0
+};
+void gz_launch_span_tokens(GzSpanTokArgs A, const int32_t* counts, int64_t* cnt64, int64_t* tok_off, hipStream_t s);
+
 // short documents packed into rows of max_len (gz_packrows.inc).  Maps: doc_len, seg_off (its scan), the row heads row by row
 // (pack_off[0 .. R], R -> *total), doc_row, doc_col.  Fill: the R rows; out_mask, out_seg, out_pos may be null.
 constexpr int GZ_PACK_TILE = 1024;      // documents per tile of the break chain

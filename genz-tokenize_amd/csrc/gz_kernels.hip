@@ -711,6 +711,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_small.inc"
 #include "gz_decode.inc"
 #include "gz_window.inc"
+#include "gz_pairwin.inc"
 #include "gz_packrows.inc"
 #include "gz_mask.inc"
 #include "gz_infill.inc"
@@ -787,6 +788,33 @@ void gz_launch_window_fill(const GzWinArgs& A, hipStream_t s)
     const bool wide = A.max_len % 4 == 0 && ((reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask)) & 15) == 0;
     if (wide) hipLaunchKernelGGL(gz_window_fill_kernel<4>, grid, block, 0, s, A);
     else hipLaunchKernelGGL(gz_window_fill_kernel<1>, grid, block, 0, s, A);
+}
+
+void gz_launch_pairwin_count(const GzPairWinArgs& A, int64_t* n_win, int64_t* win_off, hipStream_t s)
+{
+    if (A.n_rows <= 0) return;
+    hipLaunchKernelGGL(gz_pairwin_count_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A, n_win);
+    launch_scan64((const int64_t*)n_win, A.n_rows, win_off, s);
+}
+
+void gz_launch_pairwin_fill(const GzPairWinArgs& A, hipStream_t s)
+{
+    if (A.n_win <= 0) return;
+    const dim3 grid((unsigned)((A.n_win + 4 * WAVE - 1) / (4 * WAVE))), block(WAVE * 4);
+    // 16 bytes a lane where every row starts on a 16-byte boundary; one cell a lane otherwise
+    const bool wide = A.max_len % 4 == 0 &&
+                      ((reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask) | reinterpret_cast<uintptr_t>(A.out_type)) & 15) == 0;
+    if (wide) hipLaunchKernelGGL(gz_pairwin_fill_kernel<4>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(gz_pairwin_fill_kernel<1>, grid, block, 0, s, A);
+}
+
+void gz_launch_span_tokens(GzSpanTokArgs A, const int32_t* counts, int64_t* cnt64, int64_t* tok_off, hipStream_t s)
+{
+    if (A.n_marks <= 0 || A.n_docs <= 0) return;
+    if (A.n_words > 0) hipLaunchKernelGGL(gz_spantok_widen_kernel, dim3((unsigned)((A.n_words + 255) / 256)), dim3(256), 0, s, counts, A.word_off, A.n_words, cnt64);
+    launch_scan64((const int64_t*)cnt64, A.n_words, tok_off, s);
+    A.tok_off = tok_off;
+    hipLaunchKernelGGL(gz_spantok_kernel, dim3((unsigned)((A.n_marks + 255) / 256)), dim3(256), 0, s, A);
 }
 
 void gz_launch_pack_maps(const GzPackArgs& A, bool with_col, hipStream_t s)

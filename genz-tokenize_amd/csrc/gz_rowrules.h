@@ -1,7 +1,8 @@
 // gz_rowrules.h -- the rules every row-shaping call shares, as plain host C++ (no HIP, no context: tests/test_row_rules.py compiles
 // this file alone): the check of a host CSR input, the dense-row rule, the MinHash argument rules (tests/test_minhash_surface.py
 // compiles them alone too), the n-gram overlap argument rules (tests/test_ngram_surface.py), the n-gram repeats argument rules
-// (tests/test_repeat_surface.py) and the pairwise-disjoint check of a call's arrays.
+// (tests/test_repeat_surface.py), the question-context window rules (tests/test_pairwin_surface.py) and the pairwise-disjoint check of a
+// call's arrays.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -137,6 +138,42 @@ inline const char* span_labels_data_fault(const int32_t* marks, int64_t n_marks,
     for (int64_t m = 0; m < n_marks; ++m) {
         if (marks[3 * m + 2] < 0) return "span labels under BIO need labels >= 0";
         if (marks[3 * m + 2] >= (1 << 30) - 1) return "span labels under BIO need labels below 2^30 - 1";
+    }
+    return nullptr;
+}
+
+// Question-context windows and span tokens (gz_pair_window_rows*, gz_span_tokens*; tests/test_pairwin_surface.py compiles these alone):
+// the sentence of the first rule broken, or nullptr, in the order they are reported in.  With L = max_len the call is valid iff
+// L >= 5, 0 <= max_query_len <= L - 5 and 0 <= stride <= L - 5 - max_query_len (room = L - 4 - q >= stride + 1 for every q <=
+// max_query_len: every window adds a token).  pairwin_data_fault reads the caller's q_row, so only the host form can apply it; the
+// device form reads an entry outside [0, n_questions) as an empty question.
+inline const char* pairwin_fault(int64_t n_rows, int64_t n_questions, bool have_q_row, int32_t max_len, int32_t stride, int32_t max_query_len,
+                                 int32_t skip_front, int32_t skip_back, int64_t capacity_windows)
+{
+    if (n_rows < 0 || n_questions < 0) return "pair windows need n_rows >= 0 and n_questions >= 0";
+    if (capacity_windows < 0) return "pair windows need capacity_windows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "pair windows need skips of 0 or 1";
+    if (max_len < 5) return "pair windows need max_len >= 5";
+    if (max_query_len < 0 || max_query_len > max_len - 5) return "pair windows need max_query_len in [0, max_len - 5]";
+    if (stride < 0 || stride > max_len - 5 - max_query_len) return "pair windows need a stride in [0, max_len - 5 - max_query_len]";
+    if (!have_q_row && n_questions != n_rows) return "pair windows without q_row need n_questions == n_rows";
+    return nullptr;
+}
+inline const char* pairwin_data_fault(const int32_t* q_row, int64_t n_rows, int64_t n_questions)
+{
+    if (q_row) for (int64_t r = 0; r < n_rows; ++r) if (q_row[r] < 0 || (int64_t)q_row[r] >= n_questions) return "pair windows: a q_row lies outside [0, n_questions)";
+    return nullptr;
+}
+inline const char* span_tokens_fault(int64_t n_docs) { return n_docs < 0 ? "span tokens need n_docs >= 0" : nullptr; }
+// counts: the n counts of the batch; mark_words: the n_marks (first, last + 1) pairs of the batch; W_d of a mark is only known with
+// its document, so the ranges are checked against the whole batch here and clamped into their document on the device
+inline const char* span_tokens_data_fault(const int32_t* counts, int64_t n, const int32_t* mark_words, int64_t n_marks)
+{
+    for (int64_t i = 0; i < n; ++i) if (counts[i] < 1) return "span tokens: a word's piece count is below 1";
+    for (int64_t m = 0; m < n_marks; ++m) {
+        const int32_t f = mark_words[2 * m], l = mark_words[2 * m + 1];
+        if (f == -1 && l == -1) continue;
+        if (f < 0 || l < f || (int64_t)l > n) return "span tokens: a word range is neither (-1, -1) nor 0 <= first <= last + 1 <= words";
     }
     return nullptr;
 }

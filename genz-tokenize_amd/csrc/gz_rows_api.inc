@@ -67,7 +67,7 @@ int read_total(gz_ctx* c, const int64_t* src, int64_t* zero, int64_t* total)
 // ones on the caller's thread, then the check for a failed launch.
 struct StagedOut {
     struct Entry { void* host; size_t bytes; bool large; void* dev; };
-    Entry e[8];
+    Entry e[12];
     int n = 0;
     void add(void* host, size_t bytes, bool large) { e[n++] = Entry{host, bytes, large, nullptr}; }
     int32_t* dev(int k) const { return (int32_t*)e[k].dev; }
@@ -969,5 +969,173 @@ try {
     GzSpanLabArgs A{(const int32_t*)in.d_payload, in.d_off, n_docs, in.n, marks_dev ? marks_dev - 3 * mark_off[0] : nullptr, moff_dev, mk.n, scheme, outside,
                     S.dev(0) ? (uint32_t*)c->w_al[ALW_OWNER].p : nullptr, S.dev(0) ? S.dev(0) - word_off[0] : nullptr, S.dev(1)};
     gz_launch_span_labels(A, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+// ---- question-context windows with answer positions (gz_pairwin.inc) --------------------------------------------------------------
+namespace {
+constexpr RowsWords kQuestionWords{"bad question offsets", "question offsets must not decrease"};
+struct PairWinOut {
+    int32_t* ids; int32_t* mask; int32_t* type; int32_t* pair; int32_t* start; int32_t* n_real; int32_t* q_len;
+    int32_t* start_pos; int32_t* end_pos; int32_t* has_answer;
+};
+
+// the geometry of a call and its inputs, every pointer a device pointer; bos / eos / pad are the context's current special ids
+GzPairWinArgs pairwin_args(gz_ctx* c, const int32_t* q_ids, const int64_t* q_off, int64_t n_q, const int32_t* c_ids, const int64_t* c_off, int64_t n_rows,
+                           const int32_t* q_row, const int32_t* ans, int32_t max_len, int32_t stride, int32_t max_q, int32_t skip_front, int32_t skip_back)
+{
+    GzPairWinArgs A{};
+    A.q_ids = q_ids; A.q_off = q_off; A.n_q = n_q; A.c_ids = c_ids; A.c_off = c_off; A.n_rows = n_rows; A.q_row = q_row; A.ans = ans;
+    A.max_len = max_len; A.stride = stride; A.max_q = max_q; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id; A.pad_id = c->dev.pad_id;
+    return A;
+}
+
+void pairwin_fill(gz_ctx* c, GzPairWinArgs A, const int64_t* win_off_dev, int64_t n_win, const PairWinOut& O)
+{
+    A.win_off = win_off_dev; A.n_win = n_win;
+    A.out_ids = O.ids; A.out_mask = O.mask; A.out_type = O.type;
+    A.win_pair = O.pair; A.win_start = O.start; A.win_n_real = O.n_real; A.win_q_len = O.q_len;
+    A.start_pos = O.start_pos; A.end_pos = O.end_pos; A.has_answer = O.has_answer;
+    gz_launch_pairwin_fill(A, c->stream);
+}
+
+// Both passes on the context's stream, behind whatever it holds.  *total = windows of the batch.  O.ids == nullptr: the count pass
+// only.  A.pair_q is set here (the context's scratch: it lives from the count pass to the fill pass of the same call).
+int pairwin_device_locked(gz_ctx* c, GzPairWinArgs& A, const PairWinOut& O, int64_t* win_off_dev, int64_t capacity, int64_t* total)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    const size_t cnt_bytes = (size_t)(A.n_rows + 2) * 8;
+    if ((rc = ensure(c, c->w_pw_cnt, cnt_bytes + (size_t)(A.n_rows + 1) * 4))) return rc;
+    A.pair_q = (int32_t*)((uint8_t*)c->w_pw_cnt.p + cnt_bytes);
+    gz_launch_pairwin_count(A, (int64_t*)c->w_pw_cnt.p, win_off_dev, c->stream);
+    if ((rc = read_total(c, A.n_rows > 0 ? win_off_dev + A.n_rows : nullptr, win_off_dev, total))) return rc;
+    if (!O.ids) return GZ_OK;
+    if (*total > capacity) return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)*total, (long long)capacity);
+    pairwin_fill(c, A, win_off_dev, *total, O);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_pair_window_rows_device(gz_ctx* c, const int32_t* q_ids_dev, const int64_t* q_off_dev, int64_t n_questions, const int32_t* ids_dev,
+                               const int64_t* row_off_dev, int64_t n_rows, const int32_t* q_row_dev, const int32_t* ans_dev, int32_t max_len, int32_t stride,
+                               int32_t max_query_len, int32_t skip_front, int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev,
+                               int32_t* token_type_ids_dev, int32_t* win_pair_dev, int32_t* win_start_dev, int32_t* win_n_real_dev, int32_t* win_q_len_dev,
+                               int32_t* start_pos_dev, int32_t* end_pos_dev, int32_t* has_answer_dev, int64_t* win_off_dev, int64_t capacity_windows,
+                               int64_t* total_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = pairwin_fault(n_rows, n_questions, q_row_dev != nullptr, max_len, stride, max_query_len, skip_front, skip_back, capacity_windows))
+        return fail(c, GZ_E_INVALID, "%s", why);
+    if (!row_off_dev || !win_off_dev || !total_host || (n_questions > 0 && !q_off_dev)) return fail(c, GZ_E_INVALID, "bad arguments");
+    std::lock_guard<std::mutex> lk(c->mu);
+    GzPairWinArgs A = pairwin_args(c, q_ids_dev, q_off_dev, q_off_dev ? n_questions : 0, ids_dev, row_off_dev, n_rows, q_row_dev, ans_dev, max_len, stride,
+                                   max_query_len, skip_front, skip_back);
+    const PairWinOut O{input_ids_dev, attention_mask_dev, token_type_ids_dev, win_pair_dev, win_start_dev, win_n_real_dev, win_q_len_dev,
+                       start_pos_dev, end_pos_dev, has_answer_dev};
+    return pairwin_device_locked(c, A, O, win_off_dev, capacity_windows, total_host);
+} GZ_CATCH(c)
+
+int gz_pair_window_rows(gz_ctx* c, const int32_t* q_ids, const int64_t* q_off, int64_t n_questions, const int32_t* ids, const int64_t* row_off,
+                        int64_t n_rows, const int32_t* q_row, const int32_t* ans, int32_t max_len, int32_t stride, int32_t max_query_len,
+                        int32_t skip_front, int32_t skip_back, int32_t* input_ids, int32_t* attention_mask, int32_t* token_type_ids, int32_t* win_pair,
+                        int32_t* win_start, int32_t* win_n_real, int32_t* win_q_len, int32_t* start_pos, int32_t* end_pos, int32_t* has_answer,
+                        int64_t* win_off, int64_t capacity_windows, int64_t* total_host)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = pairwin_fault(n_rows, n_questions, q_row != nullptr, max_len, stride, max_query_len, skip_front, skip_back, capacity_windows))
+        return fail(c, GZ_E_INVALID, "%s", why);
+    if (!row_off || !win_off || !total_host || !q_off) return fail(c, GZ_E_INVALID, "bad arguments");
+    RowsIn in{ids, row_off, n_rows, 4}, qs{q_ids, q_off, n_questions, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords)) || (rc = rows_check(c, qs, kQuestionWords))) return rc;
+    if (const char* why = pairwin_data_fault(q_row, n_rows, n_questions)) return fail(c, GZ_E_INVALID, "%s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;                  // kept through both passes: win_off
+    const int32_t *q_ids_dev = nullptr, *q_row_dev = nullptr, *ans_dev = nullptr;
+    const int64_t* q_off_dev = nullptr;
+    if ((rc = align_stage(c, ALW_IN0, qs.n ? q_ids + q_off[0] : nullptr, (size_t)qs.n * 4, &q_ids_dev)) ||
+        (rc = align_stage64(c, ALW_IN1, q_off, (size_t)(n_questions + 1) * 8, &q_off_dev)) ||
+        (rc = align_stage(c, ALW_IN2, n_rows ? q_row : nullptr, (size_t)n_rows * 4, &q_row_dev)) ||
+        (rc = align_stage(c, ALW_IN3, n_rows ? ans : nullptr, (size_t)n_rows * 8, &ans_dev))) return rc;
+    GzPairWinArgs A = pairwin_args(c, q_ids_dev ? q_ids_dev - q_off[0] : nullptr, q_off_dev, n_questions, (const int32_t*)in.d_payload, in.d_off, n_rows,
+                                   q_row_dev, ans_dev, max_len, stride, max_query_len, skip_front, skip_back);       // (biased: indexed as the caller's array)
+    int64_t* const woff = (int64_t*)in.d_keep;
+    int64_t total = 0;
+    if ((rc = pairwin_device_locked(c, A, PairWinOut{}, woff, 0, &total))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, win_off, woff, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_windows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld windows, capacity is %lld", (long long)total, (long long)capacity_windows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len * 4, per_win = (size_t)total * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(attention_mask, cells, true); S.add(token_type_ids, cells, true);
+    S.add(win_pair, per_win, false); S.add(win_start, per_win, false); S.add(win_n_real, per_win, false); S.add(win_q_len, per_win, false);
+    S.add(ans ? start_pos : nullptr, per_win, false); S.add(ans ? end_pos : nullptr, per_win, false); S.add(ans ? has_answer : nullptr, per_win, false);
+    if ((rc = staged_ensure(c, S))) return rc;
+    pairwin_fill(c, A, woff, total, PairWinOut{S.dev(0), S.dev(1), S.dev(2), S.dev(3), S.dev(4), S.dev(5), S.dev(6), S.dev(7), S.dev(8), S.dev(9)});
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
+namespace {
+// the scan and the one launch on the context's stream; every pointer a device pointer
+int span_tokens_launch_locked(gz_ctx* c, GzSpanTokArgs A, const int32_t* counts_dev)
+{
+    int rc;
+    if ((rc = ensure(c, c->w_pw_tok, (size_t)(2 * A.n_words + 4) * 8))) return rc;
+    int64_t* const cnt64 = (int64_t*)c->w_pw_tok.p;
+    gz_launch_span_tokens(A, counts_dev, cnt64, cnt64 + A.n_words + 1, c->stream);
+    return GZ_OK;
+}
+}  // namespace
+
+int gz_span_tokens_device(gz_ctx* c, const int32_t* counts_dev, const int64_t* word_off_dev, int64_t n_docs, int64_t n_words, const int32_t* mark_words_dev,
+                          const int64_t* mark_off_dev, int64_t n_marks, int32_t* span_tokens_dev)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = span_tokens_fault(n_docs)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off_dev || !mark_off_dev || n_words < 0 || n_marks < 0 || (n_words > 0 && !counts_dev) || (n_marks > 0 && (!mark_words_dev || !span_tokens_dev)))
+        return fail(c, GZ_E_INVALID, "bad arguments");
+    if (n_words >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_docs == 0 || n_marks == 0) return GZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = span_tokens_launch_locked(c, GzSpanTokArgs{word_off_dev, n_docs, n_words, mark_words_dev, mark_off_dev, n_marks, nullptr, span_tokens_dev}, counts_dev)))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_span_tokens(gz_ctx* c, const int32_t* counts, const int64_t* word_off, int64_t n_docs, const int32_t* mark_words, const int64_t* mark_off,
+                   int32_t* span_tokens)
+try {
+    if (!c) return GZ_E_INVALID;
+    if (const char* why = span_tokens_fault(n_docs)) return fail(c, GZ_E_INVALID, "%s", why);
+    if (!word_off || !mark_off) return fail(c, GZ_E_INVALID, "bad arguments");
+    RowsIn in{counts, word_off, n_docs, 4}, mk{mark_words, mark_off, n_docs, 8};
+    int rc;
+    if ((rc = rows_check(c, in, kWordWords)) || (rc = rows_check(c, mk, kMarkWords))) return rc;
+    if (in.n >= ((int64_t)1 << 31)) return fail(c, GZ_E_LIMIT, "%s", kSpanWordLimit);
+    if (mk.n > 0 && !span_tokens) return fail(c, GZ_E_INVALID, "bad arguments");
+    if (const char* why = span_tokens_data_fault(in.n ? counts + word_off[0] : nullptr, in.n, mk.n ? mark_words : nullptr, mk.n)) return fail(c, GZ_E_INVALID, "%s", why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (n_docs == 0 || mk.n == 0) return GZ_OK;
+    if ((rc = rows_stage(c, in, 0))) return rc;
+    const int32_t* mw_dev = nullptr;
+    const int64_t* moff_dev = nullptr;
+    if ((rc = align_stage(c, ALW_IN0, mark_words, (size_t)mk.n * 8, &mw_dev)) || (rc = align_stage64(c, ALW_IN1, mark_off, (size_t)(n_docs + 1) * 8, &moff_dev)))
+        return rc;
+    StagedOut S;
+    S.add(span_tokens, (size_t)mk.n * 8, true);
+    if ((rc = staged_ensure(c, S))) return rc;
+    if ((rc = span_tokens_launch_locked(c, GzSpanTokArgs{in.d_off, n_docs, in.n, mw_dev, moff_dev, mk.n, nullptr, S.dev(0)}, (const int32_t*)in.d_payload))) return rc;
     return staged_copy_out(c, S);
 } GZ_CATCH(c)

@@ -58,6 +58,7 @@ SYMBOLS = [
     "gz_ngram_overlap_device",
     "gz_word_spans", "gz_word_spans_device", "gz_align_rows", "gz_align_rows_device", "gz_span_labels", "gz_span_labels_device",
     "gz_ngram_repeats", "gz_ngram_repeats_device",
+    "gz_pair_window_rows", "gz_pair_window_rows_device", "gz_span_tokens", "gz_span_tokens_device",
 ]
 
 _lib = None
@@ -252,6 +253,12 @@ def load_library():
         nr = [vp, vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.gz_ngram_repeats.argtypes = nr
         L.gz_ngram_repeats_device.argtypes = nr
+    if hasattr(L, "gz_pair_window_rows"):
+        pw = [vp, vp, vp, i64, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)]
+        L.gz_pair_window_rows.argtypes = pw
+        L.gz_pair_window_rows_device.argtypes = pw
+        L.gz_span_tokens.argtypes = [vp, vp, vp, i64, vp, vp, vp]
+        L.gz_span_tokens_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -652,6 +659,61 @@ class Context:
         return self._call_total(self.lib.gz_window_rows_device, self.handle, *_dptrs(d_ids), C.c_void_p(d_row_off), n_rows, max_len, stride,
                                 skip_front, skip_back, *_dptrs(d_input_ids, d_mask, d_doc, d_start, d_n_real),
                                 C.c_void_p(d_win_off), capacity)
+
+    # ---- question-context windows with answer positions -----------------------------------------------------
+    PAIRWIN_CELLS = ("input_ids", "attention_mask", "token_type_ids")
+    PAIRWIN_META = ("pair", "start", "n_real", "q_len")
+    PAIRWIN_ANSWER = ("start_positions", "end_positions", "has_answer")
+
+    def pair_window_rows(self, q_ids, q_off, ids, row_off, max_len: int, stride: int, max_query_len: int, q_row, answers, framed: bool):
+        """question rows and context rows (packed int32 + int64 offsets), q_row int32 [n] or None, answers int32 [n, 2] or None ->
+        dict(input_ids, attention_mask, token_type_ids [W, L], pair, start, n_real, q_len [W], win_off int64 [n+1] and, with answers,
+        start_positions, end_positions, has_answer [W]) (gz_pair_window_rows: a sizing call, then the windows)."""
+        q_ids = np.ascontiguousarray(q_ids, dtype=np.int32)
+        q_off = np.ascontiguousarray(q_off, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        q_row = None if q_row is None else np.ascontiguousarray(q_row, dtype=np.int32)
+        answers = None if answers is None else np.ascontiguousarray(answers, dtype=np.int32)
+        n, L, skip = len(row_off) - 1, int(max_len), 1 if framed else 0
+        win_off = np.zeros(n + 1, dtype=np.int64)
+        total = C.c_int64()
+        head = (self.handle, _ptr(q_ids) if len(q_ids) else None, _ptr(q_off), len(q_off) - 1, _ptr(ids) if len(ids) else None, _ptr(row_off), n,
+                _ptr(q_row), _ptr(answers), L, int(stride), int(max_query_len), skip, skip)
+        self._check(self.lib.gz_pair_window_rows(*head, *([None] * 10), _ptr(win_off), 0, C.byref(total)))
+        W = total.value
+        out = {k: np.empty((W, L), dtype=np.int32) for k in self.PAIRWIN_CELLS}
+        out.update({k: np.empty(W, dtype=np.int32) for k in self.PAIRWIN_META + (self.PAIRWIN_ANSWER if answers is not None else ())})
+        out["win_off"] = win_off
+        if W:
+            self._check(self.lib.gz_pair_window_rows(*head, *[_ptr(out.get(k)) for k in self.PAIRWIN_CELLS + self.PAIRWIN_META + self.PAIRWIN_ANSWER],
+                                                     _ptr(win_off), W, C.byref(total)))
+        return out
+
+    def pair_window_rows_device(self, d_q_ids, d_q_off, n_questions, d_ids, d_row_off, n_rows, d_q_row, d_answers, max_len, stride, max_query_len,
+                                skip_front, skip_back, d_input_ids, d_mask, d_type, d_pair, d_start, d_n_real, d_q_len, d_start_pos, d_end_pos,
+                                d_has_answer, d_win_off, capacity) -> int:
+        """gz_pair_window_rows_device: returns W.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = W."""
+        return self._call_total(self.lib.gz_pair_window_rows_device, self.handle, *_dptrs(d_q_ids, d_q_off), n_questions, *_dptrs(d_ids),
+                                C.c_void_p(d_row_off), n_rows, *_dptrs(d_q_row, d_answers), max_len, stride, max_query_len, skip_front, skip_back,
+                                *_dptrs(d_input_ids, d_mask, d_type, d_pair, d_start, d_n_real, d_q_len, d_start_pos, d_end_pos, d_has_answer),
+                                C.c_void_p(d_win_off), capacity)
+
+    def span_tokens(self, counts, word_off, mark_words, mark_off):
+        """counts int32 [W], word_off int64 [n+1], mark_words int32 [S, 2], mark_off int64 [n+1] -> span_tokens int32 [S, 2] (gz_span_tokens)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        mark_words = np.ascontiguousarray(mark_words, dtype=np.int32)
+        mark_off = np.ascontiguousarray(mark_off, dtype=np.int64)
+        out = np.empty((len(mark_words), 2), dtype=np.int32)
+        self._check(self.lib.gz_span_tokens(self.handle, _ptr(counts) if len(counts) else None, _ptr(word_off), len(word_off) - 1,
+                                            _ptr(mark_words) if len(mark_words) else None, _ptr(mark_off), _ptr(out) if len(out) else None))
+        return out
+
+    def span_tokens_device(self, d_counts, d_word_off, n_docs, n_words, d_mark_words, d_mark_off, n_marks, d_span_tokens):
+        """gz_span_tokens_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_span_tokens_device(self.handle, *_dptrs(d_counts), C.c_void_p(d_word_off), n_docs, n_words, *_dptrs(d_mark_words),
+                                                   C.c_void_p(d_mark_off), n_marks, *_dptrs(d_span_tokens)))
 
     # ---- short documents packed into rows of max_len ------------------------------------------------------
     def pack_rows(self, ids: np.ndarray, row_off: np.ndarray, max_len: int, framed: bool):

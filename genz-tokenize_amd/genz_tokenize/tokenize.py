@@ -940,6 +940,239 @@ class Tokenize(object):
                 out["word_labels"] = word_labels
             return out
 
+    # ---- pair windows: question-context windows with answer positions (extractive QA, reranking) --------------------------
+    @staticmethod
+    def _pair_window_rule(max_len, stride, max_query_len=None):
+        """(L, s, mq) of a pair window call, or the refusal: L >= 5 (bos, eos, eos, a context token, eos), 0 <= mq <= L - 5 and
+        0 <= s <= L - 5 - mq (room = L - 4 - q > s for every q <= mq: every window adds a token).  max_query_len None:
+        min(64, L - 5 - s)."""
+        for name, v in (("max_len", max_len), ("stride", stride)) + ((("max_query_len", max_query_len),) if max_query_len is not None else ()):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an int" % name)
+        L, s = int(max_len), int(stride)
+        if L < 5 or L >= 2 ** 31:
+            raise ValueError("pair windows need 5 <= max_len < 2**31 (bos, eos, eos, at least one context token, eos)")
+        if s < 0:
+            raise ValueError("stride must not be negative")
+        mq = min(64, L - 5 - s) if max_query_len is None else int(max_query_len)
+        if max_query_len is None and mq < 0:
+            raise ValueError("stride must lie in [0, max_len - 5]: it leaves no room for a context token")
+        if not 0 <= mq <= L - 5:
+            raise ValueError("max_query_len must lie in [0, max_len - 5]")
+        if s > L - 5 - mq:
+            raise ValueError("stride must lie in [0, max_len - 5 - max_query_len]: every window adds at least one new token")
+        return L, s, mq
+
+    @staticmethod
+    def _pair_q_row(call, q_row, n, nq):
+        """q_row as int32 [n] inside [0, nq), or None where pair r uses question r (then nq == n)"""
+        if q_row is None:
+            if nq != n:
+                raise ValueError("%s() without q_row expects one question per context: %d questions, %d contexts" % (call, nq, n))
+            return None
+        q_row = _int32_ids(call, q_row)
+        if q_row.ndim != 1 or len(q_row) != n:
+            raise ValueError("%s() expects q_row as a 1-D array of %d entries, one per context" % (call, n))
+        if n and (int(q_row.min()) < 0 or int(q_row.max()) >= nq):
+            raise ValueError("%s() expects q_row inside [0, %d)" % (call, nq))
+        return np.ascontiguousarray(q_row)
+
+    @staticmethod
+    def _pair_answers(call, answers, n):
+        """answers as int32 [n, 2] (an entry that is None, or a pair with a -1, reads as no answer: (-1, -1)), or None"""
+        if answers is None:
+            return None
+        if not isinstance(answers, np.ndarray):
+            answers = list(answers)
+            if len(answers) != n:
+                raise ValueError("%s() expects one answer per context: %d contexts, %d answers" % (call, n, len(answers)))
+            rows = []
+            for a in answers:
+                if a is None:
+                    rows.append((-1, -1))
+                    continue
+                if len(a) != 2:
+                    raise ValueError("%s() expects answers of (begin, end), or None" % call)
+                rows.append(tuple(_integer("an answer's " + k, v, -(2 ** 31), 2 ** 31) for k, v in zip(("begin", "end"), a)))
+            answers = np.asarray(rows, dtype=np.int32).reshape(n, 2)
+        answers = _int32_ids(call, answers)
+        if answers.shape != (n, 2):
+            raise ValueError("%s() expects answers as an [N, 2] array of (begin, end), one row per context" % call)
+        return np.ascontiguousarray(answers)
+
+    def pair_window_rows(self, question_rows, context_rows, max_len: int, stride: int = 0, max_query_len: Optional[int] = None, q_row=None,
+                         answers=None, framed: bool = True):
+        """Question-context rows over whole contexts, on the GPU: the question stands in front of EVERY window of its context.
+        Both row sets as `decode_batch` takes them; `framed=True`: encode results that lose their first and last entry first.
+        Pair r is (question q_row[r], context r); q_row None: question r.  With q = min(len(question), max_query_len) (the question
+        keeps its first q tokens; max_query_len None: min(64, max_len - 5 - stride)), room = max_len - 4 - q and step = room -
+        stride, window j of a context body is [bos] + question[:q] + [eos, eos] + body[j*step : j*step + room] + [eos], padded to
+        max_len; the last window is shorter, not shifted back.  A pair that fits makes one window, the reference's own pair row
+        (`encode_batch(questions, pair_texts=contexts, max_len=max_len)`).  answers [N, 2]: the [a0, a1) body positions of each
+        context's answer, anything else (such as (-1, -1)) for none.
+        Returns numpy arrays: input_ids, attention_mask (ids != pad), token_type_ids (0 up to the first separator, 1 from the second
+        to the last eos, the pad id behind) [W, L]; pair, start, n_real, q_len [W]; win_off [N+1] (pair r's windows are
+        win_off[r]:win_off[r+1]); and, with answers, start_positions, end_positions, has_answer [W]: the columns of the answer's first
+        and last token in a window that holds the whole answer, else 0, 0 (the bos column) and has_answer 0."""
+        L, s, mq = self._pair_window_rule(max_len, stride, max_query_len)
+        qf, qo = self._flat_rows(question_rows)
+        cf, co = self._flat_rows(context_rows)
+        qf, cf = _int32_ids("pair_window_rows", qf), _int32_ids("pair_window_rows", cf)
+        n = len(co) - 1
+        q_row = self._pair_q_row("pair_window_rows", q_row, n, len(qo) - 1)
+        answers = self._pair_answers("pair_window_rows", answers, n)
+        self._sync_tables()
+        return self._ctx.pair_window_rows(qf, qo, cf, co, L, s, mq, q_row, answers, bool(framed))
+
+    def span_tokens(self, word_tokens, word_off, mark_words, mark_off):
+        """The word ranges `span_labels` returns as body-token ranges, on the GPU.  word_tokens [W] / word_off [N+1]: the per-word
+        piece counts of an encode call; mark_words [S, 2] / mark_off [N+1]: per mark the [first, last + 1) words of its document, or
+        (-1, -1).  Returns int32 [S, 2]: [first token of the first word, last token of the last word + 1) among the body tokens of
+        the mark's document; (-1, -1) stays (-1, -1)."""
+        counts = self._align_vector("span_tokens", "word_tokens", word_tokens)
+        word_off = self._align_offsets("span_tokens", "word_off", word_off, len(counts))
+        if len(counts) and int(counts.min()) < 1:
+            raise ValueError("span_tokens() expects piece counts of at least 1")
+        mark_words = _int32_ids("span_tokens", mark_words)
+        if mark_words.ndim != 2 or mark_words.shape[1] != 2:
+            raise ValueError("span_tokens() expects mark_words as an [S, 2] array")
+        mark_off = self._align_offsets("span_tokens", "mark_off", mark_off, len(mark_words))
+        if len(mark_off) != len(word_off):
+            raise ValueError("span_tokens() expects mark_off and word_off over the same documents")
+        if len(mark_words):
+            doc = np.searchsorted(mark_off, np.arange(len(mark_words)), side="right") - 1
+            words = np.diff(word_off)[doc]
+            f, e = mark_words[:, 0].astype(np.int64), mark_words[:, 1].astype(np.int64)
+            if not bool(np.all(((f == -1) & (e == -1)) | ((0 <= f) & (f <= e) & (e <= words)))):
+                raise ValueError("span_tokens() expects word ranges that are (-1, -1) or 0 <= first <= last + 1 <= the document's words")
+        return self._ctx.span_tokens(counts, word_off, np.ascontiguousarray(mark_words), mark_off)
+
+    def encode_pair_windows(self, questions: Sequence[str], contexts: Sequence[str], max_len: int, stride: int = 0,
+                            max_query_len: Optional[int] = None, q_row=None, answers=None, unit: str = "char", word_table: bool = True):
+        """`pair_window_rows` over texts, with answers given as character spans: questions and contexts are encoded without a length
+        limit, and every answer goes from characters to words (`word_spans`, `span_labels`: an answer owns the words it overlaps,
+        so positions are word-granular), from words to body tokens (`span_tokens`) and from there into the columns of every window
+        that holds it.  answers: one (begin, end) span of its context per context in `unit`s ("char": str indices, "byte"), or None
+        for none, or an [N, 2] array with -1 for none.  Returns the dict of `pair_window_rows` and word_off [N+1], word_span [W, 2],
+        word_tokens [W] of the contexts and, with answers, answer_tokens [N, 2] (the body positions, -1 for none);
+        `pair_window_spans` maps predicted columns back to characters."""
+        return self._encode_pair_windows(questions, contexts, max_len, stride, max_query_len, q_row, answers, unit, word_table, False)
+
+    def encode_pair_windows_to_device(self, questions: Sequence[str], contexts: Sequence[str], max_len: int, stride: int = 0,
+                                      max_query_len: Optional[int] = None, q_row=None, answers=None, unit: str = "char", word_table: bool = True):
+        """`encode_pair_windows` whose [W, max_len] input_ids / attention_mask / token_type_ids STAY in HBM as `handoff.DeviceArray`s
+        (`torch.from_dlpack(x)` is zero-copy, as with `encode_windows_to_device`); every other entry is a host array."""
+        return self._encode_pair_windows(questions, contexts, max_len, stride, max_query_len, q_row, answers, unit, word_table, True)
+
+    def _encode_pair_windows(self, questions, contexts, max_len, stride, max_query_len, q_row, answers, unit, word_table, to_device):
+        L, s, mq = self._pair_window_rule(max_len, stride, max_query_len)
+        u = self._align_choice("unit", unit, self.ALIGN_UNITS)
+        questions, contexts = list(questions), list(contexts)
+        for t in questions + contexts:
+            _require_str(t)
+        n, nq = len(contexts), len(questions)
+        q_row = self._pair_q_row("encode_pair_windows", q_row, n, nq)
+        answers = self._pair_answers("encode_pair_windows", answers, n)
+        self._sync_tables()
+        with self._batch_lock:
+            flags = 0 if word_table else _native.GZ_NO_WORD_TABLE
+            qb, qo = _pack(questions)
+            rq = self._ctx.encode(qb, qo, None, None, None, False, False, flags)
+            tb, to = _pack(contexts)
+            rc = self._ctx.encode(tb, to, None, None, None, False, False, flags | _native.GZ_KEEP_WORDS)
+            if n:
+                counts, word_off = self._ctx.word_token_counts(0, n, 1 << 16)
+            else:
+                counts, word_off = np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64)
+            counts = np.ascontiguousarray(counts)
+            span, span_off = self._ctx.word_spans(tb, to, u)
+            if not np.array_equal(span_off, word_off):
+                raise RuntimeError("encode_pair_windows(): the word spans and the piece counts disagree on the words of the batch")
+            answer_tokens = None
+            if answers is not None:
+                gone = (answers < 0).any(axis=1)
+                marks = np.zeros((n, 3), dtype=np.int32)
+                marks[:, :2] = np.where(gone[:, None], 0, answers)                # (a mark with end <= begin overlaps nothing)
+                mark_off = np.arange(n + 1, dtype=np.int64)
+                _, mark_words = self._ctx.span_labels(span, word_off, marks, mark_off, 0, 0)
+                answer_tokens = self._ctx.span_tokens(counts, word_off, mark_words, mark_off)
+            args = (rq["input_ids"], rq["row_off"], rc["input_ids"], rc["row_off"], L, s, mq, q_row, answer_tokens)
+            out = self._pair_windows_to_device_locked(*args) if to_device else self._ctx.pair_window_rows(*args, True)
+            out["word_off"], out["word_span"], out["word_tokens"] = word_off, span, counts
+            if answer_tokens is not None:
+                out["answer_tokens"] = answer_tokens
+            return out
+
+    def _pair_windows_to_device_locked(self, q_ids, q_off, ids, row_off, L, s, mq, q_row, answers):
+        from .handoff import DeviceArray
+        ctx = self._ctx
+        n, nq = len(row_off) - 1, len(q_off) - 1
+        bufs = []
+
+        def up(a, dtype):
+            if a is None:
+                return 0
+            a = np.ascontiguousarray(a, dtype=dtype)
+            d = ctx.alloc(max(a.nbytes, 1) + 64)
+            bufs.append(d)
+            if a.nbytes:
+                ctx.h2d(d, a)
+            return d
+        try:
+            d_q, d_qo, d_c, d_co = up(q_ids, np.int32), up(q_off, np.int64), up(ids, np.int32), up(row_off, np.int64)
+            d_qr, d_ans = up(q_row, np.int32), up(answers, np.int32)
+            d_wo = up(np.zeros(n + 1, dtype=np.int64), np.int64)
+            head = (d_q, d_qo, nq, d_c, d_co, n, d_qr, d_ans, L, s, mq, 1, 1)
+            W = ctx.pair_window_rows_device(*head, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, d_wo, 0)
+            names = _native.Context.PAIRWIN_META + (_native.Context.PAIRWIN_ANSWER if answers is not None else ())
+            out = {k: DeviceArray(ctx, ctx.alloc(4 * max(W * L, 1)), (W, L)) for k in _native.Context.PAIRWIN_CELLS}
+            d_meta = up(np.zeros((7, max(W, 1)), dtype=np.int32), np.int32)
+            meta_ptrs = [d_meta + 4 * W * k if k < len(names) else 0 for k in range(7)]
+            ctx.pair_window_rows_device(*head, out["input_ids"].ptr, out["attention_mask"].ptr, out["token_type_ids"].ptr, *meta_ptrs, d_wo, W)
+            meta = np.empty((7, W), dtype=np.int32)
+            win_off = np.zeros(n + 1, dtype=np.int64)
+            if W:
+                ctx.d2h(meta, d_meta)
+            ctx.d2h(win_off, d_wo)
+            for k, name in enumerate(names):
+                out[name] = meta[k]
+            out["win_off"] = win_off
+            return out
+        finally:
+            for d in bufs:
+                ctx.free(d)
+
+    @staticmethod
+    def pair_window_spans(result, start_cols, end_cols):
+        """Predicted columns back to characters (host numpy): for every window w of an `encode_pair_windows` result the (begin, end)
+        span of its context, in the result's unit, that runs from the begin of the word of column start_cols[w]'s token to the end of
+        the word of column end_cols[w]'s token.  Returns int32 [W, 2]; a column outside the window's chunk, or end < start, gives
+        (-1, -1).  Fed `start_positions` / `end_positions` of windows with `has_answer`, it returns the span of the words the answer
+        overlaps."""
+        pair, start = np.asarray(result["pair"], dtype=np.int64), np.asarray(result["start"], dtype=np.int64)
+        n_real, q_len = np.asarray(result["n_real"], dtype=np.int64), np.asarray(result["q_len"], dtype=np.int64)
+        word_off, span = np.asarray(result["word_off"], dtype=np.int64), np.asarray(result["word_span"])
+        counts = np.asarray(result["word_tokens"], dtype=np.int64)
+        sc, ec = np.asarray(start_cols, dtype=np.int64).reshape(-1), np.asarray(end_cols, dtype=np.int64).reshape(-1)
+        W = len(pair)
+        if len(sc) != W or len(ec) != W:
+            raise ValueError("pair_window_spans() expects one start column and one end column per window: %d windows" % W)
+        out = np.full((W, 2), -1, dtype=np.int32)
+        if not W:
+            return out
+        ends = np.cumsum(counts)                                           # tokens of the batch up to and including word j
+        doc_tok0 = np.concatenate(([0], ends))[word_off[:-1]]              # tokens of the batch before a document's first word
+        ctx_col, n = q_len + 3, n_real - q_len - 4
+        ok = (sc >= ctx_col) & (ec < ctx_col + n) & (sc <= ec)
+        t0 = doc_tok0[pair] + start + sc - ctx_col                         # batch-wide token positions
+        t1 = doc_tok0[pair] + start + ec - ctx_col
+        w0 = np.searchsorted(ends, np.where(ok, t0, 0), side="right")
+        w1 = np.searchsorted(ends, np.where(ok, t1, 0), side="right")
+        ok &= (w1 < len(counts)) if len(counts) else False
+        out[ok, 0] = span[w0[ok], 0]
+        out[ok, 1] = span[w1[ok], 1]
+        return out
+
     # ---- short documents packed into rows of max_len ("sequence packing") -------------------------------------------
     PACK_CELLS = ("input_ids", "attention_mask", "segment_ids", "position_ids")
     PACK_MAPS = ("doc_row", "doc_col", "doc_len")

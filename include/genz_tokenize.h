@@ -760,6 +760,86 @@ int  gz_span_labels_device(gz_ctx *ctx, const int32_t *span_dev, const int64_t *
                            const int32_t *marks_dev, const int64_t *mark_off_dev, int64_t n_marks, int32_t scheme, int32_t outside,
                            int32_t *word_labels_dev, int32_t *mark_words_dev);
 
+/* ---- pair windows: question-context windows with answer positions ("extractive question answering", "reranking") ----------------
+ * The reference's pair row is <s> question </s></s> context </s> cut at max_len (tokenize.py:141-146): an answer behind the cut is
+ * lost.  gz_window_rows keeps a long document whole but puts no question in front and makes no type ids.  These calls repeat the
+ * question in front of EVERY window of its context, say which cells are question and which context, and carry an answer's body
+ * positions into row columns -- the (start, end) target of an extractive QA model.  One question may serve many contexts (a
+ * query and its k retrieved documents for a cross-encoder).
+ * Inputs: question rows and context rows, both packed int32 rows as gz_window_rows takes them, with ONE skip_front / skip_back pair
+ *   (each 0 or 1) applied to both; an optional q_row [N]: pair r uses question row q_row[r]; NULL means pair r uses question r, and
+ *   then NQ == N.  L = max_len, s = stride, mq = max_query_len.
+ *   The call is valid iff L >= 5, 0 <= mq <= L - 5 and 0 <= s <= L - 5 - mq.  Otherwise it returns GZ_E_INVALID and writes nothing.
+ * For pair r, let Q be the question body of Tq tokens and body the context body of T tokens.  A row shorter than its skips has an
+ * empty body.
+ *     q      = min(Tq, mq)                    (the question keeps its FIRST q tokens)
+ *     room   = L - 4 - q   (>= s + 1)         step = room - s  (>= 1)
+ *     n_win  = 1 if T <= room else 1 + ceil((T - room) / step)
+ *     window j: start = j * step, chunk = body[start : min(start + room, T)], n = len(chunk)
+ *     row    = [bos] + Q[:q] + [eos, eos] + chunk + [eos] + [pad] * (room - n)      n_real = q + 4 + n
+ *     mask   = (row != pad)                                    (tokenize.py:148-152, as everywhere)
+ *     type   = 0 on columns < q + 2, 1 on columns q + 2 .. n_real - 1, the pad id behind them
+ *     ctx_col = q + 3                                          (column of chunk[0])
+ *   The last window is shorter, not shifted back.  bos / eos / pad are the context's current special ids.
+ * Answers are optional: ans [N, 2] int32, holding the [a0, a1) body positions of the context.
+ *   An answer is present iff 0 <= a0 < a1 <= T.  Anything else means "no answer"; no input is invalid on the device.
+ *   Window j holds the answer iff start <= a0 and a1 <= start + n.
+ *   If it does, start_pos = ctx_col + a0 - start, end_pos = ctx_col + a1 - 1 - start and has_answer = 1.
+ *   Otherwise start_pos = end_pos = 0 (the bos column, the SQuAD convention) and has_answer = 0.
+ *   Without ans, all three outputs may be NULL (they are not written then).
+ * Laws:
+ *   1. Equality with the reference.  A pair with T >= 1, Tq <= mq and q + 4 + T <= L has one window, and its row and mask are those of
+ *      the reference __call__(question, context, max_len=L), which is what gz_encode_batch with pair texts returns.  If n_real < L the
+ *      type row is the reference's token_type_ids too.  If n_real == L the reference puts the eos id into the last cell (its
+ *      token-type pass overruns); here that cell is 1 and every other cell agrees: the ONE deviation.  T == 0 (the reference leaves
+ *      None cells) is outside the law.
+ *   2. Chunks rejoin.  chunk_0 ++ chunk_1[s:] ++ ... is the context body.  Every later window adds at least one token.
+ *   3. Question placement.  Columns 1 .. q of every window of pair r are Q[:q].
+ *   4. Answers.  An answer with a1 - a0 <= s + 1 is held by at least one window.  An answer longer than room is held by none.  Where
+ *      one is held, row[start_pos : end_pos + 1] == body[a0:a1].
+ * gz_pair_window_rows / gz_pair_window_rows_device, with the window calls' conventions:
+ *   q_ids / q_off [NQ + 1], ids / row_off [N + 1]   packed rows, ABSOLUTE offsets from their base pointers (off[0] need not be 0)
+ *   input_ids, attention_mask, token_type_ids   [W, max_len] int32
+ *   win_pair, win_start, win_n_real, win_q_len, start_pos, end_pos, has_answer   [W] int32: the pair, `start`, n_real, q and the answer
+ *   win_off [N + 1]        int64: pair r's windows are win_off[r] .. win_off[r+1]; win_off[N] = W
+ *   *total_host = W on GZ_OK and on GZ_E_CAPACITY.  input_ids == NULL sizes only (win_off and *total_host are filled).  When
+ *   W > capacity_windows the call returns GZ_E_CAPACITY: win_off is valid and nothing is written to the other outputs.  Each
+ *   secondary output (everything but input_ids and win_off) may be NULL.  n_rows == 0 is GZ_OK and launches nothing.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched or written: a negative n_rows,
+ *   n_questions or capacity_windows; a skip outside {0, 1}; max_len < 5; max_query_len outside [0, max_len - 5]; stride outside
+ *   [0, max_len - 5 - max_query_len]; q_row NULL with n_questions != n_rows.  GZ_E_NOTABLES without tables.
+ *   The device form: every pointer but total_host is a DEVICE pointer.  It cannot read q_row beforehand: an entry outside [0, NQ) is an
+ *   EMPTY question (q = 0), and no address is formed from it.  The host form refuses such an entry, and bad or decreasing offsets of
+ *   either row set (GZ_E_INVALID); rows go up through the library's pinned staging, only win_off and the windows come back.
+ *   Ordering: both passes run on the context's stream, as gz_window_rows_device -- rows of a gz_encode_batch_device enqueued just
+ *   before on the same context are complete when they are read here.  The call returns when the windows are complete.
+ * gz_span_tokens / gz_span_tokens_device: the word ranges gz_span_labels returns as body-token ranges.
+ *   counts [W] int32, word_off [n_docs + 1] int64 of gz_word_token_counts; mark_words [S, 2] int32 from 0 and mark_off [n_docs + 1]
+ *   int64 of gz_span_labels.  span_tokens [S, 2] int32: for a mark with the word range [f, e) of its document, with C the exclusive
+ *   scan of that document's counts (C[W_d] = T_d), (C[f], C[e]) = [first token of the first word, last token of the last word + 1)
+ *   in body positions; a (-1, -1) range stays (-1, -1).  The host form refuses a count below 1, a range that is neither (-1, -1) nor ordered inside the batch's words, and bad
+ *   offsets; the device form takes n_words and n_marks, trusts what it cannot read and clamps a range into its document's words.
+ * Not here: several answers per pair; answers finer than words (an unk piece has no length in the tables); truncating the question
+ *   from the left, "longest first" truncation; windows aligned to word boundaries; the reference's overrun and None quirks beyond law
+ *   1; pair forms of packs, masks, infill and dropout; 16-bit outputs; multi-GPU forms (shards concatenate). */
+int  gz_pair_window_rows(gz_ctx *ctx, const int32_t *q_ids, const int64_t *q_off, int64_t n_questions, const int32_t *ids,
+                         const int64_t *row_off, int64_t n_rows, const int32_t *q_row, const int32_t *ans, int32_t max_len,
+                         int32_t stride, int32_t max_query_len, int32_t skip_front, int32_t skip_back, int32_t *input_ids,
+                         int32_t *attention_mask, int32_t *token_type_ids, int32_t *win_pair, int32_t *win_start,
+                         int32_t *win_n_real, int32_t *win_q_len, int32_t *start_pos, int32_t *end_pos, int32_t *has_answer,
+                         int64_t *win_off, int64_t capacity_windows, int64_t *total_host);
+int  gz_pair_window_rows_device(gz_ctx *ctx, const int32_t *q_ids_dev, const int64_t *q_off_dev, int64_t n_questions,
+                                const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, const int32_t *q_row_dev,
+                                const int32_t *ans_dev, int32_t max_len, int32_t stride, int32_t max_query_len, int32_t skip_front,
+                                int32_t skip_back, int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *token_type_ids_dev,
+                                int32_t *win_pair_dev, int32_t *win_start_dev, int32_t *win_n_real_dev, int32_t *win_q_len_dev,
+                                int32_t *start_pos_dev, int32_t *end_pos_dev, int32_t *has_answer_dev, int64_t *win_off_dev,
+                                int64_t capacity_windows, int64_t *total_host);
+int  gz_span_tokens(gz_ctx *ctx, const int32_t *counts, const int64_t *word_off, int64_t n_docs, const int32_t *mark_words,
+                    const int64_t *mark_off, int32_t *span_tokens);
+int  gz_span_tokens_device(gz_ctx *ctx, const int32_t *counts_dev, const int64_t *word_off_dev, int64_t n_docs, int64_t n_words,
+                           const int32_t *mark_words_dev, const int64_t *mark_off_dev, int64_t n_marks, int32_t *span_tokens_dev);
+
 /* ---- repeats: n-gram repetition inside a document ("quality filtering") ---------------------------------------------------------------
  * Beside deduplication and decontamination a pretraining recipe drops documents that repeat themselves: boiler-plate, menu spam,
  * "aaaa aaaa aaaa" pages, degenerate generations.  The rule of Gopher (Rae et al., 2021, table A1), taken over by MassiveText,
