@@ -63,6 +63,23 @@ bool rccl_load()
            g_rccl.GroupStart && g_rccl.GroupEnd;
 }
 
+// The context's pinned block: the few words a call copies back from the device and then waits for.  A field a user: no two share a
+// byte, so a value can only be overwritten by the next use of its own field.  Every copy into it is enqueued under c->mu.
+struct GzPinned {
+    int64_t picks[2 * (GZ_MAX_SUB_BATCHES + 1)];   // the sub-batch cuts.  c->stream; enqueue waits for the stream right behind the copy
+    uint32_t emit_total[4];                        // entries of the last four emitted blocks.  The encode call's stream, in front of ev_blk[slot];
+                                                   // gz_block_total waits for that event
+    uint32_t compact_total;                        // entries of a compact call.  c->xstream; compact_impl waits for the stream
+    int32_t expand_bad;                            // "a block did not fit".  c->xstream, behind every expansion; sync_locked waits, reads and clears it
+    int64_t read_total;                            // the one scalar of a two-pass call.  c->stream; read_total waits for the stream
+    uint32_t prepass[5];                           // the fused pre-pass: 4 control words and the total.  c->stream; the pre-pass waits for the stream
+    uint32_t span_long;                            // "a document is too long" of the span count.  c->stream; span_count_locked waits (in read_total)
+    int64_t extent[2];                             // row_off[0] and row_off[n_rows] of a device CSR input.  c->stream; rows_extent_device waits
+    int64_t n_pieces;                              // piece_off[n_rows] of a piece count.  c->stream; pieces_count_locked waits for the stream
+    GzPieceTotals pieces;                          // ... its position total and "a body is too long".  The same copy train, the same wait
+    uint8_t small_out[64];                         // copy_out_small.  The stream the caller names; copy_out_small waits for it
+};
+
 }  // namespace
 
 struct gz_ctx {
@@ -139,7 +156,7 @@ struct gz_ctx {
     hipStream_t xstream = nullptr;
     hipEvent_t ev_tok[4] = {nullptr, nullptr, nullptr, nullptr};   // end of the last four encode calls
     // exchange block made by the encode call itself (gz_encode_emit_block arms the next call): the block of the last four calls --
-    // its number of entries goes through w_flags[8 + slot] into h_pick's tail (uint32 56 + slot) before ev_blk[slot]
+    // its number of entries goes through w_flags[8 + slot] into pin->emit_total[slot] before ev_blk[slot]
     int32_t* emit_block = nullptr; int32_t emit_bits = 0;
     hipEvent_t ev_blk[4] = {nullptr, nullptr, nullptr, nullptr};
     bool blk_valid[4] = {false, false, false, false};
@@ -152,7 +169,7 @@ struct gz_ctx {
     int x_back = 0;                                                  // exchange ops depend on encode call (last - x_back)
     bool x_used = false;
     DBuf w_pick, w_rowoff32;
-    int64_t* h_pick = nullptr;           // pinned
+    GzPinned* pin = nullptr;             // pinned: the small values the host waits for, a field a user
     int64_t n_words = 0;
     // decoder snapshot + decode workspace
     bool have_dec = false;
@@ -164,7 +181,8 @@ struct gz_ctx {
     DBuf t_dec_entries, t_dec_bytes, w_dec_rb;
     DBuf w_win_cnt;                                                                                     // overlapping windows (gz_window_rows*)
     DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol;              // packed rows (gz_pack_rows*)
-    DBuf w_mh_cnt, w_mh_off, w_mh_keys, w_mh_reps, w_mh_aux;                                            // MinHash: piece counts and offsets; the band table, EMPTY bytes + counter (gz_minhash_*)
+    DBuf w_pieces;                                                                                      // piece counts, their scan, the position total and the too-long flag of MinHash, n-gram overlap and repeats (gz_rows_api.inc: pieces_count_locked)
+    DBuf w_mh_keys, w_mh_reps, w_mh_aux;                                                                // MinHash groups: the band table, EMPTY bytes + counter (gz_minhash_groups*)
     DBuf w_rows_in, w_rows_off, w_rows_out[4], w_rows_small;      // staging of the host forms of the row calls and the pre-pass (gz_rows_api.inc: WORKSPACE)
     DBuf w_pp[2], w_ppoff[2], w_pplen, w_ppaux, w_ppctl, w_pplen32, w_pplb;                             // text pre-pass
     DBuf w_tiny[8][2];                                                     // texts of fewer than 16 bytes, see encode_device_locked
@@ -187,9 +205,9 @@ struct gz_ctx {
     int n_fresh = 0;                     // diagnostic build: running number of this context's device allocations (switch diag_fresh_only)
     DBuf w_bm[72];                       // BM25: workspace of an index build, the query arrays of a lookup / scoring / top-k call (gz_bm25.inc)
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
-    DBuf w_ng_cnt, w_ng_aux;             // n-gram overlap: piece / position counts and their scans; the distinct counter, first_hit where the caller takes only first_ref
+    DBuf w_ng_aux;                       // n-gram overlap: the distinct counter, first_hit where the caller takes only first_ref
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
-    DBuf w_rp_cnt, w_rp_tab, w_rp_top;   // n-gram repeats: piece counts, their scan and the position total; the table with its counts; top cells of long rows
+    DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
     DBuf w_al[16];                       // word spans, aligned rows, span labels: scans, scratch and staged inputs (gz_rows_api.inc, ALW_*)
     DBuf w_pw_cnt, w_pw_tok;             // pair windows: window counts and q of every pair; span tokens: the counts as 64-bit words and their scan
 };
@@ -441,7 +459,7 @@ int enqueue(gz_ctx* c)
             gz_launch_compact(p.emit_rows, off, p.emit_n, p.emit_len, p.emit_block + 2 * p.emit_n, p.emit_bits, (uint32_t*)(p.emit_block + p.emit_n), s);
             HIPCHK(c, hipMemcpyAsync(cur, off + p.emit_n, 4, hipMemcpyDeviceToDevice, s));
         }
-        HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint32_t*>(c->h_pick) + 56 + p.emit_slot, cur, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&c->pin->emit_total[p.emit_slot], cur, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(c->ev_blk[p.emit_slot], s));
         c->blk_valid[p.emit_slot] = true;
     } else c->blk_valid[c->enc_seq & 3] = false;
@@ -490,7 +508,7 @@ int sync_locked(gz_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->x_used) {
         HIPCHK(c, hipStreamSynchronize(c->xstream));
-        int32_t* const bad = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 384);
+        int32_t* const bad = &c->pin->expand_bad;
         if (*bad) {
             *bad = 0;
             HIPCHK(c, hipMemset((int32_t*)c->w_flags.p + 12, 0, 4));
@@ -664,7 +682,7 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
     // (measured on cfg 3: 2 sub-batches on two streams gain 1.5 %, 4 gain nothing, 8 lose 10 % -- the kernels of one
     // sub-batch already fill the chip -- so the default is one batch; the option sub_batches is kept for experiments)
     int nsub = (dense && n_docs >= 8 * (int64_t)c->opt.sub_batches) ? c->opt.sub_batches : 1;
-    int64_t cutA[9], cutB[9];
+    int64_t cutA[GZ_MAX_SUB_BATCHES + 1], cutB[GZ_MAX_SUB_BATCHES + 1];
     if (h_text_off) {
         for (int k = 0; k <= nsub; ++k) {
             const int64_t d = (int64_t)k * n_docs / nsub;
@@ -674,9 +692,9 @@ int encode_device_locked(gz_ctx* c, const uint8_t* text, const int64_t* text_off
     } else {
         if ((rc = ensure(c, c->w_pick, 256))) return rc;
         gz_launch_pick(text_off, pair_off, n_docs, nsub, (int64_t*)c->w_pick.p, c->stream);
-        HIPCHK(c, hipMemcpyAsync(c->h_pick, c->w_pick.p, (size_t)(2 * nsub + 2) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->pin->picks, c->w_pick.p, (size_t)(2 * nsub + 2) * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k <= nsub; ++k) { cutA[k] = c->h_pick[k]; cutB[k] = c->h_pick[nsub + 1 + k]; }
+        for (int k = 0; k <= nsub; ++k) { cutA[k] = c->pin->picks[k]; cutB[k] = c->pin->picks[nsub + 1 + k]; }
     }
     const int64_t text_bytes = cutA[nsub] - cutA[0], pair_bytes = is_pair ? cutB[nsub] - cutB[0] : 0;
     if (text_bytes < 0 || pair_bytes < 0) return fail(c, GZ_E_INVALID, "offsets are not non-decreasing");
@@ -1024,8 +1042,8 @@ try {
     for (auto& e : c->ev_tok) hipEventCreateWithFlags(&e, hipEventDisableTiming);
     hipEventCreateWithFlags(&c->ev_x, hipEventDisableTiming);
     phase("streams and events");
-    if (hipHostMalloc((void**)&c->h_pick, 512, hipHostMallocDefault) != hipSuccess) { gz_destroy(c); return fail(nullptr, GZ_E_NOMEM, "pinned memory creation failed"); }
-    std::memset(c->h_pick, 0, 512);
+    if (hipHostMalloc((void**)&c->pin, sizeof(GzPinned), hipHostMallocDefault) != hipSuccess) { gz_destroy(c); return fail(nullptr, GZ_E_NOMEM, "pinned memory creation failed"); }
+    std::memset(c->pin, 0, sizeof(GzPinned));
     phase("pinned pick buffer");
     if (ensure(c, c->w_flags, 64, /* zeroed: word 12 is only ever raised */ true) != GZ_OK) { g_create_err = c->err; gz_destroy(c); return GZ_E_NOMEM; }
     phase("device flags");
@@ -1071,13 +1089,13 @@ try {
     for (auto& e : c->ev_xfer) if (e) hipEventDestroy(e);
     release(c->w_stage);
     for (DBuf* b : {&c->w_csr_ids[0], &c->w_csr_ids[1], &c->w_csr_mask[0], &c->w_csr_mask[1], &c->w_csr_comp, &c->w_csr_nreal, &c->w_csr_off32}) release(*b);
-    if (c->h_pick) hipHostFree(c->h_pick);
+    if (c->pin) hipHostFree(c->pin);
     release(c->w_pick); release(c->w_rowoff32);
     for (auto& t2 : c->w_tiny) for (auto& t : t2) release(t);
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
-    for (DBuf* b : {&c->w_mh_cnt, &c->w_mh_off, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_cnt, &c->w_ng_aux, &c->w_rp_cnt, &c->w_rp_tab, &c->w_rp_top}) release(*b);
+    for (DBuf* b : {&c->w_pieces, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_aux, &c->w_rp_tab, &c->w_rp_top}) release(*b);
     for (auto& b : c->w_al) release(b);
     for (DBuf* b : {&c->w_pw_cnt, &c->w_pw_tok}) release(*b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
@@ -2069,7 +2087,7 @@ int preprocess_device_locked(gz_ctx* c, const int32_t* ops, int32_t n_ops, const
             HIPCHK(c, hipMemset(c->w_pplb.p, 0, c->w_pplb.cap));
         }
         gz_launch_pp_tail(F.out, off_dev, F.out_len32, n_docs, out_dev, capacity, out_off_dev, (unsigned long long*)c->w_pplb.p, ctl, c->lb_epoch + 1, c->stream);
-        uint32_t* const h = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 272);       // (pinned scratch: 4 control words + the total)
+        uint32_t* const h = c->pin->prepass;                     // (4 control words + the total)
         for (int q = 0; q < 5; ++q) h[q] = 0;
         HIPCHK(c, hipMemcpyAsync(h, ctl, 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(h + 4, F.out_len32 + n_docs, 4, hipMemcpyDeviceToHost, c->stream));
@@ -2231,7 +2249,7 @@ int compact_impl(gz_ctx* c, const int32_t* rows_dev, const int32_t* n_real_dev, 
     if ((rc = x_begin(c))) return rc;
     gz_launch_row_offsets(n_real_dev, n_rows, off, c->xstream);
     gz_launch_compact(rows_dev, off, n_rows, row_len, out_dev, bits, first_dev, c->xstream);
-    uint32_t* total = reinterpret_cast<uint32_t*>(c->h_pick) + 60;           // pinned (h_pick is 256 bytes; its tail is free)
+    uint32_t* total = &c->pin->compact_total;
     HIPCHK(c, hipMemcpyAsync(total, off + n_rows, 4, hipMemcpyDeviceToHost, c->xstream));
     if ((rc = x_end(c))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->xstream));
@@ -2260,7 +2278,7 @@ int expand_impl(gz_ctx* c, const void* compact_dev, int bits, const int32_t* n_r
     //  reported -- and cleared -- by the next synchronisation: sync_locked)
     int32_t* bad = (int32_t*)c->w_flags.p + 12;
     gz_launch_expand(compact_dev, bits, off, n_real_dev, n_rows, row_len, c->dev.pad_id, ids_dev, mask_dev, (uint32_t)total, bad, c->xstream);
-    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<uint8_t*>(c->h_pick) + 384, bad, 4, hipMemcpyDeviceToHost, c->xstream));
+    HIPCHK(c, hipMemcpyAsync(&c->pin->expand_bad, bad, 4, hipMemcpyDeviceToHost, c->xstream));
     if ((rc = x_end(c))) return rc;
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
@@ -2305,7 +2323,7 @@ try {
     if (!c->blk_valid[slot]) return fail(c, GZ_E_INVALID, "the encode call %d calls back emitted no block (gz_encode_emit_block before it)", back);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(c->ev_blk[slot]));
-    *total_host = reinterpret_cast<uint32_t*>(c->h_pick)[56 + slot];
+    *total_host = c->pin->emit_total[slot];
     return GZ_OK;
 } GZ_CATCH(c)
 

@@ -50,6 +50,7 @@ GZ_HD uint32_t gz_cp_hash(uint32_t cp)
 #ifndef GZ_TAB_SLACK
 #define GZ_TAB_SLACK 16
 #endif
+constexpr int GZ_MAX_SUB_BATCHES = 8;    // the most document ranges a dense batch is cut into (the switch sub_batches)
 struct GzOptions {
     // ---- which kernels a call takes
     int32_t small = 1;                // 1: small dense / ragged batches in ONE launch (gz_small_kernel); 0: everything through the kernel pipeline
@@ -59,7 +60,7 @@ struct GzOptions {
     int32_t assemble = 3;             // row writer of dense single texts: 3 gz_rows1_kernel, 2 the pair-mode kernel (rows through LDS), 1 the ragged layouts' scatter kernel
     int32_t word_table = 1;           // 0: every word through the merge loop (as GZ_NO_WORD_TABLE on every call)
     int32_t pp_fused = 1;             // 0: the text pre-pass filter by filter for every document
-    int32_t sub_batches = 1;          // dense batches cut into this many document ranges on two streams (1 .. 8)
+    int32_t sub_batches = 1;          // dense batches cut into this many document ranges on two streams (1 .. GZ_MAX_SUB_BATCHES)
     int32_t docs_per_wave = 0;        // documents per wave of gz_assemble_kernel (0: by the batch's shape)
     // ---- how the pipeline of one text is scheduled
     int32_t side = 1;                 // 0: no side stream (docw0, wide / long words on the main stream)

@@ -28,7 +28,7 @@ int gz_option_set(GzOptions& o, const char* key, int64_t v)
     static const Key keys[] = {
         {"small", &GzOptions::small, nullptr, 0, 1}, {"small_wgs", &GzOptions::small_wgs, nullptr, 1, 1 << 20}, {"host_direct", &GzOptions::host_direct, nullptr, 0, 1 << 20},
         {"assemble", &GzOptions::assemble, nullptr, 1, 3}, {"word_table", &GzOptions::word_table, nullptr, 0, 1},
-        {"pp_fused", &GzOptions::pp_fused, nullptr, 0, 1}, {"sub_batches", &GzOptions::sub_batches, nullptr, 1, 8},
+        {"pp_fused", &GzOptions::pp_fused, nullptr, 0, 1}, {"sub_batches", &GzOptions::sub_batches, nullptr, 1, GZ_MAX_SUB_BATCHES},
         {"docs_per_wave", &GzOptions::docs_per_wave, nullptr, 0, 16}, {"side", &GzOptions::side, nullptr, 0, 1},
         {"brk_side", &GzOptions::brk_side, nullptr, 0, 1}, {"scan_multi", nullptr, &GzOptions::scan_multi, 0, (int64_t)1 << 40},
         {"near_limit", nullptr, &GzOptions::near_limit, 0, 1 << 25}, {"hot_wgs", &GzOptions::hot_wgs, nullptr, 0, 1 << 16},

@@ -108,8 +108,8 @@ int copy_out(gz_ctx* c, void* dst_host, const void* src_dev, size_t bytes, hipSt
 // a few bytes (a total, a flag word) from the device, through the context's pinned scratch words
 int copy_out_small(gz_ctx* c, void* dst_host, const void* src_dev, size_t bytes, hipStream_t s)
 {
-    if (bytes > 64) return copy_out(c, dst_host, src_dev, bytes, s);
-    uint8_t* h = reinterpret_cast<uint8_t*>(c->h_pick) + 448;           // (h_pick is 512 bytes: [0, 256) the picks and block totals, [256, 512) scratch)
+    if (bytes > sizeof c->pin->small_out) return copy_out(c, dst_host, src_dev, bytes, s);
+    uint8_t* const h = c->pin->small_out;
     HIPCHK(c, hipMemcpyAsync(h, src_dev, bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     std::memcpy(dst_host, h, bytes);

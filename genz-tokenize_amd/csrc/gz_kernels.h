@@ -226,12 +226,18 @@ struct GzInfillArgs {
 };
 void gz_launch_infill(GzInfillArgs A, hipStream_t s);
 
+// Pieces of ragged rows (gz_pieces.inc): a row's body, the row without its skips, is cut into pieces of 4096 positions and a wave owns
+// one piece; a row with fewer positions, or none, has one piece.  Positions: GZ_PIECES_SHINGLES -- runs of w ids, one run when the
+// body is shorter than w and not empty (MinHash); GZ_PIECES_NGRAMS -- runs of w ids, none below w (n-gram overlap, repeats).
+// The count pass: n_pieces[n_rows], their exclusive scan piece_off[n_rows + 1], rebased[n_rows + 1] = row_off - row_off[0] (may be
+// null), and *totals, cleared first: n_pos = the positions of all rows (only with want_pos, which goes with GZ_PIECES_NGRAMS: only
+// the n-gram calls size a table by it), too_long = 1 when a body holds 2^31 ids or more.
+enum GzPieceRule { GZ_PIECES_SHINGLES, GZ_PIECES_NGRAMS };
+struct GzPieceTotals { unsigned long long n_pos; uint32_t too_long, unused; };     // (unused: the clear and the copy back are 16 whole bytes)
+void gz_launch_piece_count(GzPieceRule rule, const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t w, int64_t* n_pieces,
+                           int64_t* piece_off, int64_t* rebased, bool want_pos, GzPieceTotals* totals, hipStream_t s);
+
 // MinHash signatures of ragged rows and near-duplicate groups from signatures (gz_minhash.inc)
-constexpr int GZ_MINHASH_PIECE = 4096;      // shingle positions a wave takes: a row with more is split over waves (64 trips of 64)
-// Count pass: n_pieces[n_rows] = max(1, ceil(shingles / GZ_MINHASH_PIECE)), their exclusive scan piece_off[n_rows + 1], and
-// *too_long = 1 when a body holds 2^31 ids or more (cleared first).
-void gz_launch_minhash_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle, int64_t* n_pieces,
-                             int64_t* piece_off, uint32_t* too_long, hipStream_t s);
 struct GzMinhashArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31
     int32_t skip_front, skip_back, shingle, num_perm;               // skips 0 or 1, 1 <= shingle <= 32, 1 <= num_perm <= 256
@@ -258,13 +264,7 @@ inline uint64_t gz_minhash_cap(int64_t n_rows)                      // a power o
 }
 void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s);     // init, then per band clear / insert / link, then flatten + count
 
-// exact token n-gram overlap against a held-out set (gz_ngram.inc)
-constexpr int GZ_NGRAM_PIECE = 4096;        // n-gram positions a wave takes: a row with more is split over waves (64 trips of 64)
-// Count pass: n_pieces[n_rows] = max(1, ceil(n-grams / GZ_NGRAM_PIECE)) and their exclusive scan piece_off[n_rows + 1]; n_pos[n_rows] =
-// n-grams and their scan pos_off[n_rows + 1] (both null or both given); rebased[n_rows + 1] = row_off - row_off[0] (may be null);
-// *too_long = 1 when a body holds 2^31 ids or more (cleared first).
-void gz_launch_ngram_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
-                           int64_t* piece_off, int64_t* n_pos, int64_t* pos_off, int64_t* rebased, uint32_t* too_long, hipStream_t s);
+// exact token n-gram overlap against a held-out set (gz_ngram.inc); pieces of n-gram positions at the index's width
 struct GzNgramArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // the rows walked: row r = ids[row_off[r] .. row_off[r + 1]); bodies shorter than 2^31
     int32_t skip_front, skip_back, n;                               // skips 0 or 1, 1 <= n <= 32
@@ -287,11 +287,7 @@ inline uint64_t gz_ngram_slots(int64_t n_positions)                 // the small
 void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s);          // into a cleared table
 void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s);           // presets the counts when a row has more than one piece; then resolves first_ref
 
-// n-gram repetition inside a document (gz_repeat.inc); pieces of GZ_NGRAM_PIECE positions at the call's smallest width
-// Count pass: n_pieces[n_rows] at width n and their exclusive scan piece_off[n_rows + 1]; *n_pos = the n-gram positions of all rows;
-// *too_long = 1 when a body holds 2^31 ids or more (both cleared first).
-void gz_launch_repeat_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
-                            int64_t* piece_off, unsigned long long* n_pos, uint32_t* too_long, hipStream_t s);
+// n-gram repetition inside a document (gz_repeat.inc); pieces of n-gram positions at the call's smallest width
 struct GzRepeatArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31
     int64_t off0;                                                   // row_off[0]: a slot's position counts from here (fewer than 2^32 - 1 ids behind it)

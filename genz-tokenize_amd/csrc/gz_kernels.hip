@@ -715,6 +715,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_packrows.inc"
 #include "gz_mask.inc"
 #include "gz_infill.inc"
+#include "gz_pieces.inc"
 #include "gz_minhash.inc"
 #include "gz_ngram.inc"
 #include "gz_repeat.inc"
@@ -894,13 +895,22 @@ void gz_launch_infill(GzInfillArgs A, hipStream_t s)
     else hipLaunchKernelGGL((gz_infill_kernel<false>), grid, block, 0, s, A);
 }
 
-void gz_launch_minhash_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t shingle, int64_t* n_pieces,
-                             int64_t* piece_off, uint32_t* too_long, hipStream_t s)
+void gz_launch_piece_count(GzPieceRule rule, const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t w, int64_t* n_pieces,
+                           int64_t* piece_off, int64_t* rebased, bool want_pos, GzPieceTotals* totals, hipStream_t s)
 {
     if (n_rows <= 0) return;
-    (void)hipMemsetAsync(too_long, 0, 4, s);
-    hipLaunchKernelGGL(gz_minhash_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back,
-                       shingle, n_pieces, too_long);
+    (void)hipMemsetAsync(totals, 0, sizeof *totals, s);
+    const int64_t per_block = 256 * (want_pos ? GZ_PIECE_TOTAL_ROWS : 1);
+    const dim3 grid((unsigned)((n_rows + per_block - 1) / per_block)), block(256);
+    if (want_pos)                                                                    // (only the n-gram calls size a table by the total)
+        hipLaunchKernelGGL((gz_piece_count_kernel<GZ_PIECES_NGRAMS, GZ_PIECE_TOTAL_ROWS>), grid, block, 0, s, row_off, n_rows, skip_front, skip_back, w,
+                           n_pieces, rebased, &totals->n_pos, &totals->too_long);
+    else if (rule == GZ_PIECES_SHINGLES)
+        hipLaunchKernelGGL((gz_piece_count_kernel<GZ_PIECES_SHINGLES, 1>), grid, block, 0, s, row_off, n_rows, skip_front, skip_back, w, n_pieces, rebased,
+                           (unsigned long long*)nullptr, &totals->too_long);
+    else
+        hipLaunchKernelGGL((gz_piece_count_kernel<GZ_PIECES_NGRAMS, 1>), grid, block, 0, s, row_off, n_rows, skip_front, skip_back, w, n_pieces, rebased,
+                           (unsigned long long*)nullptr, &totals->too_long);
     launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
 }
 
@@ -932,17 +942,6 @@ void gz_launch_minhash_groups(const GzMinhashGroupArgs& A, hipStream_t s)
     hipLaunchKernelGGL(gz_minhash_flatten_kernel, grid, block, 0, s, A);
 }
 
-void gz_launch_ngram_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
-                           int64_t* piece_off, int64_t* n_pos, int64_t* pos_off, int64_t* rebased, uint32_t* too_long, hipStream_t s)
-{
-    if (n_rows <= 0) return;
-    (void)hipMemsetAsync(too_long, 0, 4, s);
-    hipLaunchKernelGGL(gz_ngram_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back, n,
-                       n_pieces, n_pos, rebased, too_long);
-    launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
-    if (n_pos) launch_scan64((const int64_t*)n_pos, n_rows, pos_off, s);
-}
-
 void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s)
 {
     if (A.n_rows <= 0 || A.n_pieces <= 0) return;
@@ -961,17 +960,6 @@ void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s)
     }
     hipLaunchKernelGGL(gz_ngram_query_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
     if (A.first_ref) hipLaunchKernelGGL(gz_ngram_resolve_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
-}
-
-void gz_launch_repeat_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, int64_t* n_pieces,
-                            int64_t* piece_off, unsigned long long* n_pos, uint32_t* too_long, hipStream_t s)
-{
-    if (n_rows <= 0) return;
-    (void)hipMemsetAsync(n_pos, 0, 8, s);
-    (void)hipMemsetAsync(too_long, 0, 4, s);
-    hipLaunchKernelGGL(gz_repeat_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back, n,
-                       n_pieces, n_pos, too_long);
-    launch_scan64((const int64_t*)n_pieces, n_rows, piece_off, s);
 }
 
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)

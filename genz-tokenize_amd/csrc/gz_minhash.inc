@@ -1,4 +1,5 @@
-// gz_minhash.inc -- MinHash signatures of ragged token rows and near-duplicate groups from signatures (included by gz_kernels.hip).
+// gz_minhash.inc -- MinHash signatures of ragged token rows and near-duplicate groups from signatures (included by gz_kernels.hip
+// behind gz_pieces.inc).
 //
 // The rule (include/genz_tokenize.h, "near-duplicate documents by MinHash signatures"): the body of a row is the row without its skips;
 // its shingles are the runs of w ids (one run, the whole body, when it is shorter), each hashed with H = MurmurHash3_x86_32 over the
@@ -6,9 +7,8 @@
 // rep_j(d) is the smallest non-empty row with d's key in band j; d and rep_j(d) are joined when they agree in min_agree slots;
 // group[d] is the smallest row of d's component.
 //
-// SIGNATURES.  Work is divided over PIECES of GZ_MINHASH_PIECE = 4096 shingle positions, never over documents: a count pass (one
-// thread a row, then the 64-bit scan every ragged pass uses) gives every row max(1, ceil(shingles / 4096)) pieces, and a wave owns one
-// piece, whatever row it comes from (a binary search in piece_off, skipped when every row has one piece).  A trip is 64 shingle
+// SIGNATURES.  Work is divided over PIECES of GZ_PIECE = 4096 shingle positions, never over documents (gz_pieces.inc: the body rule,
+// the count pass and the walk from a wave's piece to its row are the ones the n-gram kernels use).  A trip is 64 shingle
 // positions: lane l loads id t + l (and id t + 64 + l for the w - 1 ids beyond the trip) -- one coalesced load each, not w loads a
 // lane --, takes the ids of its own run from its neighbours by wave shuffles and computes ONE H.  The lanes then own the k: lane l
 // keeps slots l, l + 64, ... (at most 4 with K <= 256) in registers and folds each of the trip's hashes, read out of the owning lane
@@ -37,28 +37,6 @@ __device__ __forceinline__ uint32_t mh_fmix32(uint32_t x)
 }
 __device__ __forceinline__ uint32_t mh_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
-// the body of row r: where it starts in ids and how many ids it holds (0 for a row shorter than its skips)
-__device__ __forceinline__ int64_t mh_body(const int64_t* __restrict__ row_off, int64_t r, int32_t skip_front, int32_t skip_back, int64_t* n)
-{
-    const int64_t a = row_off[r] + skip_front, b = row_off[r + 1] - skip_back;
-    *n = b > a ? b - a : 0;
-    return a;
-}
-__device__ __forceinline__ int64_t mh_shingles(int64_t n, int32_t w) { return n >= w ? n - w + 1 : (n > 0 ? 1 : 0); }
-
-__global__ __launch_bounds__(256) void gz_minhash_count_kernel(const int64_t* __restrict__ row_off, int64_t n_rows, int32_t skip_front,
-                                                               int32_t skip_back, int32_t w, int64_t* __restrict__ n_pieces,
-                                                               uint32_t* __restrict__ too_long)
-{
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    int64_t n;
-    mh_body(row_off, r, skip_front, skip_back, &n);
-    if (n >= ((int64_t)1 << 31)) atomicOr(too_long, 1u);
-    const int64_t s = mh_shingles(n, w);
-    n_pieces[r] = s <= GZ_MINHASH_PIECE ? 1 : (s + GZ_MINHASH_PIECE - 1) / GZ_MINHASH_PIECE;
-}
-
 // NK slots a lane: K <= 64 * NK
 template <int NK>
 __global__ __launch_bounds__(WAVE * 4) void gz_minhash_sig_kernel(GzMinhashArgs A)
@@ -66,22 +44,13 @@ __global__ __launch_bounds__(WAVE * 4) void gz_minhash_sig_kernel(GzMinhashArgs 
     const int lane = lane_id();
     const int64_t p = (int64_t)blockIdx.x * 4 + threadIdx.x / WAVE;                  // the wave's piece
     if (p >= A.n_pieces) return;
-    int64_t r = p;
-    if (!A.one_each) {                                                               // the last row with piece_off[r] <= p (every row has a piece)
-        int64_t lo = 0, hi = p < A.n_rows - 1 ? p : A.n_rows - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (A.piece_off[mid] <= p) lo = mid; else hi = mid - 1;
-        }
-        r = lo;
-    }
-    int64_t n;
-    const int64_t a = mh_body(A.row_off, r, A.skip_front, A.skip_back, &n);
-    const int64_t n_sh = mh_shingles(n, A.shingle);
+    int64_t j, n_pc, n;
+    const int64_t r = piece_row(A, p, &j, &n_pc);
+    const int64_t a = piece_body(A.row_off, r, A.skip_front, A.skip_back, &n);
+    const int64_t n_sh = piece_shingles(n, A.shingle);
     const int m = n >= A.shingle ? A.shingle : (int)n;                               // ids of a shingle of this body
-    const int64_t j = A.one_each ? 0 : p - A.piece_off[r];
-    const bool alone = A.one_each || A.piece_off[r + 1] - A.piece_off[r] == 1;
-    const int64_t s0 = j * GZ_MINHASH_PIECE, s1 = s0 + GZ_MINHASH_PIECE < n_sh ? s0 + GZ_MINHASH_PIECE : n_sh;
+    const bool alone = n_pc == 1;
+    const int64_t s0 = j * GZ_PIECE, s1 = s0 + GZ_PIECE < n_sh ? s0 + GZ_PIECE : n_sh;
     if (j == 0 && lane == 0 && A.n_shingles) A.n_shingles[r] = (int32_t)n_sh;
     uint32_t c[NK], mn[NK];
 #pragma unroll

@@ -1,6 +1,6 @@
 // gz_ngram.inc -- exact token n-gram overlap of ragged rows against a held-out set: an index of n-grams resident in HBM, and the
-// membership probe + token coverage of query rows (included by gz_kernels.hip behind gz_minhash.inc, whose body rule, rotl and
-// fmix32 it shares).
+// membership probe + token coverage of query rows (included by gz_kernels.hip behind gz_pieces.inc, whose body rule, position rule
+// and piece walk it uses, and gz_minhash.inc, whose rotl and fmix32 it shares).
 //
 // The rule (include/genz_tokenize.h, "token n-gram overlap against a held-out set"): the body of a row is the row without its skips;
 // its n-grams are the max(0, m - n + 1) runs of n ids (a body shorter than n has NONE: a shorter run is no evidence of leakage); S is
@@ -26,8 +26,8 @@
 // probe sequence that holds it -- and that slot ends at the n-gram's smallest position, whatever the order of the inserts.
 // first(g) = the row of that position: a binary search in the index's offsets.  Distinct n-grams = successful claims.
 //
-// BUILD AND QUERY walk the rows as gz_minhash_sig_kernel does: PIECES of GZ_NGRAM_PIECE = 4096 n-gram positions, a wave a piece
-// whatever row it comes from (binary search in piece_off, skipped when every row has one piece); a trip is 64 positions: two
+// BUILD AND QUERY walk the rows as gz_minhash_sig_kernel does: PIECES of GZ_PIECE = 4096 n-gram positions, a wave a piece
+// whatever row it comes from (gz_pieces.inc: count pass, piece_row, piece_body, piece_grams); a trip is 64 positions: two
 // coalesced loads, one hash a lane, one probe a lane.  QUERY: hits = ballot(hit); lane l then owns TOKEN t + l of the trip, which is
 // covered when one of the positions t + l - n + 1 .. t + l hit: the trip's hit bits shifted so that position t + l stands at bit 63,
 // ORed with the carried hit bits of the previous 64 positions shifted in below them, and the top n bits tested -- shifts and ORs,
@@ -40,7 +40,7 @@
 // resolves first_ref.
 // Bounds: a position i is probed only when i < n_g = m - n + 1, so body[i .. i + n) lies inside the body; a slot's position was
 // inserted under the same rule, so ref_ids[q .. q + n) lies inside a reference body.  Look-back trips start at s0 - 64 >= 4032.
-// Workspace of a call: 16 bytes a row (piece counts and their scan); of a build also 16 bytes a row (position counts and scan).
+// Workspace of a call, build or query: 16 bytes a row (piece counts and their scan; the position total is one word behind them).
 // The index: 4 bytes a reference id (the copy), 8 bytes a reference row (offsets), 8 bytes a slot: 16 to 32 bytes a position.
 
 __device__ __forceinline__ void ng_mix(uint32_t& h1, uint32_t& h2, uint32_t id)
@@ -87,46 +87,6 @@ __device__ __forceinline__ bool ng_equal(const int32_t* __restrict__ x, const in
     return true;
 }
 
-__device__ __forceinline__ int64_t ng_grams(int64_t m, int32_t n) { return m >= n ? m - n + 1 : 0; }
-
-// Count pass, a thread a row: n_pieces[r] = max(1, ceil(n-grams / GZ_NGRAM_PIECE)); n_pos[r] = n-grams (may be null);
-// rebased[r] = row_off[r] - row_off[0], rebased[n_rows] too (may be null); *too_long |= a body of 2^31 ids or more.
-__global__ __launch_bounds__(256) void gz_ngram_count_kernel(const int64_t* __restrict__ row_off, int64_t n_rows, int32_t skip_front,
-                                                             int32_t skip_back, int32_t n, int64_t* __restrict__ n_pieces,
-                                                             int64_t* __restrict__ n_pos, int64_t* __restrict__ rebased,
-                                                             uint32_t* __restrict__ too_long)
-{
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    int64_t m;
-    mh_body(row_off, r, skip_front, skip_back, &m);
-    if (m >= ((int64_t)1 << 31)) atomicOr(too_long, 1u);
-    const int64_t g = ng_grams(m, n);
-    n_pieces[r] = g <= GZ_NGRAM_PIECE ? 1 : (g + GZ_NGRAM_PIECE - 1) / GZ_NGRAM_PIECE;
-    if (n_pos) n_pos[r] = g;
-    if (rebased) {
-        const int64_t base = row_off[0];
-        rebased[r] = row_off[r] - base;
-        if (r == n_rows - 1) rebased[n_rows] = row_off[n_rows] - base;
-    }
-}
-
-// the wave's piece p: its row (the last row with piece_off[r] <= p; every row has a piece) and which of the row's pieces it is
-// (Args: GzNgramArgs, or GzRepeatArgs of gz_repeat.inc -- their one_each, n_rows and piece_off)
-template <class Args>
-__device__ __forceinline__ int64_t ng_piece_row(const Args& A, int64_t p, int64_t* j, int64_t* n_pc)
-{
-    if (A.one_each) { *j = 0; *n_pc = 1; return p; }
-    int64_t lo = 0, hi = p < A.n_rows - 1 ? p : A.n_rows - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (A.piece_off[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    *j = p - A.piece_off[lo];
-    *n_pc = A.piece_off[lo + 1] - A.piece_off[lo];
-    return lo;
-}
-
 // Insert the n-gram at position pos of the index's id copy; 1 when this thread claimed a free slot (a new distinct n-gram).
 __device__ __forceinline__ int ng_insert(const GzNgramArgs& A, uint64_t h, uint64_t pos)
 {
@@ -160,10 +120,10 @@ __global__ __launch_bounds__(WAVE * 4) void gz_ngram_insert_kernel(GzNgramArgs A
     const int64_t p = (int64_t)blockIdx.x * 4 + threadIdx.x / WAVE;                  // the wave's piece
     if (p >= A.n_pieces) return;
     int64_t j, n_pc, m;
-    const int64_t r = ng_piece_row(A, p, &j, &n_pc);
-    const int64_t a = mh_body(A.row_off, r, A.skip_front, A.skip_back, &m);
-    const int64_t n_g = ng_grams(m, A.n);
-    const int64_t s0 = j * GZ_NGRAM_PIECE, s1 = s0 + GZ_NGRAM_PIECE < n_g ? s0 + GZ_NGRAM_PIECE : n_g;
+    const int64_t r = piece_row(A, p, &j, &n_pc);
+    const int64_t a = piece_body(A.row_off, r, A.skip_front, A.skip_back, &m);
+    const int64_t n_g = piece_grams(m, A.n);
+    const int64_t s0 = j * GZ_PIECE, s1 = s0 + GZ_PIECE < n_g ? s0 + GZ_PIECE : n_g;
     const int32_t* const body = A.ids + a;                                           // (never read when m == 0)
     int claimed = 0;
     for (int64_t t = s0; t < s1; t += WAVE) {                                        // (wave-uniform bounds: every lane stays for the shuffles)
@@ -181,10 +141,10 @@ __global__ __launch_bounds__(WAVE * 4) void gz_ngram_query_kernel(GzNgramArgs A)
     const int64_t p = (int64_t)blockIdx.x * 4 + threadIdx.x / WAVE;                  // the wave's piece
     if (p >= A.n_pieces) return;
     int64_t j, n_pc, m;
-    const int64_t r = ng_piece_row(A, p, &j, &n_pc);
-    const int64_t a = mh_body(A.row_off, r, A.skip_front, A.skip_back, &m);
-    const int64_t n_g = ng_grams(m, A.n);
-    const int64_t s0 = j * GZ_NGRAM_PIECE, s1 = s0 + GZ_NGRAM_PIECE < n_g ? s0 + GZ_NGRAM_PIECE : n_g;
+    const int64_t r = piece_row(A, p, &j, &n_pc);
+    const int64_t a = piece_body(A.row_off, r, A.skip_front, A.skip_back, &m);
+    const int64_t n_g = piece_grams(m, A.n);
+    const int64_t s0 = j * GZ_PIECE, s1 = s0 + GZ_PIECE < n_g ? s0 + GZ_PIECE : n_g;
     const int64_t tok_end = j == n_pc - 1 ? m : s1;                                   // the last piece owns the tail, which starts no n-gram
     const int32_t* const body = A.ids + a;                                           // (never read when m == 0)
     if (j == 0) {
@@ -239,7 +199,7 @@ __global__ __launch_bounds__(256) void gz_ngram_resolve_kernel(GzNgramArgs A)
     int32_t ref = -1;
     if (fh >= 0) {
         int64_t m;
-        const int32_t* const g = A.ids + mh_body(A.row_off, r, A.skip_front, A.skip_back, &m) + fh;
+        const int32_t* const g = A.ids + piece_body(A.row_off, r, A.skip_front, A.skip_back, &m) + fh;
         const uint32_t v = ng_probe(A, ng_hash_serial(g, A.n) & A.hmask, g);
         if (v != 0u) {                                                               // (always: first_hit is a position that hit)
             const int64_t q = (int64_t)(v - 1u);

@@ -1,6 +1,7 @@
 // Exact token n-gram overlap against a held-out set behind the C ABI (gz_ngram_index_*, gz_ngram_overlap*).  Included by gz_api.cpp
-// behind gz_rows_api.inc, whose row front (RowsIn, rows_check, rows_stage, StagedOut) the host forms use; the kernels are in
-// gz_ngram.inc, the argument rules without HIP in them in gz_rowrules.h.
+// behind gz_rows_api.inc, whose row front both forms use (RowsIn, rows_check, rows_stage, StagedOut for the host forms;
+// rows_extent_device for the device form's extent; pieces_count_locked and its limit sentence for the count pass); the kernels are in
+// gz_ngram.inc and gz_pieces.inc, the argument rules without HIP in them in gz_rowrules.h.
 //
 // An index owns three device buffers: a copy of the reference ids (so the caller's may go), the rows' offsets from 0 and the table.
 // It belongs to its context: every call on it runs on the context's stream under the context's lock, and gz_destroy frees what is
@@ -23,38 +24,9 @@ void ngram_index_free(gz_ngram_index* ix) { delete ix; }
 const char* const kNgramBuildBuffers = "n-gram index needs ids and row_off";
 const char* const kNgramOverlapBuffers = "n-gram overlap needs ids and row_off";
 const char* const kNgramOverlapDisjoint = "n-gram overlap needs output arrays that overlap neither the input nor each other";
-const char* const kNgramBodyLimit = "a row's body holds 2^31 ids or more: split the document";
 const char* const kNgramIdsLimit = "an n-gram index takes fewer than 2^32 - 1 reference ids: shard the held-out set";
 
-// three words of the pinned scratch (h_pick + 264 ..: free of read_total's, the MinHash flag's and copy_out_small's)
-int64_t* ngram_scratch(gz_ctx* c) { return reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 264); }
-
-// The count pass over n_rows > 0 rows into w_ng_cnt: n_pieces, piece_off, and with_pos: n_pos, pos_off.  One wait: *n_pieces, *n_pos
-// (0 without with_pos) and whether a body is too long (GZ_E_LIMIT then).
-int ngram_count_locked(gz_ctx* c, const int64_t* row_off_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n, bool with_pos,
-                       int64_t* rebased_dev, const int64_t** piece_off_dev, int64_t* n_pieces, int64_t* n_pos)
-{
-    int rc;
-    const size_t words = (size_t)n_rows + 1;
-    if ((rc = ensure(c, c->w_ng_cnt, words * 8 * (with_pos ? 4 : 2) + 16))) return rc;
-    int64_t* const cnt = (int64_t*)c->w_ng_cnt.p;
-    int64_t* const piece_off = cnt + words;
-    int64_t* const pos_cnt = with_pos ? cnt + 2 * words : nullptr;
-    int64_t* const pos_off = with_pos ? cnt + 3 * words : nullptr;
-    uint32_t* const too_long = (uint32_t*)(cnt + (with_pos ? 4 : 2) * words);
-    gz_launch_ngram_count(row_off_dev, n_rows, skip_front, skip_back, n, cnt, piece_off, pos_cnt, pos_off, rebased_dev, too_long, c->stream);
-    int64_t* const h = ngram_scratch(c);
-    h[0] = h[1] = h[2] = 0;
-    HIPCHK(c, hipMemcpyAsync(h, piece_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    if (with_pos) HIPCHK(c, hipMemcpyAsync(h + 1, pos_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 2, too_long, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (h[2]) return fail(c, GZ_E_LIMIT, "%s", kNgramBodyLimit);
-    *piece_off_dev = piece_off;
-    *n_pieces = h[0];
-    *n_pos = h[1];
-    return GZ_OK;
-}
+const char* const kNgramPositions = "internal: the n-gram positions read back from the device do not fit the rows";
 
 // The index of the rows ids_dev[row_off_dev[r] .. row_off_dev[r + 1]) (absolute offsets; the ids lie in [off0, off0 + n_ids)), on the
 // context's stream behind whatever it holds.  Nothing is handed out before the index is complete.
@@ -69,12 +41,12 @@ int ngram_build_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off
     int rc;
     if ((rc = ensure(c, ix->ids, (size_t)n_ids * 4 + 16)) || (rc = ensure(c, ix->off, (size_t)(n_rows + 1) * 8))) return rc;
     if (n_ids) HIPCHK(c, hipMemcpyAsync(ix->ids.p, ids_dev + off0, (size_t)n_ids * 4, hipMemcpyDeviceToDevice, c->stream));
-    const int64_t* piece_off = nullptr;
-    int64_t n_pieces = 0;
+    Pieces P{nullptr, 0, 0};
     if (n_rows > 0) {
-        if ((rc = ngram_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, n, true, (int64_t*)ix->off.p, &piece_off, &n_pieces, &ix->n_pos)))
-            return rc;
+        if ((rc = pieces_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, n, GZ_PIECES_NGRAMS, true, (int64_t*)ix->off.p, &P))) return rc;
+        if (!ngram_positions_possible(P.n_pos, n_ids, n_rows, skip_front, skip_back, n)) return fail(c, GZ_E_HIP, "%s", kNgramPositions);
     } else HIPCHK(c, hipMemsetAsync(ix->off.p, 0, 8, c->stream));
+    ix->n_pos = P.n_pos;
     ix->slots = gz_ngram_slots(ix->n_pos);
     if ((rc = ensure(c, ix->table, (size_t)ix->slots * 8)) || (rc = ensure(c, c->w_ng_aux, 16))) return rc;
     HIPCHK(c, hipMemsetAsync(ix->table.p, 0, (size_t)ix->slots * 8, c->stream));
@@ -83,7 +55,7 @@ int ngram_build_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off
         GzNgramArgs A{};
         A.ids = A.ref_ids = (const int32_t*)ix->ids.p; A.row_off = A.ref_off = (const int64_t*)ix->off.p; A.n_rows = A.ref_rows = n_rows;
         A.skip_front = skip_front; A.skip_back = skip_back; A.n = n;
-        A.piece_off = piece_off; A.n_pieces = n_pieces;
+        A.piece_off = P.piece_off; A.n_pieces = P.n_pieces;
         A.table = (unsigned long long*)ix->table.p; A.mask = ix->slots - 1; A.hmask = ix->hmask;
         A.n_distinct = (unsigned long long*)c->w_ng_aux.p;
         gz_launch_ngram_insert(A, c->stream);
@@ -127,13 +99,12 @@ int ngram_overlap_locked(gz_ctx* c, gz_ngram_index* ix, const int32_t* ids_dev, 
         if ((rc = ensure(c, c->w_ng_aux, (size_t)n_rows * 4 + 16))) return rc;
         O.first_hit = (int32_t*)((uint8_t*)c->w_ng_aux.p + 16);
     }
-    const int64_t* piece_off = nullptr;
-    int64_t n_pieces = 0, unused = 0;
-    if ((rc = ngram_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, ix->n, false, nullptr, &piece_off, &n_pieces, &unused))) return rc;
+    Pieces P;
+    if ((rc = pieces_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, ix->n, GZ_PIECES_NGRAMS, false, nullptr, &P))) return rc;
     GzNgramArgs A{};
     A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows;
     A.skip_front = skip_front; A.skip_back = skip_back; A.n = ix->n;
-    A.piece_off = piece_off; A.n_pieces = n_pieces;
+    A.piece_off = P.piece_off; A.n_pieces = P.n_pieces;
     A.table = (unsigned long long*)ix->table.p; A.mask = ix->slots - 1; A.hmask = ix->hmask;
     A.ref_ids = (const int32_t*)ix->ids.p; A.ref_off = (const int64_t*)ix->off.p; A.ref_rows = ix->n_rows;
     A.n_grams = O.n_grams; A.n_hits = O.n_hits; A.n_covered = O.n_covered; A.first_hit = O.first_hit; A.first_ref = O.first_ref; A.covered = O.covered;
@@ -155,14 +126,8 @@ try {
     HIPCHK(c, hipSetDevice(c->device));
     int64_t off0 = 0, n_ids = 0;
     if (n_rows > 0) {
-        int64_t* const h = ngram_scratch(c);
-        h[0] = h[1] = 0;
-        HIPCHK(c, hipMemcpyAsync(h, row_off_dev, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h + 1, row_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        off0 = h[0];
-        n_ids = (int64_t)((uint64_t)h[1] - (uint64_t)h[0]);
-        if (n_ids < 0) return fail(c, GZ_E_INVALID, "bad row offsets");
+        int rc;
+        if ((rc = rows_extent_device(c, row_off_dev, n_rows, &off0, &n_ids))) return rc;
         if (n_ids > 0 && !ids_dev) return fail(c, GZ_E_INVALID, "%s", kNgramBuildBuffers);
         if (!ngram_ids_fit(n_ids)) return fail(c, GZ_E_LIMIT, "%s", kNgramIdsLimit);
     }
@@ -181,7 +146,7 @@ try {
     int rc;
     if ((rc = rows_check(c, in, kRowWords))) return rc;
     if (!ngram_ids_fit(in.n)) return fail(c, GZ_E_LIMIT, "%s", kNgramIdsLimit);
-    if (!minhash_bodies_fit(in.off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kNgramBodyLimit);
+    if (!minhash_bodies_fit(in.off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kBodyLimit);
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = rows_stage(c, in, 0))) return rc;
     return ngram_build_locked(c, (const int32_t*)in.d_payload, in.d_off, n_rows, in.off[0], in.n, skip_front, skip_back, n, out);
@@ -247,7 +212,7 @@ try {
     if (!ngram_overlap_disjoint(in.n ? ids + row_off[0] : nullptr, (uintptr_t)in.n * 4u, row_off, n_rows, O, covered && in.n ? covered + row_off[0] : nullptr,
                                 (uintptr_t)in.n))
         return fail(c, GZ_E_INVALID, "%s", kNgramOverlapDisjoint);
-    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kNgramBodyLimit);
+    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kBodyLimit);
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = rows_stage(c, in, 0))) return rc;
     const size_t per_row = (size_t)n_rows * 4;

@@ -1,6 +1,7 @@
 // gz_repeat.inc -- n-gram repetition INSIDE a document: per row and width, how many n-grams there are, how many different ones, how
 // many positions hold an n-gram that occurs twice or more, how many tokens lie inside such an n-gram, and the most frequent n-gram
-// (included by gz_kernels.hip behind gz_ngram.inc, whose hash, comparison, piece walk and coverage by ballots and shifts it shares).
+// (included by gz_kernels.hip behind gz_pieces.inc, whose body rule, n-gram rule and piece walk it uses, and gz_ngram.inc, whose
+// hash, comparison and coverage by ballots and shifts it shares).
 //
 // The rule (include/genz_tokenize.h, "repeats: n-gram repetition inside a document"): the body q of a row is the row without its
 // skips, m ids; for width n its n-grams are the G = max(0, m - n + 1) runs q[i:i+n]; c(g) = the positions whose n-gram is g
@@ -25,7 +26,7 @@
 // c << 32 | (0xFFFFFFFF - first_in_body) is a maximum: more occurrences win, then the smaller first position.  Coverage comes from
 // ballot(repeated) exactly as gz_ngram_query_kernel derives it from its hits.
 //
-// PIECES are those of the SMALLEST width for every width (one count pass): piece j of a row takes positions [4096 j, 4096 (j + 1))
+// PIECES (gz_pieces.inc) are those of the SMALLEST width for every width (one count pass): piece j of a row takes positions [4096 j, 4096 (j + 1))
 // below G and owns the tokens of that range; the row's last piece owns the tokens up to m.  At a larger width a piece's last
 // positions, or all of them, may lie at or beyond G: they are tail tokens, covered through the carry.  A piece that is not its row's
 // first evaluates the n - 1 positions before its start once more, for the carry only.  Every body token belongs to exactly one
@@ -53,26 +54,6 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v)
         v = y > v ? y : v;
     }
     return v;
-}
-
-// Count pass at the smallest width, a thread a row: n_pieces[r] = max(1, ceil(n-grams / GZ_NGRAM_PIECE)); *n_pos += n-grams (a
-// wave's sum in one atomic); *too_long |= a body of 2^31 ids or more.
-__global__ __launch_bounds__(256) void gz_repeat_count_kernel(const int64_t* __restrict__ row_off, int64_t n_rows, int32_t skip_front,
-                                                              int32_t skip_back, int32_t n, int64_t* __restrict__ n_pieces,
-                                                              unsigned long long* __restrict__ n_pos, uint32_t* __restrict__ too_long)
-{
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    int64_t g = 0;
-    if (r < n_rows) {
-        int64_t m;
-        mh_body(row_off, r, skip_front, skip_back, &m);
-        if (m >= ((int64_t)1 << 31)) atomicOr(too_long, 1u);
-        g = ng_grams(m, n);
-        n_pieces[r] = g <= GZ_NGRAM_PIECE ? 1 : (g + GZ_NGRAM_PIECE - 1) / GZ_NGRAM_PIECE;
-    }
-    // (every lane stays for the shuffles; 64 bodies below 2^31 fit 37 bits: the halves are summed apart)
-    const int lo = wave_sum((int)(g & 0xFFFF)), hi = wave_sum((int)(g >> 16));
-    if (lane_id() == 0 && (lo | hi)) atomicAdd(n_pos, (unsigned long long)lo + ((unsigned long long)hi << 16));
 }
 
 // One occurrence of the n-gram at position pos (relative to off0) of a row whose n-gram positions are [lo, lo + n_g).
@@ -114,12 +95,12 @@ __device__ __forceinline__ uint32_t rp_probe(const GzRepeatArgs& A, uint64_t h, 
 __device__ __forceinline__ void rp_piece(const GzRepeatArgs& A, int64_t p, int64_t* r, int64_t* a, int64_t* m, int64_t* n_g, int64_t* s0,
                                          int64_t* s1, int64_t* tok_end, int64_t* j, int64_t* n_pc)
 {
-    *r = ng_piece_row(A, p, j, n_pc);
-    *a = mh_body(A.row_off, *r, A.skip_front, A.skip_back, m);
-    *n_g = ng_grams(*m, A.n);
-    *s0 = *j * GZ_NGRAM_PIECE;
-    *s1 = *s0 + GZ_NGRAM_PIECE < *n_g ? *s0 + GZ_NGRAM_PIECE : *n_g;
-    *tok_end = *j == *n_pc - 1 ? *m : *s0 + GZ_NGRAM_PIECE;                            // the last piece owns the tail, which starts no n-gram
+    *r = piece_row(A, p, j, n_pc);
+    *a = piece_body(A.row_off, *r, A.skip_front, A.skip_back, m);
+    *n_g = piece_grams(*m, A.n);
+    *s0 = *j * GZ_PIECE;
+    *s1 = *s0 + GZ_PIECE < *n_g ? *s0 + GZ_PIECE : *n_g;
+    *tok_end = *j == *n_pc - 1 ? *m : *s0 + GZ_PIECE;                            // the last piece owns the tail, which starts no n-gram
 }
 
 __global__ __launch_bounds__(WAVE * 4) void gz_repeat_insert_kernel(GzRepeatArgs A)

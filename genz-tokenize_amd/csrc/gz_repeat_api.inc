@@ -1,11 +1,12 @@
 // n-gram repetition inside a document behind the C ABI (gz_ngram_repeats, gz_ngram_repeats_device).  Included by gz_api.cpp behind
-// gz_ngram_api.inc, whose pinned scratch words and limit sentences it shares, and gz_rows_api.inc, whose row front (RowsIn,
-// rows_check, rows_stage, StagedOut) the host form uses; the kernels are in gz_repeat.inc, the argument rules without HIP in them in
-// gz_rowrules.h (repeat_fault).
+// gz_ngram_api.inc, whose "internal" sentence it shares, and gz_rows_api.inc, whose row front both forms use (RowsIn, rows_check,
+// rows_stage, StagedOut for the host form; rows_extent_device for the device form's extent; pieces_count_locked and its limit sentence
+// for the count pass); the kernels are in gz_repeat.inc and gz_pieces.inc, the argument rules without HIP in them in gz_rowrules.h
+// (repeat_fault).
 //
-// A call owns nothing beyond the context's workspace: w_rp_cnt (16 bytes a row: piece counts and their scan, then the position total
-// and the too-long flag), w_rp_tab (12 bytes a slot: the slots, then their counts) and, only where a row has several pieces and a
-// top output is asked for, w_rp_top (8 bytes a row).  It waits once for the piece count, the positions and the flag, then runs the
+// A call owns nothing beyond the context's workspace: the row front's w_pieces (16 bytes a row: piece counts and their scan, then the
+// position total and the too-long flag), w_rp_tab (12 bytes a slot: the slots, then their counts) and, only where a row has several
+// pieces and a top output is asked for, w_rp_top (8 bytes a row).  It waits once for the piece count, the positions and the flag, then runs the
 // widths in the caller's order on the context's stream, and waits for its outputs.
 
 namespace {
@@ -26,29 +27,18 @@ bool repeat_disjoint(const void* ids_at, uintptr_t n_ids, const int64_t* row_off
 }
 
 // The call on the context's stream, behind whatever it holds; the caller waits for the outputs.  Every pointer of O a device pointer.
-// Nothing is written to the outputs when a body is too long.  n_rows > 0; off0 = row_off[0].
-int repeats_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int64_t off0, int32_t skip_front, int32_t skip_back,
+// Nothing is written to the outputs when a body is too long.  n_rows > 0; off0 = row_off[0], n_ids = row_off[n_rows] - off0.
+int repeats_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int64_t off0, int64_t n_ids, int32_t skip_front, int32_t skip_back,
                    const int32_t* widths, int32_t n_widths, const RepeatOut& O)
 {
     int rc;
-    const size_t words = (size_t)n_rows + 1;
-    if ((rc = ensure(c, c->w_rp_cnt, words * 16 + 16))) return rc;
-    int64_t* const cnt = (int64_t*)c->w_rp_cnt.p;
-    int64_t* const piece_off = cnt + words;
-    unsigned long long* const n_pos = (unsigned long long*)(cnt + 2 * words);
-    uint32_t* const too_long = (uint32_t*)(n_pos + 1);
     int32_t n_min = widths[0];
     for (int32_t k = 1; k < n_widths; ++k) n_min = widths[k] < n_min ? widths[k] : n_min;
-    gz_launch_repeat_count(row_off_dev, n_rows, skip_front, skip_back, n_min, cnt, piece_off, n_pos, too_long, c->stream);
-    int64_t* const h = ngram_scratch(c);
-    h[0] = h[1] = h[2] = 0;
-    HIPCHK(c, hipMemcpyAsync(h, piece_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 1, n_pos, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 2, too_long, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (h[2]) return fail(c, GZ_E_LIMIT, "%s", kNgramBodyLimit);
-    const int64_t n_pieces = h[0];
-    const uint64_t slots = gz_ngram_slots(h[1]);
+    Pieces P;
+    if ((rc = pieces_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, n_min, GZ_PIECES_NGRAMS, true, nullptr, &P))) return rc;
+    if (!ngram_positions_possible(P.n_pos, n_ids, n_rows, skip_front, skip_back, n_min)) return fail(c, GZ_E_HIP, "%s", kNgramPositions);
+    const int64_t n_pieces = P.n_pieces;
+    const uint64_t slots = gz_ngram_slots(P.n_pos);
     if ((rc = ensure(c, c->w_rp_tab, (size_t)slots * 12))) return rc;
     const bool want_top = O.v[4] || O.v[5];
     if (n_pieces != n_rows && want_top && (rc = ensure(c, c->w_rp_top, (size_t)n_rows * 8))) return rc;
@@ -56,7 +46,7 @@ int repeats_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev
     GzRepeatArgs A{};
     A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows; A.off0 = off0;
     A.skip_front = skip_front; A.skip_back = skip_back;
-    A.piece_off = piece_off; A.n_pieces = n_pieces;
+    A.piece_off = P.piece_off; A.n_pieces = n_pieces;
     A.table = (unsigned long long*)c->w_rp_tab.p; A.count = (uint32_t*)(A.table + slots); A.mask = slots - 1;
     A.hmask = bits > 0 ? (1ull << bits) - 1ull : ~0ull;
     A.top = n_pieces != n_rows && want_top ? (unsigned long long*)c->w_rp_top.p : nullptr;
@@ -83,20 +73,15 @@ try {
     if (!row_off_dev) return fail(c, GZ_E_INVALID, "%s", kRepeatBuffers);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int64_t* const h = ngram_scratch(c);
-    h[0] = h[1] = 0;
-    HIPCHK(c, hipMemcpyAsync(h, row_off_dev, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h + 1, row_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int64_t off0 = h[0], n_ids = (int64_t)((uint64_t)h[1] - (uint64_t)h[0]);
-    if (n_ids < 0) return fail(c, GZ_E_INVALID, "bad row offsets");
+    int rc;
+    int64_t off0 = 0, n_ids = 0;
+    if ((rc = rows_extent_device(c, row_off_dev, n_rows, &off0, &n_ids))) return rc;
     if (n_ids > 0 && !ids_dev) return fail(c, GZ_E_INVALID, "%s", kRepeatBuffers);
     if (!ngram_ids_fit(n_ids)) return fail(c, GZ_E_LIMIT, "%s", kRepeatIdsLimit);
     const RepeatOut O{{n_grams_dev, n_distinct_dev, n_repeated_dev, n_covered_dev, top_count_dev, top_pos_dev}, covered_dev};
     if (!repeat_disjoint(n_ids ? ids_dev + off0 : nullptr, (uintptr_t)n_ids, row_off_dev, n_rows, n_widths, O, covered_dev && n_ids ? covered_dev + off0 : nullptr))
         return fail(c, GZ_E_INVALID, "%s", kRepeatDisjoint);
-    int rc;
-    if ((rc = repeats_locked(c, ids_dev, row_off_dev, n_rows, off0, skip_front, skip_back, widths, n_widths, O))) return rc;
+    if ((rc = repeats_locked(c, ids_dev, row_off_dev, n_rows, off0, n_ids, skip_front, skip_back, widths, n_widths, O))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
@@ -114,7 +99,7 @@ try {
     int rc;
     if ((rc = rows_check(c, in, kRowWords))) return rc;
     if (!ngram_ids_fit(in.n)) return fail(c, GZ_E_LIMIT, "%s", kRepeatIdsLimit);
-    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kNgramBodyLimit);
+    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kBodyLimit);
     const RepeatOut O{{n_grams, n_distinct, n_repeated, n_covered, top_count, top_pos}, covered};
     if (!repeat_disjoint(in.n ? ids + row_off[0] : nullptr, (uintptr_t)in.n, row_off, n_rows, n_widths, O, covered && in.n ? covered + row_off[0] : nullptr))
         return fail(c, GZ_E_INVALID, "%s", kRepeatDisjoint);
@@ -126,7 +111,7 @@ try {
     for (int i = 0; i < 6; ++i) S.add(O.v[i], per, false);
     if ((rc = staged_ensure(c, S))) return rc;
     const RepeatOut D{{S.dev(1), S.dev(2), S.dev(3), S.dev(4), S.dev(5), S.dev(6)}, S.e[0].dev ? (uint16_t*)S.e[0].dev - row_off[0] : nullptr};
-    if ((rc = repeats_locked(c, (const int32_t*)in.d_payload, in.d_off, n_rows, row_off[0], skip_front, skip_back, widths, n_widths, D))) return rc;
+    if ((rc = repeats_locked(c, (const int32_t*)in.d_payload, in.d_off, n_rows, row_off[0], in.n, skip_front, skip_back, widths, n_widths, D))) return rc;
     return staged_copy_out(c, S);
 } GZ_CATCH(c)
 

@@ -75,6 +75,18 @@ inline const char* ngram_overlap_fault(int64_t n_rows, int32_t skip_front, int32
 // the reference ids an index takes: a slot holds position + 1 in 32 bits, so 2^32 - 1 ids or more are refused (GZ_E_LIMIT); so is a
 // body of 2^31 ids or more (minhash_bodies_fit)
 inline bool ngram_ids_fit(int64_t n_ids) { return n_ids >= 0 && (uint64_t)n_ids < 0xFFFFFFFFull; }
+// What the n-gram positions of n_rows rows that hold n_ids ids between them can add up to at width n: a row of L ids has between
+// L - skip_front - skip_back - (n - 1) and L of them.  A position total outside that range read back from the device is no total: a
+// table sized by one that is too small is one a probe loop never leaves.  The range holds for offsets that do not decrease -- the
+// host forms check that, the device forms take it from their caller (offsets that go back and forth can add up to more than n_ids
+// and are refused here, where the sum once sized a table).  n_ids >= 0, n_rows >= 0, skips 0 or 1, 1 <= n <= 32.
+inline bool ngram_positions_possible(int64_t n_pos, int64_t n_ids, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n)
+{
+    const int64_t lost = (int64_t)skip_front + skip_back + n - 1;                  // (at most 33 a row)
+    int64_t least = n_ids;
+    if (lost) least = n_rows > n_ids / lost ? 0 : n_ids - n_rows * lost;          // (the product is at most n_ids: it does not wrap)
+    return n_pos >= least && n_pos <= n_ids;
+}
 
 // n-gram repeats (gz_ngram_repeats*; tests/test_repeat_surface.py compiles this alone): the sentence of the first rule an argument
 // list breaks, or nullptr, in the order they are reported in.  The ids of a call obey ngram_ids_fit (a slot holds position + 1 in 32

@@ -1,12 +1,14 @@
 // The row-shaping calls behind the C ABI: batch decode, overlapping windows, packed rows, masked-LM rows, span-corruption rows,
-// MinHash signatures and groups.
+// MinHash signatures and groups; and what the n-gram calls (gz_ngram_api.inc, gz_repeat_api.inc) share with them: the piece count and the
+// extent of a device input.
 // Included by gz_api.cpp behind gz_ctx, fail, HIPCHK, ensure and the copy helpers; the kernels are in gz_decode.inc, gz_window.inc,
-// gz_packrows.inc, gz_mask.inc, gz_infill.inc and gz_minhash.inc.  A call supplies its rule, its launch and its list of outputs; the row front
+// gz_packrows.inc, gz_mask.inc, gz_infill.inc, gz_pieces.inc and gz_minhash.inc.  A call supplies its rule, its launch and its list of outputs; the row front
 // below does the rest of a host form (DESIGN.md, "the row front"); its rules without HIP in them are in gz_rowrules.h.
-// WORKSPACE: the host forms share w_rows_in, w_rows_off, w_rows_out[4] and w_rows_small.  That is sound because every use lies
-// inside c->mu and every access -- copy, kernel, memset -- is enqueued on c->stream: a later call's accesses are ordered behind an
-// earlier call's even where that one returned early.  A kernel's own scratch (w_win_cnt, the w_pk_* maps, w_dec_rb, the w_mh_* piece
-// counts, band table and EMPTY bytes) is not shared.
+// WORKSPACE: the host forms share w_rows_in, w_rows_off, w_rows_out[4] and w_rows_small, and the calls that divide rows into pieces
+// (MinHash signatures, the n-gram index and its queries, n-gram repeats; host and device forms) share w_pieces.  That is sound
+// because every use lies inside c->mu and every access -- copy, kernel, memset -- is enqueued on c->stream: a later call's accesses
+// are ordered behind an earlier call's even where that one returned early.  A kernel's own scratch (w_win_cnt, the w_pk_* maps,
+// w_dec_rb, the MinHash band table and EMPTY bytes, the n-gram and repeat tables) is not shared.
 
 // ---- the row front -----------------------------------------------------------------------------------------------------
 namespace {
@@ -52,12 +54,55 @@ int rows_stage(gz_ctx* c, RowsIn& in, size_t keep_bytes)
 int read_total(gz_ctx* c, const int64_t* src, int64_t* zero, int64_t* total)
 {
     *total = 0;
-    int64_t* const h_total = reinterpret_cast<int64_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 256);       // (pinned scratch)
+    int64_t* const h_total = &c->pin->read_total;
     *h_total = 0;
     if (src) HIPCHK(c, hipMemcpyAsync(h_total, src, 8, hipMemcpyDeviceToHost, c->stream));
     else if (zero) HIPCHK(c, hipMemsetAsync(zero, 0, 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *total = *h_total;
+    return GZ_OK;
+}
+
+// The extent of a device CSR input of n_rows > 0 rows: *off0 = row_off[0], *n_ids = row_off[n_rows] - row_off[0], read from the device
+// after one wait of the context's stream; a negative extent is refused.
+int rows_extent_device(gz_ctx* c, const int64_t* row_off_dev, int64_t n_rows, int64_t* off0, int64_t* n_ids)
+{
+    int64_t* const h = c->pin->extent;
+    h[0] = h[1] = 0;
+    HIPCHK(c, hipMemcpyAsync(h, row_off_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h + 1, row_off_dev + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *off0 = h[0];
+    *n_ids = (int64_t)((uint64_t)h[1] - (uint64_t)h[0]);
+    if (*n_ids < 0) return fail(c, GZ_E_INVALID, "bad row offsets");
+    return GZ_OK;
+}
+
+// Rows divided into pieces (gz_pieces.inc; DESIGN.md, "the row front"): the count pass of the calls whose waves own a piece of a row's
+// body -- MinHash signatures, the n-gram index and its queries, n-gram repeats.  w_pieces holds the counts, their scan, then the
+// position total and the too-long flag: 16 bytes a row (plus 32).  ONE wait of the context's stream: piece_off (on the device, valid
+// until the next count on this context), the pieces, the positions (0 unless want_pos), or GZ_E_LIMIT when a body holds 2^31 ids or
+// more -- nothing was launched over the rows then.  rebased_dev: n_rows + 1 words for row_off - row_off[0], or null.  n_rows > 0.
+const char* const kBodyLimit = "a row's body holds 2^31 ids or more: split the document";
+struct Pieces { const int64_t* piece_off; int64_t n_pieces, n_pos; };
+int pieces_count_locked(gz_ctx* c, const int64_t* row_off_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t w, GzPieceRule rule,
+                        bool want_pos, int64_t* rebased_dev, Pieces* out)
+{
+    int rc;
+    const size_t words = (size_t)n_rows + 1;
+    if ((rc = ensure(c, c->w_pieces, words * 16 + sizeof(GzPieceTotals)))) return rc;
+    int64_t* const cnt = (int64_t*)c->w_pieces.p;
+    int64_t* const piece_off = cnt + words;
+    GzPieceTotals* const totals = (GzPieceTotals*)(piece_off + words);
+    gz_launch_piece_count(rule, row_off_dev, n_rows, skip_front, skip_back, w, cnt, piece_off, rebased_dev, want_pos, totals, c->stream);
+    GzPinned* const h = c->pin;
+    h->n_pieces = 0;
+    h->pieces = GzPieceTotals{};
+    HIPCHK(c, hipMemcpyAsync(&h->n_pieces, piece_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h->pieces, totals, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h->pieces.too_long) return fail(c, GZ_E_LIMIT, "%s", kBodyLimit);
+    *out = Pieces{piece_off, h->n_pieces, (int64_t)h->pieces.n_pos};
     return GZ_OK;
 }
 
@@ -623,27 +668,19 @@ bool minhash_rows_buffers_ok(const void* ids, uintptr_t ids_bytes, const int64_t
     return disjoint(s, 4);
 }
 
-// Both passes on the context's stream, behind whatever it holds; the caller waits for the signatures.  piece_off_dev: n_rows + 1 words
-// of the caller's.  Nothing is written to the outputs when a body is too long.  n_rows > 0.
+// Both passes on the context's stream, behind whatever it holds; the caller waits for the signatures.  Nothing is written to the
+// outputs when a body is too long.  n_rows > 0.
 int minhash_rows_locked(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back,
-                        int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t* sig_dev, int32_t* n_shingles_dev, int64_t* piece_off_dev)
+                        int32_t shingle, int32_t num_perm, uint64_t seed, uint32_t* sig_dev, int32_t* n_shingles_dev)
 {
     int rc;
-    if ((rc = ensure(c, c->w_mh_cnt, (size_t)(n_rows + 1) * 8 + 16))) return rc;
-    int64_t* const cnt = (int64_t*)c->w_mh_cnt.p;
-    uint32_t* const too_long = (uint32_t*)(cnt + n_rows + 1);
-    gz_launch_minhash_count(row_off_dev, n_rows, skip_front, skip_back, shingle, cnt, piece_off_dev, too_long, c->stream);
-    uint32_t* const h_long = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 352);       // (pinned scratch)
-    *h_long = 0;
-    HIPCHK(c, hipMemcpyAsync(h_long, too_long, 4, hipMemcpyDeviceToHost, c->stream));
-    int64_t n_pieces = 0;
-    if ((rc = read_total(c, piece_off_dev + n_rows, nullptr, &n_pieces))) return rc;
-    if (*h_long) return fail(c, GZ_E_LIMIT, "a row's body holds 2^31 ids or more: split the document");
+    Pieces P;
+    if ((rc = pieces_count_locked(c, row_off_dev, n_rows, skip_front, skip_back, shingle, GZ_PIECES_SHINGLES, false, nullptr, &P))) return rc;
     GzMinhashArgs A{};
     A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows;
     A.skip_front = skip_front; A.skip_back = skip_back; A.shingle = shingle; A.num_perm = num_perm;
     A.seed_lo = (uint32_t)seed; A.seed_hi = (uint32_t)(seed >> 32);
-    A.piece_off = piece_off_dev; A.n_pieces = n_pieces;
+    A.piece_off = P.piece_off; A.n_pieces = P.n_pieces;
     A.sig = sig_dev; A.n_shingles = n_shingles_dev;
     gz_launch_minhash_sig(A, c->stream);
     return GZ_OK;
@@ -680,9 +717,8 @@ try {
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->w_mh_off, (size_t)(n_rows + 1) * 8))) return rc;
-    if ((rc = minhash_rows_locked(c, ids_dev, row_off_dev, n_rows, skip_front, skip_back, shingle, num_perm, seed, signatures_dev, n_shingles_dev,
-                                  (int64_t*)c->w_mh_off.p))) return rc;
+    if ((rc = minhash_rows_locked(c, ids_dev, row_off_dev, n_rows, skip_front, skip_back, shingle, num_perm, seed, signatures_dev, n_shingles_dev)))
+        return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     return GZ_OK;
@@ -700,14 +736,14 @@ try {
     if ((rc = rows_check(c, in, kRowWords))) return rc;
     if (!minhash_rows_buffers_ok(in.n ? ids + row_off[0] : nullptr, (uintptr_t)in.n * 4u, row_off, n_rows, num_perm, signatures, n_shingles))
         return fail(c, GZ_E_INVALID, "%s", kMinhashRowsBuffers);
-    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "a row's body holds 2^31 ids or more: split the document");
+    if (!minhash_bodies_fit(row_off, n_rows, skip_front, skip_back)) return fail(c, GZ_E_LIMIT, "%s", kBodyLimit);
     std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;                 // kept through both passes: piece_off
+    if ((rc = rows_stage(c, in, 0))) return rc;
     StagedOut S;
     S.add(signatures, (size_t)n_rows * (size_t)num_perm * 4, true); S.add(n_shingles, (size_t)n_rows * 4, false);
     if ((rc = staged_ensure(c, S))) return rc;
     if ((rc = minhash_rows_locked(c, (const int32_t*)in.d_payload, in.d_off, n_rows, skip_front, skip_back, shingle, num_perm, seed,
-                                  (uint32_t*)S.e[0].dev, S.dev(1), (int64_t*)in.d_keep))) return rc;
+                                  (uint32_t*)S.e[0].dev, S.dev(1)))) return rc;
     return staged_copy_out(c, S);
 } GZ_CATCH(c)
 
@@ -790,7 +826,7 @@ int span_count_locked(gz_ctx* c, GzSpanArgs& A, int64_t* total)
     A.too_long = (uint32_t*)(A.lead0 + A.n_docs + 1);
     A.span = nullptr; A.n_words = 0;
     gz_launch_span_count(A, c->stream);
-    uint32_t* const h_long = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(c->h_pick) + 360);       // (pinned scratch)
+    uint32_t* const h_long = &c->pin->span_long;
     *h_long = 0;
     HIPCHK(c, hipMemcpyAsync(h_long, A.too_long, 4, hipMemcpyDeviceToHost, c->stream));
     if ((rc = read_total(c, A.word_off + A.n_docs, nullptr, total))) return rc;

@@ -657,7 +657,7 @@ int  gz_bpe_learn_result(gz_wordset *ws, int64_t *merge_off, uint8_t *merge_byte
  *                    in one slot, which holds its smallest position; first(g) is the row of that position (a binary search in the
  *                    reference offsets): membership and first do not depend on the order of the inserts
  *   memory           the index: 4 bytes a reference id, 8 bytes a reference row, 8 bytes a slot -- 20 to 36 bytes a reference token
- *                    with one position a token; workspace of a build or a query: 16 to 32 bytes a row
+ *                    with one position a token; workspace of a build or a query: 16 bytes a row
  *   ids / row_off    packed int32 rows as gz_decode_batch takes them;  the five per-row outputs int32 [n_rows], each may be NULL;
  *                    covered uint8, may be NULL.
  *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched or written: n_rows < 0; 2^31 reference

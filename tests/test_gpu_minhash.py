@@ -12,7 +12,7 @@ import window_oracle as WO
 
 pytestmark = pytest.mark.gpu
 
-PIECE = 4096                                                             # shingle positions a wave takes (csrc/gz_kernels.h: GZ_MINHASH_PIECE)
+PIECE = 4096                                                             # shingle positions a wave takes (csrc/gz_pieces.inc: GZ_PIECE)
 M32 = 0xFFFFFFFF
 FILL = 0x5A5A5A5A
 

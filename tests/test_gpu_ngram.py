@@ -13,7 +13,7 @@ import window_oracle as WO
 
 pytestmark = pytest.mark.gpu
 
-PIECE = 4096                                                             # n-gram positions a wave takes (csrc/gz_kernels.h: GZ_NGRAM_PIECE)
+PIECE = 4096                                                             # n-gram positions a wave takes (csrc/gz_pieces.inc: GZ_PIECE)
 FILL = 0x5A5A5A5A
 OUT = ("n_grams", "n_hits", "n_covered", "first_hit", "first_ref")
 
@@ -240,6 +240,51 @@ def test_reference_positions_at_table_sizes(tok, P):
             assert not f2 and (w2["n_hits"] == 0).all()
     if P >= 255:
         occur(want, first, ref, n)
+
+
+@pytest.mark.parametrize("N", [63, 64, 65, 257])
+def test_reference_positions_summed_over_waves(tok, N):
+    """The position total that sizes the table is a wave's sum of the rows' counts in 16-bit halves and one atomic a wave: N rows of
+    about 5000 ids (64 of them carry out of the low half; 63, 65 and 257 rows leave partial waves and a partial block) and one row
+    of 70 000 ids, whose own count has a high half.  A total that came out too small would size a table too small for its n-grams."""
+    n = 5
+    rng = np.random.default_rng(300 + N)
+    ref = [rng.integers(0, 50000, size=int(T)).astype(np.int32) for T in rng.integers(4990, 5011, size=N)]
+    ref.insert(N // 2, rng.integers(0, 50000, size=70000).astype(np.int32))
+    P = NO.positions(ref, n)
+    assert P == sum(len(b) - n + 1 for b in ref) > 64 * 4990
+    slots = 1
+    while slots < 2 * P:
+        slots *= 2
+    with tok.ngram_index(ref, n, framed=False) as ix:
+        info = tok._ctx.ngram_index_info(ix._handle)
+        assert info["n_grams"] == P and info["slots"] == slots and info["n_rows"] == N + 1 and info["n_ids"] == P + (N + 1) * (n - 1)
+        got = tok.ngram_overlap_rows(ref, ix, framed=False)                # the reference against its own index: every position hits
+    assert got["n_grams"].tolist() == [len(b) - n + 1 for b in ref]
+    assert np.array_equal(got["n_hits"], got["n_grams"]) and np.array_equal(got["n_covered"], got["body_len"])
+    assert (got["first_hit"] == 0).all() and (got["first_ref"] <= np.arange(N + 1)).all() and (got["first_ref"] >= 0).all()
+
+
+@pytest.mark.parametrize("N", [511, 513, 2047, 2048, 2049, 4100])
+def test_reference_row_counts_at_the_count_blocks_edges(tok, N):
+    """Where the position total is asked for, a thread of the count pass takes 8 rows, 256 apart, so a block covers 2048 rows: one
+    below, at and above a block, two blocks and a few rows, and row counts at which the threads of one block leave their loop after
+    different numbers of rows.  Short rows, some shorter than n; the total, the distinct n-grams and every row's count are the
+    oracle's, and the reference queried against its own index hits at every position."""
+    n = 5
+    rng = np.random.default_rng(500 + N)
+    ref = [rng.integers(0, 50000, size=int(T)).astype(np.int32) for T in rng.integers(0, 61, size=N)]
+    first = NO.index(ref, n)
+    P = NO.positions(ref, n)
+    slots = 1
+    while slots < 2 * P:
+        slots *= 2
+    with tok.ngram_index(ref, n, framed=False) as ix:
+        info = tok._ctx.ngram_index_info(ix._handle)
+        assert (info["n_rows"], info["n_grams"], info["n_distinct"], info["slots"]) == (N, P, len(first), slots)
+        got = tok.ngram_overlap_rows(ref, ix, framed=False)
+    assert got["n_grams"].tolist() == [max(len(b) - n + 1, 0) for b in ref] and got["n_grams"].sum() == P
+    assert np.array_equal(got["n_hits"], got["n_grams"]) and (got["n_grams"] == 0).any()
 
 
 @pytest.mark.parametrize("N", [0, 1, 255, 256, 257])

@@ -13,7 +13,7 @@ import window_oracle as WO
 
 pytestmark = pytest.mark.gpu
 
-PIECE = 4096                                                             # n-gram positions a wave takes (csrc/gz_kernels.h: GZ_NGRAM_PIECE)
+PIECE = 4096                                                             # n-gram positions a wave takes (csrc/gz_pieces.inc: GZ_PIECE)
 FILL = 0x5A5A5A5A
 OUT = RO.KEYS
 
@@ -73,6 +73,34 @@ def planted(T, *plants):
 
 
 # ---- the rule's edges, the trips' and the pieces' ------------------------------------------------------------------------
+def test_piece_workspace_shared_with_minhash_and_overlap(tok):
+    """MinHash signatures, the n-gram index, its queries and this call count their pieces into ONE workspace buffer of the context.
+    Five calls on one context whose row counts grow and shrink and whose long rows follow short ones, each against its own oracle:
+    offsets left over from an earlier call, or a buffer too small for a later one, would show."""
+    import minhash_oracle as MO
+    import ngram_oracle as NO
+    rng = np.random.default_rng(77)
+
+    def signed(bodies):
+        want = MO.batch(bodies, 64, 5, 9)
+        got = tok.minhash_rows(bodies, 64, 5, 9, framed=False)
+        assert np.array_equal(got["signatures"], want["signatures"]) and np.array_equal(got["n_shingles"], want["n_shingles"])
+    signed([rng.integers(5, 48423, size=int(T)).tolist() for T in rng.integers(0, 60, size=300)])
+    n = 4
+    ref = [rng.integers(0, 7, size=T).tolist() for T in (40, 0, 90, 3, 200)]
+    first = NO.index(ref, n)
+    with tok.ngram_index(ref, n, framed=False) as ix:
+        assert (ix.n_rows, ix.n_grams, ix.n_distinct) == (5, NO.positions(ref, n), len(first))
+        check(tok, [looped(rng, int(T), 3) for T in rng.integers(0, 41, size=4097)] + [looped(rng, PIECE + 9, 3)], (2, 5))
+        rows = [rng.integers(0, 7, size=2 * PIECE + 12).tolist()]
+        want = NO.overlap(first, n, rows)
+        got = tok.ngram_overlap_rows(rows, ix, framed=False, return_covered=True)
+        assert want["n_hits"][0] > 0
+        for k in NO.KEYS + ("covered", "row_off"):
+            assert np.array_equal(got[k], want[k]), k
+    signed([[7, 8, 9], rng.integers(5, 48423, size=PIECE + 70).tolist(), []])
+
+
 @pytest.mark.parametrize("n", [1, 2, 13, 32])
 def test_body_lengths_at_the_rules_the_trips_and_the_pieces_edges(tok, n):
     """nothing, one id, around the width; around one trip of 64 positions; exactly one piece and two pieces -- over an alphabet of

@@ -84,11 +84,11 @@ def test_header_documents_the_rule():
 
 def test_kernels_are_their_own_file():
     hip = open(os.path.join(CSRC, "gz_kernels.hip")).read()
-    assert hip.index('#include "gz_minhash.inc"') < hip.index('#include "gz_ngram.inc"')       # (it shares the body rule and fmix32)
+    assert hip.index('#include "gz_pieces.inc"') < hip.index('#include "gz_minhash.inc"') < hip.index('#include "gz_ngram.inc"')   # (the piece rules; fmix32)
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert "gz_ngram.inc" in make and "gz_ngram_api.inc" in make           # the build identity covers both
     inc = open(os.path.join(CSRC, "gz_ngram.inc")).read()
-    for word in ("gz_ngram_count_kernel", "gz_ngram_insert_kernel", "gz_ngram_query_kernel", "gz_ngram_resolve_kernel", "atomicCAS", "atomicMin",
+    for word in ("piece_row", "gz_ngram_insert_kernel", "gz_ngram_query_kernel", "gz_ngram_resolve_kernel", "atomicCAS", "atomicMin",
                  "wballot", "__shfl"):
         assert word in inc, word
     assert "__shared__" not in inc                                         # coverage by ballots and shifts: no LDS

@@ -88,10 +88,30 @@ def test_kernels_are_their_own_file():
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert "gz_repeat.inc" in make and "gz_repeat_api.inc" in make          # the build identity covers both
     inc = open(os.path.join(CSRC, "gz_repeat.inc")).read()
-    for word in ("gz_repeat_count_kernel", "gz_repeat_insert_kernel", "gz_repeat_query_kernel", "atomicCAS", "atomicMin", "atomicAdd", "atomicMax",
-                 "wballot", "ng_trip_hash", "ng_equal", "ng_grams", "GZ_NGRAM_PIECE", "GzRepeatArgs"):
+    for word in ("piece_row", "gz_repeat_insert_kernel", "gz_repeat_query_kernel", "atomicCAS", "atomicMin", "atomicAdd", "atomicMax",
+                 "wballot", "ng_trip_hash", "ng_equal", "piece_grams", "GZ_PIECE", "GzRepeatArgs"):
         assert word in inc, word
     assert "__shared__" not in inc                                         # one path: no LDS table
+    # rows are divided into pieces in ONE place: the constant, the count kernel and the walk stand in gz_pieces.inc, which the
+    # build identity covers and which comes in front of its three users; each of them uses the walk
+    pieces = open(os.path.join(CSRC, "gz_pieces.inc")).read()
+    for word in ("constexpr int GZ_PIECE = 4096;", "void gz_piece_count_kernel(", "piece_row(const Args& A", "piece_body(", "piece_shingles(", "piece_grams(",
+                 "wave_sum", "atomicAdd", "atomicOr"):
+        assert word in pieces, word
+    hdrs = re.search(r"^HDRS := (.*)$", make, flags=re.M).group(1).split()
+    assert "gz_pieces.inc" in hdrs
+    assert hip.index('#include "gz_pieces.inc"') < hip.index('#include "gz_minhash.inc"') < hip.index('#include "gz_ngram.inc"')
+    for name in ("gz_minhash.inc", "gz_ngram.inc", "gz_repeat.inc"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert "piece_row(A, p, " in text, name
+        assert not re.search(r"constexpr\s+\w+\s+GZ_\w*PIECE\b", text) and "lo + hi + 1" not in text.split("gz_ngram_resolve_kernel")[0], name
+    whole = {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".inc", ".h", ".hip", ".cpp", ".c"))}
+    for name, text in whole.items():
+        assert not re.search(r"\bh_pick\b", text), name                    # the pinned block is a struct: no user reaches it by a number
+        assert not re.search(r"gz_(minhash|ngram|repeat)_count_kernel|gz_launch_(minhash|ngram|repeat)_count|GZ_(MINHASH|NGRAM)_PIECE", text), name
+    assert sum(text.count("void gz_piece_count_kernel(") for text in whole.values()) == 1
+    assert sum(len(re.findall(r"^void gz_launch_piece_count\(", text, flags=re.M)) for text in whole.values()) == 2      # declared, defined
+    assert "struct GzPinned" in api and "sizeof(GzPinned)" in api
     assert "__shared__" not in open(os.path.join(CSRC, "gz_ngram.inc")).read()
     assert "struct GzRepeatArgs" in open(os.path.join(CSRC, "gz_kernels.h")).read()
     host = open(os.path.join(CSRC, "gz_host_api.cpp")).read()
@@ -175,6 +195,16 @@ int main()
         std::printf("body_bare|%d\n", minhash_bodies_fit(off.data(), 3, 0, 0) ? 1 : 0);              // a body of 2^31 + 1
         std::printf("body_framed|%d\n", minhash_bodies_fit(off.data(), 3, 1, 1) ? 1 : 0);            // 2^31 - 1
     }
+    // the position total a count pass may report: 10 rows, 1000 ids, framed, n = 5: between 1000 - 10 * 6 and 1000
+    std::printf("ids_pos_least|%d\n", ngram_positions_possible(940, 1000, 10, 1, 1, 5) ? 1 : 0);
+    std::printf("ids_pos_most|%d\n", ngram_positions_possible(1000, 1000, 10, 1, 1, 5) ? 1 : 0);
+    std::printf("ids_pos_below|%d\n", ngram_positions_possible(939, 1000, 10, 1, 1, 5) ? 1 : 0);
+    std::printf("ids_pos_above|%d\n", ngram_positions_possible(1001, 1000, 10, 1, 1, 5) ? 1 : 0);
+    std::printf("ids_pos_short_rows|%d\n", ngram_positions_possible(0, 1000, 500, 0, 0, 32) ? 1 : 0);        // every row may be shorter than n
+    std::printf("ids_pos_negative|%d\n", ngram_positions_possible(-1, 1000, 500, 0, 0, 32) ? 1 : 0);
+    std::printf("ids_pos_unigrams|%d\n", ngram_positions_possible(1000, 1000, 10, 0, 0, 1) ? 1 : 0);          // n = 1, bare: exactly the ids
+    std::printf("ids_pos_unigrams_fewer|%d\n", ngram_positions_possible(999, 1000, 10, 0, 0, 1) ? 1 : 0);
+    std::printf("ids_pos_many_rows|%d\n", ngram_positions_possible(0, 5, INT64_MAX, 1, 1, 32) ? 1 : 0);       // (no product wraps)
     return 0;
 }
 """
@@ -191,6 +221,8 @@ EXPECTED = {
     "repeated": "n-gram repeats need distinct widths", "repeated_32": "n-gram repeats need distinct widths",
     "first_of_many": "n-gram repeats need n_rows >= 0", "list_order": "n-gram repeats need distinct widths",
     "ids_most": "1", "ids_limit": "0", "body_bare": "0", "body_framed": "1",
+    "ids_pos_least": "1", "ids_pos_most": "1", "ids_pos_below": "0", "ids_pos_above": "0", "ids_pos_short_rows": "1", "ids_pos_negative": "0", "ids_pos_unigrams": "1",
+    "ids_pos_unigrams_fewer": "0", "ids_pos_many_rows": "1",
 }
 
 
