@@ -2330,10 +2330,13 @@ try {
 int gz_compact_block(gz_ctx* c, const int32_t* rows_dev, const int32_t* n_real_dev, int64_t n_rows, int32_t row_len, int32_t bits,
                      int32_t* block_dev, int64_t* total_host)
 try {
-    if (!c || !block_dev || !n_real_dev || n_rows < 0 || (bits != 16 && bits != 32)) return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    // (everything compact_impl refuses is refused HERE: a refused call must not have written the row lengths into the block)
+    if (!c || !block_dev || !rows_dev || !n_real_dev || !total_host || n_rows < 0 || row_len <= 0 || (bits != 16 && bits != 32))
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
     {
         // the row lengths in front of the entries (on the exchange stream, behind the encode call they belong to)
         std::lock_guard<std::mutex> lk(c->mu);
+        if (bits == 16 && (!c->have_tables || !ids_fit_16(c))) return fail(c, GZ_E_LIMIT, "the vocabulary has ids that do not fit 16 bits");
         HIPCHK(c, hipSetDevice(c->device));
         int rc;
         if ((rc = x_begin(c))) return rc;

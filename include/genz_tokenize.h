@@ -970,7 +970,10 @@ int  gz_exchange_timing_history(gz_ctx *ctx, double *out_ms, int32_t max, int32_
 /* Compact form of dense rows for the exchange step: most of a [n_rows, row_len] block is padding, so a rank sends
  * only the n_real[i] leading entries of every row (+ the counts) and the root re-creates padding and mask.
  *   gz_compact_rows   rows_dev [n_rows,row_len] + n_real_dev [n_rows] -> out_dev (concatenated leading entries);
- *                     *total_host = number of entries written (the call synchronises the context's stream)
+ *                     *total_host = number of entries written (the call synchronises the context's stream).
+ *                     PRECONDITION, of gz_compact_rows[16] and gz_compact_block alike: every n_real[i] lies in [0, row_len].
+ *                     The compact calls do not check it (the rows are the caller's own): a larger or a negative count
+ *                     reads beyond the row, behind the last row beyond rows_dev.
  *   gz_expand_rows    the inverse on the receiving side: compact_dev + n_real_dev -> ids_dev, mask_dev
  *                     ([n_rows,row_len] each; padding = the pad id of the loaded tables, mask = id != pad) */
 int  gz_compact_rows(gz_ctx *ctx, const int32_t *rows_dev, const int32_t *n_real_dev, int64_t n_rows, int32_t row_len,
