@@ -78,6 +78,7 @@ struct GzPinned {
     int64_t n_pieces;                              // piece_off[n_rows] of a piece count.  c->stream; pieces_count_locked waits for the stream
     GzPieceTotals pieces;                          // ... its position total and "a body is too long".  The same copy train, the same wait
     uint8_t small_out[64];                         // copy_out_small.  The stream the caller names; copy_out_small waits for it
+    int32_t fit_hist[GZ_FIT_MAX_LEN + 4];          // the length histogram of a best-fit pack call.  c->stream; fit_maps_locked waits for the stream
 };
 
 }  // namespace
@@ -181,6 +182,9 @@ struct gz_ctx {
     DBuf t_dec_entries, t_dec_bytes, w_dec_rb;
     DBuf w_win_cnt;                                                                                     // overlapping windows (gz_window_rows*)
     DBuf w_pk_len, w_pk_jc, w_pk_nxt, w_pk_jc2, w_pk_tile, w_pk_seg, w_pk_drow, w_pk_dcol;              // packed rows (gz_pack_rows*)
+    GzFitPlan fit_plan; std::vector<uint8_t> fit_upload;                                                // the host plan of a best-fit call and the one block it goes up in (used under mu)
+    double fit_plan_ms = 0; int64_t fit_events = 0, fit_segments = 0;                                   // the last best-fit call's host plan (gz_pack_rows_fit_info)
+    DBuf w_pf_rank, w_pf_tab, w_pf_plan, w_pf_rdocs, w_pf_dlen;                                         // best-fit packed rows (gz_pack_rows_fit*); they share the w_pk_* maps
     DBuf w_pieces;                                                                                      // piece counts, their scan, the position total and the too-long flag of MinHash, n-gram overlap and repeats (gz_rows_api.inc: pieces_count_locked)
     DBuf w_mh_keys, w_mh_reps, w_mh_aux;                                                                // MinHash groups: the band table, EMPTY bytes + counter (gz_minhash_groups*)
     DBuf w_rows_in, w_rows_off, w_rows_out[4], w_rows_small;      // staging of the host forms of the row calls and the pre-pass (gz_rows_api.inc: WORKSPACE)
@@ -1095,6 +1099,7 @@ try {
     for (DBuf* b : {&c->w_pp[0], &c->w_pp[1], &c->w_ppoff[0], &c->w_ppoff[1], &c->w_pplen, &c->w_ppaux, &c->w_ppctl, &c->w_pplen32, &c->w_pplb}) release(*b);
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
+    for (DBuf* b : {&c->w_pf_rank, &c->w_pf_tab, &c->w_pf_plan, &c->w_pf_rdocs, &c->w_pf_dlen}) release(*b);
     for (DBuf* b : {&c->w_pieces, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_aux, &c->w_rp_tab, &c->w_rp_top}) release(*b);
     for (auto& b : c->w_al) release(b);
     for (DBuf* b : {&c->w_pw_cnt, &c->w_pw_tok}) release(*b);

@@ -1,6 +1,7 @@
 // Kernel argument blocks and launchers (gz_kernels.hip) used by the C ABI (gz_api.cpp).
 #pragma once
 #include "gz_common.h"
+#include "gz_packfit.h"
 #include <hip/hip_runtime.h>
 
 constexpr int GZ_WAVES_PER_BLOCK = 2;
@@ -178,6 +179,7 @@ struct GzPackArgs {
     int64_t* len64; int32_t* jc; int32_t* nxt; int32_t* jc2; int32_t* tile; int64_t* total;
     int64_t capacity;                                               // rows the cell arrays hold: the fill writes nothing when *total exceeds it
     int32_t* out_ids; int32_t* out_mask; int32_t* out_seg; int32_t* out_pos;     // [*total, max_len]
+    const int32_t* row_docs; int64_t fit_rows;                      // best-fit order only (gz_packfit.inc): the packed order [n_rows] and R
 };
 inline int64_t gz_pack_tiles(int64_t n_rows) { return (n_rows + GZ_PACK_TILE - 1) / GZ_PACK_TILE; }
 inline int64_t gz_pack_groups(int64_t n_rows) { return (gz_pack_tiles(n_rows) + GZ_PACK_GROUP - 1) / GZ_PACK_GROUP; }
@@ -188,6 +190,24 @@ inline int32_t gz_pack_entries(int32_t max_len)                     // where a c
 void gz_launch_pack_maps(const GzPackArgs& A, bool with_col /* false: a fill follows and writes doc_col */, hipStream_t s);
 void gz_launch_pack_col(const GzPackArgs& A, hipStream_t s);
 void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s);     // R = *A.total, read on the device
+
+// best-fit packing (gz_packfit.inc; the rule and the host plan: gz_packfit.h).  P holds the batch, the cell arrays and the maps
+// (doc_row, doc_col, doc_len and pack_off are never null here; seg_off may be; P.len64 [n_rows + 1] is scratch; the break chain's
+// workspace is not used).  hist: len, rank and the column scan -> rank, tab, hist.  maps, once the plan is on the device: pack_off,
+// doc_row, doc_col, row_docs, seg_off.  fill: the R rows.
+constexpr int GZ_FIT_TILE = 1024;       // documents per tile of the rank pass
+constexpr int GZ_FIT_MAX_LEN = 4096;    // = GZ_PACK_FIT_MAX_LEN: the histogram, the tiles' length tables and the plan are sized by max_len
+struct GzFitArgs {
+    GzPackArgs P;                                                   // (P.row_docs and P.fit_rows are set by the fill's launcher)
+    int32_t* row_docs;                                              // [n_rows]
+    int32_t* rank; int32_t* tab; int32_t* hist;                     // [n_rows], [gz_fit_tiles * (max_len + 1)], [max_len + 1]
+    const GzFitEvent* ev; const int32_t* ev_off; const GzFitSeg* seg; int32_t n_seg;       // the plan: ev_off [max_len + 2], seg with its closing entry
+    int64_t R;
+};
+inline int64_t gz_fit_tiles(int64_t n_rows) { return (n_rows + GZ_FIT_TILE - 1) / GZ_FIT_TILE; }
+void gz_launch_packfit_hist(const GzFitArgs& F, hipStream_t s);
+void gz_launch_packfit_maps(const GzFitArgs& F, hipStream_t s);
+void gz_launch_packfit_fill(const GzFitArgs& F, hipStream_t s);
 
 // masked-LM inputs and labels over dense rows (gz_mask.inc): one launch; ids, out_ids and labels are [n_rows, row_len] and disjoint
 constexpr int GZ_MASK_LDS_MAX_BYTES = 48 * 1024;      // the continuation bitmap goes to LDS up to this size (393 216 ids)

@@ -713,6 +713,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_window.inc"
 #include "gz_pairwin.inc"
 #include "gz_packrows.inc"
+#include "gz_packfit.inc"
 #include "gz_mask.inc"
 #include "gz_infill.inc"
 #include "gz_pieces.inc"
@@ -853,6 +854,47 @@ void gz_launch_pack_fill(const GzPackArgs& A, hipStream_t s)
                            reinterpret_cast<uintptr_t>(A.out_pos);
     if (A.max_len % 4 == 0 && (bits & 15) == 0) hipLaunchKernelGGL(gz_pack_fill_kernel<4>, grid, block, 0, s, A);
     else hipLaunchKernelGGL(gz_pack_fill_kernel<1>, grid, block, 0, s, A);
+}
+
+void gz_launch_packfit_hist(const GzFitArgs& F, hipStream_t s)
+{
+    const GzPackArgs& A = F.P;
+    if (A.n_rows <= 0) return;
+    const int32_t n = (int32_t)A.n_rows, L = A.max_len;
+    int32_t nbits = 1;
+    while ((1 << nbits) <= L) ++nbits;                                     // bits of a len (<= L)
+    const unsigned tiles = (unsigned)gz_fit_tiles(A.n_rows);
+    hipLaunchKernelGGL(gz_pack_len_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A.row_off, n, L - 2, A.skip_front + A.skip_back,
+                       A.len64, A.doc_len);
+    hipLaunchKernelGGL(gz_packfit_rank_kernel, dim3(tiles), dim3(256), (size_t)8 * (L + 1), s, (const int32_t*)A.doc_len, n, L, nbits, F.tab, F.rank);
+    hipLaunchKernelGGL(gz_packfit_cols_kernel, dim3((unsigned)(L + 1 + WAVE - 1) / WAVE), dim3(1024), 0, s, F.tab, (int32_t)tiles, L + 1, F.hist);
+}
+
+void gz_launch_packfit_maps(const GzFitArgs& F, hipStream_t s)
+{
+    const GzPackArgs& A = F.P;
+    if (A.n_rows <= 0) return;
+    const int32_t n = (int32_t)A.n_rows;
+    const dim3 per_doc((unsigned)((A.n_rows + 255) / 256)), block(256);
+    hipLaunchKernelGGL(gz_packfit_rows_kernel, dim3((unsigned)(F.R / 256 + 1)), block, 0, s, F.seg, F.n_seg, F.R, A.pack_off);
+    hipLaunchKernelGGL(gz_packfit_place_kernel, per_doc, block, 0, s, (const int32_t*)A.doc_len, (const int32_t*)F.rank, (const int32_t*)F.tab, n,
+                       A.max_len, F.R, F.ev, F.ev_off, (const int64_t*)A.pack_off, A.doc_row, A.doc_col, F.row_docs);
+    if (!A.seg_off) return;
+    hipLaunchKernelGGL(gz_packfit_seglen_kernel, per_doc, block, 0, s, (const int32_t*)A.doc_len, (const int32_t*)F.row_docs, n, A.len64);
+    launch_scan64((const int64_t*)A.len64, A.n_rows, A.seg_off, s);
+}
+
+void gz_launch_packfit_fill(const GzFitArgs& F, hipStream_t s)
+{
+    GzPackArgs A = F.P;
+    if (A.n_rows <= 0 || F.R <= 0) return;
+    A.row_docs = F.row_docs; A.fit_rows = F.R;
+    const dim3 grid((unsigned)((A.n_rows + PK_FD - 1) / PK_FD)), block(PK_FD);
+    // the rule of gz_launch_pack_fill: 16 bytes a thread where every row starts on a 16-byte boundary; one cell a thread otherwise
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(A.out_ids) | reinterpret_cast<uintptr_t>(A.out_mask) | reinterpret_cast<uintptr_t>(A.out_seg) |
+                           reinterpret_cast<uintptr_t>(A.out_pos);
+    if (A.max_len % 4 == 0 && (bits & 15) == 0) hipLaunchKernelGGL((gz_pack_fill_kernel<4, true>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((gz_pack_fill_kernel<1, true>), grid, block, 0, s, A);
 }
 
 // The division of the dense-row launches (masked rows, infill rows), written into A: about 4096 cells a wave (a long row: one wave a

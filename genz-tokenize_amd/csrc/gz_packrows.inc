@@ -185,7 +185,9 @@ __global__ __launch_bounds__(256) void gz_pack_col_kernel(const int64_t* __restr
 }
 
 // U cells per thread and store: 4 (rows and base pointers 16-byte aligned) or 1 (any L)
-template <int U>
+// FIT (best-fit order, gz_packfit.inc): the same cells over the PACKED slots -- slot d is document A.row_docs[d], the maps are
+// complete, and the host knows R = A.fit_rows and has checked the capacity before the launch.
+template <int U, bool FIT = false>
 __global__ __launch_bounds__(PK_FD) void gz_pack_fill_kernel(GzPackArgs A)
 {
     // documents d0 .. d0 + PK_FD + PK_AL / 2 - 1: a cell less than PK_AL behind document d0 + PK_FD's first can belong to PK_AL / 2
@@ -193,14 +195,26 @@ __global__ __launch_bounds__(PK_FD) void gz_pack_fill_kernel(GzPackArgs A)
     constexpr int ND = PK_FD + PK_AL / 2 + 1;
     __shared__ int64_t P[ND], src[ND];                                     // the document's first cell in the flat output, its body in ids
     __shared__ int32_t ln[ND], sg[ND];                                     // its len, its index within its row
-    const int64_t n_pack = *A.total;                                       // (from the maps' pass on this stream: the host has not seen it yet)
-    if (n_pack > A.capacity) return;                                       // the caller's arrays are too small: nothing is written, the host reports it
+    int64_t n_pack;
+    if constexpr (FIT) n_pack = A.fit_rows;
+    else {
+        n_pack = *A.total;                                                 // (from the maps' pass on this stream: the host has not seen it yet)
+        if (n_pack > A.capacity) return;                                   // the caller's arrays are too small: nothing is written, the host reports it
+    }
     const int64_t d0 = (int64_t)blockIdx.x * PK_FD, L = A.max_len, end = n_pack * L;
     for (int k = threadIdx.x; k < ND; k += PK_FD) {
         const int64_t d = d0 + k;
         int64_t p = end, s = 0;
         int32_t l = 0, q = 0;
-        if (d < A.n_rows) {
+        if constexpr (FIT) {
+            if (d < A.n_rows) {
+                const int32_t doc = A.row_docs[d], row = A.doc_row[doc];
+                p = row * L + A.doc_col[doc];
+                l = A.doc_len[doc];
+                s = A.row_off[doc] + A.skip_front;
+                q = (int32_t)(d - A.pack_off[row]);
+            }
+        } else if (d < A.n_rows) {
             const int32_t row = A.doc_row[d];
             const int64_t head = A.pack_off[row], at = A.seg_off[d];
             const int32_t col = (int32_t)(at - A.seg_off[head]);

@@ -474,6 +474,149 @@ try {
     return staged_copy_out(c, S);
 } GZ_CATCH(c)
 
+// ---- best-fit packing: short documents packed into FULL rows of max_len ----------------------------------------------------
+namespace {
+// The maps of a batch in best-fit order on the context's stream, behind whatever it holds (gz_packfit.inc): the histogram comes down
+// through the pinned block (the first wait), the plan of gz_packfit.h runs on the host, the events and the final segments go up
+// through the library's pinned staging, then pack_off, doc_row, doc_col, row_docs and seg_off (when F.P.seg_off is given) and, with
+// `fill` and R <= F.P.capacity, the rows; the second wait is for all of that.  A map the caller does not take lives in the
+// workspace (pack_off is the caller's).  *total = R, known from the plan.
+int fit_maps_locked(gz_ctx* c, GzFitArgs& F, int64_t* total, bool fill)
+{
+    if (!c->have_tables) return fail(c, GZ_E_NOTABLES, "gz_load_tables has not been called");
+    HIPCHK(c, hipSetDevice(c->device));
+    GzPackArgs& A = F.P;
+    const int64_t n = A.n_rows;
+    const int32_t L = A.max_len;
+    int rc;
+    *total = 0;
+    if (n <= 0) {
+        HIPCHK(c, hipMemsetAsync(A.pack_off, 0, 8, c->stream));
+        if (A.seg_off) HIPCHK(c, hipMemsetAsync(A.seg_off, 0, 8, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return GZ_OK;
+    }
+    if (!A.doc_row) { if ((rc = ensure(c, c->w_pk_drow, (size_t)(n + 1) * 4))) return rc; A.doc_row = (int32_t*)c->w_pk_drow.p; }
+    if (!A.doc_col) { if ((rc = ensure(c, c->w_pk_dcol, (size_t)(n + 1) * 4))) return rc; A.doc_col = (int32_t*)c->w_pk_dcol.p; }
+    if (!A.doc_len) { if ((rc = ensure(c, c->w_pf_dlen, (size_t)(n + 1) * 4))) return rc; A.doc_len = (int32_t*)c->w_pf_dlen.p; }
+    if (!F.row_docs) { if ((rc = ensure(c, c->w_pf_rdocs, (size_t)(n + 1) * 4))) return rc; F.row_docs = (int32_t*)c->w_pf_rdocs.p; }
+    const size_t W = (size_t)L + 1, tiles = (size_t)gz_fit_tiles(n);
+    if ((rc = ensure(c, c->w_pk_len, (size_t)(n + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->w_pf_rank, (size_t)(n + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->w_pf_tab, (tiles + 1) * W * 4))) return rc;
+    A.len64 = (int64_t*)c->w_pk_len.p;
+    F.rank = (int32_t*)c->w_pf_rank.p; F.tab = (int32_t*)c->w_pf_tab.p; F.hist = F.tab + tiles * W;
+    A.bos_id = c->dev.bos_id; A.eos_id = c->dev.eos_id; A.pad_id = c->dev.pad_id;
+    gz_launch_packfit_hist(F, c->stream);
+    int32_t* const h = c->pin->fit_hist;
+    HIPCHK(c, hipMemcpyAsync(h, F.hist, W * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    GzFitPlan& plan = c->fit_plan;                                         // (the context's: its tables keep their capacity from call to call)
+    alloc_site(c);
+    const auto t0 = std::chrono::steady_clock::now();
+    gz_packfit_plan(h, L, plan);
+    c->fit_plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->fit_events = (int64_t)plan.ev.size(); c->fit_segments = (int64_t)plan.seg.size() - 1;
+    // events, ev_off and segments in ONE host block and one upload (16-byte aligned parts)
+    const size_t ev_raw = plan.ev.size() * sizeof(GzFitEvent), off_raw = (W + 1) * 4, seg_bytes = plan.seg.size() * sizeof(GzFitSeg);
+    const size_t ev_bytes = (ev_raw + 15) & ~(size_t)15, off_bytes = (off_raw + 15) & ~(size_t)15;
+    std::vector<uint8_t>& up = c->fit_upload;
+    up.assign(ev_bytes + off_bytes + seg_bytes, 0);
+    if (ev_raw) std::memcpy(up.data(), plan.ev.data(), ev_raw);
+    std::memcpy(up.data() + ev_bytes, plan.ev_off.data(), off_raw);
+    std::memcpy(up.data() + ev_bytes + off_bytes, plan.seg.data(), seg_bytes);
+    if ((rc = ensure(c, c->w_pf_plan, up.size()))) return rc;
+    uint8_t* const d_plan = (uint8_t*)c->w_pf_plan.p;
+    if ((rc = copy_in(c, d_plan, up.data(), up.size(), c->stream))) return rc;
+    F.ev = (const GzFitEvent*)d_plan; F.ev_off = (const int32_t*)(d_plan + ev_bytes); F.seg = (const GzFitSeg*)(d_plan + ev_bytes + off_bytes);
+    F.n_seg = (int32_t)plan.seg.size(); F.R = plan.R;
+    *total = plan.R;
+    gz_launch_packfit_maps(F, c->stream);
+    if (fill && plan.R <= A.capacity) gz_launch_packfit_fill(F, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return GZ_OK;
+}
+
+const char* const kFitRule = "best-fit packed rows need max_len <= 4096";
+}  // namespace
+
+int gz_pack_rows_fit_device(gz_ctx* c, const int32_t* ids_dev, const int64_t* row_off_dev, int64_t n_rows, int32_t max_len, int32_t skip_front,
+                            int32_t skip_back, int32_t* input_ids_dev, int32_t* attention_mask_dev, int32_t* segment_ids_dev,
+                            int32_t* position_ids_dev, int32_t* doc_row_dev, int32_t* doc_col_dev, int32_t* doc_len_dev, int32_t* row_docs_dev,
+                            int64_t* pack_off_dev, int64_t* seg_off_dev, int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off_dev || !pack_off_dev || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    if (max_len > GZ_PACK_FIT_MAX_LEN) return fail(c, GZ_E_INVALID, "%s", kFitRule);
+    std::lock_guard<std::mutex> lk(c->mu);
+    GzFitArgs F{};
+    GzPackArgs& A = F.P;
+    A.ids = ids_dev; A.row_off = row_off_dev; A.n_rows = n_rows; A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.doc_row = doc_row_dev; A.doc_col = doc_col_dev; A.doc_len = doc_len_dev; A.pack_off = pack_off_dev; A.seg_off = seg_off_dev;
+    F.row_docs = row_docs_dev;
+    A.capacity = capacity_rows;
+    A.out_ids = input_ids_dev; A.out_mask = attention_mask_dev; A.out_seg = segment_ids_dev; A.out_pos = position_ids_dev;
+    int rc;
+    if ((rc = fit_maps_locked(c, F, total_host, input_ids_dev != nullptr))) return rc;
+    if (!input_ids_dev || *total_host <= capacity_rows) return GZ_OK;
+    return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)*total_host, (long long)capacity_rows);
+} GZ_CATCH(c)
+
+int gz_pack_rows_fit_info(gz_ctx* c, double* plan_ms, int64_t* events, int64_t* segments)
+try {
+    if (!c) return GZ_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (plan_ms) *plan_ms = c->fit_plan_ms;
+    if (events) *events = c->fit_events;
+    if (segments) *segments = c->fit_segments;
+    return GZ_OK;
+} GZ_CATCH(c)
+
+int gz_pack_rows_fit(gz_ctx* c, const int32_t* ids, const int64_t* row_off, int64_t n_rows, int32_t max_len, int32_t skip_front, int32_t skip_back,
+                     int32_t* input_ids, int32_t* attention_mask, int32_t* segment_ids, int32_t* position_ids, int32_t* doc_row, int32_t* doc_col,
+                     int32_t* doc_len, int32_t* row_docs, int64_t* pack_off, int64_t* seg_off, int64_t capacity_rows, int64_t* total_host)
+try {
+    if (!c || !row_off || !pack_off || !total_host || n_rows < 0 || capacity_rows < 0)
+        return c ? fail(c, GZ_E_INVALID, "bad arguments") : GZ_E_INVALID;
+    if (!pack_rule_ok(n_rows, max_len, skip_front, skip_back)) return fail(c, GZ_E_INVALID, "%s", kPackRule);
+    if (max_len > GZ_PACK_FIT_MAX_LEN) return fail(c, GZ_E_INVALID, "%s", kFitRule);
+    RowsIn in{ids, row_off, n_rows, 4};
+    int rc;
+    if ((rc = rows_check(c, in, kRowWords))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = rows_stage(c, in, (size_t)(n_rows + 1) * 8))) return rc;               // kept through both passes: pack_off
+    GzFitArgs F{};
+    GzPackArgs& A = F.P;
+    A.ids = (const int32_t*)in.d_payload; A.row_off = in.d_off; A.n_rows = n_rows;
+    A.max_len = max_len; A.skip_front = skip_front; A.skip_back = skip_back;
+    A.pack_off = (int64_t*)in.d_keep;                                                 // (the other maps: the workspace's)
+    if (seg_off) { if ((rc = ensure(c, c->w_pk_seg, (size_t)(n_rows + 1) * 8))) return rc; A.seg_off = (int64_t*)c->w_pk_seg.p; }
+    int64_t total = 0;
+    if ((rc = fit_maps_locked(c, F, &total, false))) return rc;
+    *total_host = total;
+    if ((rc = copy_out(c, pack_off, A.pack_off, (size_t)(total + 1) * 8, c->stream))) return rc;
+    if (seg_off && (rc = copy_out(c, seg_off, A.seg_off, (size_t)(n_rows + 1) * 8, c->stream))) return rc;
+    if (doc_row && (rc = copy_out(c, doc_row, A.doc_row, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_col && (rc = copy_out(c, doc_col, A.doc_col, (size_t)n_rows * 4, c->stream))) return rc;
+    if (doc_len && (rc = copy_out(c, doc_len, A.doc_len, (size_t)n_rows * 4, c->stream))) return rc;
+    if (row_docs && (rc = copy_out(c, row_docs, F.row_docs, (size_t)n_rows * 4, c->stream))) return rc;
+    if (!input_ids) return GZ_OK;
+    if (total > capacity_rows)
+        return fail(c, GZ_E_CAPACITY, "the batch makes %lld packed rows, capacity is %lld", (long long)total, (long long)capacity_rows);
+    if (total == 0) return GZ_OK;
+    const size_t cells = (size_t)total * (size_t)max_len * 4;
+    StagedOut S;
+    S.add(input_ids, cells, true); S.add(attention_mask, cells, true); S.add(segment_ids, cells, true); S.add(position_ids, cells, true);
+    if ((rc = staged_ensure(c, S))) return rc;
+    A.capacity = total;
+    A.out_ids = S.dev(0); A.out_mask = S.dev(1); A.out_seg = S.dev(2); A.out_pos = S.dev(3);
+    gz_launch_packfit_fill(F, c->stream);
+    return staged_copy_out(c, S);
+} GZ_CATCH(c)
+
 // ---- masked-LM inputs and labels over dense rows -------------------------------------------------------------------------
 namespace {
 struct MaskRule {

@@ -59,6 +59,7 @@ SYMBOLS = [
     "gz_word_spans", "gz_word_spans_device", "gz_align_rows", "gz_align_rows_device", "gz_span_labels", "gz_span_labels_device",
     "gz_ngram_repeats", "gz_ngram_repeats_device",
     "gz_pair_window_rows", "gz_pair_window_rows_device", "gz_span_tokens", "gz_span_tokens_device",
+    "gz_pack_rows_fit", "gz_pack_rows_fit_device", "gz_pack_rows_fit_info",
 ]
 
 _lib = None
@@ -118,6 +119,11 @@ def load_library():
     pk = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, P(i64)]
     L.gz_pack_rows.argtypes = pk
     L.gz_pack_rows_device.argtypes = pk
+    if hasattr(L, "gz_pack_rows_fit"):
+        pf = pk[:14] + [vp] + pk[14:]                                  # ... plus row_docs in front of pack_off
+        L.gz_pack_rows_fit.argtypes = pf
+        L.gz_pack_rows_fit_device.argtypes = pf
+        L.gz_pack_rows_fit_info.argtypes = [vp, P(C.c_double), P(i64), P(i64)]
     if hasattr(L, "gz_mask_rows"):
         u64 = C.c_uint64
         mk = [vp, vp, i64, i32, i64, u64, u64, u64, u64, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -741,6 +747,34 @@ class Context:
         """gz_pack_rows_device: returns R.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = R."""
         opt = _dptrs(d_input_ids, d_mask, d_seg, d_pos, d_doc_row, d_doc_col, d_doc_len)
         return self._call_total(self.lib.gz_pack_rows_device, self.handle, *_dptrs(d_ids), C.c_void_p(d_row_off), n_rows, max_len, skip_front,
+                                skip_back, *opt, C.c_void_p(d_pack_off), *_dptrs(d_seg_off), capacity)
+
+    # ---- best-fit packing -----------------------------------------------------------------------------------
+    def pack_rows_fit(self, ids: np.ndarray, row_off: np.ndarray, max_len: int, framed: bool):
+        """`pack_rows` in best-fit order (gz_pack_rows_fit): the same dict plus row_docs int32 [n], the documents in packed order;
+        row_off int64 [R+1] indexes row_docs, seg_off int64 [n+1] is the scan of doc_len[row_docs]."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, L, skip = len(row_off) - 1, int(max_len), 1 if framed else 0
+        maps = dict(doc_row=np.empty(n, dtype=np.int32), doc_col=np.empty(n, dtype=np.int32), doc_len=np.empty(n, dtype=np.int32),
+                    row_docs=np.empty(n, dtype=np.int32), row_off=np.zeros(n + 1, dtype=np.int64), seg_off=np.zeros(n + 1, dtype=np.int64))
+        total = C.c_int64()
+        head = (self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), n, L, skip, skip)
+        tail = tuple(_ptr(maps[k]) for k in ("doc_row", "doc_col", "doc_len", "row_docs", "row_off", "seg_off"))
+        self._check(self.lib.gz_pack_rows_fit(*head, None, None, None, None, *tail, 0, C.byref(total)))
+        R = total.value
+        out = {k: np.empty((R, L), dtype=np.int32) for k in ("input_ids", "attention_mask", "segment_ids", "position_ids")}
+        if R:
+            self._check(self.lib.gz_pack_rows_fit(*head, *[_ptr(v) for v in out.values()], *tail, R, C.byref(total)))
+        out.update(maps)
+        out["row_off"] = maps["row_off"][:R + 1].copy()
+        return out
+
+    def pack_rows_fit_device(self, d_ids, d_row_off, n_rows, max_len, skip_front, skip_back, d_input_ids, d_mask, d_seg, d_pos, d_doc_row,
+                             d_doc_col, d_doc_len, d_row_docs, d_pack_off, d_seg_off, capacity) -> int:
+        """gz_pack_rows_fit_device: returns R.  d_input_ids == 0 sizes only; on GZ_E_CAPACITY the GzError carries `.total` = R."""
+        opt = _dptrs(d_input_ids, d_mask, d_seg, d_pos, d_doc_row, d_doc_col, d_doc_len, d_row_docs)
+        return self._call_total(self.lib.gz_pack_rows_fit_device, self.handle, *_dptrs(d_ids), C.c_void_p(d_row_off), n_rows, max_len, skip_front,
                                 skip_back, *opt, C.c_void_p(d_pack_off), *_dptrs(d_seg_off), capacity)
 
     # ---- masked-LM inputs and labels ------------------------------------------------------------------------

@@ -400,6 +400,55 @@ int  gz_pack_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row
                          int32_t *doc_row_dev, int32_t *doc_col_dev, int32_t *doc_len_dev, int64_t *pack_off_dev, int64_t *seg_off_dev,
                          int64_t capacity_rows, int64_t *total_host);
 
+/* ---- best-fit packing: short documents packed into FULL rows of max_len ("sequence packing", best-fit-decreasing) ----------
+ * gz_pack_rows keeps the documents' order and pays for it with padding.  These calls place the same segments by
+ * best-fit-decreasing on their lengths (Krell et al., 2021) and fill the rows almost completely; the output is still dense
+ * [R, L] rows with segment ids, so everything behind a pack call composes unchanged.  seg_r and len_r are gz_pack_rows' own:
+ *     seg_r = [bos] + body[:min(T, L-2)] + [eos],   len_r = min(T, L-2) + 2      (2 <= len_r <= L)
+ * The rule, with L = max_len in [3, GZ_PACK_FIT_MAX_LEN]:
+ *   Take the documents in the order (len descending, index ascending).
+ *   Rows are numbered in the order they are opened.  A row carries free (L at first) and stamp (the time of its last
+ *   placement, a counter t that goes up by one per placed document).
+ *   A document of length l goes into the row with the smallest (free, stamp) among the rows with free >= l; if there is none
+ *   it opens row R, and R += 1.
+ *   Then doc_row = row, doc_col = L - free, free -= l, stamp = ++t.
+ * The result depends on the lengths and the documents' order alone, never on timing: a document's place follows from its rank
+ * among the documents of its length, by index.  Rows come out ordered from the longest documents to the shortest.
+ *   input_ids, attention_mask, segment_ids, position_ids [R, L]    as gz_pack_rows: the segments of a row back to back in column
+ *                         order, then the pad id; mask = input_ids != pad; segment_ids = 1 + the document's position within its
+ *                         row, 0 in the tail only; position_ids = column - doc_col, 0 in the tail
+ *   doc_row, doc_col, doc_len [n_rows] int32, indexed by document
+ *   row_docs [n_rows]     int32: the document indices sorted by (doc_row, doc_col) -- the packed order
+ *   pack_off              int64: packed row i holds documents row_docs[pack_off[i] .. pack_off[i+1]), in column order.  R + 1
+ *                         entries are written; the array must hold n_rows + 1
+ *   seg_off [n_rows+1]    int64: the exclusive scan of doc_len[row_docs[.]] -- the cumulative sequence lengths in the order the
+ *                         segments lie in the rows, which is what variable-length attention takes
+ *   *total_host = R on GZ_OK and on GZ_E_CAPACITY.  input_ids == NULL sizes only: the maps and *total_host are filled.  When
+ *   R > capacity_rows the call returns GZ_E_CAPACITY: the maps are valid and nothing is written to the four cell arrays.
+ *   attention_mask, segment_ids, position_ids, doc_row, doc_col, doc_len, row_docs and seg_off may each be NULL.  GZ_E_INVALID:
+ *   gz_pack_rows' conditions, and max_len > GZ_PACK_FIT_MAX_LEN (the length histogram and the plan are sized by max_len; longer
+ *   rows are refused, not handled slowly).
+ * gz_pack_rows_fit_device: every pointer but total_host is a DEVICE pointer; offsets are ABSOLUTE from the base pointer.
+ *   Ordering: as gz_pack_rows_device -- all passes run on the context's stream, behind a gz_encode_batch_device (ragged layout)
+ *   enqueued just before with no gz_sync in between.  The call waits for the device twice: for the length histogram (the
+ *   sequential decisions are made on the host, over at most max_len bins), and when the rows are complete.
+ * gz_pack_rows_fit: host pointers, through the library's pinned staging like gz_pack_rows.
+ * gz_pack_rows_fit_info: the host plan of the context's last best-fit call over a non-empty batch -- its time in milliseconds, its
+ *   events and its final segments (zeros before the first); each pointer may be NULL.
+ * Not here: pair texts, max_len > 4096, the windows of over-long documents, 16-bit outputs. */
+#define GZ_PACK_FIT_MAX_LEN 4096
+int  gz_pack_rows_fit(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows,
+                      int32_t max_len, int32_t skip_front, int32_t skip_back,
+                      int32_t *input_ids, int32_t *attention_mask, int32_t *segment_ids, int32_t *position_ids,
+                      int32_t *doc_row, int32_t *doc_col, int32_t *doc_len, int32_t *row_docs, int64_t *pack_off, int64_t *seg_off,
+                      int64_t capacity_rows, int64_t *total_host);
+int  gz_pack_rows_fit_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                             int32_t max_len, int32_t skip_front, int32_t skip_back,
+                             int32_t *input_ids_dev, int32_t *attention_mask_dev, int32_t *segment_ids_dev, int32_t *position_ids_dev,
+                             int32_t *doc_row_dev, int32_t *doc_col_dev, int32_t *doc_len_dev, int32_t *row_docs_dev,
+                             int64_t *pack_off_dev, int64_t *seg_off_dev, int64_t capacity_rows, int64_t *total_host);
+int  gz_pack_rows_fit_info(gz_ctx *ctx, double *plan_ms, int64_t *events, int64_t *segments);
+
 /* ---- masked-LM inputs and labels over dense rows, whole-word ----------------------------------------------------------------
  * The reference reserves <mask> as id 3 (tokenize.py:11, :35) and never produces it.  These calls take dense [n_rows, row_len]
  * int32 rows -- the input_ids of an encode, window or pack call -- and make the inputs and labels of masked-language-model

@@ -1,7 +1,7 @@
 """Short documents packed into rows of max_len (gz_pack_rows_device, csrc/gz_packrows.inc) on the configs[2] corpus, the host route it
 replaces, and the window call over the same rows.
 
-    python tools/pack_bench.py [--docs 1000000] [--reps 5] [--host-reps 3] [--out profiles/pack_bench.json]
+    python tools/pack_bench.py [--docs 1000000] [--reps 5] [--host-reps 3] [--order kept|fit] [--out profiles/pack_bench.json]
 
 The corpus (corpus.config_corpus(3, n_docs=--docs)) is encoded once on the device without a length limit; the ragged rows stay
 in HBM.  For max_len in (128, 256), host clock around the call plus gz_sync, after a warm-up call, median of --reps:
@@ -16,7 +16,13 @@ and, in the same run, the only route there was before (median of --host-reps):
   host_encode_ms       encode_packed(max_len=None): the ragged rows into host memory
   host_rule_ms         the rule on the host: the break chain with bisect over the scanned lengths, the cells with numpy
   host_route_ms        their sum;  speedup = host_route_ms / pack_device_ms
-The host arrays are compared with the device's once per shape (checked: true).  One JSON line on stdout."""
+The host arrays are compared with the device's once per shape (checked: true).  One JSON line on stdout.
+--order fit adds, per max_len and in the same run, on the same resident rows and with the same clocking (a "fit" object in the row):
+  rows, fill_ratio     R and sum(len) / (R L) of gz_pack_rows_fit_device (best-fit order, csrc/gz_packfit.inc)
+  rows_ok              rows <= the kept order's rows: the one hard condition; the exit status is 1 where it does not hold
+  device_ms, maps_ms   the whole call and the sizing call; over_kept = device_ms / pack_device_ms (the bar: at most 1.25)
+  plan_ms, events, segments   the host plan alone (gz_pack_rows_fit_info after the last call)
+  checked_4096         the first 4 096 documents as a batch of their own: every array equals tests/packfit_oracle.py's"""
 import argparse
 import bisect
 import json
@@ -74,11 +80,50 @@ def median_ms(fn, reps):
     return float(np.median(ts)), [round(t, 3) for t in ts]
 
 
+def fit_row(ctx, tok, d_ids, d_ro, row_off, n, L, maps, d_po, d_so, sum_len, kept_ms, reps, special):
+    """The best-fit call on the same resident rows: R, fill, the call, the sizing call, the plan's host time, the events."""
+    import ctypes
+    d_rd = ctx.alloc(4 * n)
+    R = ctx.pack_rows_fit_device(d_ids, d_ro, n, L, 1, 1, 0, 0, 0, 0, *maps, d_rd, d_po, d_so, 0)
+    d_out = [ctx.alloc(4 * R * L) for _ in range(4)]
+
+    def device():
+        ctx.pack_rows_fit_device(d_ids, d_ro, n, L, 1, 1, *d_out, *maps, d_rd, d_po, d_so, R)
+        ctx.sync()
+
+    def sizing():
+        ctx.pack_rows_fit_device(d_ids, d_ro, n, L, 1, 1, 0, 0, 0, 0, *maps, d_rd, d_po, d_so, 0)
+        ctx.sync()
+    device()
+    dev_ms, dev_all = median_ms(device, reps)
+    sizing()
+    map_ms, map_all = median_ms(sizing, reps)
+    plan_ms, events, segments = ctypes.c_double(), ctypes.c_int64(), ctypes.c_int64()
+    ctx._check(ctx.lib.gz_pack_rows_fit_info(ctx.handle, ctypes.byref(plan_ms), ctypes.byref(events), ctypes.byref(segments)))
+    for d in d_out + [d_rd]:
+        ctx.free(d)
+    # the first 4 096 documents as a batch of their own, against the sequential rule
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import packfit_oracle as FO
+    m = min(n, 4096)
+    ids = np.empty(int(row_off[m] - row_off[0]), dtype=np.int32)
+    ctx.d2h(ids, d_ids + 4 * int(row_off[0]))
+    framed = [ids[row_off[r] - row_off[0]:row_off[r + 1] - row_off[0]].tolist() for r in range(m)]
+    pad, bos, eos = special
+    got = tok.pack_rows(framed, L, framed=True, order="fit")
+    want = FO.batch([r[1:-1] for r in framed], L, bos, eos, pad, fast=True)
+    checked = sorted(got) == sorted(want) and all(np.array_equal(got[k], want[k]) for k in want)
+    return {"rows": int(R), "fill_ratio": round(sum_len / (R * L), 4), "device_ms": round(dev_ms, 3), "device_all_ms": dev_all,
+            "maps_ms": round(map_ms, 3), "maps_all_ms": map_all, "fill_ms": round(dev_ms - map_ms, 3), "plan_ms": round(plan_ms.value, 4),
+            "events": int(events.value), "segments": int(segments.value), "over_kept": round(dev_ms / kept_ms, 3), "checked_4096": bool(checked)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-reps", type=int, default=3)
+    ap.add_argument("--order", choices=("kept", "fit"), default="kept")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import corpus
@@ -169,11 +214,16 @@ def main():
             rec.update({"host_encode_ms": round(enc_ms, 1), "host_rule_ms": round(rule_ms, 1), "host_rule_all_ms": rule_all,
                         "host_route_ms": round(enc_ms + rule_ms, 1), "speedup": round((enc_ms + rule_ms) / dev_ms, 1), "checked": checked})
             del res, got
+        if args.order == "fit":
+            rec["fit"] = fit_row(ctx, tok, d_ids, d_ro, row_off, n, L, maps, d_po, d_so, sum_len, dev_ms, args.reps, (pad, bos, eos))
+            rec["fit"]["rows_ok"] = bool(rec["fit"]["rows"] <= rec["rows"])
         rows.append(rec)
         for d in d_out:
             ctx.free(d)
         print("# L=%d R=%d pack %.3f ms (maps %.3f) window %.3f ms host %s ms" %
               (L, R, dev_ms, map_ms, win_ms, rec.get("host_route_ms")), file=sys.stderr, flush=True)
+        if "fit" in rec:
+            print("# L=%d fit %s" % (L, json.dumps(rec["fit"])), file=sys.stderr, flush=True)
     for d in (d_ids, d_ro, d_maps, d_po, d_so, d_wo):
         ctx.free(d)
     rec = {"bench": "pack", "docs": n, "body_tokens": body_tokens, "hbm_peak_gbs": HBM_PEAK_GBS, "host_encode_all_ms": enc_all, "rows": rows}
@@ -182,7 +232,7 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
-    return 0 if all(r.get("checked", True) for r in rows) else 1
+    return 0 if all(r.get("checked", True) and r.get("fit", {}).get("checked_4096", True) and r.get("fit", {}).get("rows_ok", True) for r in rows) else 1
 
 
 if __name__ == "__main__":
