@@ -212,6 +212,7 @@ struct gz_ctx {
     DBuf w_ng_aux;                       // n-gram overlap: the distinct counter, first_hit where the caller takes only first_ref
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
+    DBuf w_q[8];                         // text quality signals: control words, counts, scans, span halves, table, long list, staged text and outputs (gz_quality_api.inc, QW_*)
     DBuf w_al[16];                       // word spans, aligned rows, span labels: scans, scratch and staged inputs (gz_rows_api.inc, ALW_*)
     DBuf w_pw_cnt, w_pw_tok;             // pair windows: window counts and q of every pair; span tokens: the counts as 64-bit words and their scan
 };
@@ -1102,6 +1103,7 @@ try {
     for (DBuf* b : {&c->w_pf_rank, &c->w_pf_tab, &c->w_pf_plan, &c->w_pf_rdocs, &c->w_pf_dlen}) release(*b);
     for (DBuf* b : {&c->w_pieces, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_aux, &c->w_rp_tab, &c->w_rp_top}) release(*b);
     for (auto& b : c->w_al) release(b);
+    for (auto& b : c->w_q) release(b);
     for (DBuf* b : {&c->w_pw_cnt, &c->w_pw_tok}) release(*b);
     for (DBuf* b : {&c->w_rows_in, &c->w_rows_off, &c->w_rows_out[0], &c->w_rows_out[1], &c->w_rows_out[2], &c->w_rows_out[3], &c->w_rows_small}) release(*b);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
@@ -2044,6 +2046,7 @@ try {
 #include "gz_rows_api.inc"
 #include "gz_ngram_api.inc"
 #include "gz_repeat_api.inc"
+#include "gz_quality_api.inc"
 
 // ---- text pre-pass ----------------------------------------------------------------------------------------------------
 namespace {

@@ -324,6 +324,45 @@ struct GzRepeatArgs {
 // One width: clears the table and the counts, presets the add / max cells where a row has several pieces, inserts, queries, unpacks.
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s);
 
+// text quality signals, duplicate lines and paragraphs (gz_quality.inc)
+constexpr int GZ_QUALITY_WPB = 4;                                   // documents per workgroup of the walk
+#ifndef GZ_Q_SIGNALS                                                // the rows of signals, as include/genz_tokenize.h defines them
+#define GZ_Q_N_CHARS              0
+#define GZ_Q_N_WORDS              1
+#define GZ_Q_WORD_CHARS           2
+#define GZ_Q_N_ALPHA_WORDS        3
+#define GZ_Q_N_HASH               4
+#define GZ_Q_N_ELLIPSIS           5
+#define GZ_Q_N_LINES              6
+#define GZ_Q_N_BULLET_LINES       7
+#define GZ_Q_N_ELLIPSIS_LINES     8
+#define GZ_Q_DUP_LINES            9
+#define GZ_Q_DUP_LINE_CHARS      10
+#define GZ_Q_N_PARAGRAPHS        11
+#define GZ_Q_DUP_PARAGRAPHS      12
+#define GZ_Q_DUP_PARAGRAPH_CHARS 13
+#define GZ_Q_SIGNALS             14
+#endif
+enum { GZ_QC_OFF0, GZ_QC_OFFN, GZ_QC_FLAGS, GZ_QC_LINES, GZ_QC_PARAS, GZ_QC_LONG, GZ_QC_WORDS };   // the control words (8 bytes each)
+constexpr int GZ_QUALITY_SPAN_WORDS = 12;                           // u32 arrays of n_spans entries behind sp_start (GzQualityArgs)
+struct GzQualityArgs {
+    const uint8_t* text; const int64_t* off; int64_t n_docs;        // document d = text[off[d] .. off[d + 1]) (absolute offsets), shorter than 2^31
+    int32_t* wsig; int32_t* signals;                                // [GZ_Q_SIGNALS, n_docs]: pass A's rows in the workspace; the caller's, may be null
+    uint32_t* lcnt; uint32_t* pcnt; unsigned long long* ctl;        // pass A: lines and paragraphs a document; the control words (GZ_QC_*)
+    const uint32_t* loff; const uint32_t* poff;                     // their exclusive scans [n_docs + 1]
+    int64_t n_lines, n_spans;                                       // loff[n_docs]; that + poff[n_docs]: span q < n_lines is a line, else a paragraph
+    // a span's head half, end half (byte position, characters and the two prefix polynomials at both), R^-start, document and slot
+    uint32_t* sp_start; uint32_t* sp_end; uint32_t* sp_cs; uint32_t* sp_ce; uint32_t* sp_fs1; uint32_t* sp_fs2; uint32_t* sp_fe1; uint32_t* sp_fe2;
+    uint32_t* sp_i1; uint32_t* sp_i2; uint32_t* sp_doc; uint32_t* sp_slot;
+    unsigned long long* table; uint64_t mask;                       // slots - 1 (a power of two of slots, at least twice n_spans), cleared
+    unsigned long long hmask;                                       // hash bits kept (switch quality_hash_bits)
+    uint32_t* long_list;                                            // the spans a wave inserts; ctl[GZ_QC_LONG] counts them
+    int64_t* line_span; int32_t* line_first; int64_t* para_span; int32_t* para_first;      // each may be null
+};
+inline uint64_t gz_quality_slots(int64_t n_spans) { uint64_t cap = 16; while (cap < 2 * (uint64_t)n_spans) cap <<= 1; return cap; }
+void gz_launch_quality_count(const GzQualityArgs& A, hipStream_t s);
+void gz_launch_quality_spans(const GzQualityArgs& A, int64_t long_max, hipStream_t s);
+
 // word spans, word ids and aligned labels (gz_align.inc)
 constexpr int64_t GZ_SPAN_BLOCK = 4096;                            // bytes of packed text per block of the span kernels
 inline int64_t gz_span_blocks(int64_t text_bytes) { return (text_bytes + GZ_SPAN_BLOCK - 1) / GZ_SPAN_BLOCK; }

@@ -722,6 +722,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_repeat.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
+#include "gz_quality.inc"
 #include "gz_topk.inc"
 #include "gz_vocab.inc"
 #include "gz_search.inc"

@@ -206,3 +206,29 @@ inline bool disjoint(const Span* s, int k)
         }
     return true;
 }
+
+// Text quality signals (gz_text_signals*; tests/test_quality_inputs.py compiles these alone, under the sanitizers): the outputs of
+// a call, each may be null, and the sentence of the first rule an argument list breaks, or nullptr, in the order they are reported
+// in.  quality_disjoint comes once the call knows its lines and paragraphs, still before anything of the caller's is written.
+struct QualityOut { int32_t* signals; uint32_t* line_off; int64_t* line_span; int32_t* line_first; uint32_t* para_off; int64_t* para_span; int32_t* para_first; };
+inline const char* quality_fault(int64_t n_docs, const void* text, const void* off, const QualityOut& O)
+{
+    if (n_docs < 0) return "text signals need n_docs >= 0";
+    if (n_docs == 0) return nullptr;
+    if (!text || !off) return "text signals need text and offsets";
+    if ((O.line_span || O.line_first) && !O.line_off) return "text signals write line_span and line_first only beside line_off";
+    if ((O.para_span || O.para_first) && !O.para_off) return "text signals write para_span and para_first only beside para_off";
+    return nullptr;
+}
+// text_at: the first byte of the call's text, n_bytes of them; the byte counts below do not wrap for n_docs < 2^31, spans < 2^32
+inline bool quality_disjoint(const void* text_at, uintptr_t n_bytes, const void* off, int64_t n_docs, int32_t n_signals, uint64_t n_lines, uint64_t n_paras,
+                             const QualityOut& O)
+{
+    const uintptr_t n = (uintptr_t)n_docs, L = (uintptr_t)n_lines, P = (uintptr_t)n_paras;
+    const Span s[9] = {span_of(text_at, n_bytes), span_of(off, (n + 1) * 8u), span_of(O.signals, n * (uintptr_t)n_signals * 4u),
+                       span_of(O.line_off, (n + 1) * 4u), span_of(O.line_span, L * 16u), span_of(O.line_first, L * 4u),
+                       span_of(O.para_off, (n + 1) * 4u), span_of(O.para_span, P * 16u), span_of(O.para_first, P * 4u)};
+    return disjoint(s, 9);
+}
+// lines + paragraphs of a call: a slot holds a span index in 32 bits
+inline bool quality_spans_fit(uint64_t n_lines, uint64_t n_paras) { return n_lines + n_paras < 0xFFFFFFFFull && n_lines + n_paras >= n_lines; }

@@ -24,6 +24,10 @@ GZ_BM25_GROUP_MAX = 64
 GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP_WORDS = 0x1, 0x2, 0x4, 0x100, 0x200, 0x400
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
+# the rows of gz_text_signals' signals (GZ_Q_*), in order; the walk's bytes a trip and documents a workgroup (what the tests place edges by)
+GZ_Q_NAMES = ("n_chars", "n_words", "word_chars", "n_alpha_words", "n_hash", "n_ellipsis", "n_lines", "n_bullet_lines", "n_ellipsis_lines",
+              "dup_lines", "dup_line_chars", "n_paragraphs", "dup_paragraphs", "dup_paragraph_chars")
+GZ_QUALITY_TRIP, GZ_QUALITY_WPB, GZ_QUALITY_LONG = 256, 4, 512
 
 # every symbol include/genz_tokenize.h declares (tests/test_abi.py checks the export list against the header)
 SYMBOLS = [
@@ -60,6 +64,7 @@ SYMBOLS = [
     "gz_ngram_repeats", "gz_ngram_repeats_device",
     "gz_pair_window_rows", "gz_pair_window_rows_device", "gz_span_tokens", "gz_span_tokens_device",
     "gz_pack_rows_fit", "gz_pack_rows_fit_device", "gz_pack_rows_fit_info",
+    "gz_text_signals", "gz_text_signals_device",
 ]
 
 _lib = None
@@ -265,6 +270,9 @@ def load_library():
         L.gz_pair_window_rows_device.argtypes = pw
         L.gz_span_tokens.argtypes = [vp, vp, vp, i64, vp, vp, vp]
         L.gz_span_tokens_device.argtypes = [vp, vp, vp, i64, i64, vp, vp, i64, vp]
+    if hasattr(L, "gz_text_signals"):
+        L.gz_text_signals.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.gz_text_signals_device.argtypes = L.gz_text_signals.argtypes
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -928,6 +936,32 @@ class Context:
         w = np.ascontiguousarray(widths, dtype=np.int32)
         self._check(self.lib.gz_ngram_repeats_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, _ptr(w), len(w),
                                                      *_dptrs(d_n_grams, d_n_distinct, d_n_repeated, d_n_covered, d_top_count, d_top_pos, d_covered)))
+
+    # ---- text quality signals, duplicate lines and paragraphs ----------------------------------------------------
+    def text_signals(self, text: np.ndarray, off: np.ndarray, lines: bool, paragraphs: bool):
+        """packed UTF-8, int64 offsets [n+1] -> signals int32 [14, n] and, when asked for, (line_off uint32 [n+1], line_span int64
+        [L, 2], line_first int32 [L]) and the same for paragraphs (gz_text_signals: a sizing call for the offsets, then the spans)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        if len(text) == 0:
+            text = np.zeros(1, dtype=np.uint8)
+        signals = np.zeros((len(GZ_Q_NAMES), n), dtype=np.int32)
+        offs = [np.zeros(n + 1, dtype=np.uint32) if want else None for want in (lines, paragraphs)]
+        call = lambda *outs: self._check(self.lib.gz_text_signals(self.handle, _ptr(text), _ptr(off), n, *[_ptr(o) for o in outs]))  # noqa: E731
+        if not (lines or paragraphs):
+            call(signals, None, None, None, None, None, None)
+            return signals, None, None
+        call(None, offs[0], None, None, offs[1], None, None)
+        arrays = [(o, np.zeros((int(o[n]), 2), dtype=np.int64), np.zeros(int(o[n]), dtype=np.int32)) if o is not None else (None, None, None) for o in offs]
+        call(signals, *arrays[0], *arrays[1])
+        return signals, (arrays[0] if lines else None), (arrays[1] if paragraphs else None)
+
+    def text_signals_device(self, d_text, d_off, n_docs, d_signals, d_line_off=0, d_line_span=0, d_line_first=0, d_para_off=0, d_para_span=0,
+                            d_para_first=0):
+        """gz_text_signals_device: text, offsets and outputs device addresses (0: NULL)."""
+        self._check(self.lib.gz_text_signals_device(self.handle, *_dptrs(d_text, d_off), n_docs,
+                                                    *_dptrs(d_signals, d_line_off, d_line_span, d_line_first, d_para_off, d_para_span, d_para_first)))
 
     # ---- word spans, word ids and aligned labels ----------------------------------------------------------------
     def word_spans(self, text: np.ndarray, text_off: np.ndarray, unit: int):

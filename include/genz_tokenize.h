@@ -297,6 +297,9 @@ int64_t gz_limit(int which);
  *                              (0: all of it); with k = 1 almost every probe collides in start slot and tag: results must not change
  *   repeat_hash_bits (0..32; 0)  gz_ngram_repeats* keep only the low k bits of every (row, n-gram) hash (0: all of it); with k = 1 almost
  *                              every probe collides in start slot and tag, between rows too: results must not change
+ *   quality_hash_bits (0..32; 0)  gz_text_signals* keep only the low k bits of every (kind, document, span) hash (0: all of it); with
+ *                              k = 1 almost every probe collides in start slot and tag, between documents and kinds too: results must
+ *                              not change
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -946,8 +949,8 @@ int  gz_span_tokens_device(gz_ctx *ctx, const int32_t *counts_dev, const int64_t
  * gz_ngram_repeats_device: ids, row_off and the outputs DEVICE pointers; offsets are ABSOLUTE from the base pointer and row_off_dev[0]
  *   need not be 0.  Ordering: every pass runs on the context's stream, behind a gz_encode_batch_device (ragged layout) enqueued just
  *   before with no gz_sync in between; the call returns when its outputs are complete.
- * Not here: character weighting of the shares, line and paragraph duplicates and the other Gopher heuristics (word lengths, symbol
- *   ratios, stop words), which work on text; a table in LDS for short rows; removing the repeated spans (the caller reads covered);
+ * Not here: character weighting of the shares; stop words; a table in LDS for short rows; (line and paragraph duplicates and the
+ *   other Gopher heuristics that work on text -- word lengths, symbol ratios, bullet and ellipsis lines -- are gz_text_signals, below); removing the repeated spans (the caller reads covered);
  *   repetition across documents (gz_minhash_rows, gz_ngram_index_build); multi-GPU forms (shards concatenate). */
 int  gz_ngram_repeats(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
                       const int32_t *widths, int32_t n_widths, int32_t *n_grams, int32_t *n_distinct, int32_t *n_repeated,
@@ -956,6 +959,89 @@ int  gz_ngram_repeats_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t 
                              int32_t skip_back, const int32_t *widths, int32_t n_widths, int32_t *n_grams_dev, int32_t *n_distinct_dev,
                              int32_t *n_repeated_dev, int32_t *n_covered_dev, int32_t *top_count_dev, int32_t *top_pos_dev,
                              uint16_t *covered_dev);
+
+/* ---- quality: Gopher text signals and duplicate lines of a document ("quality filtering", the text half) --------------------------------
+ * The half of the Gopher quality rule (Rae et al., 2021, table A1; MassiveText, RefinedWeb, FineWeb) that works on TEXT, where
+ * gz_ngram_repeats serves the half that works on tokens: word counts and lengths, symbol ratios, bullet and ellipsis lines, the
+ * alphabetic-word share, and the duplicate lines and paragraphs of a document by count and by characters.  The reference has nothing
+ * of the kind: the rule is this library's.  Neither form needs the tables.
+ *   documents, characters  a document is the bytes t = text[off[d] .. off[d+1]).  A character begins at every byte outside 0x80..0xBF.
+ *                    This defines the rule on any bytes; Python callers pass valid UTF-8.
+ *   words            the tokenizer's words: maximal runs of bytes that belong to no whitespace character -- the 29 code points of
+ *                    str.isspace(), exactly as gz_bm25_build cuts them.  Word k has a byte span; gap_k is the bytes between word k - 1
+ *                    and word k; nl_k is the number of 0x0A bytes in gap_k.
+ *   lines            word k heads a line iff k == 0 or nl_k >= 1.  A line is the bytes from its head word's first byte to the last
+ *                    byte of the last word before the next line head: trimmed, interior whitespace as it is.  A document without
+ *                    words has no lines.
+ *   paragraphs       word k heads a paragraph iff k == 0 or nl_k >= 2 (a blank or whitespace-only line separates paragraphs).  A
+ *                    paragraph's span is defined like a line's; its interior '\n' bytes stay.
+ *   duplicates       a line is a duplicate iff its bytes equal those of an EARLIER line of the same document: every occurrence after
+ *                    the first counts.  Paragraphs the same.  Nothing ever compares across documents:
+ *                    signals(docs[a:b]) == signals(docs)[:, a:b].
+ *                    A hash decides where to look, never whether two spans are equal, nor whether they stand in the same document.
+ *   signals          int32 [GZ_Q_SIGNALS, N], row GZ_Q_x, entry x * N + d:
+ *     N_CHARS            characters in the document          N_WORDS   words in the document       WORD_CHARS   characters inside words
+ *     N_ALPHA_WORDS      words that hold at least one letter: A-Z, a-z, or a code point >= U+00C0 other than U+00D7 and U+00F7,
+ *                        U+2000..U+2BFF, U+3000..U+303F, U+FE00..U+FE0F and everything >= U+1F000.  A range rule, NOT Unicode's Alphabetic
+ *                        property.  (On any bytes: the code point of a lead byte >= 0xC0 is put together from the 1, 2 or 3 bytes it
+ *                        announces, whatever they are, absent ones as 0.)
+ *     N_HASH             bytes equal to '#'
+ *     N_ELLIPSIS         for each maximal run of k '.' bytes, k / 3 (str.count("...")), plus the occurrences of U+2026
+ *     N_LINES            lines                               N_BULLET_LINES   lines whose first character is '-', '*', U+2022 or U+25CF
+ *     N_ELLIPSIS_LINES   lines that end in "..." or U+2026
+ *     DUP_LINES          duplicate lines                     DUP_LINE_CHARS   characters inside duplicate lines
+ *     N_PARAGRAPHS, DUP_PARAGRAPHS, DUP_PARAGRAPH_CHARS      the same for paragraphs
+ *   optional outputs for callers that remove the duplicates (CCNet-style cleaning):
+ *     line_off uint32 [N+1]   where each document's lines start in the flat line arrays (line_off[N] = L, the lines of the call)
+ *     line_span int64 [L, 2]  byte start and end of each line, relative to its document
+ *     line_first int32 [L]    the document-local index of the earliest equal line, the line's own index if there is none
+ *     para_off, para_span, para_first: the same for paragraphs.  A sizing call (the *_off alone) tells L and P.
+ *   walk             one wave per document, a lane 4 consecutive bytes a trip of 256; two passes over the text: pass A the text-only
+ *                    signals and the line and paragraph counts (scanned into offsets; ONE small readback: totals, extent, refusals),
+ *                    pass B the spans.  A span's hash needs no second pass over its bytes: with F(x) = sum over q < x of
+ *                    (byte[q] + 1) * R^q mod 2^32 for two odd R, (F(end) - F(start)) * R^-start is a polynomial of the span's bytes
+ *                    alone; length, characters, kind and document are mixed in through the finalizer of splitmix64, and the result
+ *                    is cut to its low quality_hash_bits bits when that switch is set.  Correctness does not depend on it.
+ *   table            one open-addressing table a call, linear probing, slots = the smallest power of two that is at least twice
+ *                    (lines + paragraphs), 8 bytes a slot: tag << 32 | span index, tag = h64 >> 32 | 2^31, 0 = free, start slot =
+ *                    h64 & (slots - 1).  Key: (kind, document, bytes).  Insert: 64-bit compare-and-swap on a free slot; on a taken
+ *                    slot whose tag agrees the occupant is the same key only if kind, document and length agree AND the bytes are
+ *                    equal: then a 64-bit atomic minimum leaves the smallest span index; otherwise the next slot.  A slot once taken
+ *                    holds one key for good.  Spans above 512 bytes are inserted a wave per span.  After the kernel boundary a wave per
+ *                    document reads `first` for its spans.  All order-dependent state is an integer sum or minimum.
+ *   memory           workspace of the context, kept between calls: 64 bytes a document, 48 bytes a span, 8 bytes a slot.
+ *   every output pointer may be NULL.  n_docs == 0 is GZ_OK and touches nothing.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error, with the outputs untouched: n_docs < 0; NULL text or offsets with
+ *   n_docs > 0; offsets that decrease (the host form before anything is launched; the device form where pass A meets them); a *_span or
+ *   *_first output without its *_off; output arrays that overlap the input or each other.
+ *   GZ_E_LIMIT and nothing written: a document of 2^31 bytes or more; 2^31 documents or more; 2^32 - 1 or more lines plus paragraphs.
+ * gz_text_signals: host pointers; the text goes up through the library's pinned staging and the outputs come back.
+ * gz_text_signals_device: text, offsets and outputs DEVICE pointers; offsets are ABSOLUTE from the base pointer and off_dev[0] need not
+ *   be 0.  Ordering: every pass runs on the context's stream, behind whatever was enqueued before it; the call returns when its outputs
+ *   are complete.
+ * Not here: stop-word counts (gz_bm25_match_count_groups over a stop list); Unicode's Alphabetic property; C4's terminal-punctuation and
+ *   line-length rules; removing the duplicate lines (the caller has line_span and line_first); duplicates across documents
+ *   (gz_minhash_rows, gz_ngram_index_build); multi-GPU forms (shards concatenate). */
+#define GZ_Q_N_CHARS              0
+#define GZ_Q_N_WORDS              1
+#define GZ_Q_WORD_CHARS           2
+#define GZ_Q_N_ALPHA_WORDS        3
+#define GZ_Q_N_HASH               4
+#define GZ_Q_N_ELLIPSIS           5
+#define GZ_Q_N_LINES              6
+#define GZ_Q_N_BULLET_LINES       7
+#define GZ_Q_N_ELLIPSIS_LINES     8
+#define GZ_Q_DUP_LINES            9
+#define GZ_Q_DUP_LINE_CHARS      10
+#define GZ_Q_N_PARAGRAPHS        11
+#define GZ_Q_DUP_PARAGRAPHS      12
+#define GZ_Q_DUP_PARAGRAPH_CHARS 13
+#define GZ_Q_SIGNALS             14
+int  gz_text_signals(gz_ctx *ctx, const uint8_t *text, const int64_t *off, int64_t n_docs, int32_t *signals, uint32_t *line_off,
+                     int64_t *line_span, int32_t *line_first, uint32_t *para_off, int64_t *para_span, int32_t *para_first);
+int  gz_text_signals_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *off_dev, int64_t n_docs, int32_t *signals_dev,
+                            uint32_t *line_off_dev, int64_t *line_span_dev, int32_t *line_first_dev, uint32_t *para_off_dev,
+                            int64_t *para_span_dev, int32_t *para_first_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
