@@ -212,6 +212,7 @@ struct gz_ctx {
     DBuf w_ng_aux;                       // n-gram overlap: the distinct counter, first_hit where the caller takes only first_ref
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
+    DBuf w_ss_cut, w_ss_drop, w_ss_aux;  // the cut: piece counts and their scan, the staged drop bytes; duplicate substrings: first_dup where the caller takes only first_src
     DBuf w_q[8];                         // text quality signals: control words, counts, scans, span halves, table, long list, staged text and outputs (gz_quality_api.inc, QW_*)
     DBuf w_al[16];                       // word spans, aligned rows, span labels: scans, scratch and staged inputs (gz_rows_api.inc, ALW_*)
     DBuf w_pw_cnt, w_pw_tok;             // pair windows: window counts and q of every pair; span tokens: the counts as 64-bit words and their scan
@@ -1101,7 +1102,7 @@ try {
     for (DBuf* b : {&c->t_dec_cont, &c->t_dec_entries, &c->t_dec_bytes, &c->w_dec_rb, &c->w_win_cnt}) release(*b);
     for (DBuf* b : {&c->w_pk_len, &c->w_pk_jc, &c->w_pk_nxt, &c->w_pk_jc2, &c->w_pk_tile, &c->w_pk_seg, &c->w_pk_drow, &c->w_pk_dcol}) release(*b);
     for (DBuf* b : {&c->w_pf_rank, &c->w_pf_tab, &c->w_pf_plan, &c->w_pf_rdocs, &c->w_pf_dlen}) release(*b);
-    for (DBuf* b : {&c->w_pieces, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_aux, &c->w_rp_tab, &c->w_rp_top}) release(*b);
+    for (DBuf* b : {&c->w_pieces, &c->w_mh_keys, &c->w_mh_reps, &c->w_mh_aux, &c->w_ng_aux, &c->w_rp_tab, &c->w_rp_top, &c->w_ss_cut, &c->w_ss_drop, &c->w_ss_aux}) release(*b);
     for (auto& b : c->w_al) release(b);
     for (auto& b : c->w_q) release(b);
     for (DBuf* b : {&c->w_pw_cnt, &c->w_pw_tok}) release(*b);
@@ -2046,6 +2047,7 @@ try {
 #include "gz_rows_api.inc"
 #include "gz_ngram_api.inc"
 #include "gz_repeat_api.inc"
+#include "gz_substr_api.inc"
 #include "gz_quality_api.inc"
 
 // ---- text pre-pass ----------------------------------------------------------------------------------------------------

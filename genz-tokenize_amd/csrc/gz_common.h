@@ -95,6 +95,8 @@ struct GzOptions {
                                       // (almost every probe collides in start slot and tag: results must not change); 0 the whole hash
     int32_t repeat_hash_bits = 0;     // n-gram repeats: k > 0 keeps only the low k bits of every (row, n-gram) hash (the same forced collisions,
                                       // between rows too: results must not change); 0 the whole hash
+    int32_t substr_hash_bits = 0;     // duplicate substrings: k > 0 keeps only the low k bits of every n-gram's 64-bit hash (the same forced
+                                      // collisions: results must not change); 0 the whole hash
     int32_t quality_hash_bits = 0;    // text quality signals: k > 0 keeps only the low k bits of every (kind, document, span) hash (the same
                                       // forced collisions, between documents and kinds too: results must not change); 0 the whole hash
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)

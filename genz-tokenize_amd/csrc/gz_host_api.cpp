@@ -50,6 +50,7 @@ int gz_option_set(GzOptions& o, const char* key, int64_t v)
         {"ngram_hash_bits", &GzOptions::ngram_hash_bits, nullptr, 0, 32},
         {"repeat_hash_bits", &GzOptions::repeat_hash_bits, nullptr, 0, 32},
         {"quality_hash_bits", &GzOptions::quality_hash_bits, nullptr, 0, 32},
+        {"substr_hash_bits", &GzOptions::substr_hash_bits, nullptr, 0, 32},
     };
     for (const Key& k : keys)
         if (std::strcmp(k.name, key) == 0) {

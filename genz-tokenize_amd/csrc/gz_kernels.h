@@ -324,8 +324,46 @@ struct GzRepeatArgs {
 // One width: clears the table and the counts, presets the add / max cells where a row has several pieces, inserts, queries, unpacks.
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s);
 
+// duplicate substrings across the rows of a call (gz_substr.inc); pieces of n-gram positions at the call's width
+constexpr int GZ_SUBSTR_MAX_N = 256;                                // the widest n-gram: a trip stages 64 + n - 1 ids in the wave's LDS
+struct GzSubstrArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31
+    int64_t off0, n_ids;                                            // row_off[0] and the ids behind it (fewer than 2^32 - 1): a position counts from off0
+    int32_t skip_front, skip_back, n;                               // skips 0 or 1, 1 <= n <= GZ_SUBSTR_MAX_N
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    unsigned long long* table; uint64_t mask;                       // slots - 1 (gz_substr_slots of the positions)
+    uint64_t hmask;                                                 // hash bits kept (switch substr_hash_bits)
+    uint32_t* slot_of;                                              // [n_ids]: the slot the n-gram at a position ended in (written by the insert pass)
+    int32_t* n_grams; int32_t* n_later; int32_t* n_dup; int32_t* first_dup; int32_t* first_src;      // [n_rows], each may be null -- but
+                                                                    // first_dup is needed where first_src is given
+    uint8_t* dup;                                                   // dup[k] belongs to ids[k]; may be null
+};
+// the smallest power of two that is at least twice the positions, and at most 2^32: slot_of holds a slot's index in 32 bits (beyond 2^31
+// positions the table is more than half full; it is never full, the positions stay below 2^32 - 1)
+inline uint64_t gz_substr_slots(int64_t n_positions)
+{
+    uint64_t cap = 1;
+    while (cap < 2 * (uint64_t)n_positions && cap < (1ull << 32)) cap <<= 1;
+    return cap;
+}
+// clears the table, presets the counts where a row has more than one piece, inserts, marks, resolves first_src
+void gz_launch_substr_dups(GzSubstrArgs A, hipStream_t s);
+
+// the cut of marked ids out of ragged rows (gz_substr.inc); pieces of 4096 ids of a whole row (the piece count at width 1, no skips)
+struct GzCutArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets)
+    int64_t n_ids;                                                  // the ids of the call: out_ids has room for as many
+    const uint8_t* drop;                                            // drop[k] belongs to ids[k]: 0 keeps the id
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    int64_t* piece_kept; int64_t* piece_base;                       // [n_pieces] kept ids of a piece; [n_pieces + 1] their exclusive scan
+    int32_t* out_ids; int64_t* out_row_off; int32_t* n_kept;        // out_ids and n_kept may be null (a call that only sizes)
+};
+void gz_launch_cut_rows(GzCutArgs A, hipStream_t s);               // count, scan, write
+
 // text quality signals, duplicate lines and paragraphs (gz_quality.inc)
-constexpr int GZ_QUALITY_WPB = 4;                                   // documents per workgroup of the walk
+constexpr int GZ_QUALITY_WPB = 4;                                  // documents per workgroup of the walk
 #ifndef GZ_Q_SIGNALS                                                // the rows of signals, as include/genz_tokenize.h defines them
 #define GZ_Q_N_CHARS              0
 #define GZ_Q_N_WORDS              1

@@ -720,6 +720,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_minhash.inc"
 #include "gz_ngram.inc"
 #include "gz_repeat.inc"
+#include "gz_substr.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
 #include "gz_quality.inc"
@@ -1020,6 +1021,33 @@ void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)
     hipLaunchKernelGGL(gz_repeat_insert_kernel, grid, block, 0, s, A);
     hipLaunchKernelGGL(gz_repeat_query_kernel, grid, block, 0, s, A);
     if (A.top) hipLaunchKernelGGL(gz_repeat_top_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
+}
+
+void gz_launch_substr_dups(GzSubstrArgs A, hipStream_t s)
+{
+    static_assert(SS_STAGE >= WAVE + GZ_SUBSTR_MAX_N - 1, "a trip's ids do not fit the wave's stage");
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    (void)hipMemsetAsync(A.table, 0, (size_t)(A.mask + 1) * 8, s);
+    if (!A.one_each) {                                                               // the pieces of a long row meet by atomicAdd / atomicMin
+        if (A.n_later) (void)hipMemsetAsync(A.n_later, 0, (size_t)A.n_rows * 4, s);
+        if (A.n_dup) (void)hipMemsetAsync(A.n_dup, 0, (size_t)A.n_rows * 4, s);
+        if (A.first_dup) (void)hipMemsetAsync(A.first_dup, 0xFF, (size_t)A.n_rows * 4, s);
+    }
+    const dim3 grid((unsigned)((A.n_pieces + 3) / 4)), block(WAVE * 4);
+    hipLaunchKernelGGL(gz_substr_insert_kernel, grid, block, 0, s, A);
+    hipLaunchKernelGGL(gz_substr_mark_kernel, grid, block, 0, s, A);
+    if (A.first_src) hipLaunchKernelGGL(gz_substr_resolve_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
+}
+
+void gz_launch_cut_rows(GzCutArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    const dim3 grid((unsigned)((A.n_pieces + 3) / 4)), block(WAVE * 4);
+    hipLaunchKernelGGL(gz_cut_count_kernel, grid, block, 0, s, A);
+    launch_scan64((const int64_t*)A.piece_kept, A.n_pieces, A.piece_base, s);
+    hipLaunchKernelGGL(gz_cut_write_kernel, grid, block, 0, s, A);
 }
 
 // one filter, one pass (0: html look-ahead only; 1: classify + write into the document's slot + new length)

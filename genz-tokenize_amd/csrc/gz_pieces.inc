@@ -1,5 +1,6 @@
 // gz_pieces.inc -- how a ragged row's body is divided over waves: the one decision MinHash signatures (gz_minhash.inc), the n-gram
-// overlap index (gz_ngram.inc) and n-gram repeats (gz_repeat.inc) share (included by gz_kernels.hip in front of the three).
+// overlap index (gz_ngram.inc), n-gram repeats (gz_repeat.inc) and duplicate substrings with their cut (gz_substr.inc) share (included by
+// gz_kernels.hip in front of them).
 //
 // The BODY of a row is the row without its skips.  Its POSITIONS are what a lane evaluates: the shingles of a signature (runs of w
 // ids; ONE run, the whole body, when it is shorter: a non-empty body always has a position) or the n-grams of an index, a query or a
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void gz_piece_count_kernel(const int64_t* __re
 }
 
 // the wave's piece p: its row (the last row with piece_off[r] <= p; every row has a piece), which of the row's pieces it is (*j) and
-// how many the row has (*n_pc).  Args: GzMinhashArgs, GzNgramArgs or GzRepeatArgs -- their one_each, n_rows and piece_off.
+// how many the row has (*n_pc).  Args: GzMinhashArgs, GzNgramArgs, GzRepeatArgs, GzSubstrArgs or GzCutArgs -- their one_each, n_rows and piece_off.
 template <class Args>
 __device__ __forceinline__ int64_t piece_row(const Args& A, int64_t p, int64_t* j, int64_t* n_pc)
 {

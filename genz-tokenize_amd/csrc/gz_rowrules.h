@@ -1,7 +1,7 @@
 // gz_rowrules.h -- the rules every row-shaping call shares, as plain host C++ (no HIP, no context: tests/test_row_rules.py compiles
 // this file alone): the check of a host CSR input, the dense-row rule, the MinHash argument rules (tests/test_minhash_surface.py
 // compiles them alone too), the n-gram overlap argument rules (tests/test_ngram_surface.py), the n-gram repeats argument rules
-// (tests/test_repeat_surface.py), the question-context window rules (tests/test_pairwin_surface.py) and the pairwise-disjoint check of a
+// (tests/test_repeat_surface.py), the duplicate-substring and cut rules, the question-context window rules (tests/test_pairwin_surface.py) and the pairwise-disjoint check of a
 // call's arrays.
 #pragma once
 #include <cstddef>
@@ -105,6 +105,20 @@ inline const char* repeat_fault(int64_t n_rows, int32_t skip_front, int32_t skip
     }
     return nullptr;
 }
+
+// Duplicate substrings across the rows of a call and the cut of marked ids (gz_substr_dups*, gz_cut_rows*): the sentence of the first
+// rule an argument list breaks, or nullptr, in the order they are reported in.  first_src is an int32 a row: the rows stay below 2^31.
+// The ids of a call obey ngram_ids_fit (a slot holds position + 1 in 32 bits), its bodies minhash_bodies_fit, and the position total
+// read back from the device ngram_positions_possible (whose arithmetic holds for every n >= 1: a row loses at most 257 positions).
+inline const char* substr_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t n)
+{
+    if (n_rows < 0) return "duplicate substrings need n_rows >= 0";
+    if (n_rows > (int64_t)INT32_MAX) return "duplicate substrings need fewer than 2^31 rows";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "duplicate substrings need skips of 0 or 1";
+    if (n < 1 || n > 256) return "duplicate substrings need a width n in 1..256";
+    return nullptr;
+}
+inline const char* cut_fault(int64_t n_rows) { return n_rows < 0 ? "cut rows need n_rows >= 0" : nullptr; }
 
 // Word spans, aligned rows, span labels (gz_word_spans*, gz_align_rows*, gz_span_labels*; tests/test_align_surface.py compiles these
 // alone): the sentence of the first rule broken, or nullptr, in the order they are reported in.  The *_data_fault rules read the

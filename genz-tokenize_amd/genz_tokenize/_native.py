@@ -65,6 +65,7 @@ SYMBOLS = [
     "gz_pair_window_rows", "gz_pair_window_rows_device", "gz_span_tokens", "gz_span_tokens_device",
     "gz_pack_rows_fit", "gz_pack_rows_fit_device", "gz_pack_rows_fit_info",
     "gz_text_signals", "gz_text_signals_device",
+    "gz_substr_dups", "gz_substr_dups_device", "gz_cut_rows", "gz_cut_rows_device",
 ]
 
 _lib = None
@@ -273,6 +274,12 @@ def load_library():
     if hasattr(L, "gz_text_signals"):
         L.gz_text_signals.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.gz_text_signals_device.argtypes = L.gz_text_signals.argtypes
+    if hasattr(L, "gz_substr_dups"):
+        sd = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.gz_substr_dups.argtypes = sd
+        L.gz_substr_dups_device.argtypes = sd
+        L.gz_cut_rows.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+        L.gz_cut_rows_device.argtypes = L.gz_cut_rows.argtypes
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -936,6 +943,45 @@ class Context:
         w = np.ascontiguousarray(widths, dtype=np.int32)
         self._check(self.lib.gz_ngram_repeats_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, _ptr(w), len(w),
                                                      *_dptrs(d_n_grams, d_n_distinct, d_n_repeated, d_n_covered, d_top_count, d_top_pos, d_covered)))
+
+    # ---- duplicate substrings across the rows of a call, and the cut of marked ids ------------------------------
+    SUBSTR_OUT = ("n_grams", "n_later", "n_dup", "first_dup", "first_src")
+
+    def substr_dups(self, ids: np.ndarray, row_off: np.ndarray, n: int, framed: bool, with_dup: bool):
+        """ids int32 (packed rows), row_off int64 [R+1] -> dict of the five int32 [R] arrays, and `dup` uint8 when asked for
+        (gz_substr_dups)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        R, skip = len(row_off) - 1, 1 if framed else 0
+        out = {k: np.empty(R, dtype=np.int32) for k in self.SUBSTR_OUT}
+        dup = np.zeros(len(ids), dtype=np.uint8) if with_dup else None
+        self._check(self.lib.gz_substr_dups(self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), R, skip, skip, int(n),
+                                            *[_ptr(v) if R else None for v in out.values()], _ptr(dup) if with_dup and len(ids) else None))
+        if with_dup:
+            out["dup"] = dup
+        return out
+
+    def substr_dups_device(self, d_ids, d_row_off, n_rows, skip_front, skip_back, n, d_n_grams, d_n_later, d_n_dup, d_first_dup, d_first_src, d_dup):
+        """gz_substr_dups_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_substr_dups_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, n,
+                                                   *_dptrs(d_n_grams, d_n_later, d_n_dup, d_first_dup, d_first_src, d_dup)))
+
+    def cut_rows(self, ids: np.ndarray, row_off: np.ndarray, drop: np.ndarray):
+        """ids int32 (packed rows), row_off int64 [R+1], drop uint8 per id -> (kept ids int32, out_row_off int64 [R+1], n_kept int32 [R])
+        (gz_cut_rows)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        drop = np.ascontiguousarray(drop, dtype=np.uint8)
+        R = len(row_off) - 1
+        out_ids, out_off, n_kept = np.empty(len(ids), dtype=np.int32), np.zeros(R + 1, dtype=np.int64), np.empty(R, dtype=np.int32)
+        some = len(ids) > 0
+        self._check(self.lib.gz_cut_rows(self.handle, _ptr(ids) if some else None, _ptr(row_off), R, _ptr(drop) if some else None,
+                                         _ptr(out_ids) if some else None, _ptr(out_off), _ptr(n_kept) if R else None))
+        return out_ids[:int(out_off[R])], out_off, n_kept
+
+    def cut_rows_device(self, d_ids, d_row_off, n_rows, d_drop, d_out_ids, d_out_row_off, d_n_kept):
+        """gz_cut_rows_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_cut_rows_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, *_dptrs(d_drop, d_out_ids, d_out_row_off, d_n_kept)))
 
     # ---- text quality signals, duplicate lines and paragraphs ----------------------------------------------------
     def text_signals(self, text: np.ndarray, off: np.ndarray, lines: bool, paragraphs: bool):

@@ -674,8 +674,8 @@ class Tokenize(object):
     @contextlib.contextmanager
     def _encode_ragged_to_device(self, texts, word_table):
         """The texts encoded without a length limit into HBM, enqueued on the context's stream and NOT synchronised, so that what
-        shapes the rows goes right behind it: yields (d_ids, d_row_off, n, dev) -- dev(nbytes) allocates more -- and frees every
-        allocation on exit."""
+        shapes the rows goes right behind it: yields (d_ids, d_row_off, n, dev) -- dev(nbytes) allocates more, dev.cap is the room of
+        d_ids in ids -- and frees every allocation on exit."""
         ctx = self._ctx
         t, to = _packing.pack_pinned(texts, self, ctx)
         n = len(to) - 1
@@ -686,6 +686,7 @@ class Tokenize(object):
             d = ctx.alloc(max(int(nbytes), 1) + 64)
             bufs.append(d)
             return d
+        dev.cap = cap                                                  # (ids the rows can hold between them: what a per-id array needs)
         try:
             d_t, d_to = dev(t.nbytes), dev(to.nbytes)
             if t.nbytes:
@@ -1751,8 +1752,99 @@ class Tokenize(object):
         out["keep"] = covered <= f * body
         return out
 
+    # ---- duplicate substrings across documents ("exact substring deduplication") --------------------------------------------
+    def substring_dup_rows(self, rows, n=50, framed=True, return_dup=False):
+        """Which runs of `n` tokens or more of token `rows` already occurred EARLIER in the same call -- in an earlier row or earlier
+        in the same row -- on the GPU: the ExactSubstr rule of Lee et al. 2021 at threshold `n`, 1 <= n <= 256 (the paper and
+        RefinedWeb use 50).  `rows` as `ngram_overlap_rows` takes them (`framed=True`: each row loses its first and last entry
+        first).  Per row with body q of m ids: n_grams = max(0, m - n + 1); n_later = the positions i whose n-gram q[i:i+n] stands
+        at a smaller (row, position); n_dup = the body tokens inside some such n-gram; first_dup = the smallest such i (-1: none);
+        first_src = the row of the first occurrence of the n-gram at first_dup (-1: none); body_len = m.  Everything is exact -- a
+        hash decides where to look, never whether two n-grams are equal.  The result depends on the rows AND their order, and a
+        shard is deduplicated against itself only: results of shards do not concatenate.
+        Returns a dict of numpy int32 [N] arrays; with `return_dup` also `dup`, uint8 over the rows back to back (1 on the dup
+        body tokens, 0 elsewhere, the frame cells included: `cut_rows(rows, dup)` is the rows without their later copies) and
+        `row_off` int64 [N+1]."""
+        n = _integer("n", n, 1, 257)
+        flat, off = self._ngram_rows("substring_dup_rows", rows)
+        out = self._ctx.substr_dups(flat, off, n, bool(framed), bool(return_dup))
+        skip = 2 if framed else 0
+        out["body_len"] = np.maximum(np.diff(off) - skip, 0).astype(np.int32)
+        if return_dup:
+            out["row_off"] = off
+        return out
+
+    def cut_rows(self, rows, drop):
+        """`rows` without the ids whose `drop` entry is not 0, on the GPU: `drop` holds one entry per id, rows back to back (the
+        `dup` of `substring_dup_rows`, the `covered` of `ngram_overlap_rows`, or any mask).  Returns {"ids": int32, the kept ids
+        back to back, "row_off": int64 [N+1] from 0, "n_kept": int32 [N]}; the order inside a row stays."""
+        flat, off = self._ngram_rows("cut_rows", rows)
+        drop = np.asarray(drop)
+        if drop.dtype.kind not in "biu":
+            raise TypeError("cut_rows() expects drop entries that are integers or bools")
+        if drop.ndim != 1 or len(drop) != len(flat):
+            raise ValueError("cut_rows() expects one drop entry per id, rows back to back")
+        ids, row_off, n_kept = self._ctx.cut_rows(flat, off, (drop != 0).astype(np.uint8))
+        return {"ids": ids, "row_off": row_off, "n_kept": n_kept}
+
+    def _encode_substring_dups(self, texts, n, word_table, cut):
+        """encode -> dups (-> cut) on the device; the per-document arrays, and with `cut` the cleaned rows"""
+        n = _integer("n", n, 1, 257)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        names = _native.Context.SUBSTR_OUT
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, N, dev):
+                d_out = dev(4 * len(names) * max(N, 1))
+                cap = dev.cap
+                d_dup = dev(cap) if cut and N else 0
+                ctx.substr_dups_device(d_ids, d_ro, N, 1, 1, n, *[d_out + 4 * N * k if N else 0 for k in range(len(names))], d_dup)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+                host = np.empty((len(names), N), dtype=np.int32)
+                row_off = np.zeros(N + 1, dtype=np.int64)
+                if N:
+                    ctx.d2h(host, d_out)
+                ctx.d2h(row_off, d_ro)
+                out = {k: host[i] for i, k in enumerate(names)}
+                out["body_len"] = np.maximum(np.diff(row_off) - 2, 0).astype(np.int32)
+                if cut:
+                    out_off = np.zeros(N + 1, dtype=np.int64)
+                    if N:
+                        d_ids2, d_off2 = dev(4 * cap), dev(8 * (N + 1))
+                        ctx.cut_rows_device(d_ids, d_ro, N, d_dup, d_ids2, d_off2, 0)
+                        ctx.d2h(out_off, d_off2)
+                    ids = np.empty(int(out_off[N]), dtype=np.int32)
+                    if len(ids):
+                        ctx.d2h(ids, d_ids2)
+                    out["ids"], out["row_off"] = ids, out_off
+        return out
+
+    def encode_substring_dups(self, texts: Sequence[str], n=50, word_table=True):
+        """`substring_dup_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, marked there, and only the per-document arrays come back -- n_grams, n_later, n_dup, first_dup, first_src and
+        body_len, int32 [N].  The rule is `substring_dup_rows`'s over the rows of `encode_batch(texts, max_len=None)` without
+        their frame, in the order of `texts`; a shard is deduplicated against itself only.  Single texts only."""
+        return self._encode_substring_dups(texts, n, word_table, False)
+
+    def dedup_substrings(self, texts: Sequence[str], n=50, max_fraction=None):
+        """`encode_substring_dups` plus what a recipe does with it, all on the device: the later copies of every run of `n` tokens
+        or more are CUT out of the encoded rows.  Returns the counts of `encode_substring_dups`; fraction = n_dup /
+        max(body_len, 1) (float64, the share of a document that repeats earlier text); keep (bool [N]) = n_dup <= max_fraction *
+        body_len for a `max_fraction` in [0, 1] -- RefinedWeb drops documents that are mostly copies -- and all True when it is
+        None; and the cleaned rows as `ids` int32 / `row_off` int64 [N+1], each still in its frame, ready for `window_rows`,
+        `pack_rows` or `decode_batch` (a cut does not snap to words: it may leave a dangling `@@` piece)."""
+        f = None if max_fraction is None else _share("max_fraction", max_fraction)
+        out = self._encode_substring_dups(texts, n, True, True)
+        dup, body = out["n_dup"].astype(np.float64), out["body_len"].astype(np.float64)
+        out["fraction"] = dup / np.maximum(body, 1.0)
+        out["keep"] = np.ones(len(body), dtype=bool) if f is None else dup <= f * body
+        return out
+
     # ---- n-gram repetition inside a document ("quality filtering") -----------------------------------------------------------
-    REPEAT_WIDTHS = (2, 3, 4, 5, 6, 7, 8, 9, 10)
+    REPEAT_WIDTHS =(2, 3, 4, 5, 6, 7, 8, 9, 10)
     REPEAT_TOP_MAX = {2: 0.20, 3: 0.18, 4: 0.16}
     REPEAT_DUP_MAX = {5: 0.15, 6: 0.14, 7: 0.13, 8: 0.12, 9: 0.11, 10: 0.10}
 

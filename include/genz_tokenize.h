@@ -300,6 +300,8 @@ int64_t gz_limit(int which);
  *   quality_hash_bits (0..32; 0)  gz_text_signals* keep only the low k bits of every (kind, document, span) hash (0: all of it); with
  *                              k = 1 almost every probe collides in start slot and tag, between documents and kinds too: results must
  *                              not change
+ *   substr_hash_bits (0..32; 0)  gz_substr_dups* keep only the low k bits of every n-gram's hash (0: all of it); with k = 1 almost every
+ *                              probe collides in start slot and tag: results must not change
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -727,9 +729,10 @@ int  gz_bpe_learn_result(gz_wordset *ws, int64_t *merge_off, uint8_t *merge_byte
  *   frees what is left.
  * gz_ngram_overlap: host pointers, the outputs come back.  gz_ngram_overlap_device: every pointer a DEVICE pointer, offsets ABSOLUTE
  *   as above, same ordering; the call returns when its outputs are complete.  Both use the index's n; the skips are the call's own.
- * Not here: appending to a live index, saving and loading one, multi-GPU indexes (shards query one replicated index), removing or
- *   splitting the contaminated spans, text or character n-grams, exact whole-document deduplication, approximate (Bloom) tables,
- *   per-reference-row "seen" marks. */
+ * Removing the contaminated spans: gz_cut_rows with drop = covered (below, "duplicate substrings across documents"), which also
+ *   holds the exact deduplication of repeated text against the corpus itself.
+ * Not here: appending to a live index, saving and loading one, multi-GPU indexes (shards query one replicated index), text or
+ *   character n-grams, approximate (Bloom) tables, per-reference-row "seen" marks. */
 typedef struct gz_ngram_index gz_ngram_index;
 int  gz_ngram_index_build(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
                           int32_t n, gz_ngram_index **out);
@@ -959,6 +962,69 @@ int  gz_ngram_repeats_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t 
                              int32_t skip_back, const int32_t *widths, int32_t n_widths, int32_t *n_grams_dev, int32_t *n_distinct_dev,
                              int32_t *n_repeated_dev, int32_t *n_covered_dev, int32_t *top_count_dev, int32_t *top_pos_dev,
                              uint16_t *covered_dev);
+
+/* ---- duplicate substrings across documents ("exact substring deduplication"), and the cut of marked ids ---------------------------
+ * The ExactSubstr half of Lee et al. 2021 ("Deduplicating training data makes language models better"), beside the NearDup half that
+ * gz_minhash_rows serves: every run of at least n tokens (50 in the paper and in RefinedWeb) that already occurred EARLIER in the
+ * corpus -- in an earlier document or earlier in the same one -- is found, and gz_cut_rows removes all occurrences but the first.
+ * This catches boilerplate, licence texts, quoted articles and templated pages, which MinHash cannot see because the documents around
+ * them differ.  A token lies inside a repeated substring of n ids or more exactly when it lies inside a repeated n-gram window, so
+ * one hash table over the call's own n-gram positions gives ExactSubstr's answer at threshold n; there is no suffix array.
+ * Neither call needs the tables or the decoder snapshot.
+ *   body of row r    as in gz_ngram_overlap: ids[row_off[r] + skip_front .. row_off[r+1] - skip_back), skips 0 or 1; a row shorter
+ *                    than its skips has an empty body
+ *   positions        of a body of m ids, width n in 1..256: the max(0, m - n + 1) runs body[i .. i + n).  They are ordered by
+ *                    (row, i), the order in which they stand in ids
+ *   later(r, i)      the same n ids stand at some smaller position (r', i') < (r, i): in an earlier row, or earlier in row r
+ *   per row, int32 [n_rows], each may be NULL:
+ *                    n_grams[r] = max(0, m - n + 1);  n_later[r] = the number of i with later(r, i);
+ *                    n_dup[r] = the number of body tokens t for which some i has later(r, i) and i <= t < i + n;
+ *                    first_dup[r] = the smallest i with later(r, i), -1 when there is none;
+ *                    first_src[r] = the row of the smallest position in the whole call that holds the n-gram at first_dup, -1 when
+ *                    there is none
+ *   dup (optional)   one uint8 per id of the input, dup[k] belongs to ids[k] for k in [row_off[0], row_off[n_rows]): 1 on those body
+ *                    tokens, 0 elsewhere, the skipped frame cells included
+ *   The outputs are a pure function of (rows in their order, skips, n): not of launch geometry, scheduling or the hash.  A hash
+ *   decides where to look, never whether two n-grams are equal: every tag match is followed by a comparison of the n ids.
+ *   NOT shard-invariant: a shard is deduplicated against itself only, dups(rows[a:b]) is not dups(rows)[a:b].
+ *   A periodic body such as one id repeated has every window but its first as later, so all its tokens but the first are dup.
+ *   hash             the two MurmurHash3_x86_32 streams of gz_ngram_index_build over the n ids, seeds 0 and 0x9E3779B9, each ^ 4 n and
+ *                    fmix32; h64 = H_0 << 32 | H_0x9E3779B9, cut to its low substr_hash_bits bits when that switch is set;
+ *                    tag = h64 >> 32;  start slot = h64 & (slots - 1).  A trip of 64 positions stages its 64 + n - 1 ids in LDS
+ *   table            open addressing, linear probing, 8 bytes a slot: tag << 32 | (position + 1), position counted from row_off[0];
+ *                    0 = free; slots = the smallest power of two that is at least twice the positions (and at most 2^32: a slot
+ *                    index is kept in 32 bits, so beyond 2^31 positions the table is more than half full, never full).  Insert as in
+ *                    gz_ngram_index_build: compare-and-swap on a free slot, comparison of the n ids on an equal tag, atomic
+ *                    minimum: every occurrence of an n-gram ends in one slot, which ends at its smallest position, whatever the
+ *                    order.  Each position stores the slot it ended in; later = that slot holds another position.  No second hash
+ *   memory           workspace of a call, given back before it returns: 8 bytes a slot and 4 bytes an id -- 20 to 36 bytes a token
+ *                    with one position a token; kept by the context: 16 bytes a row
+ *   cut              given ids, row_off and one drop byte per id (drop[k] belongs to ids[k]), output row r = the ids of row r whose
+ *                    byte is 0, in order.  out_row_off int64 [n_rows + 1] from 0 (out_row_off[0] = 0), n_kept int32 [n_rows] (may
+ *                    be NULL), out_ids with room for as many ids as the input holds, filled from its first cell.  cut with
+ *                    drop = dup is the corpus without its later copies (the frames are kept: their bytes are 0); cut with
+ *                    drop = covered of gz_ngram_overlap removes the contaminated spans.  Workspace: 16 bytes a piece of 4096 ids
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error, before anything is launched and with the outputs untouched: n_rows < 0;
+ *   2^31 rows or more; a skip outside {0, 1}; n outside 1..256; NULL ids or row_off with n_rows > 0 (the cut: NULL drop, out_ids or
+ *   out_row_off too); output arrays that overlap the input or each other; bad or decreasing row offsets (the host forms).
+ *   GZ_E_LIMIT and nothing written: 2^32 - 1 ids or more in the call (a slot holds position + 1 in 32 bits: shard the rows), or a body
+ *   of 2^31 ids or more.  n_rows == 0 is GZ_OK and launches nothing.
+ * gz_substr_dups, gz_cut_rows: host pointers; the rows go up through the library's pinned staging and the outputs come back (of
+ *   out_ids the kept ids only).
+ * gz_substr_dups_device, gz_cut_rows_device: every pointer a DEVICE pointer; offsets are ABSOLUTE from the base pointer and
+ *   row_off_dev[0] need not be 0.  Ordering: every pass runs on the context's stream, behind a gz_encode_batch_device (ragged layout)
+ *   enqueued just before with no gz_sync in between; a call returns when its outputs are complete.
+ * Not here: whole-word snapping of the cuts (a cut may leave a dangling continuation piece); a persistent index across shards;
+ *   multi-GPU forms; a list of the spans. */
+int  gz_substr_dups(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                    int32_t n, int32_t *n_grams, int32_t *n_later, int32_t *n_dup, int32_t *first_dup, int32_t *first_src, uint8_t *dup);
+int  gz_substr_dups_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, int32_t skip_front,
+                           int32_t skip_back, int32_t n, int32_t *n_grams_dev, int32_t *n_later_dev, int32_t *n_dup_dev,
+                           int32_t *first_dup_dev, int32_t *first_src_dev, uint8_t *dup_dev);
+int  gz_cut_rows(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, const uint8_t *drop, int32_t *out_ids,
+                 int64_t *out_row_off, int32_t *n_kept);
+int  gz_cut_rows_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, const uint8_t *drop_dev,
+                        int32_t *out_ids_dev, int64_t *out_row_off_dev, int32_t *n_kept_dev);
 
 /* ---- quality: Gopher text signals and duplicate lines of a document ("quality filtering", the text half) --------------------------------
  * The half of the Gopher quality rule (Rae et al., 2021, table A1; MassiveText, RefinedWeb, FineWeb) that works on TEXT, where
