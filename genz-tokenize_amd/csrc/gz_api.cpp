@@ -78,6 +78,7 @@ struct GzPinned {
     int64_t n_pieces;                              // piece_off[n_rows] of a piece count.  c->stream; pieces_count_locked waits for the stream
     GzPieceTotals pieces;                          // ... its position total and "a body is too long".  The same copy train, the same wait
     uint8_t small_out[64];                         // copy_out_small.  The stream the caller names; copy_out_small waits for it
+    int64_t lm_stats[8];                           // gram positions, then claims, per order of an n-gram model build.  c->stream; lm_build_locked waits for the stream
     int32_t fit_hist[GZ_FIT_MAX_LEN + 4];          // the length histogram of a best-fit pack call.  c->stream; fit_maps_locked waits for the stream
 };
 
@@ -211,6 +212,8 @@ struct gz_ctx {
     std::vector<gz_bm25*> bm25_live;     // indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_ng_aux;                       // n-gram overlap: the distinct counter, first_hit where the caller takes only first_ref
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
+    DBuf w_lm_aux;                       // n-gram language model build: gram positions and claims per order
+    std::vector<gz_ngram_lm*> lm_live;   // n-gram language models built on this context (gz_destroy frees what is left of them)
     DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
     DBuf w_ss_cut, w_ss_drop, w_ss_aux;  // the cut: piece counts and their scan, the staged drop bytes; duplicate substrings: first_dup where the caller takes only first_src
     DBuf w_q[8];                         // text quality signals: control words, counts, scans, span halves, table, long list, staged text and outputs (gz_quality_api.inc, QW_*)
@@ -1058,6 +1061,7 @@ try {
 } GZ_CATCH(nullptr)
 
 namespace { void ngram_index_free(gz_ngram_index* ix); }                  // (gz_ngram_api.inc)
+namespace { void ngram_lm_free(gz_ngram_lm* lm); }                        // (gz_lm_api.inc)
 
 void gz_destroy(gz_ctx* c)
 try {
@@ -1070,6 +1074,9 @@ try {
     c->bm25_live.clear();
     for (gz_ngram_index* ix : c->ngram_live) ngram_index_free(ix);
     c->ngram_live.clear();
+    for (gz_ngram_lm* lm : c->lm_live) ngram_lm_free(lm);
+    c->lm_live.clear();
+    release(c->w_lm_aux);
     for (DBuf& b : c->w_bm) release(b);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -2046,6 +2053,7 @@ try {
 
 #include "gz_rows_api.inc"
 #include "gz_ngram_api.inc"
+#include "gz_lm_api.inc"
 #include "gz_repeat_api.inc"
 #include "gz_substr_api.inc"
 #include "gz_quality_api.inc"

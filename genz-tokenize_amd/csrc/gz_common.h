@@ -99,6 +99,10 @@ struct GzOptions {
                                       // collisions: results must not change); 0 the whole hash
     int32_t quality_hash_bits = 0;    // text quality signals: k > 0 keeps only the low k bits of every (kind, document, span) hash (the same
                                       // forced collisions, between documents and kinds too: results must not change); 0 the whole hash
+    int32_t lm_hash_bits = 0;         // n-gram language model build (and the score calls of that model): k > 0 keeps only the low k bits of every
+                                      // gram's 64-bit hash (the same forced collisions, between orders too: results must not change); 0 the whole hash
+    int32_t lm_combine = 1;           // n-gram language model build: 1 adds the equal unigrams and bigrams of a trip once (a ballot-match loop in
+                                      // the wave); the counts are the same either way
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

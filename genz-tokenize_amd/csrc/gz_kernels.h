@@ -307,6 +307,28 @@ inline uint64_t gz_ngram_slots(int64_t n_positions)                 // the small
 void gz_launch_ngram_insert(GzNgramArgs A, hipStream_t s);          // into a cleared table
 void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s);           // presets the counts when a row has more than one piece; then resolves first_ref
 
+// token n-gram language model and perplexity (gz_lm.inc); pieces of END positions: the count pass at width 1, a position a body token
+constexpr int GZ_LM_MAX_ORDER = 8;
+struct GzLmArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // the rows walked: row r = ids[row_off[r] .. row_off[r + 1]); bodies shorter than 2^31
+    int64_t off0;                                                   // build: row_off[0]; a gram's end counts from here into ref_ids
+    int32_t skip_front, skip_back, order;                           // skips 0 or 1, 1 <= order <= GZ_LM_MAX_ORDER
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    unsigned long long* table; uint64_t mask;                       // two words a slot (key, count); slots - 1 (a power of two of slots, at least twice the gram positions)
+    uint64_t hmask;                                                 // hash bits kept (switch lm_hash_bits)
+    const int32_t* ref_ids; int64_t ref_n_ids;                      // the model's id copy
+    unsigned long long* stats;                                      // build: [GZ_LM_MAX_ORDER], successful claims per order are added
+    int32_t combine;                                                // build: equal unigrams and bigrams of a trip are added once (switch lm_combine)
+    uint32_t T; double lam;                                         // score: training body tokens (>= 1); -log2(alpha)
+    int32_t* n_tokens; unsigned long long* bits_fx; int32_t* n_order;     // score: [n_rows], [n_rows], [order + 1, n_rows]; each may be null
+    uint8_t* token_order; uint32_t* token_num; uint32_t* token_den;       // score: cell k belongs to ids[k]; each may be null
+};
+// gram positions of every order 1..order of the rows, added to stats[GZ_LM_MAX_ORDER], which is cleared first
+void gz_launch_lm_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t order, unsigned long long* stats, hipStream_t s);
+void gz_launch_lm_build(GzLmArgs A, hipStream_t s);                 // into a cleared table; clears stats first
+void gz_launch_lm_score(GzLmArgs A, hipStream_t s);                 // presets the sums when a row has more than one piece
+
 // n-gram repetition inside a document (gz_repeat.inc); pieces of n-gram positions at the call's smallest width
 struct GzRepeatArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31

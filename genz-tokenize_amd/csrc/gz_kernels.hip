@@ -719,6 +719,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_pieces.inc"
 #include "gz_minhash.inc"
 #include "gz_ngram.inc"
+#include "gz_lm.inc"
 #include "gz_repeat.inc"
 #include "gz_substr.inc"
 #include "gz_preproc.inc"
@@ -1004,6 +1005,34 @@ void gz_launch_ngram_query(GzNgramArgs A, hipStream_t s)
     }
     hipLaunchKernelGGL(gz_ngram_query_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
     if (A.first_ref) hipLaunchKernelGGL(gz_ngram_resolve_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
+}
+
+void gz_launch_lm_count(const int64_t* row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t order, unsigned long long* stats, hipStream_t s)
+{
+    (void)hipMemsetAsync(stats, 0, GZ_LM_MAX_ORDER * 8, s);
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(gz_lm_count_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, row_off, n_rows, skip_front, skip_back, order, stats);
+}
+
+void gz_launch_lm_build(GzLmArgs A, hipStream_t s)
+{
+    (void)hipMemsetAsync(A.stats, 0, GZ_LM_MAX_ORDER * 8, s);
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    const dim3 grid((unsigned)((A.n_pieces + 3) / 4)), block(WAVE * 4);
+    if (A.combine) hipLaunchKernelGGL(gz_lm_build_kernel<true>, grid, block, 0, s, A);
+    else hipLaunchKernelGGL(gz_lm_build_kernel<false>, grid, block, 0, s, A);
+}
+
+void gz_launch_lm_score(GzLmArgs A, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    if (!A.one_each) {                                                               // the pieces of a long row meet by atomicAdd
+        if (A.bits_fx) (void)hipMemsetAsync(A.bits_fx, 0, (size_t)A.n_rows * 8, s);
+        if (A.n_order) (void)hipMemsetAsync(A.n_order, 0, (size_t)A.n_rows * (size_t)(A.order + 1) * 4, s);
+    }
+    hipLaunchKernelGGL(gz_lm_score_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
 }
 
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)

@@ -88,6 +88,44 @@ inline bool ngram_positions_possible(int64_t n_pos, int64_t n_ids, int64_t n_row
     return n_pos >= least && n_pos <= n_ids;
 }
 
+// Token n-gram language model and perplexity (gz_ngram_lm_build*, gz_ngram_lm_score*; tests/test_lm_surface.py compiles these alone,
+// under the sanitizers): the sentence of the first rule an argument list breaks, or nullptr, in the order they are reported in.  The
+// training ids obey ngram_ids_fit (a slot holds end + 1 in 32 bits, and T fits the per-token den), the bodies minhash_bodies_fit.
+constexpr int32_t LM_MAX_ORDER = 8;
+inline const char* lm_build_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, int32_t order)
+{
+    if (n_rows < 0) return "n-gram model needs n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "n-gram model needs skips of 0 or 1";
+    if (order < 1 || order > LM_MAX_ORDER) return "n-gram model needs an order in 1..8";
+    return nullptr;
+}
+inline const char* lm_score_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, double alpha)
+{
+    if (n_rows < 0) return "perplexity needs n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "perplexity needs skips of 0 or 1";
+    if (!(alpha >= 1.0 / 256.0 && alpha <= 1.0)) return "perplexity needs alpha in [2^-8, 1]";      // (a NaN fails both comparisons)
+    return nullptr;
+}
+// gram positions of a body of m ids at order k >= 1: a body shorter than k has none
+inline int64_t lm_grams(int64_t m, int32_t k) { return m >= k ? m - k + 1 : 0; }
+// What the gram positions of order k can add up to when the bodies hold T ids between them in n_rows rows: every row with a body
+// loses at most k - 1.  A total outside that range read back from the device is no total (a table sized by one that is too small is
+// one a probe loop never leaves).  T >= 0, n_rows >= 0, k >= 1.
+inline bool lm_grams_possible(int64_t grams, int64_t T, int64_t n_rows, int32_t k)
+{
+    const int64_t lost = k - 1;
+    int64_t least = T;
+    if (lost) least = n_rows > T / lost ? 0 : T - n_rows * lost;                     // (the product is at most T: it does not wrap)
+    return grams >= least && grams <= T;
+}
+// the slots of a model: the smallest power of two that is at least twice the gram positions of all orders (at most 8 x 2^32: no wrap)
+inline uint64_t lm_slots(int64_t n_grams_total)
+{
+    uint64_t cap = 1;
+    while (cap < 2 * (uint64_t)n_grams_total) cap <<= 1;
+    return cap;
+}
+
 // n-gram repeats (gz_ngram_repeats*; tests/test_repeat_surface.py compiles this alone): the sentence of the first rule an argument
 // list breaks, or nullptr, in the order they are reported in.  The ids of a call obey ngram_ids_fit (a slot holds position + 1 in 32
 // bits) and its bodies minhash_bodies_fit.

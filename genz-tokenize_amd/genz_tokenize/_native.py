@@ -66,6 +66,7 @@ SYMBOLS = [
     "gz_pack_rows_fit", "gz_pack_rows_fit_device", "gz_pack_rows_fit_info",
     "gz_text_signals", "gz_text_signals_device",
     "gz_substr_dups", "gz_substr_dups_device", "gz_cut_rows", "gz_cut_rows_device",
+    "gz_ngram_lm_build", "gz_ngram_lm_build_device", "gz_ngram_lm_info", "gz_ngram_lm_destroy", "gz_ngram_lm_score", "gz_ngram_lm_score_device",
 ]
 
 _lib = None
@@ -280,12 +281,22 @@ def load_library():
         L.gz_substr_dups_device.argtypes = sd
         L.gz_cut_rows.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
         L.gz_cut_rows_device.argtypes = L.gz_cut_rows.argtypes
+    if hasattr(L, "gz_ngram_lm_build"):
+        lb = [vp, vp, vp, i64, i32, i32, i32, P(vp)]
+        L.gz_ngram_lm_build.argtypes = lb
+        L.gz_ngram_lm_build_device.argtypes = lb
+        L.gz_ngram_lm_info.argtypes = [vp, vp]
+        L.gz_ngram_lm_destroy.argtypes = [vp]; L.gz_ngram_lm_destroy.restype = None
+        ls = [vp, vp, vp, vp, i64, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp]
+        L.gz_ngram_lm_score.argtypes = ls
+        L.gz_ngram_lm_score_device.argtypes = ls
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_bpe_word_dropout", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
-                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy", "gz_ngram_index_destroy"):
+                        "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy", "gz_ngram_index_destroy",
+                        "gz_ngram_lm_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -918,6 +929,60 @@ class Context:
         """gz_ngram_overlap_device: every pointer a device address (0: NULL)."""
         self._check(self.lib.gz_ngram_overlap_device(self.handle, C.c_void_p(index), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
                                                      *_dptrs(d_n_grams, d_n_hits, d_n_covered, d_first_hit, d_first_ref, d_covered)))
+
+    # ---- token n-gram language model and perplexity -----------------------------------------------------------------
+    LM_MAX_ORDER = 8
+    LM_TOKEN_OUT = (("token_order", np.uint8), ("token_num", np.uint32), ("token_den", np.uint32))
+
+    def ngram_lm_build(self, ids: np.ndarray, row_off: np.ndarray, order: int, framed: bool) -> int:
+        """ids int32 (packed training rows), row_off int64 [R+1] -> handle of an n-gram language model (gz_ngram_lm_build)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        R, skip = len(row_off) - 1, 1 if framed else 0
+        h = C.c_void_p()
+        self._check(self.lib.gz_ngram_lm_build(self.handle, _ptr(ids) if len(ids) else None, _ptr(row_off), R, skip, skip, int(order), C.byref(h)))
+        return h.value
+
+    def ngram_lm_build_device(self, d_ids, d_row_off, n_rows, skip_front, skip_back, order) -> int:
+        """gz_ngram_lm_build_device: ids and offsets device addresses (0: NULL) -> handle."""
+        h = C.c_void_p()
+        self._check(self.lib.gz_ngram_lm_build_device(self.handle, *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, order, C.byref(h)))
+        return h.value
+
+    def ngram_lm_info(self, lm: int):
+        """dict(order, n_rows, n_ids, n_tokens, slots, device_bytes, hash_bits, n_grams_total) plus n_grams and n_distinct, tuples
+        indexed by the order k (entry 0: n_tokens and 1, the empty gram) (gz_ngram_lm_info)"""
+        info = np.zeros(24, dtype=np.int64)
+        self._check(self.lib.gz_ngram_lm_info(C.c_void_p(lm), _ptr(info)))
+        out = dict(zip(("order", "n_rows", "n_ids", "n_tokens", "slots", "device_bytes", "hash_bits", "n_grams_total"), (int(v) for v in info[:8])))
+        N = out["order"]
+        out["n_grams"] = (out["n_tokens"],) + tuple(int(v) for v in info[8:8 + N])
+        out["n_distinct"] = (1,) + tuple(int(v) for v in info[16:16 + N])
+        return out
+
+    def ngram_lm_destroy(self, lm: int):
+        if lm and getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.gz_ngram_lm_destroy(C.c_void_p(lm))
+
+    def ngram_lm_score(self, lm: int, order: int, ids: np.ndarray, row_off: np.ndarray, framed: bool, alpha: float, with_tokens: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict(n_tokens int32 [n], bits_fx uint64 [n], n_order int32 [order + 1, n]), and
+        the three per-token arrays when asked for (gz_ngram_lm_score)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        out = dict(n_tokens=np.zeros(n, dtype=np.int32), bits_fx=np.zeros(n, dtype=np.uint64), n_order=np.zeros((order + 1, n), dtype=np.int32))
+        tok = {k: np.zeros(len(ids), dtype=t) for k, t in self.LM_TOKEN_OUT} if with_tokens else {}
+        self._check(self.lib.gz_ngram_lm_score(self.handle, C.c_void_p(lm), _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip, float(alpha),
+                                               *[_ptr(v) if n else None for v in out.values()],
+                                               *[_ptr(tok[k]) if with_tokens and len(ids) else None for k, _ in self.LM_TOKEN_OUT]))
+        out.update(tok)
+        return out
+
+    def ngram_lm_score_device(self, lm: int, d_ids, d_row_off, n_rows, skip_front, skip_back, alpha, d_n_tokens, d_bits_fx, d_n_order, d_token_order,
+                              d_token_num, d_token_den):
+        """gz_ngram_lm_score_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_ngram_lm_score_device(self.handle, C.c_void_p(lm), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, float(alpha),
+                                                      *_dptrs(d_n_tokens, d_bits_fx, d_n_order, d_token_order, d_token_num, d_token_den)))
 
     # ---- n-gram repetition inside a document -----------------------------------------------------------------------
     REPEAT_OUT = ("n_grams", "n_distinct", "n_repeated", "n_covered", "top_count", "top_pos")

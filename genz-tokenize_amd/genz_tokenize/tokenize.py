@@ -121,6 +121,49 @@ class NgramIndex(object):
         return "NgramIndex(n=%d, n_rows=%d, n_distinct=%d%s)" % (self.n, self.n_rows, self.n_distinct, ", closed" if self.closed else "")
 
 
+class NgramLM(object):
+    """A token n-gram language model resident in HBM (`Tokenize.ngram_lm`, `Tokenize.encode_ngram_lm`): the counts of every k-gram,
+    k = 1..order, of the training rows -- what `perplexity_rows`, `encode_perplexity`, `perplexity_to_device` and
+    `perplexity_filter` of the SAME Tokenize object score against.  It owns a copy of the training ids.  `close()` (or leaving a
+    `with` block, or garbage collection) frees the device memory; a closed model is refused.  Properties: order, n_rows (training
+    rows), n_ids (training ids), n_tokens (training body tokens, T), n_grams[k] and n_distinct[k] (gram positions and distinct
+    grams of order k, tuples indexed 0..order; entry 0 is the empty gram: T and 1) and device_bytes."""
+
+    def __init__(self, ctx, handle):
+        self._ctx = ctx
+        self._handle = handle
+        self._info = ctx.ngram_lm_info(handle)
+        # (the finalizer holds the context: the model is freed before it)
+        self._finalizer = weakref.finalize(self, ctx.ngram_lm_destroy, handle)
+
+    order = property(lambda self: self._info["order"])
+    n_rows = property(lambda self: self._info["n_rows"])
+    n_ids = property(lambda self: self._info["n_ids"])
+    n_tokens = property(lambda self: self._info["n_tokens"])
+    n_grams = property(lambda self: self._info["n_grams"])
+    n_distinct = property(lambda self: self._info["n_distinct"])
+    device_bytes = property(lambda self: self._info["device_bytes"])
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def close(self):
+        if self._handle is not None:
+            self._handle = None
+            self._finalizer()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __repr__(self):
+        return "NgramLM(order=%d, n_rows=%d, n_tokens=%d%s)" % (self.order, self.n_rows, self.n_tokens, ", closed" if self.closed else "")
+
+
 class Tokenize(object):
     def __init__(self, pad_token='<pad>', bos_token='<s>', eos_token='</s>', mask_token='<mask>',
                  unk_token='<unk>', device: Optional[int] = None) -> None:
@@ -1750,6 +1793,146 @@ class Tokenize(object):
         covered, body = out["n_covered"].astype(np.float64), out["body_len"].astype(np.float64)
         out["fraction"] = covered / np.maximum(body, 1.0)
         out["keep"] = covered <= f * body
+        return out
+
+    # ---- token n-gram language model and perplexity ("model-based quality filtering") ----------------------------------------
+    @staticmethod
+    def _lm_order(order=5):
+        """The order of a model as an integer, or the refusal."""
+        return _integer("order", order, 1, _native.Context.LM_MAX_ORDER + 1)
+
+    @staticmethod
+    def _lm_alpha(alpha=0.4):
+        """The backoff factor as a float in [2^-8, 1], or the refusal."""
+        a = _number("alpha", alpha)
+        if not 2.0 ** -8 <= a <= 1.0:                                   # (NaN fails here too)
+            raise ValueError("alpha must lie in [2**-8, 1]")
+        return a
+
+    def _ngram_lm_of(self, lm):
+        """The live handle of `lm`, or the refusal: not an NgramLM, closed, or of another Tokenize object."""
+        if not isinstance(lm, NgramLM):
+            raise TypeError("lm must be an NgramLM (Tokenize.ngram_lm, Tokenize.encode_ngram_lm)")
+        if lm.closed:
+            raise ValueError("the NgramLM is closed")
+        if lm._ctx is not self._ctx:
+            raise ValueError("the NgramLM belongs to another Tokenize object's device context")
+        return lm._handle
+
+    @staticmethod
+    def _perplexity(out):
+        """bits_per_token and perplexity (float64) from the exact per-row sums"""
+        n = out["n_tokens"].astype(np.float64)
+        out["bits_per_token"] = out["bits_fx"].astype(np.float64) / 2.0 ** 24 / np.maximum(n, 1.0)
+        with np.errstate(over="ignore"):
+            out["perplexity"] = np.where(n > 0, 2.0 ** out["bits_per_token"], np.inf)
+        return out
+
+    def ngram_lm(self, rows, order=5, framed=True):
+        """An `NgramLM` over clean training `rows` (Wikipedia, curated books), built on the GPU and resident in HBM: the number of
+        occurrences c(g) of every k-gram g, k = 1..order, 1 <= order <= 8, and T, the number of training body tokens.  `rows` as
+        `ngram_index` takes them (`framed=True`: each row loses its first and last entry first); a k-gram never crosses a row.
+        The model owns a copy of the ids.  Training rows without a single body token are refused."""
+        order = self._lm_order(order)
+        flat, off = self._ngram_rows("ngram_lm", rows)
+        return NgramLM(self._ctx, self._ctx.ngram_lm_build(flat, off, order, bool(framed)))
+
+    def encode_ngram_lm(self, texts: Sequence[str], order=5, word_table=True):
+        """`ngram_lm` over the whole token sequence of every text: the texts are encoded without a length limit on the device and
+        the model is built there, over the rows of `encode_batch(texts, max_len=None)` without their frame.  Single texts only."""
+        order = self._lm_order(order)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx = self._ctx
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, R, dev):
+                handle = ctx.ngram_lm_build_device(d_ids, d_ro, R, 1, 1, order)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+        return NgramLM(ctx, handle)
+
+    def perplexity_rows(self, rows, lm, alpha=0.4, framed=True, return_tokens=False):
+        """The perplexity of token `rows` under the n-gram model `lm`, on the GPU: Stupid Backoff (Brants et al., 2007).  For a
+        body q of m ids and position i, with N = lm.order and T = lm.n_tokens: K = min(i + 1, N); j = the largest k in 0..K whose
+        k-gram q[i-k+1 .. i] was seen in training; num = its count and den = the count of q[i-j+1 .. i-1] (T when j = 1); an
+        unseen token (j = 0) has num = 1, den = T; the position costs log2(den) - log2(num) + (K - j) * -log2(alpha) bits
+        (float64), rounded to a grid of 2^-24.  `alpha` is a number in [2^-8, 1].  Returns n_tokens (int32 [R], m), bits_fx (uint64
+        [R], the sum of the grid values: an exact integer), n_order (int32 [N + 1, R], the positions with each j; row 0 counts the
+        unseen tokens), bits_per_token = bits_fx / 2^24 / max(n_tokens, 1) and perplexity = 2 ** bits_per_token (float64; inf
+        where n_tokens == 0).  With `return_tokens` also token_order (uint8), token_num and token_den (uint32) over the rows back
+        to back, zero on frame cells, and `row_off` int64 [R+1]: exact integers from which any other smoothing (Kneser-Ney, ...)
+        can be computed on the host.  A row's outputs depend on its own body, the model and alpha alone:
+        `perplexity_rows(rows[a:b])` is `perplexity_rows(rows)[a:b]`, and results of shards concatenate.  Moore-Lewis selection is
+        the difference of the bits_per_token of two models, the in-domain one's minus the general one's."""
+        handle = self._ngram_lm_of(lm)
+        a = self._lm_alpha(alpha)
+        flat, off = self._ngram_rows("perplexity_rows", rows)
+        out = self._perplexity(self._ctx.ngram_lm_score(handle, lm.order, flat, off, bool(framed), a, bool(return_tokens)))
+        if return_tokens:
+            out["row_off"] = off
+        return out
+
+    def _encode_perplexity(self, texts, lm, alpha, word_table, to_device):
+        from .handoff import DeviceArray
+        handle = self._ngram_lm_of(lm)
+        a = self._lm_alpha(alpha)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx, K = self._ctx, lm.order + 1
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, N, dev):
+                shapes = (("bits_fx", (N,), np.uint64), ("n_tokens", (N,), np.int32), ("n_order", (K, N), np.int32))
+                out = {}
+                try:
+                    for k, shape, dtype in shapes:
+                        d = ctx.alloc(8 * max(N * shape[0] if len(shape) == 2 else N, 1))
+                        try:
+                            out[k] = DeviceArray(ctx, d, shape, dtype=dtype)
+                        except BaseException:
+                            ctx.free(d)
+                            raise
+                    ctx.ngram_lm_score_device(handle, d_ids, d_ro, N, 1, 1, a, *[out[k].ptr if N else 0 for k in ("n_tokens", "bits_fx", "n_order")],
+                                              0, 0, 0)
+                    ctx.sync()                                         # (what the encode call deferred is reported here)
+                    if to_device:
+                        handed, out = out, {}                          # the caller's from here on
+                        return handed
+                    return {k: v.numpy() for k, v in out.items()}
+                finally:
+                    for v in out.values():                             # (on an error too, whichever form was asked for)
+                        v.free()
+
+    def encode_perplexity(self, texts: Sequence[str], lm, alpha=0.4, word_table=True):
+        """`perplexity_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
+        device, scored there, and only the per-document arrays come back -- n_tokens, bits_fx, n_order, bits_per_token and
+        perplexity.  The rule is `perplexity_rows`'s over the rows of `encode_batch(texts, max_len=None)` without their frame;
+        `encode_perplexity(texts[a:b])` is `encode_perplexity(texts)[a:b]`, and results of shards concatenate.  Single texts only."""
+        return self._perplexity(self._encode_perplexity(texts, lm, alpha, word_table, False))
+
+    def perplexity_to_device(self, texts: Sequence[str], lm, alpha=0.4):
+        """`encode_perplexity` whose exact per-document arrays STAY in HBM as `handoff.DeviceArray`s (`torch.from_dlpack(x)` is
+        zero-copy): n_tokens int32 [N], bits_fx uint64 [N] and n_order int32 [order + 1, N]; bits_per_token is
+        bits_fx / 2^24 / max(n_tokens, 1)."""
+        return self._encode_perplexity(texts, lm, alpha, True, True)
+
+    def perplexity_filter(self, texts: Sequence[str], lm, max_perplexity, min_perplexity=None, alpha=0.4):
+        """`encode_perplexity` plus the decision a recipe takes from it: keep = n_tokens > 0 and min_perplexity <= perplexity <=
+        max_perplexity (bool [N]; no lower bound when `min_perplexity` is None).  `max_perplexity` has no default: the bound
+        depends on the corpus and the model -- CCNet takes percentiles of the perplexities of a sample (its head / middle / tail
+        buckets are the thirds), so score a sample with `encode_perplexity` first.  `texts[i]` for the i with keep[i] is the
+        filtered corpus.  Moore-Lewis selection is the difference of the bits_per_token of two models."""
+        hi = _number("max_perplexity", max_perplexity)
+        lo = None if min_perplexity is None else _number("min_perplexity", min_perplexity)
+        if math.isnan(hi) or (lo is not None and math.isnan(lo)):
+            raise ValueError("the perplexity bounds must not be NaN")
+        out = self.encode_perplexity(texts, lm, alpha)
+        keep = (out["n_tokens"] > 0) & (out["perplexity"] <= hi)
+        if lo is not None:
+            keep &= out["perplexity"] >= lo
+        out["keep"] = keep
         return out
 
     # ---- duplicate substrings across documents ("exact substring deduplication") --------------------------------------------

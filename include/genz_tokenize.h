@@ -302,6 +302,10 @@ int64_t gz_limit(int which);
  *                              not change
  *   substr_hash_bits (0..32; 0)  gz_substr_dups* keep only the low k bits of every n-gram's hash (0: all of it); with k = 1 almost every
  *                              probe collides in start slot and tag: results must not change
+ *   lm_hash_bits (0..32; 0)  gz_ngram_lm_build* and the score calls of that model keep only the low k bits of every gram's hash (0: all
+ *                              of it); with k = 1 every probe of every order starts in one of two slots: results must not change
+ *   lm_combine (0..1; 1)  gz_ngram_lm_build* add the equal unigrams and bigrams of 64 neighbouring positions to the table once (1) or
+ *                              one by one (0); the counts are the same either way
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -1108,6 +1112,78 @@ int  gz_text_signals(gz_ctx *ctx, const uint8_t *text, const int64_t *off, int64
 int  gz_text_signals_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t *off_dev, int64_t n_docs, int32_t *signals_dev,
                             uint32_t *line_off_dev, int64_t *line_span_dev, int32_t *line_first_dev, uint32_t *para_off_dev,
                             int64_t *para_span_dev, int32_t *para_first_dev);
+
+/* ---- token n-gram language model and perplexity ("model-based quality filtering") -------------------------------------------------
+ * CCNet and the recipes descended from it train a small n-gram language model on clean text (Wikipedia, curated books), score every
+ * web document's perplexity under it and keep documents by perplexity bucket; Moore-Lewis selection takes the difference of two such
+ * scores.  A MODEL of the training rows' k-gram counts, k = 1..N, lives in device memory; a score call walks it once per token
+ * position.  Stupid Backoff (Brants et al., 2007): plain counts, exact integers.  Neither call needs the tables or the decoder
+ * snapshot.
+ *   body of row r    ids[row_off[r] + skip_front .. row_off[r+1] - skip_back); the skips are 0 or 1 as in gz_ngram_index_build; a row
+ *                    shorter than its skips has an empty body
+ *   model            order N in 1..8.  For k = 1..N, c(g) = the number of occurrences of the k-gram g in the training bodies; a k-gram
+ *                    never crosses a row, a body shorter than k has none.  T = the number of training body tokens (c of the empty
+ *                    gram).  A model with T = 0 is refused.  The model owns a copy of the training ids.
+ *   score            alpha a double in [2^-8, 1], lam = -log2(alpha).  For a query body q of m ids and position i:
+ *                    K = min(i + 1, N);  j = the largest k in 0..K with c(q[i-k+1 .. i]) > 0 (counts are monotone: j is the first
+ *                    k at which walking upward from k = 1 misses, minus one);
+ *                    num = c(q[i-j+1 .. i]),  den = c(q[i-j+1 .. i-1]), which is T when j = 1;  j = 0 (the token itself unseen):
+ *                    num = 1, den = T;  back = K - j;
+ *                    cost = log2(den) - log2(num) + back * lam  in float64;  fx = rint(cost * 2^24), an integer below 2^31
+ *   per row          n_tokens[r] = m (int32);  bits_fx[r] = the sum of fx over the body (uint64: an integer, so it does not depend
+ *                    on the order in which waves or pieces add);  n_order int32 [N + 1, n_rows]: n_order[j, r] = the positions of
+ *                    row r with that j, row 0 the unseen tokens
+ *   per token        (optional) one cell per id of the input, cell k belongs to ids[k] for k in [row_off[0], row_off[n_rows]), zero
+ *                    on the skipped frame cells: token_order uint8 = j, token_num uint32 = num, token_den uint32 = den.  Exact
+ *                    integers: any other smoothing can be computed from them on the host
+ *   score(rows[a:b]) == score(rows)[a:b], bits_fx included: a row's outputs depend on its own body, the model and alpha alone.
+ *   The outputs are a pure function of (training rows, N, query rows, alpha): not of launch geometry, scheduling or the hash.
+ *   bits per token = bits_fx / 2^24 / max(n_tokens, 1);  perplexity = 2 ^ bits per token.
+ *   hash             a hash decides where to look, never whether two n-grams are equal.  It extends BACKWARDS, one step per order:
+ *                    the two MurmurHash3_x86_32 streams of gz_ngram_index_build (seeds 0 and 0x9E3779B9),  H_1 = mix(seed, q[e]),
+ *                    H_k = mix(H_{k-1}, q[e-k+1]); the k-gram's  h64 = fmix32(H_k ^ 4 k) of both streams, cut to its low
+ *                    lm_hash_bits bits when that switch is set;  start slot = h64 & (slots - 1);  tag = h64 >> 32 with its low 3
+ *                    bits replaced by k - 1.  The N grams of a position share one chain: N steps a position
+ *   table            ONE table for all orders, open addressing, linear probing, slots = the smallest power of two that is at least
+ *                    twice the gram positions of all orders, 16 bytes a slot: a 64-bit key word tag << 32 | (end + 1), end = the
+ *                    global index of the gram's LAST id in the model's id copy, 0 = free, and a 32-bit count.  Insert: 64-bit
+ *                    compare-and-swap on a free slot; on a taken slot with an equal tag (and so order) the k ids at the occupant's
+ *                    end are compared with the inserter's: equal -- atomic add on the count; else the next slot.  Successful claims
+ *                    per order are the distinct grams
+ *   memory           the model: 4 bytes a training id and 16 bytes a slot -- with N = 5, 164 to 324 bytes a training token;
+ *                    workspace of a build or a score call: 16 bytes a row
+ *   ids / row_off    packed int32 rows as gz_ngram_index_build takes them; every output may be NULL.
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched, built or written: n_rows < 0; a skip
+ *   outside {0, 1}; an order outside 1..8; alpha outside [2^-8, 1] or NaN; T = 0 (no rows, or empty bodies only); a NULL out handle;
+ *   NULL ids or row_off with n_rows > 0; output arrays that overlap the input or each other; bad or decreasing row offsets (the host
+ *   forms); a model that is NULL, destroyed or of another context.  GZ_E_LIMIT and nothing built or written: training ids that total
+ *   2^32 - 1 or more, or a body of 2^31 ids or more.  A score call with n_rows == 0 is GZ_OK and launches nothing.
+ * gz_ngram_lm_build: host pointers.  gz_ngram_lm_build_device: DEVICE pointers; offsets are ABSOLUTE from the base pointer and
+ *   row_off_dev[0] need not be 0; every pass runs on the context's stream, behind a gz_encode_batch_device (ragged layout) enqueued
+ *   just before with no gz_sync in between.  The model is complete on return.
+ * gz_ngram_lm_info: info[24] = order, training rows, training ids, T, table slots, device bytes, hash bits kept (0: all), gram
+ *   positions of all orders; info[8 + k - 1] = gram positions of order k; info[16 + k - 1] = distinct grams of order k (k = 1..8).
+ * gz_ngram_lm_destroy: frees the model (NULL is fine).  A model belongs to its context and is destroyed before it; gz_destroy frees
+ *   what is left.
+ * gz_ngram_lm_score: host pointers, the outputs come back.  gz_ngram_lm_score_device: every pointer a DEVICE pointer, offsets
+ *   ABSOLUTE as above, same ordering; the call returns when its outputs are complete.  Both use the model's order; the skips are the
+ *   call's own.
+ * Not here: Kneser-Ney or other discounting (the per-token counts let a caller do it on the host), adding rows to a live model or
+ *   merging two, saving and loading, pruning by count, <s> / </s> context padding, multi-GPU models (shards score against one
+ *   replicated model and the outputs concatenate), text or character n-grams. */
+typedef struct gz_ngram_lm gz_ngram_lm;
+int  gz_ngram_lm_build(gz_ctx *ctx, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front, int32_t skip_back,
+                       int32_t order, gz_ngram_lm **out);
+int  gz_ngram_lm_build_device(gz_ctx *ctx, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows, int32_t skip_front,
+                              int32_t skip_back, int32_t order, gz_ngram_lm **out);
+int  gz_ngram_lm_info(gz_ngram_lm *lm, int64_t info[24]);
+void gz_ngram_lm_destroy(gz_ngram_lm *lm);
+int  gz_ngram_lm_score(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front,
+                       int32_t skip_back, double alpha, int32_t *n_tokens, uint64_t *bits_fx, int32_t *n_order, uint8_t *token_order,
+                       uint32_t *token_num, uint32_t *token_den);
+int  gz_ngram_lm_score_device(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                              int32_t skip_front, int32_t skip_back, double alpha, int32_t *n_tokens_dev, uint64_t *bits_fx_dev,
+                              int32_t *n_order_dev, uint8_t *token_order_dev, uint32_t *token_num_dev, uint32_t *token_den_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
