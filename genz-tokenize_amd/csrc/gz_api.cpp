@@ -79,6 +79,7 @@ struct GzPinned {
     GzPieceTotals pieces;                          // ... its position total and "a body is too long".  The same copy train, the same wait
     uint8_t small_out[64];                         // copy_out_small.  The stream the caller names; copy_out_small waits for it
     int64_t lm_stats[8];                           // gram positions, then claims, per order of an n-gram model build.  c->stream; lm_build_locked waits for the stream
+    int64_t kn_cells[GZ_LM_KN_CELLS];              // the empty context's record and the counts of counts of a Kneser-Ney derivation.  c->stream; lm_kn_prepare_locked waits
     int32_t fit_hist[GZ_FIT_MAX_LEN + 4];          // the length histogram of a best-fit pack call.  c->stream; fit_maps_locked waits for the stream
 };
 
@@ -2054,6 +2055,7 @@ try {
 #include "gz_rows_api.inc"
 #include "gz_ngram_api.inc"
 #include "gz_lm_api.inc"
+#include "gz_lm_kn_api.inc"
 #include "gz_repeat_api.inc"
 #include "gz_substr_api.inc"
 #include "gz_quality_api.inc"

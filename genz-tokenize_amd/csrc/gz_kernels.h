@@ -329,6 +329,22 @@ void gz_launch_lm_count(const int64_t* row_off, int64_t n_rows, int32_t skip_fro
 void gz_launch_lm_build(GzLmArgs A, hipStream_t s);                 // into a cleared table; clears stats first
 void gz_launch_lm_score(GzLmArgs A, hipStream_t s);                 // presets the sums when a row has more than one piece
 
+// modified Kneser-Ney over the same table (gz_lm_kn.inc): the sidecar's two derivation passes and the scoring walk
+constexpr int GZ_LM_KN_CELLS = 4 + 4 * GZ_LM_MAX_ORDER;             // the empty context's A, F1..F3, then n_1..n_4 of order 1, of order 2, ...
+struct GzLmKnArgs {
+    GzLmArgs M;                                                     // the model and, for a score call, the rows and the outputs it shares with Stupid Backoff
+    uint64_t slots;                                                 // M.mask + 1
+    uint32_t* left;                                                 // [slots]: L of the slot's gram
+    uint32_t* rec;                                                  // [slots][4]: A, F1, F2, F3 of the slot's gram as a context
+    unsigned long long* cells;                                      // derivation: [GZ_LM_KN_CELLS], cleared by the launcher
+    double D[GZ_LM_MAX_ORDER][3];                                   // score: the discounts of order k at [k - 1]
+    double p0;                                                      // score: 1 / (V + 1)
+    uint32_t A0, F0[3];                                             // score: the empty context's statistics
+    uint32_t* token_bits_fx;                                        // score: cell k belongs to ids[k]; may be null (M.token_num and M.token_den are not used)
+};
+void gz_launch_lm_kn_derive(GzLmKnArgs K, hipStream_t s);           // clears left, rec and cells, then pass 1 and pass 2
+void gz_launch_lm_kn_score(GzLmKnArgs K, hipStream_t s);            // presets the sums when a row has more than one piece
+
 // n-gram repetition inside a document (gz_repeat.inc); pieces of n-gram positions at the call's smallest width
 struct GzRepeatArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31

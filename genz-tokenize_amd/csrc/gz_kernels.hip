@@ -720,6 +720,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_minhash.inc"
 #include "gz_ngram.inc"
 #include "gz_lm.inc"
+#include "gz_lm_kn.inc"
 #include "gz_repeat.inc"
 #include "gz_substr.inc"
 #include "gz_preproc.inc"
@@ -1033,6 +1034,28 @@ void gz_launch_lm_score(GzLmArgs A, hipStream_t s)
         if (A.n_order) (void)hipMemsetAsync(A.n_order, 0, (size_t)A.n_rows * (size_t)(A.order + 1) * 4, s);
     }
     hipLaunchKernelGGL(gz_lm_score_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, A);
+}
+
+void gz_launch_lm_kn_derive(GzLmKnArgs K, hipStream_t s)
+{
+    (void)hipMemsetAsync(K.left, 0, (size_t)K.slots * 4, s);
+    (void)hipMemsetAsync(K.rec, 0, (size_t)K.slots * 16, s);
+    (void)hipMemsetAsync(K.cells, 0, GZ_LM_KN_CELLS * 8, s);
+    const dim3 grid((unsigned)((K.slots + 255) / 256)), block(256);
+    hipLaunchKernelGGL(gz_lm_kn_left_kernel, grid, block, 0, s, K);
+    hipLaunchKernelGGL(gz_lm_kn_context_kernel, grid, block, 0, s, K);               // (behind pass 1 on the stream: L is complete)
+}
+
+void gz_launch_lm_kn_score(GzLmKnArgs K, hipStream_t s)
+{
+    GzLmArgs& A = K.M;
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    if (!A.one_each) {                                                               // the pieces of a long row meet by atomicAdd
+        if (A.bits_fx) (void)hipMemsetAsync(A.bits_fx, 0, (size_t)A.n_rows * 8, s);
+        if (A.n_order) (void)hipMemsetAsync(A.n_order, 0, (size_t)A.n_rows * (size_t)(A.order + 1) * 4, s);
+    }
+    hipLaunchKernelGGL(gz_lm_kn_score_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, K);
 }
 
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)

@@ -18,7 +18,13 @@ struct gz_ngram_lm {
     int64_t n_grams[GZ_LM_MAX_ORDER] = {}, n_distinct[GZ_LM_MAX_ORDER] = {};
     uint64_t slots = 0, hmask = ~0ull;
     DBuf ids, table;
-    ~gz_ngram_lm() { release(ids); release(table); }
+    // modified Kneser-Ney (gz_lm_kn_api.inc): the sidecar and what the derivation read back; nothing of it exists before the first prepare
+    bool kn_ready = false;
+    DBuf kn_left, kn_rec;
+    int64_t kn_cells[GZ_LM_KN_CELLS] = {};
+    double kn_D[GZ_LM_MAX_ORDER][3] = {};
+    bool kn_fallback[GZ_LM_MAX_ORDER] = {};
+    ~gz_ngram_lm() { release(ids); release(table); release(kn_left); release(kn_rec); }
     int64_t device_bytes() const { return (int64_t)(ids.cap + table.cap); }
 };
 

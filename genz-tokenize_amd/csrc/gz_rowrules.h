@@ -125,6 +125,32 @@ inline uint64_t lm_slots(int64_t n_grams_total)
     while (cap < 2 * (uint64_t)n_grams_total) cap <<= 1;
     return cap;
 }
+// Modified Kneser-Ney over that model (gz_ngram_lm_score_kn*; tests/test_lm_kn_surface.py compiles these alone, under the sanitizers).
+// The first rule an argument list breaks, or nullptr: lm_score_fault's without alpha, then the caller's discounts, which may be null
+// (the rule's own) or [order, 3] with D[k - 1][j - 1] in (0, j].
+inline const char* lm_kn_score_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back, const double* discounts, int32_t order)
+{
+    if (const char* why = lm_score_fault(n_rows, skip_front, skip_back, 1.0)) return why;
+    for (int32_t i = 0; discounts && i < 3 * order; ++i)
+        if (!(discounts[i] > 0.0 && discounts[i] <= (double)(i % 3 + 1))) return "perplexity needs discounts D[k][j] in (0, j]";      // (a NaN fails the first comparison)
+    return nullptr;
+}
+// The discounts of one order from its counts of counts n[j - 1] = n_j, j = 1..4 (each below 2^32): Y = n1 / (n1 + 2 n2), D_j = j - (j + 1) Y
+// n_{j+1} / n_j in float64.  True, and D = (0.5, 1, 1.5), when an n_j is 0 or some D_j is not in (0, j).  Every D_j is below j once the
+// counts are positive, and D_1 = n1 / (n1 + 2 n2) lies in (0, 1); D_2 > 0 and D_3 > 0 are decided in integers: 2 n2 (n1 + 2 n2) > 3 n1 n3
+// and 3 n3 (n1 + 2 n2) > 4 n1 n4 (products below 2^68).
+inline bool lm_kn_discounts(const int64_t n[4], double D[3])
+{
+    typedef unsigned __int128 u128;
+    const u128 n1 = (u128)n[0], n2 = (u128)n[1], n3 = (u128)n[2], n4 = (u128)n[3], s = n1 + 2 * n2;
+    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0 || n[3] <= 0 || !(2 * n2 * s > 3 * n1 * n3) || !(3 * n3 * s > 4 * n1 * n4)) {
+        D[0] = 0.5; D[1] = 1.0; D[2] = 1.5;
+        return true;
+    }
+    const double Y = (double)n[0] / ((double)n[0] + 2.0 * (double)n[1]);
+    for (int j = 1; j <= 3; ++j) D[j - 1] = (double)j - (double)(j + 1) * Y * (double)n[j] / (double)n[j - 1];
+    return false;
+}
 
 // n-gram repeats (gz_ngram_repeats*; tests/test_repeat_surface.py compiles this alone): the sentence of the first rule an argument
 // list breaks, or nullptr, in the order they are reported in.  The ids of a call obey ngram_ids_fit (a slot holds position + 1 in 32

@@ -67,6 +67,7 @@ SYMBOLS = [
     "gz_text_signals", "gz_text_signals_device",
     "gz_substr_dups", "gz_substr_dups_device", "gz_cut_rows", "gz_cut_rows_device",
     "gz_ngram_lm_build", "gz_ngram_lm_build_device", "gz_ngram_lm_info", "gz_ngram_lm_destroy", "gz_ngram_lm_score", "gz_ngram_lm_score_device",
+    "gz_ngram_lm_kn_prepare", "gz_ngram_lm_kn_info", "gz_ngram_lm_kn_discounts", "gz_ngram_lm_score_kn", "gz_ngram_lm_score_kn_device",
 ]
 
 _lib = None
@@ -290,6 +291,13 @@ def load_library():
         ls = [vp, vp, vp, vp, i64, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp]
         L.gz_ngram_lm_score.argtypes = ls
         L.gz_ngram_lm_score_device.argtypes = ls
+    if hasattr(L, "gz_ngram_lm_score_kn"):
+        L.gz_ngram_lm_kn_prepare.argtypes = [vp, vp]
+        L.gz_ngram_lm_kn_info.argtypes = [vp, vp]
+        L.gz_ngram_lm_kn_discounts.argtypes = [vp, vp]
+        lk = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.gz_ngram_lm_score_kn.argtypes = lk
+        L.gz_ngram_lm_score_kn_device.argtypes = lk
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
@@ -983,6 +991,52 @@ class Context:
         """gz_ngram_lm_score_device: every pointer a device address (0: NULL)."""
         self._check(self.lib.gz_ngram_lm_score_device(self.handle, C.c_void_p(lm), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back, float(alpha),
                                                       *_dptrs(d_n_tokens, d_bits_fx, d_n_order, d_token_order, d_token_num, d_token_den)))
+
+    # ---- modified Kneser-Ney over the n-gram model ------------------------------------------------------------------
+    LM_KN_TOKEN_OUT = (("token_order", np.uint8), ("token_bits_fx", np.uint32))
+
+    def ngram_lm_kn_prepare(self, lm: int):
+        """gz_ngram_lm_kn_prepare: derive the model's Kneser-Ney sidecar (idempotent)."""
+        self._check(self.lib.gz_ngram_lm_kn_prepare(self.handle, C.c_void_p(lm)))
+
+    def ngram_lm_kn_info(self, lm: int):
+        """dict(prepared, V, sidecar_bytes, A, F (F_1..F_3 of the empty context), counts_of_counts int64 [N, 4], fallback bool [N]) and,
+        once prepared, discounts float64 [N, 3] (gz_ngram_lm_kn_info, gz_ngram_lm_kn_discounts)"""
+        info = np.zeros(48, dtype=np.int64)
+        self._check(self.lib.gz_ngram_lm_kn_info(C.c_void_p(lm), _ptr(info)))
+        N = int(info[7])
+        out = dict(prepared=bool(info[0]), V=int(info[1]), sidecar_bytes=int(info[2]), A=int(info[3]), F=tuple(int(v) for v in info[4:7]),
+                   counts_of_counts=info[8:8 + 4 * N].reshape(N, 4).copy(), fallback=info[40:40 + N].astype(bool))
+        if out["prepared"]:
+            out["discounts"] = self.ngram_lm_kn_discounts(lm)[:N]
+        return out
+
+    def ngram_lm_kn_discounts(self, lm: int) -> np.ndarray:
+        """float64 [8, 3]: D_k1..D_k3 of the rule at [k - 1], zero beyond the model's order (gz_ngram_lm_kn_discounts; a prepared model)"""
+        D = np.zeros((8, 3), dtype=np.float64)
+        self._check(self.lib.gz_ngram_lm_kn_discounts(C.c_void_p(lm), _ptr(D)))
+        return D
+
+    def ngram_lm_score_kn(self, lm: int, order: int, ids: np.ndarray, row_off: np.ndarray, framed: bool, discounts, with_tokens: bool):
+        """ids int32 (packed rows), row_off int64 [n+1], discounts None or float64 [order, 3] -> dict(n_tokens int32 [n], bits_fx uint64 [n],
+        n_order int32 [order + 1, n]), and the two per-token arrays when asked for (gz_ngram_lm_score_kn)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        out = dict(n_tokens=np.zeros(n, dtype=np.int32), bits_fx=np.zeros(n, dtype=np.uint64), n_order=np.zeros((order + 1, n), dtype=np.int32))
+        tok = {k: np.zeros(len(ids), dtype=t) for k, t in self.LM_KN_TOKEN_OUT} if with_tokens else {}
+        self._check(self.lib.gz_ngram_lm_score_kn(self.handle, C.c_void_p(lm), _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip,
+                                                  None if discounts is None else _ptr(discounts), *[_ptr(v) if n else None for v in out.values()],
+                                                  *[_ptr(tok[k]) if with_tokens and len(ids) else None for k, _ in self.LM_KN_TOKEN_OUT]))
+        out.update(tok)
+        return out
+
+    def ngram_lm_score_kn_device(self, lm: int, d_ids, d_row_off, n_rows, skip_front, skip_back, discounts, d_n_tokens, d_bits_fx, d_n_order, d_token_order,
+                                 d_token_bits_fx):
+        """gz_ngram_lm_score_kn_device: every pointer a device address (0: NULL) but `discounts`, None or a float64 [order, 3] host array."""
+        self._check(self.lib.gz_ngram_lm_score_kn_device(self.handle, C.c_void_p(lm), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
+                                                         None if discounts is None else _ptr(discounts),
+                                                         *_dptrs(d_n_tokens, d_bits_fx, d_n_order, d_token_order, d_token_bits_fx)))
 
     # ---- n-gram repetition inside a document -----------------------------------------------------------------------
     REPEAT_OUT = ("n_grams", "n_distinct", "n_repeated", "n_covered", "top_count", "top_pos")

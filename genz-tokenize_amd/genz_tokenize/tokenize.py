@@ -148,6 +148,16 @@ class NgramLM(object):
     def closed(self):
         return self._handle is None
 
+    def kneser_ney(self):
+        """Prepare the model for `smoothing="kneser_ney"` (two passes over its table on the GPU, once; the score calls do it on first
+        use) and return what the rule's discounts come from: dict(prepared, V (distinct unigrams), sidecar_bytes, A and F (the empty
+        context's statistics), counts_of_counts int64 [order, 4] (n_1..n_4 per order), discounts float64 [order, 3] (D_k1..D_k3) and
+        fallback bool [order] (the order uses (0.5, 1, 1.5))."""
+        if self.closed:
+            raise ValueError("the NgramLM is closed")
+        self._ctx.ngram_lm_kn_prepare(self._handle)
+        return self._ctx.ngram_lm_kn_info(self._handle)
+
     def close(self):
         if self._handle is not None:
             self._handle = None
@@ -1809,6 +1819,22 @@ class Tokenize(object):
             raise ValueError("alpha must lie in [2**-8, 1]")
         return a
 
+    @staticmethod
+    def _lm_smoothing(lm, smoothing, discounts):
+        """False for Stupid Backoff; for Kneser-Ney True and the caller's discounts as float64 [order, 3] or None -- or the refusal."""
+        if smoothing not in ("stupid_backoff", "kneser_ney"):
+            raise ValueError('smoothing must be "stupid_backoff" or "kneser_ney"')
+        if discounts is None:
+            return smoothing == "kneser_ney", None
+        if smoothing != "kneser_ney":
+            raise ValueError('discounts belong to smoothing="kneser_ney"')
+        D = np.ascontiguousarray(discounts, dtype=np.float64)
+        if D.shape != (lm.order, 3):
+            raise ValueError("discounts must have the shape [order, 3]")
+        if not ((D > 0) & (D <= np.array([1.0, 2.0, 3.0]))).all():        # (NaN fails here too)
+            raise ValueError("discounts[k][j - 1] must lie in (0, j]")
+        return True, D
+
     def _ngram_lm_of(self, lm):
         """The live handle of `lm`, or the refusal: not an NgramLM, closed, or of another Tokenize object."""
         if not isinstance(lm, NgramLM):
@@ -1852,7 +1878,7 @@ class Tokenize(object):
                 ctx.sync()                                             # (what the encode call deferred is reported here)
         return NgramLM(ctx, handle)
 
-    def perplexity_rows(self, rows, lm, alpha=0.4, framed=True, return_tokens=False):
+    def perplexity_rows(self, rows, lm, alpha=0.4, framed=True, return_tokens=False, *, smoothing="stupid_backoff", discounts=None):
         """The perplexity of token `rows` under the n-gram model `lm`, on the GPU: Stupid Backoff (Brants et al., 2007).  For a
         body q of m ids and position i, with N = lm.order and T = lm.n_tokens: K = min(i + 1, N); j = the largest k in 0..K whose
         k-gram q[i-k+1 .. i] was seen in training; num = its count and den = the count of q[i-j+1 .. i-1] (T when j = 1); an
@@ -1861,22 +1887,33 @@ class Tokenize(object):
         [R], the sum of the grid values: an exact integer), n_order (int32 [N + 1, R], the positions with each j; row 0 counts the
         unseen tokens), bits_per_token = bits_fx / 2^24 / max(n_tokens, 1) and perplexity = 2 ** bits_per_token (float64; inf
         where n_tokens == 0).  With `return_tokens` also token_order (uint8), token_num and token_den (uint32) over the rows back
-        to back, zero on frame cells, and `row_off` int64 [R+1]: exact integers from which any other smoothing (Kneser-Ney, ...)
-        can be computed on the host.  A row's outputs depend on its own body, the model and alpha alone:
+        to back, zero on frame cells, and `row_off` int64 [R+1].  A row's outputs depend on its own body, the model and alpha alone:
         `perplexity_rows(rows[a:b])` is `perplexity_rows(rows)[a:b]`, and results of shards concatenate.  Moore-Lewis selection is
-        the difference of the bits_per_token of two models, the in-domain one's minus the general one's."""
+        the difference of the bits_per_token of two models, the in-domain one's minus the general one's.
+        `smoothing="kneser_ney"` scores with interpolated modified Kneser-Ney instead (what KenLM models score with; `alpha` is not
+        used): p_0 = 1 / (V + 1), and for k = 1..K, p_k = (max(a(g) - D_k,min(a,3), 0) + (D_k1 F_1(x) + D_k2 F_2(x) + D_k3 F_3(x)) *
+        p_{k-1}) / A(x) over the context x = q[i-k+1 .. i-1] and g = x.q[i], until x is unseen -- a the adjusted counts (distinct left
+        neighbours below the top order), A and F_j a context's follower statistics, D the discounts of `lm.kneser_ney()` or the
+        caller's `discounts` (float [order, 3], D[k-1][j-1] in (0, j]).  The p of a context sum to one over the V seen tokens and one
+        unseen token.  A position costs min(-log2 p, 120) bits on the same grid; n_order counts j as above; `return_tokens` gives
+        token_order and token_bits_fx (uint32).  The model is prepared on first use."""
         handle = self._ngram_lm_of(lm)
         a = self._lm_alpha(alpha)
+        kn, D = self._lm_smoothing(lm, smoothing, discounts)
         flat, off = self._ngram_rows("perplexity_rows", rows)
-        out = self._perplexity(self._ctx.ngram_lm_score(handle, lm.order, flat, off, bool(framed), a, bool(return_tokens)))
+        if kn:
+            out = self._perplexity(self._ctx.ngram_lm_score_kn(handle, lm.order, flat, off, bool(framed), D, bool(return_tokens)))
+        else:
+            out = self._perplexity(self._ctx.ngram_lm_score(handle, lm.order, flat, off, bool(framed), a, bool(return_tokens)))
         if return_tokens:
             out["row_off"] = off
         return out
 
-    def _encode_perplexity(self, texts, lm, alpha, word_table, to_device):
+    def _encode_perplexity(self, texts, lm, alpha, word_table, to_device, smoothing="stupid_backoff", discounts=None):
         from .handoff import DeviceArray
         handle = self._ngram_lm_of(lm)
         a = self._lm_alpha(alpha)
+        kn, D = self._lm_smoothing(lm, smoothing, discounts)
         texts = list(texts)
         for t in texts:
             _require_str(t)
@@ -1894,8 +1931,11 @@ class Tokenize(object):
                         except BaseException:
                             ctx.free(d)
                             raise
-                    ctx.ngram_lm_score_device(handle, d_ids, d_ro, N, 1, 1, a, *[out[k].ptr if N else 0 for k in ("n_tokens", "bits_fx", "n_order")],
-                                              0, 0, 0)
+                    ptrs = [out[k].ptr if N else 0 for k in ("n_tokens", "bits_fx", "n_order")]
+                    if kn:
+                        ctx.ngram_lm_score_kn_device(handle, d_ids, d_ro, N, 1, 1, D, *ptrs, 0, 0)
+                    else:
+                        ctx.ngram_lm_score_device(handle, d_ids, d_ro, N, 1, 1, a, *ptrs, 0, 0, 0)
                     ctx.sync()                                         # (what the encode call deferred is reported here)
                     if to_device:
                         handed, out = out, {}                          # the caller's from here on
@@ -1905,20 +1945,22 @@ class Tokenize(object):
                     for v in out.values():                             # (on an error too, whichever form was asked for)
                         v.free()
 
-    def encode_perplexity(self, texts: Sequence[str], lm, alpha=0.4, word_table=True):
+    def encode_perplexity(self, texts: Sequence[str], lm, alpha=0.4, word_table=True, *, smoothing="stupid_backoff", discounts=None):
         """`perplexity_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the
         device, scored there, and only the per-document arrays come back -- n_tokens, bits_fx, n_order, bits_per_token and
         perplexity.  The rule is `perplexity_rows`'s over the rows of `encode_batch(texts, max_len=None)` without their frame;
-        `encode_perplexity(texts[a:b])` is `encode_perplexity(texts)[a:b]`, and results of shards concatenate.  Single texts only."""
-        return self._perplexity(self._encode_perplexity(texts, lm, alpha, word_table, False))
+        `encode_perplexity(texts[a:b])` is `encode_perplexity(texts)[a:b]`, and results of shards concatenate.  Single texts only.
+        `smoothing` and `discounts` as `perplexity_rows` takes them."""
+        return self._perplexity(self._encode_perplexity(texts, lm, alpha, word_table, False, smoothing, discounts))
 
-    def perplexity_to_device(self, texts: Sequence[str], lm, alpha=0.4):
+    def perplexity_to_device(self, texts: Sequence[str], lm, alpha=0.4, *, smoothing="stupid_backoff", discounts=None):
         """`encode_perplexity` whose exact per-document arrays STAY in HBM as `handoff.DeviceArray`s (`torch.from_dlpack(x)` is
         zero-copy): n_tokens int32 [N], bits_fx uint64 [N] and n_order int32 [order + 1, N]; bits_per_token is
         bits_fx / 2^24 / max(n_tokens, 1)."""
-        return self._encode_perplexity(texts, lm, alpha, True, True)
+        return self._encode_perplexity(texts, lm, alpha, True, True, smoothing, discounts)
 
-    def perplexity_filter(self, texts: Sequence[str], lm, max_perplexity, min_perplexity=None, alpha=0.4):
+    def perplexity_filter(self, texts: Sequence[str], lm, max_perplexity, min_perplexity=None, alpha=0.4, *, smoothing="stupid_backoff",
+                          discounts=None):
         """`encode_perplexity` plus the decision a recipe takes from it: keep = n_tokens > 0 and min_perplexity <= perplexity <=
         max_perplexity (bool [N]; no lower bound when `min_perplexity` is None).  `max_perplexity` has no default: the bound
         depends on the corpus and the model -- CCNet takes percentiles of the perplexities of a sample (its head / middle / tail
@@ -1928,7 +1970,7 @@ class Tokenize(object):
         lo = None if min_perplexity is None else _number("min_perplexity", min_perplexity)
         if math.isnan(hi) or (lo is not None and math.isnan(lo)):
             raise ValueError("the perplexity bounds must not be NaN")
-        out = self.encode_perplexity(texts, lm, alpha)
+        out = self.encode_perplexity(texts, lm, alpha, smoothing=smoothing, discounts=discounts)
         keep = (out["n_tokens"] > 0) & (out["perplexity"] <= hi)
         if lo is not None:
             keep &= out["perplexity"] >= lo

@@ -1135,7 +1135,7 @@ int  gz_text_signals_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t 
  *                    row r with that j, row 0 the unseen tokens
  *   per token        (optional) one cell per id of the input, cell k belongs to ids[k] for k in [row_off[0], row_off[n_rows]), zero
  *                    on the skipped frame cells: token_order uint8 = j, token_num uint32 = num, token_den uint32 = den.  Exact
- *                    integers: any other smoothing can be computed from them on the host
+ *                    integers (modified Kneser-Ney needs more than these: the next section)
  *   score(rows[a:b]) == score(rows)[a:b], bits_fx included: a row's outputs depend on its own body, the model and alpha alone.
  *   The outputs are a pure function of (training rows, N, query rows, alpha): not of launch geometry, scheduling or the hash.
  *   bits per token = bits_fx / 2^24 / max(n_tokens, 1);  perplexity = 2 ^ bits per token.
@@ -1168,7 +1168,7 @@ int  gz_text_signals_device(gz_ctx *ctx, const uint8_t *text_dev, const int64_t 
  * gz_ngram_lm_score: host pointers, the outputs come back.  gz_ngram_lm_score_device: every pointer a DEVICE pointer, offsets
  *   ABSOLUTE as above, same ordering; the call returns when its outputs are complete.  Both use the model's order; the skips are the
  *   call's own.
- * Not here: Kneser-Ney or other discounting (the per-token counts let a caller do it on the host), adding rows to a live model or
+ * Not here: discounting other than the modified Kneser-Ney of the next section, adding rows to a live model or
  *   merging two, saving and loading, pruning by count, <s> / </s> context padding, multi-GPU models (shards score against one
  *   replicated model and the outputs concatenate), text or character n-grams. */
 typedef struct gz_ngram_lm gz_ngram_lm;
@@ -1184,6 +1184,57 @@ int  gz_ngram_lm_score(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids, const i
 int  gz_ngram_lm_score_device(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
                               int32_t skip_front, int32_t skip_back, double alpha, int32_t *n_tokens_dev, uint64_t *bits_fx_dev,
                               int32_t *n_order_dev, uint8_t *token_order_dev, uint32_t *token_num_dev, uint32_t *token_den_dev);
+
+/* ---- modified Kneser-Ney perplexity over the n-gram model ---------------------------------------------------------------------------
+ * What CCNet's KenLM models score with: interpolated modified Kneser-Ney (Chen & Goodman 1998; Heafield et al. 2013), whose scores are
+ * probabilities -- they sum to one over the next token -- so published perplexity buckets and Moore-Lewis log-likelihood ratios carry
+ * over.  It needs, per gram, its distinct left neighbours and, per context, its distinct followers by adjusted count: two passes over
+ * the model's table derive them on the device into a SIDECAR the model owns.  The model is a gz_ngram_lm of order N, with c(g) and the
+ * distinct grams of each order as they are; its table, its id copy and the Stupid Backoff calls do not change.
+ *   adjusted counts  for a distinct k-gram g: L(g) = the number of distinct (k+1)-grams in the model whose last k ids are g (its distinct
+ *                    left neighbours); L = 0 for k = N.  a(g) = c(g) if k = N, else max(L(g), 1): a gram seen only at the starts of
+ *                    bodies has no left neighbour and counts as one type, so every gram the model holds has a >= 1.
+ *   context          for a context x (a (k-1)-gram; the empty gram for k = 1), over the distinct k-grams x.w of the model:
+ *   statistics       A(x) = the sum of a(x.w);  F_j(x) = the number of them with min(a, 3) = j, j = 1, 2, 3.  The empty context's four
+ *                    numbers are global.  V = the number of distinct unigrams.
+ *   discounts        per order k, n_j(k) = the number of distinct k-grams with a = j, j = 1..4.  Y = n1 / (n1 + 2 n2);
+ *                    D_k1 = 1 - 2 Y n2 / n1;  D_k2 = 2 - 3 Y n3 / n2;  D_k3 = 3 - 4 Y n4 / n3.  The fallback (0.5, 1, 1.5) holds for
+ *                    that order when any of n1..n4 is 0 or some D_kj is not in (0, j) (KenLM's --discount_fallback).  Computed on the
+ *                    host in float64 from the 4 N integers.  A caller may pass its own [N, 3] discounts, each in (0, j].
+ *   score            for a query body q, position i, K = min(i + 1, N):  p_0 = 1 / (V + 1).  For k = 1..K let x = q[i-k+1 .. i-1] and
+ *                    g = x.q[i].  If k > 1 and the model does not hold x, or if A(x) = 0 (x occurs only at body ends), stop: the
+ *                    result is p_{k-1}.  Else
+ *                    p_k = ( max(a(g) - D_k,min(a(g),3), 0) + (D_k1 F_1(x) + D_k2 F_2(x) + D_k3 F_3(x)) p_{k-1} ) / A(x),
+ *                    with a(g) = 0 and no discount when g is unseen: the walk goes on through seen contexts after the token's own
+ *                    gram has missed.  j = the largest k with g seen, as in the section above.
+ *                    cost = -log2(p) in float64;  fx = rint(min(cost, 120) * 2^24), an integer below 2^31
+ *   per row          n_tokens, bits_fx (the uint64 sum of fx) and n_order [N + 1, n_rows] as above
+ *   per token        (optional) token_order uint8 = j and token_bits_fx uint32 = fx, zero on the skipped frame cells
+ *   score(rows[a:b]) == score(rows)[a:b].  The outputs are a pure function of (training rows, N, query rows, discounts).
+ *   Over the V seen tokens and one unseen token the p of a context sum to 1.
+ *   sidecar          two arrays parallel to the table's slots, allocated by the first prepare or score call and owned by the model:
+ *                    L as uint32, and one 16-byte record {A, F1, F2, F3} (uint32 each) of the slot's gram as a context: 20 bytes a
+ *                    slot.  A model that was never prepared is byte for byte the model of the section above.
+ *   GZ_E_INVALID, before anything is launched or written: what gz_ngram_lm_score refuses apart from alpha; a discount outside (0, j] or
+ *   NaN.  GZ_E_LIMIT as there.  GZ_E_NOMEM from a prepare: the sidecar is freed and the model scores with Stupid Backoff as before.
+ * gz_ngram_lm_kn_prepare: derives the sidecar; idempotent.  The score calls prepare on first use.
+ * gz_ngram_lm_kn_info: info[48]: [0] prepared (0 / 1), [1] V, [2] sidecar bytes, [3] A and [4..6] F_1..F_3 of the empty context, [7] N,
+ *   [8 + 4 (k - 1) + (j - 1)] = n_j(k) for k = 1..8, j = 1..4, [40 + k - 1] = 1 when order k uses the fallback.  Before a prepare only
+ *   [1], [2] and [7] are set.
+ * gz_ngram_lm_kn_discounts: out[3 (k - 1) + (j - 1)] = D_kj of the rule for k = 1..N, 0 beyond; refused before a prepare.  Which orders
+ *   fell back is in gz_ngram_lm_kn_info.
+ * gz_ngram_lm_score_kn: host pointers.  gz_ngram_lm_score_kn_device: DEVICE pointers, ordered like gz_ngram_lm_score_device.
+ *   discounts: NULL (the rule's) or [N, 3] doubles on the HOST in both forms.
+ * Not here: <s> / </s> context padding, pruning, ARPA export and import, updates of a live model, multi-GPU models. */
+int  gz_ngram_lm_kn_prepare(gz_ctx *ctx, gz_ngram_lm *lm);
+int  gz_ngram_lm_kn_info(gz_ngram_lm *lm, int64_t info[48]);
+int  gz_ngram_lm_kn_discounts(gz_ngram_lm *lm, double out[24]);
+int  gz_ngram_lm_score_kn(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front,
+                          int32_t skip_back, const double *discounts, int32_t *n_tokens, uint64_t *bits_fx, int32_t *n_order,
+                          uint8_t *token_order, uint32_t *token_bits_fx);
+int  gz_ngram_lm_score_kn_device(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                                 int32_t skip_front, int32_t skip_back, const double *discounts, int32_t *n_tokens_dev,
+                                 uint64_t *bits_fx_dev, int32_t *n_order_dev, uint8_t *token_order_dev, uint32_t *token_bits_fx_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)

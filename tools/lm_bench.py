@@ -14,6 +14,10 @@ run the calls one after the other (interleaved), medians.
   score        per training size: the per-document arrays over the whole corpus: ms, the overlap query's ms beside it and
                ratio_to_overlap; probes_per_position = 1 + the mean j below the order (from the order histogram: a position probes
                orders 1 .. min(j + 1, K)), tokens_per_s
+  kneser_ney   per training size: kn_prepare_ms (the two derivation passes over a fresh model's table, with their clears and the read-back)
+               and its ratio to the build; score_kn_ms over the whole corpus and its ratio to the Stupid Backoff score of the same round;
+               the sidecar's bytes and bytes a training token; the discounts and which orders fell back.  tests/kn_oracle.py over the
+               first --oracle-rows / 8 documents against the smallest model: counts of counts and n_order equal, bits_fx within n_tokens
   oracle       tests/lm_oracle.py over the first --oracle-rows documents against the smallest model: n_tokens and n_order equal,
                bits_fx within n_tokens (the bound of tests/test_gpu_lm.py); asserted
 One JSON line on stdout.
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import corpus
+    import kn_oracle as KO
     import lm_oracle as LO
     from genz_tokenize import Tokenize, _native
     text, offs, _ = corpus.config_corpus(3, n_docs=args.docs)
@@ -70,6 +75,7 @@ def main():
     tokens = int(body.sum())
     d_out = ctx.alloc(8 * n + 4 * n + 4 * (N + 1) * n + 64)              # bits_fx, n_tokens, n_order
     d_bits, d_ntok, d_order = d_out, d_out + 8 * n, d_out + 12 * n
+    d_kn = ctx.alloc(8 * n + 4 * n + 4 * (N + 1) * n + 64)               # the same three arrays for the Kneser-Ney calls
     d_ng = ctx.alloc(4 * 5 * n + 64)
     ng_outs = [d_ng + 4 * n * k for k in range(5)]
     rows = []
@@ -93,14 +99,23 @@ def main():
 
         def overlap():
             ctx.ngram_overlap_device(held["ix"], d_ids, d_ro, n, 1, 1, *ng_outs, 0)
-        build(1); build(0); build_index(); score(); overlap()
-        t = {k: [] for k in ("plain", "combined", "index", "score", "overlap")}
+
+        def kn_prepare():                                               # (a model is derived once: a fresh one each time, its build not timed)
+            build(1)
+            return timed(lambda: ctx.ngram_lm_kn_prepare(held["lm"]))
+
+        def score_kn():
+            ctx.ngram_lm_score_kn_device(held["lm"], d_ids, d_ro, n, 1, 1, None, d_kn + 8 * n, d_kn, d_kn + 12 * n, 0, 0)
+        build(1); build(0); build_index(); score(); overlap(); kn_prepare(); score_kn()
+        t = {k: [] for k in ("plain", "combined", "index", "score", "overlap", "kn_prepare", "score_kn")}
         for _ in range(args.reps):
             t["combined"].append(timed(lambda: build(1)))
             t["plain"].append(timed(lambda: build(0)))
             t["index"].append(timed(build_index))
             t["score"].append(timed(score))
             t["overlap"].append(timed(overlap))
+            t["kn_prepare"].append(kn_prepare())
+            t["score_kn"].append(timed(score_kn))
         _native.debug_set("lm_combine", 1, ctx)
         med = {k: float(np.median(v)) for k, v in t.items()}
         info = ctx.ngram_lm_info(held["lm"])
@@ -117,9 +132,17 @@ def main():
                "score_ratio_to_overlap": round(med["score"] / med["overlap"], 3), "order_histogram": hist.tolist(),
                "probes_per_position_at_most": round(probes, 3), "positions_below_full_context": full, "tokens_per_s": round(tokens / med["score"] * 1e3, 0),
                "all_ms": {k: [round(x, 3) for x in v] for k, v in t.items()}}
+        kn = ctx.ngram_lm_kn_info(held["lm"])
+        rec.update({"kn_prepare_ms": round(med["kn_prepare"], 3), "kn_prepare_ratio_to_build": round(med["kn_prepare"] / med["combined"], 3),
+                    "score_kn_ms": round(med["score_kn"], 3), "score_kn_ratio_to_score": round(med["score_kn"] / med["score"], 3),
+                    "kn_sidecar_bytes": kn["sidecar_bytes"], "kn_sidecar_bytes_per_training_token": round(kn["sidecar_bytes"] / max(info["n_tokens"], 1), 2),
+                    "kn_discounts": [[round(x, 6) for x in row] for row in kn["discounts"].tolist()], "kn_fallback": kn["fallback"].tolist(),
+                    "kn_counts_of_counts": kn["counts_of_counts"].tolist()})
         rows.append(rec)
         print("# train %d docs: build %.3f ms (combined %.3f), index %.3f ms; score %.3f ms, overlap %.3f ms; <= %.2f probes/position; %.1f bytes/token" %
               (R, med["plain"], med["combined"], med["index"], med["score"], med["overlap"], probes, rec["bytes_per_training_token"]), file=sys.stderr, flush=True)
+        print("# Kneser-Ney: prepare %.3f ms, score %.3f ms; sidecar %.1f bytes/token; fallback %s" %
+              (med["kn_prepare"], med["score_kn"], rec["kn_sidecar_bytes_per_training_token"], rec["kn_fallback"]), file=sys.stderr, flush=True)
         if first_model is None:
             first_model = R
             k = min(args.oracle_rows, n)
@@ -144,9 +167,22 @@ def main():
                           "bits_fx_max_diff": int(diff.max()), "checked": checked}
             print("# oracle: train %.0f ms, score %.1f ns/token; device %.4f ns/token; checked %s" %
                   (train_ms, oracle_rec["oracle_ns_per_token"], oracle_rec["device_ns_per_token"], checked), file=sys.stderr, flush=True)
+            kk = max(k // 8, 1)
+            kn_bits = np.empty(n, dtype=np.uint64)
+            kn_order = np.empty((N + 1, n), dtype=np.int32)
+            ctx.d2h(kn_bits, d_kn); ctx.d2h(kn_order, d_kn + 12 * n)
+            t0 = time.perf_counter()
+            derived = KO.derive(model, N)
+            kn_want = KO.score(derived, N, docs[:kk], framed=True)
+            kn_ms = (time.perf_counter() - t0) * 1e3
+            kn_diff = np.abs(kn_bits[:kk].astype(np.int64) - kn_want["bits_fx"].astype(np.int64))
+            kn_checked = bool(np.array_equal(kn_order[:, :kk], kn_want["n_order"]) and (kn_diff <= kn_want["n_tokens"]).all()
+                              and np.array_equal(kn["counts_of_counts"], derived["n"]) and kn["V"] == derived["V"])
+            assert kn_checked, "the device's Kneser-Ney outputs differ from the host rule on the first %d documents" % kk
+            oracle_rec.update({"kn_oracle_rows": int(kk), "kn_oracle_ms": round(kn_ms, 1), "kn_bits_fx_max_diff": int(kn_diff.max()), "kn_checked": kn_checked})
         ctx.ngram_lm_destroy(held.pop("lm"))
         ctx.ngram_index_destroy(held.pop("ix"))
-    for d in (d_t, d_to, d_ids, d_am, d_ro, d_out, d_ng):
+    for d in (d_t, d_to, d_ids, d_am, d_ro, d_out, d_kn, d_ng):
         ctx.free(d)
     rec = {"bench": "lm", "docs": n, "tokens": tokens, "reps": args.reps, "piece": 4096, "alpha": 0.4, "models": rows, "oracle": oracle_rec}
     line = json.dumps(rec)
