@@ -80,6 +80,7 @@ struct GzPinned {
     uint8_t small_out[64];                         // copy_out_small.  The stream the caller names; copy_out_small waits for it
     int64_t lm_stats[8];                           // gram positions, then claims, per order of an n-gram model build.  c->stream; lm_build_locked waits for the stream
     int64_t kn_cells[GZ_LM_KN_CELLS];              // the empty context's record and the counts of counts of a Kneser-Ney derivation.  c->stream; lm_kn_prepare_locked waits
+    int64_t clf_stats[GZ_CLF_STATS];               // features and pieces per class and the bad-label flag of a class-model fit.  c->stream; clf_fit_locked waits for the stream
     int32_t fit_hist[GZ_FIT_MAX_LEN + 4];          // the length histogram of a best-fit pack call.  c->stream; fit_maps_locked waits for the stream
 };
 
@@ -215,6 +216,9 @@ struct gz_ctx {
     std::vector<gz_ngram_index*> ngram_live;    // n-gram indexes built on this context (gz_destroy frees what is left of them)
     DBuf w_lm_aux;                       // n-gram language model build: gram positions and claims per order
     std::vector<gz_ngram_lm*> lm_live;   // n-gram language models built on this context (gz_destroy frees what is left of them)
+    DBuf w_clf_aux, w_clf_sort, w_clf_lab, w_clf_bits;     // hashed n-gram class models: the rows pass's words and the sort's cursors, the class-ordered
+                                         // piece list, the staged labels, the sums where the caller takes only best
+    std::vector<gz_ngram_clf*> clf_live; // class models created on this context (gz_destroy frees what is left of them)
     DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
     DBuf w_ss_cut, w_ss_drop, w_ss_aux;  // the cut: piece counts and their scan, the staged drop bytes; duplicate substrings: first_dup where the caller takes only first_src
     DBuf w_q[8];                         // text quality signals: control words, counts, scans, span halves, table, long list, staged text and outputs (gz_quality_api.inc, QW_*)
@@ -1063,6 +1067,7 @@ try {
 
 namespace { void ngram_index_free(gz_ngram_index* ix); }                  // (gz_ngram_api.inc)
 namespace { void ngram_lm_free(gz_ngram_lm* lm); }                        // (gz_lm_api.inc)
+namespace { void ngram_clf_free(gz_ngram_clf* clf); }                     // (gz_clf_api.inc)
 
 void gz_destroy(gz_ctx* c)
 try {
@@ -1078,6 +1083,9 @@ try {
     for (gz_ngram_lm* lm : c->lm_live) ngram_lm_free(lm);
     c->lm_live.clear();
     release(c->w_lm_aux);
+    for (gz_ngram_clf* clf : c->clf_live) ngram_clf_free(clf);
+    c->clf_live.clear();
+    for (DBuf* b : {&c->w_clf_aux, &c->w_clf_sort, &c->w_clf_lab, &c->w_clf_bits}) release(*b);
     for (DBuf& b : c->w_bm) release(b);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -2056,6 +2064,7 @@ try {
 #include "gz_ngram_api.inc"
 #include "gz_lm_api.inc"
 #include "gz_lm_kn_api.inc"
+#include "gz_clf_api.inc"
 #include "gz_repeat_api.inc"
 #include "gz_substr_api.inc"
 #include "gz_quality_api.inc"

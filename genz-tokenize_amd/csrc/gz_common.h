@@ -103,6 +103,8 @@ struct GzOptions {
                                       // gram's 64-bit hash (the same forced collisions, between orders too: results must not change); 0 the whole hash
     int32_t lm_combine = 1;           // n-gram language model build: 1 adds the equal unigrams and bigrams of a trip once (a ballot-match loop in
                                       // the wave); the counts are the same either way
+    int32_t clf_lds = 1;              // hashed n-gram class models: 1 keeps the fit's histogram and the score's weight table in LDS where they fit; 0
+                                      // forces the global-memory path of both; every output is the same either way
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

@@ -345,6 +345,36 @@ struct GzLmKnArgs {
 void gz_launch_lm_kn_derive(GzLmKnArgs K, hipStream_t s);           // clears left, rec and cells, then pass 1 and pass 2
 void gz_launch_lm_kn_score(GzLmKnArgs K, hipStream_t s);            // presets the sums when a row has more than one piece
 
+// hashed n-gram class models (gz_clf.inc); pieces of END positions as the language model's.  A feature is a k-gram, k = 1..order, and
+// its bucket the low `bits` bits of the gram's hash: the model is count[B][C], bucket-major, and the weights derived from it
+constexpr int GZ_CLF_MAX_ORDER = 4;
+constexpr int GZ_CLF_MAX_CLASSES = 8;
+constexpr size_t GZ_CLF_LDS_BYTES = 128 << 10;                      // what a workgroup keeps of a model in LDS: the fit's histogram of 4 B bytes, the
+                                                                    // score's weight table of 4 B CP bytes (CP: the classes rounded up to 1, 2, 4, 8)
+constexpr int GZ_CLF_STATS = 2 * GZ_CLF_MAX_CLASSES + 1;            // of the rows pass: features per class, pieces per class, "a label is out of range"
+inline int gz_clf_cp(int n_classes) { return n_classes <= 1 ? 1 : n_classes <= 2 ? 2 : n_classes <= 4 ? 4 : 8; }
+struct GzClfArgs {
+    const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // the rows walked: row r = ids[row_off[r] .. row_off[r + 1]); bodies shorter than 2^31
+    int32_t skip_front, skip_back, order, bits, n_classes, cp;      // skips 0 or 1, 1 <= order <= 4, 8 <= bits <= 22, 1 <= n_classes <= 8, cp = gz_clf_cp
+    const int64_t* piece_off; int64_t n_pieces;                     // of the count pass; n_pieces = piece_off[n_rows]
+    int32_t one_each;                                               // set by the launcher: n_pieces == n_rows, piece p is row p
+    const int32_t* labels;                                          // fit: [n_rows]
+    int64_t* sorted;                                                // fit: [n_pieces], the pieces ordered by class (set up by the launcher)
+    int64_t cls_start[GZ_CLF_MAX_CLASSES + 1];                      // fit: where each class's pieces start in `sorted` (launcher)
+    int64_t wg_start[GZ_CLF_MAX_CLASSES + 1], run;                  // fit: the first workgroup of each class; pieces a workgroup takes (launcher)
+    uint32_t* count;                                                // fit, derive: [B][C]; derive: null when the weights are the caller's
+    double tb[GZ_CLF_MAX_CLASSES], smoothing;                       // derive: total[c] + a B, and a
+    int32_t* w; int32_t* wpad;                                      // derive: [B][C] and [B][cp] (one array when C == cp); score reads wpad
+    int32_t* n_features; long long* bits_fx; int32_t* best;         // score: [n_rows], [C, n_rows], [n_rows]; each may be null -- but a row of several
+                                                                    // pieces needs bits_fx where best is given
+};
+// per class the features and the pieces of the rows and the flag of a bad label into stats[GZ_CLF_STATS], which is cleared first
+void gz_launch_clf_rows(GzClfArgs A, unsigned long long* stats, hipStream_t s);
+// orders the pieces by class (cls_pieces: what gz_launch_clf_rows counted; cursor: 8 words of scratch), then adds the rows' features
+void gz_launch_clf_fit(GzClfArgs A, const int64_t* cls_pieces, unsigned long long* cursor, bool lds, hipStream_t s);
+void gz_launch_clf_derive(const GzClfArgs& A, hipStream_t s);
+void gz_launch_clf_score(GzClfArgs A, bool lds, hipStream_t s);     // presets the sums when a row has more than one piece; best last
+
 // n-gram repetition inside a document (gz_repeat.inc); pieces of n-gram positions at the call's smallest width
 struct GzRepeatArgs {
     const int32_t* ids; const int64_t* row_off; int64_t n_rows;      // row r = ids[row_off[r] .. row_off[r + 1]) (absolute offsets); bodies shorter than 2^31

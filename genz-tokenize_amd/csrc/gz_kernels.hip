@@ -721,6 +721,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_ngram.inc"
 #include "gz_lm.inc"
 #include "gz_lm_kn.inc"
+#include "gz_clf.inc"
 #include "gz_repeat.inc"
 #include "gz_substr.inc"
 #include "gz_preproc.inc"
@@ -1056,6 +1057,84 @@ void gz_launch_lm_kn_score(GzLmKnArgs K, hipStream_t s)
         if (A.n_order) (void)hipMemsetAsync(A.n_order, 0, (size_t)A.n_rows * (size_t)(A.order + 1) * 4, s);
     }
     hipLaunchKernelGGL(gz_lm_kn_score_kernel, dim3((unsigned)((A.n_pieces + 3) / 4)), dim3(WAVE * 4), 0, s, K);
+}
+
+void gz_launch_clf_rows(GzClfArgs A, unsigned long long* stats, hipStream_t s)
+{
+    (void)hipMemsetAsync(stats, 0, GZ_CLF_STATS * 8, s);
+    if (A.n_rows <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    hipLaunchKernelGGL(gz_clf_rows_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A, stats);
+}
+
+// the compute units of the current device: what the persistent grids of the class models are sized from
+static int clf_cus()
+{
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n;
+}
+
+void gz_launch_clf_fit(GzClfArgs A, const int64_t* cls_pieces, unsigned long long* cursor, bool lds, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    // LDS: about a workgroup a compute unit, so that a histogram is flushed as seldom as the machine allows; otherwise a piece a wave
+    const int64_t per_cu = (A.n_pieces + clf_cus() - 1) / clf_cus();
+    A.run = lds && per_cu > CLF_WAVES ? per_cu : CLF_WAVES;
+    A.cls_start[0] = A.wg_start[0] = 0;
+    for (int c = 0; c < GZ_CLF_MAX_CLASSES; ++c) {
+        const int64_t n = c < A.n_classes ? cls_pieces[c] : 0;
+        A.cls_start[c + 1] = A.cls_start[c] + n;
+        A.wg_start[c + 1] = A.wg_start[c] + (n + A.run - 1) / A.run;
+    }
+    const int64_t wgs = A.wg_start[GZ_CLF_MAX_CLASSES];
+    if (A.cls_start[GZ_CLF_MAX_CLASSES] != A.n_pieces || wgs <= 0 || wgs > 0x7FFFFFFF) return;      // (the caller checked the sum)
+    (void)hipMemsetAsync(cursor, 0, GZ_CLF_MAX_CLASSES * 8, s);
+    hipLaunchKernelGGL(gz_clf_sort_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A, cursor);
+    static const bool attr = [] {                                  // (more than 64 KB of dynamic LDS needs the attribute)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gz_clf_fit_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+        return true;
+    }();
+    (void)attr;
+    const dim3 grid((unsigned)wgs), block(WAVE * CLF_WAVES);
+    if (lds) hipLaunchKernelGGL(gz_clf_fit_kernel<true>, grid, block, (size_t)4 << A.bits, s, A);
+    else hipLaunchKernelGGL(gz_clf_fit_kernel<false>, grid, block, 0, s, A);
+}
+
+void gz_launch_clf_derive(const GzClfArgs& A, hipStream_t s)
+{
+    const uint64_t cells = (uint64_t)A.n_classes << A.bits;
+    hipLaunchKernelGGL(gz_clf_derive_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, A);
+}
+
+template <int CP>
+static void clf_score_launch(const GzClfArgs& A, bool lds, hipStream_t s)
+{
+    static const bool attr = [] {                                  // (more than 64 KB of dynamic LDS needs the attribute)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gz_clf_score_kernel<CP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+        return true;
+    }();
+    (void)attr;
+    const int64_t each = (A.n_pieces + CLF_WAVES - 1) / CLF_WAVES;                   // workgroups at a piece a wave
+    const dim3 block(WAVE * CLF_WAVES);
+    // LDS: a persistent grid, a workgroup a compute unit at the most: every workgroup pays for one copy of the table
+    if (lds) hipLaunchKernelGGL((gz_clf_score_kernel<CP, true>), dim3((unsigned)(each < clf_cus() ? each : clf_cus())), block, ((size_t)4 * CP) << A.bits, s, A);
+    else hipLaunchKernelGGL((gz_clf_score_kernel<CP, false>), dim3((unsigned)(each < (1 << 20) ? each : (1 << 20))), block, 0, s, A);
+}
+
+void gz_launch_clf_score(GzClfArgs A, bool lds, hipStream_t s)
+{
+    if (A.n_rows <= 0 || A.n_pieces <= 0) return;
+    A.one_each = A.n_pieces == A.n_rows ? 1 : 0;
+    if (!A.one_each && A.bits_fx) (void)hipMemsetAsync(A.bits_fx, 0, (size_t)A.n_rows * (size_t)A.n_classes * 8, s);      // the pieces of a long row meet by atomicAdd
+    switch (A.cp) {
+    case 1: clf_score_launch<1>(A, lds, s); break;
+    case 2: clf_score_launch<2>(A, lds, s); break;
+    case 4: clf_score_launch<4>(A, lds, s); break;
+    default: clf_score_launch<8>(A, lds, s); break;
+    }
+    if (!A.one_each && A.best && A.bits_fx) hipLaunchKernelGGL(gz_clf_best_kernel, dim3((unsigned)((A.n_rows + 255) / 256)), dim3(256), 0, s, A);
 }
 
 void gz_launch_repeat_width(GzRepeatArgs A, hipStream_t s)

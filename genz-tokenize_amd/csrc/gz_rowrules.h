@@ -118,6 +118,21 @@ inline bool lm_grams_possible(int64_t grams, int64_t T, int64_t n_rows, int32_t 
     if (lost) least = n_rows > T / lost ? 0 : T - n_rows * lost;                     // (the product is at most T: it does not wrap)
     return grams >= least && grams <= T;
 }
+// Hashed n-gram class models (gz_ngram_clf_*): the first rule an argument list breaks, or nullptr.  The bodies obey minhash_bodies_fit.
+inline const char* clf_create_fault(int32_t order, int32_t bits, int32_t n_classes, double smoothing)
+{
+    if (order < 1 || order > 4) return "a class model needs an order in 1..4";
+    if (bits < 8 || bits > 22) return "a class model needs bits in 8..22";
+    if (n_classes < 1 || n_classes > 8) return "a class model needs 1..8 classes";
+    if (!(smoothing >= 1.0 / 65536.0 && smoothing <= 65536.0)) return "a class model needs a smoothing in [2^-16, 2^16]";      // (a NaN fails both comparisons)
+    return nullptr;
+}
+inline const char* clf_rows_fault(int64_t n_rows, int32_t skip_front, int32_t skip_back)
+{
+    if (n_rows < 0) return "a class model needs n_rows >= 0";
+    if (skip_front < 0 || skip_front > 1 || skip_back < 0 || skip_back > 1) return "a class model needs skips of 0 or 1";
+    return nullptr;
+}
 // the slots of a model: the smallest power of two that is at least twice the gram positions of all orders (at most 8 x 2^32: no wrap)
 inline uint64_t lm_slots(int64_t n_grams_total)
 {

@@ -68,6 +68,9 @@ SYMBOLS = [
     "gz_substr_dups", "gz_substr_dups_device", "gz_cut_rows", "gz_cut_rows_device",
     "gz_ngram_lm_build", "gz_ngram_lm_build_device", "gz_ngram_lm_info", "gz_ngram_lm_destroy", "gz_ngram_lm_score", "gz_ngram_lm_score_device",
     "gz_ngram_lm_kn_prepare", "gz_ngram_lm_kn_info", "gz_ngram_lm_kn_discounts", "gz_ngram_lm_score_kn", "gz_ngram_lm_score_kn_device",
+    "gz_ngram_clf_create", "gz_ngram_clf_destroy", "gz_ngram_clf_fit", "gz_ngram_clf_fit_device", "gz_ngram_clf_info", "gz_ngram_clf_totals",
+    "gz_ngram_clf_counts", "gz_ngram_clf_weights", "gz_ngram_clf_set_counts", "gz_ngram_clf_set_weights", "gz_ngram_clf_score",
+    "gz_ngram_clf_score_device",
 ]
 
 _lib = None
@@ -298,13 +301,24 @@ def load_library():
         lk = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
         L.gz_ngram_lm_score_kn.argtypes = lk
         L.gz_ngram_lm_score_kn_device.argtypes = lk
+    if hasattr(L, "gz_ngram_clf_create"):
+        L.gz_ngram_clf_create.argtypes = [vp, i32, i32, i32, C.c_double, P(vp)]
+        L.gz_ngram_clf_destroy.argtypes = [vp]; L.gz_ngram_clf_destroy.restype = None
+        cf = [vp, vp, vp, vp, vp, i64, i32, i32]
+        L.gz_ngram_clf_fit.argtypes = cf
+        L.gz_ngram_clf_fit_device.argtypes = cf
+        for name in ("info", "totals", "counts", "weights", "set_counts", "set_weights"):
+            getattr(L, "gz_ngram_clf_" + name).argtypes = [vp, vp, vp]
+        cs = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
+        L.gz_ngram_clf_score.argtypes = cs
+        L.gz_ngram_clf_score_device.argtypes = cs
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_bpe_word_dropout", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
                         "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy", "gz_ngram_index_destroy",
-                        "gz_ngram_lm_destroy"):
+                        "gz_ngram_lm_destroy", "gz_ngram_clf_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -1037,6 +1051,80 @@ class Context:
         self._check(self.lib.gz_ngram_lm_score_kn_device(self.handle, C.c_void_p(lm), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
                                                          None if discounts is None else _ptr(discounts),
                                                          *_dptrs(d_n_tokens, d_bits_fx, d_n_order, d_token_order, d_token_bits_fx)))
+
+    # ---- hashed n-gram class models --------------------------------------------------------------------------------
+    CLF_CP = (0, 1, 2, 4, 4, 8, 8, 8, 8)                                 # the classes rounded up to 1, 2, 4, 8: a bucket's row of the score's table
+    CLF_INFO = ("order", "bits", "n_classes", "n_rows", "n_features", "device_bytes", "given", "fresh", "fit_lds", "score_lds", "lds_bytes", "cp")
+
+    def ngram_clf_create(self, order: int, bits: int, n_classes: int, smoothing: float) -> int:
+        """handle of an empty class model (gz_ngram_clf_create)"""
+        h = C.c_void_p()
+        self._check(self.lib.gz_ngram_clf_create(self.handle, int(order), int(bits), int(n_classes), float(smoothing), C.byref(h)))
+        return h.value
+
+    def ngram_clf_destroy(self, clf: int):
+        if clf and getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.gz_ngram_clf_destroy(C.c_void_p(clf))
+
+    def ngram_clf_fit(self, clf: int, ids: np.ndarray, row_off: np.ndarray, labels: np.ndarray, framed: bool):
+        """ids int32 (packed rows), row_off int64 [n+1], labels int32 [n]: the rows' features are added to the counts (gz_ngram_clf_fit)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        if len(labels) != n:
+            raise ValueError("one label a row")
+        self._check(self.lib.gz_ngram_clf_fit(self.handle, C.c_void_p(clf), _ptr(ids) if len(ids) else None, _ptr(row_off), _ptr(labels) if n else None, n,
+                                              skip, skip))
+
+    def ngram_clf_fit_device(self, clf: int, d_ids, d_row_off, d_labels, n_rows, skip_front, skip_back):
+        """gz_ngram_clf_fit_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_ngram_clf_fit_device(self.handle, C.c_void_p(clf), *_dptrs(d_ids, d_row_off, d_labels), n_rows, skip_front, skip_back))
+
+    def ngram_clf_info(self, clf: int):
+        """dict of CLF_INFO (gz_ngram_clf_info); given, fresh, fit_lds and score_lds as bools"""
+        info = np.zeros(16, dtype=np.int64)
+        self._check(self.lib.gz_ngram_clf_info(self.handle, C.c_void_p(clf), _ptr(info)))
+        out = dict(zip(self.CLF_INFO, (int(v) for v in info)))
+        for k in ("given", "fresh", "fit_lds", "score_lds"):
+            out[k] = bool(out[k])
+        return out
+
+    def _ngram_clf_array(self, fn, clf: int, shape, dtype) -> np.ndarray:
+        out = np.zeros(shape, dtype=dtype)
+        self._check(fn(self.handle, C.c_void_p(clf), _ptr(out)))
+        return out
+
+    def ngram_clf_totals(self, clf: int, n_classes: int) -> np.ndarray:
+        return self._ngram_clf_array(self.lib.gz_ngram_clf_totals, clf, n_classes, np.uint64)
+
+    def ngram_clf_counts(self, clf: int, bits: int, n_classes: int) -> np.ndarray:
+        return self._ngram_clf_array(self.lib.gz_ngram_clf_counts, clf, (1 << bits, n_classes), np.uint32)
+
+    def ngram_clf_weights(self, clf: int, bits: int, n_classes: int) -> np.ndarray:
+        return self._ngram_clf_array(self.lib.gz_ngram_clf_weights, clf, (1 << bits, n_classes), np.int32)
+
+    def ngram_clf_set_counts(self, clf: int, counts: np.ndarray):
+        self._check(self.lib.gz_ngram_clf_set_counts(self.handle, C.c_void_p(clf), _ptr(np.ascontiguousarray(counts, dtype=np.uint32))))
+
+    def ngram_clf_set_weights(self, clf: int, weights: np.ndarray):
+        self._check(self.lib.gz_ngram_clf_set_weights(self.handle, C.c_void_p(clf), _ptr(np.ascontiguousarray(weights, dtype=np.int32))))
+
+    def ngram_clf_score(self, clf: int, n_classes: int, ids: np.ndarray, row_off: np.ndarray, framed: bool):
+        """ids int32 (packed rows), row_off int64 [n+1] -> dict(n_features int32 [n], bits_fx int64 [n_classes, n], best int32 [n])
+        (gz_ngram_clf_score)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+        n, skip = len(row_off) - 1, 1 if framed else 0
+        out = dict(n_features=np.zeros(n, dtype=np.int32), bits_fx=np.zeros((n_classes, n), dtype=np.int64), best=np.zeros(n, dtype=np.int32))
+        self._check(self.lib.gz_ngram_clf_score(self.handle, C.c_void_p(clf), _ptr(ids) if len(ids) else None, _ptr(row_off), n, skip, skip,
+                                                *[_ptr(v) if n else None for v in out.values()]))
+        return out
+
+    def ngram_clf_score_device(self, clf: int, d_ids, d_row_off, n_rows, skip_front, skip_back, d_n_features, d_bits_fx, d_best):
+        """gz_ngram_clf_score_device: every pointer a device address (0: NULL)."""
+        self._check(self.lib.gz_ngram_clf_score_device(self.handle, C.c_void_p(clf), *_dptrs(d_ids, d_row_off), n_rows, skip_front, skip_back,
+                                                       *_dptrs(d_n_features, d_bits_fx, d_best)))
 
     # ---- n-gram repetition inside a document -----------------------------------------------------------------------
     REPEAT_OUT = ("n_grams", "n_distinct", "n_repeated", "n_covered", "top_count", "top_pos")

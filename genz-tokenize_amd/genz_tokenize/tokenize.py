@@ -174,6 +174,108 @@ class NgramLM(object):
         return "NgramLM(order=%d, n_rows=%d, n_tokens=%d%s)" % (self.order, self.n_rows, self.n_tokens, ", closed" if self.closed else "")
 
 
+class NgramClassifier(object):
+    """A hashed n-gram class model resident in HBM (`Tokenize.ngram_classifier`, `NgramClassifier.from_weights`): per class the counts
+    of the rows' unigrams .. `order`-grams hashed into 2^bits buckets, and the weights of one multinomial a class derived from them --
+    what `class_bits_rows`, `encode_class_bits`, `class_bits_to_device`, `importance_weights` and `classifier_filter` of the SAME
+    Tokenize object score against.  Fits add: rows fitted in several calls, in any split or order, give the counts of one call, and
+    the `counts()` of shard models, summed on the host, are uploaded with `set_counts`.  `close()` (or leaving a `with` block, or
+    garbage collection) frees the device memory; a closed model is refused.  Properties: order, bits, n_classes, n_rows and
+    n_features (fitted so far), totals (uint64 [n_classes]) and device_bytes."""
+
+    def __init__(self, tok, handle):
+        self._tok = tok
+        self._ctx = ctx = tok._ctx
+        self._handle = handle
+        self._static = ctx.ngram_clf_info(handle)
+        # (the finalizer holds the context: the model is freed before it)
+        self._finalizer = weakref.finalize(self, ctx.ngram_clf_destroy, handle)
+
+    @classmethod
+    def from_weights(cls, tok, weights, order):
+        """A model that scores with the caller's int32 [2^bits, n_classes] table, which may hold negative values: a linear model
+        trained elsewhere over the same hashing.  It has no counts and refuses fits."""
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.dtype.kind not in "iu" or w.shape[0] < 256 or w.shape[0] & (w.shape[0] - 1):
+            raise ValueError("weights must be an integer array [2**bits, n_classes], 8 <= bits <= 22")
+        if w.size and (int(w.min()) < -(2 ** 31) or int(w.max()) >= 2 ** 31):
+            raise ValueError("weights must fit int32")
+        clf = tok.ngram_classifier(w.shape[1], order=order, bits=w.shape[0].bit_length() - 1)
+        tok._ctx.ngram_clf_set_weights(clf._handle, w.astype(np.int32))
+        return clf
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("the NgramClassifier is closed")
+        return self._handle
+
+    order = property(lambda self: self._static["order"])
+    bits = property(lambda self: self._static["bits"])
+    n_classes = property(lambda self: self._static["n_classes"])
+    n_rows = property(lambda self: self._ctx.ngram_clf_info(self._live())["n_rows"])
+    n_features = property(lambda self: self._ctx.ngram_clf_info(self._live())["n_features"])
+    device_bytes = property(lambda self: self._ctx.ngram_clf_info(self._live())["device_bytes"])
+    totals = property(lambda self: self._ctx.ngram_clf_totals(self._live(), self.n_classes))
+
+    @property
+    def closed(self):
+        return self._handle is None
+
+    def fit_rows(self, rows, labels, framed=True):
+        """Add token `rows` (as `ngram_lm` takes them) to the counts of their classes: labels[r] in 0..n_classes-1.  Returns self."""
+        flat, off = Tokenize._ngram_rows("fit_rows", rows)
+        self._ctx.ngram_clf_fit(self._live(), flat, off, Tokenize._clf_labels(labels, len(off) - 1), bool(framed))
+        return self
+
+    def fit(self, texts, labels, word_table=True):
+        """`fit_rows` over the whole token sequence of every text, encoded without a length limit on the device and counted there."""
+        handle, texts = self._live(), list(texts)
+        for t in texts:
+            _require_str(t)
+        lab = Tokenize._clf_labels(labels, len(texts))
+        tok, ctx = self._tok, self._ctx
+        tok._sync_tables()
+        with tok._batch_lock:                                          # (the pinned text arena is one buffer per object: see pack_pinned)
+            with tok._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, R, dev):
+                if R:
+                    d_lab = dev(lab.nbytes)
+                    ctx.h2d(d_lab, lab)
+                    ctx.ngram_clf_fit_device(handle, d_ids, d_ro, d_lab, R, 1, 1)
+                ctx.sync()                                             # (what the encode call deferred is reported here)
+        return self
+
+    def counts(self):
+        """uint32 [2^bits, n_classes], read back from the device"""
+        return self._ctx.ngram_clf_counts(self._live(), self.bits, self.n_classes)
+
+    def weights(self):
+        """int32 [2^bits, n_classes]: rint(2^24 (log2(total[c] + a B) - log2(count[b][c] + a))), derived on the device"""
+        return self._ctx.ngram_clf_weights(self._live(), self.bits, self.n_classes)
+
+    def set_counts(self, counts):
+        """Replace the counts by uint32 [2^bits, n_classes] -- the sum of shard models' `counts()`, or a saved model's."""
+        a = np.asarray(counts)
+        if a.shape != (1 << self.bits, self.n_classes) or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32)):
+            raise ValueError("counts must be an unsigned 32-bit array [2**bits, n_classes]")
+        self._ctx.ngram_clf_set_counts(self._live(), a.astype(np.uint32))
+        return self
+
+    def close(self):
+        if self._handle is not None:
+            self._handle = None
+            self._finalizer()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __repr__(self):
+        return "NgramClassifier(n_classes=%d, order=%d, bits=%d%s)" % (self.n_classes, self.order, self.bits, ", closed" if self.closed else "")
+
+
 class Tokenize(object):
     def __init__(self, pad_token='<pad>', bos_token='<s>', eos_token='</s>', mask_token='<mask>',
                  unk_token='<unk>', device: Optional[int] = None) -> None:
@@ -1975,6 +2077,112 @@ class Tokenize(object):
         if lo is not None:
             keep &= out["perplexity"] >= lo
         out["keep"] = keep
+        return out
+
+    # ---- hashed n-gram class models ("classifier-based quality filtering", DSIR importance weights) ---------------------------
+    @staticmethod
+    def _clf_labels(labels, n):
+        """The labels as int32 [n], or the refusal."""
+        lab = np.asarray(labels)
+        if lab.size and lab.dtype.kind not in "iu":
+            raise TypeError("labels must be integers")
+        if lab.shape != (n,):
+            raise ValueError("one label a row")
+        return np.ascontiguousarray(np.clip(lab, -1, 2 ** 31 - 1), dtype=np.int32)          # (out of range stays out of range)
+
+    def ngram_classifier(self, n_classes, order=2, bits=14, smoothing=1.0):
+        """An empty `NgramClassifier` on this object's device: `n_classes` in 1..8 multinomials over the unigrams .. `order`-grams
+        (1 <= order <= 4) of token rows, hashed into 2^bits buckets (8 <= bits <= 22), add-`smoothing` (a number in [2^-16, 2^16]).
+        DSIR (Xie et al., 2023) is order 2, about 10 000 buckets, class 0 fitted on raw text and class 1 on target text."""
+        a = _number("smoothing", smoothing)
+        if not 2.0 ** -16 <= a <= 2.0 ** 16:                            # (NaN fails here too)
+            raise ValueError("smoothing must lie in [2**-16, 2**16]")
+        return NgramClassifier(self, self._ctx.ngram_clf_create(_integer("order", order, 1, 5), _integer("bits", bits, 8, 23),
+                                                                _integer("n_classes", n_classes, 1, 9), a))
+
+    def _ngram_clf_of(self, clf):
+        """The live handle of `clf`, or the refusal: not an NgramClassifier, closed, or of another Tokenize object."""
+        if not isinstance(clf, NgramClassifier):
+            raise TypeError("clf must be an NgramClassifier (Tokenize.ngram_classifier, NgramClassifier.from_weights)")
+        if clf.closed:
+            raise ValueError("the NgramClassifier is closed")
+        if clf._ctx is not self._ctx:
+            raise ValueError("the NgramClassifier belongs to another Tokenize object's device context")
+        return clf._handle
+
+    def class_bits_rows(self, rows, clf, framed=True):
+        """The bits of token `rows` under every class of `clf`, on the GPU.  A feature is a k-gram, k = 1..clf.order, that ends at a
+        body position (a body of m ids has sum_k max(0, m - k + 1)); its bucket is the low clf.bits bits of its hash, and its cost
+        under class c the weight w[bucket][c] = rint(2^24 (log2(total[c] + a B) - log2(count[bucket][c] + a))).  Returns n_features
+        (int32 [R]), bits_fx (int64 [C, R], the sums of the weights: exact integers), bits = bits_fx / 2^24 (float64) and best (int32
+        [R]: the class with the fewest bits, the smallest on ties, -1 for a row without features).  `rows` as `perplexity_rows`
+        takes them.  `class_bits_rows(rows[a:b])` is `class_bits_rows(rows)[..., a:b]`, and results of shards concatenate."""
+        handle = self._ngram_clf_of(clf)
+        flat, off = self._ngram_rows("class_bits_rows", rows)
+        out = self._ctx.ngram_clf_score(handle, clf.n_classes, flat, off, bool(framed))
+        out["bits"] = out["bits_fx"] / 2.0 ** 24
+        return out
+
+    def _encode_class_bits(self, texts, clf, word_table, to_device):
+        from .handoff import DeviceArray
+        handle = self._ngram_clf_of(clf)
+        texts = list(texts)
+        for t in texts:
+            _require_str(t)
+        self._sync_tables()
+        ctx, C = self._ctx, clf.n_classes
+        with self._batch_lock:                                         # (the pinned text arena is one buffer per object: see pack_pinned)
+            with self._encode_ragged_to_device(texts, word_table) as (d_ids, d_ro, N, dev):
+                shapes = (("n_features", (N,), np.int32), ("bits_fx", (C, N), np.int64), ("best", (N,), np.int32))
+                out = {}
+                try:
+                    for k, shape, dtype in shapes:
+                        d = ctx.alloc(8 * max(N * shape[0] if len(shape) == 2 else N, 1))
+                        try:
+                            out[k] = DeviceArray(ctx, d, shape, dtype=dtype)
+                        except BaseException:
+                            ctx.free(d)
+                            raise
+                    ctx.ngram_clf_score_device(handle, d_ids, d_ro, N, 1, 1, *[out[k].ptr if N else 0 for k, _, _ in shapes])
+                    ctx.sync()                                         # (what the encode call deferred is reported here)
+                    if to_device:
+                        handed, out = out, {}                          # the caller's from here on
+                        return handed
+                    return {k: v.numpy() for k, v in out.items()}
+                finally:
+                    for v in out.values():                             # (on an error too, whichever form was asked for)
+                        v.free()
+
+    def encode_class_bits(self, texts: Sequence[str], clf, word_table=True):
+        """`class_bits_rows` over the whole token sequence of every text: the texts are encoded without a length limit on the device,
+        scored there, and only the per-document arrays come back.  Single texts only."""
+        out = self._encode_class_bits(texts, clf, word_table, False)
+        out["bits"] = out["bits_fx"] / 2.0 ** 24
+        return out
+
+    def class_bits_to_device(self, texts: Sequence[str], clf):
+        """`encode_class_bits` whose exact per-document arrays STAY in HBM as `handoff.DeviceArray`s (`torch.from_dlpack(x)` is
+        zero-copy): n_features int32 [N], bits_fx int64 [C, N] and best int32 [N]; bits is bits_fx / 2^24."""
+        return self._encode_class_bits(texts, clf, True, True)
+
+    def importance_weights(self, texts: Sequence[str], clf, target=1, raw=0):
+        """`encode_class_bits` plus DSIR's log importance weight of every document, in bits: log_weight = bits[raw] - bits[target]
+        (log2 of p_target / p_raw over the document's features; positive: more like the target), and log_weight_per_feature =
+        log_weight / max(n_features, 1).  Resampling is Gumbel top-k over log_weight (in nats: times ln 2) on the host."""
+        t, r = _integer("target", target, 0, clf.n_classes), _integer("raw", raw, 0, clf.n_classes)
+        out = self.encode_class_bits(texts, clf)
+        out["log_weight"] = (out["bits_fx"][r] - out["bits_fx"][t]) / 2.0 ** 24
+        out["log_weight_per_feature"] = out["log_weight"] / np.maximum(out["n_features"], 1)
+        return out
+
+    def classifier_filter(self, texts: Sequence[str], clf, target=1, raw=0, min_log_weight=0.0, per_feature=True):
+        """`importance_weights` plus the decision: keep = n_features > 0 and log_weight_per_feature >= min_log_weight (log_weight
+        with `per_feature=False`), bool [N].  `texts[i]` for the i with keep[i] is the filtered corpus."""
+        lo = _number("min_log_weight", min_log_weight)
+        if math.isnan(lo):
+            raise ValueError("min_log_weight must not be NaN")
+        out = self.importance_weights(texts, clf, target, raw)
+        out["keep"] = (out["n_features"] > 0) & (out["log_weight_per_feature" if per_feature else "log_weight"] >= lo)
         return out
 
     # ---- duplicate substrings across documents ("exact substring deduplication") --------------------------------------------

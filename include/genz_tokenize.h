@@ -306,6 +306,8 @@ int64_t gz_limit(int which);
  *                              of it); with k = 1 every probe of every order starts in one of two slots: results must not change
  *   lm_combine (0..1; 1)  gz_ngram_lm_build* add the equal unigrams and bigrams of 64 neighbouring positions to the table once (1) or
  *                              one by one (0); the counts are the same either way
+ *   clf_lds (0..1; 1)  gz_ngram_clf_fit* and gz_ngram_clf_score* keep the fit's histogram and the score's weight table in LDS where they
+ *                              fit (1) or take the global-memory path of both (0); every output is the same either way
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -1235,6 +1237,74 @@ int  gz_ngram_lm_score_kn(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids, cons
 int  gz_ngram_lm_score_kn_device(gz_ctx *ctx, gz_ngram_lm *lm, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
                                  int32_t skip_front, int32_t skip_back, const double *discounts, int32_t *n_tokens_dev,
                                  uint64_t *bits_fx_dev, int32_t *n_order_dev, uint8_t *token_order_dev, uint32_t *token_bits_fx_dev);
+
+/* ---- hashed n-gram class models ("classifier-based quality filtering", DSIR importance weights) -------------------------------------
+ * GPT-3's and DCLM's quality classifiers and DSIR (Xie et al., 2023) score a document by a linear model over its bag of hashed
+ * n-grams.  A MODEL is a table of B buckets by C classes in device memory: the counts of the features of labelled rows, one
+ * multinomial a class derived from them, and the rows' bits under every class.  DSIR's log importance weight of a document is
+ * bits_fx[raw] - bits_fx[target].  Counts add, so shards fit models of their own and their sum is one model.  No call needs the
+ * tables or the decoder snapshot.
+ *   parameters       order N in 1..4;  bits in 8..22, B = 2^bits buckets;  C classes in 1..8;  smoothing a, a double in [2^-16, 2^16]
+ *   body of row r    ids[row_off[r] + skip_front .. row_off[r+1] - skip_back); the skips are 0 or 1 as in gz_ngram_lm_build
+ *   features         every k-gram, k = 1..N, that ends at body position i with k <= i + 1 is one feature: a body of m ids has
+ *                    sum over k of max(0, m - k + 1) of them
+ *   hash and bucket  the backward chain of gz_ngram_lm_build over the two streams of gz_ngram_index_build:  H_1 = mix(seed, q[i]),
+ *                    H_k = mix(H_{k-1}, q[i-k+1]),  h64 = fmix32(H_k ^ 4 k) of both streams;  bucket = h64 & (B - 1) (the low bits of
+ *                    the second stream's word).  The hash decides the bucket and nothing else: two grams in one bucket ARE the same
+ *                    feature here
+ *   fit              count[b][c] = the number of features with bucket b in rows whose labels[r] == c (uint32, [B][C] bucket-major);
+ *                    total[c] = the sum of count[b][c] over b.  Calls add: fitting rows in two calls, in any split or order, gives
+ *                    the counts of one call.  A fit that would take a class total past 2^32 - 1 is GZ_E_LIMIT and leaves the model
+ *                    unchanged
+ *   weights          w[b][c] = rint(2^24 * (log2(total[c] + a B) - log2(count[b][c] + a)))  in float64, stored as int32 [B][C], always
+ *                    within 0..2^30; derived on the device the first time a score call follows a change of the counts
+ *   score            n_features[r] (int32; 2^31 - 1 where a body has more);  bits_fx int64 [C, n_rows]: bits_fx[c][r] = the sum of
+ *                    w[bucket(f)][c] over the features f of row r -- an integer, so no order of addition changes it;  best[r] = the
+ *                    class with the smallest bits_fx, the smallest class on ties, -1 for a row without features.  bits = bits_fx / 2^24
+ *   score(rows[a:b]) == score(rows)[a:b].  The outputs are a pure function of (counts, a, query rows): not of launch geometry,
+ *   scheduling, or whether a table was held in LDS (switch clf_lds).
+ *   caller's weights gz_ngram_clf_set_weights gives the model an int32 [B][C] table of the caller's, which may hold negative values: a
+ *                    linear model trained elsewhere over the same hashing.  Such a model scores with that table, has no counts or
+ *                    totals, and refuses fits
+ *   memory           the model: 8 B C bytes, and 4 B CP more where C is not 1, 2, 4 or 8 (CP: C rounded up to one of them);
+ *                    workspace of a call: 16 bytes a row, and of a fit 8 bytes a piece of 4096 tokens
+ *   GZ_E_INVALID, each with its own sentence in gz_last_error and before anything is launched, counted or written: a parameter out of
+ *   range or NaN; n_rows < 0; a skip outside {0, 1}; a label outside 0..C-1; NULL ids, row_off or labels with n_rows > 0; a NULL out
+ *   handle or array; a fit, gz_ngram_clf_counts, _totals or _set_counts on a model with a caller's weights; output arrays that overlap
+ *   the input or each other; bad or decreasing row offsets (the host forms); a model that is NULL, destroyed or of another context.
+ *   GZ_E_LIMIT: a body of 2^31 ids or more; a class total past 2^32 - 1 (a fit, gz_ngram_clf_set_counts).  A call with n_rows == 0 is
+ *   GZ_OK and launches nothing.  Scoring a model without fitted rows is valid: a > 0 keeps every weight finite.
+ * gz_ngram_clf_create: an empty model.  gz_ngram_clf_destroy frees it (NULL is fine); gz_destroy frees what is left.
+ * gz_ngram_clf_fit: host pointers.  gz_ngram_clf_fit_device: DEVICE pointers (labels_dev too); offsets are ABSOLUTE from the base
+ *   pointer and row_off_dev[0] need not be 0; every pass runs on the context's stream, behind a gz_encode_batch_device (ragged layout)
+ *   enqueued just before with no gz_sync in between.  The counts are complete on return.
+ * gz_ngram_clf_info: info[16] = order, bits, classes, rows fitted, features fitted, device bytes, 1 when the weights are the caller's,
+ *   1 when the weights belong to the counts as they are, 1 when a fit / a score call would keep its table in LDS, the LDS bytes
+ *   either may use, CP; the rest 0.  gz_ngram_clf_set_counts sets the rows to 0 and the features to the sum of the counts.
+ * gz_ngram_clf_totals: out[C].  gz_ngram_clf_counts / _weights: out[B * C] on the host (_weights derives them first if needed).
+ * gz_ngram_clf_set_counts: replaces the counts with counts[B * C] from the host, e.g. the sum of shard models.
+ * gz_ngram_clf_score: host pointers, the outputs come back.  gz_ngram_clf_score_device: every pointer a DEVICE pointer, offsets
+ *   ABSOLUTE as above, same ordering; the call returns when its outputs are complete.  Every output may be NULL.
+ * Not here: training by gradient descent, character or byte n-grams, more than 8 classes or orders above 4, bucket spaces per order
+ *   or class, TF-IDF or length-normalised features, the resampling itself, saving and loading beyond counts / set_counts, multi-GPU
+ *   fitting (shards add their counts on the host). */
+typedef struct gz_ngram_clf gz_ngram_clf;
+int  gz_ngram_clf_create(gz_ctx *ctx, int32_t order, int32_t bits, int32_t n_classes, double smoothing, gz_ngram_clf **out);
+void gz_ngram_clf_destroy(gz_ngram_clf *clf);
+int  gz_ngram_clf_fit(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids, const int64_t *row_off, const int32_t *labels, int64_t n_rows,
+                      int32_t skip_front, int32_t skip_back);
+int  gz_ngram_clf_fit_device(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids_dev, const int64_t *row_off_dev,
+                             const int32_t *labels_dev, int64_t n_rows, int32_t skip_front, int32_t skip_back);
+int  gz_ngram_clf_info(gz_ctx *ctx, gz_ngram_clf *clf, int64_t info[16]);
+int  gz_ngram_clf_totals(gz_ctx *ctx, gz_ngram_clf *clf, uint64_t *out);
+int  gz_ngram_clf_counts(gz_ctx *ctx, gz_ngram_clf *clf, uint32_t *out);
+int  gz_ngram_clf_weights(gz_ctx *ctx, gz_ngram_clf *clf, int32_t *out);
+int  gz_ngram_clf_set_counts(gz_ctx *ctx, gz_ngram_clf *clf, const uint32_t *counts);
+int  gz_ngram_clf_set_weights(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *weights);
+int  gz_ngram_clf_score(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids, const int64_t *row_off, int64_t n_rows, int32_t skip_front,
+                        int32_t skip_back, int32_t *n_features, int64_t *bits_fx, int32_t *best);
+int  gz_ngram_clf_score_device(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
+                               int32_t skip_front, int32_t skip_back, int32_t *n_features_dev, int64_t *bits_fx_dev, int32_t *best_dev);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
