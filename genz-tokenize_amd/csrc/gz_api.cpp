@@ -219,6 +219,8 @@ struct gz_ctx {
     DBuf w_clf_aux, w_clf_sort, w_clf_lab, w_clf_bits;     // hashed n-gram class models: the rows pass's words and the sort's cursors, the class-ordered
                                          // piece list, the staged labels, the sums where the caller takes only best
     std::vector<gz_ngram_clf*> clf_live; // class models created on this context (gz_destroy frees what is left of them)
+    DBuf w_seg[20];                      // word segmentation: tokens, candidates, stretches, staged outputs (gz_segment_api.inc, SGW_*)
+    std::vector<gz_lexicon*> lex_live;   // lexicons created on this context (gz_destroy frees what is left of them)
     DBuf w_rp_tab, w_rp_top;             // n-gram repeats: the table with its counts; top cells of long rows
     DBuf w_ss_cut, w_ss_drop, w_ss_aux;  // the cut: piece counts and their scan, the staged drop bytes; duplicate substrings: first_dup where the caller takes only first_src
     DBuf w_q[8];                         // text quality signals: control words, counts, scans, span halves, table, long list, staged text and outputs (gz_quality_api.inc, QW_*)
@@ -1068,6 +1070,7 @@ try {
 namespace { void ngram_index_free(gz_ngram_index* ix); }                  // (gz_ngram_api.inc)
 namespace { void ngram_lm_free(gz_ngram_lm* lm); }                        // (gz_lm_api.inc)
 namespace { void ngram_clf_free(gz_ngram_clf* clf); }                     // (gz_clf_api.inc)
+namespace { void lexicon_free(gz_lexicon* lex); }                         // (gz_segment_api.inc)
 
 void gz_destroy(gz_ctx* c)
 try {
@@ -1086,6 +1089,9 @@ try {
     for (gz_ngram_clf* clf : c->clf_live) ngram_clf_free(clf);
     c->clf_live.clear();
     for (DBuf* b : {&c->w_clf_aux, &c->w_clf_sort, &c->w_clf_lab, &c->w_clf_bits}) release(*b);
+    for (gz_lexicon* lex : c->lex_live) lexicon_free(lex);
+    c->lex_live.clear();
+    for (DBuf& b : c->w_seg) release(b);
     for (DBuf& b : c->w_bm) release(b);
     if (c->stream2) hipStreamDestroy(c->stream2);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
@@ -2065,6 +2071,7 @@ try {
 #include "gz_lm_api.inc"
 #include "gz_lm_kn_api.inc"
 #include "gz_clf_api.inc"
+#include "gz_segment_api.inc"
 #include "gz_repeat_api.inc"
 #include "gz_substr_api.inc"
 #include "gz_quality_api.inc"

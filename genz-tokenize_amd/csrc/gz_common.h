@@ -105,6 +105,10 @@ struct GzOptions {
                                       // the wave); the counts are the same either way
     int32_t clf_lds = 1;              // hashed n-gram class models: 1 keeps the fit's histogram and the score's weight table in LDS where they fit; 0
                                       // forces the global-memory path of both; every output is the same either way
+    int32_t seg_hash_bits = 0;        // lexicons (read when one is created): k > 0 keeps only the low k bits of every key's 64-bit hash (distinct keys share
+                                      // hashes, filter bits and probe chains: the byte comparison decides, results must not change); 0 the whole hash
+    int32_t seg_lds = 1;              // word segmentation: 1 keeps the lexicon's bit filter in LDS and answers most keys there; 0 sends every key to
+                                      // the table in memory; every output is the same either way
     // ---- diagnostic build only (results are WRONG with ablate / rows_dbg)
     int32_t diag_poison = 0, rows_dpw = 0, rows_dbg = 0, ablate = 0;
     int32_t diag_fresh = 0;           // v > 0: every FRESH device allocation is filled with byte v - 1 before it is used (fresh memory is usually zero:

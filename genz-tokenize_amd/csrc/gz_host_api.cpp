@@ -53,6 +53,7 @@ int gz_option_set(GzOptions& o, const char* key, int64_t v)
         {"substr_hash_bits", &GzOptions::substr_hash_bits, nullptr, 0, 32},
         {"lm_hash_bits", &GzOptions::lm_hash_bits, nullptr, 0, 32}, {"lm_combine", &GzOptions::lm_combine, nullptr, 0, 1},
         {"clf_lds", &GzOptions::clf_lds, nullptr, 0, 1},
+        {"seg_hash_bits", &GzOptions::seg_hash_bits, nullptr, 0, 62}, {"seg_lds", &GzOptions::seg_lds, nullptr, 0, 1},
     };
     for (const Key& k : keys)
         if (std::strcmp(k.name, key) == 0) {

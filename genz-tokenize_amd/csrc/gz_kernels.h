@@ -838,3 +838,68 @@ void gz_launch_wordset_count(const GzBm25Args& A, const long long* weight, long 
 // word t = tb[tstart[t] .. + tlen[t]) -> arena[toff[t] ..)
 void gz_launch_wordset_gather(const uint8_t* tb, const int64_t* tstart, const uint32_t* tlen, const uint32_t* toff, uint8_t* arena, int64_t n,
                               hipStream_t s);
+
+// Word segmentation by lexicon (gz_segment.inc; include/genz_tokenize.h, "segment").  A TOKEN is a whitespace piece of the word front
+// or, with split_punct, one of a piece's leading / trailing ASCII punctuation characters or its core; a CANDIDATE is k <= K consecutive
+// tokens of one document joined by '_' whose (case-folded) bytes are a lexicon entry.
+constexpr int GZ_SEG_MAX_SYLLABLES = 8;
+constexpr uint32_t GZ_SEG_COST_LIMIT = 1u << 24;                    // costs lie in [1, 2^24)
+constexpr uint32_t GZ_SEG_NONE = 0xFFFFFFFFu;                       // cand[i][k - 1]: no entry
+constexpr int GZ_SEG_FILTER_BITS = 20;                              // the bit filter over the keys' hashes: 2^20 bits = 128 KB of LDS
+constexpr int GZ_SEG_TILE = 1024;                                   // token starts (= threads) of a trip of the candidate kernel
+constexpr int GZ_SEG_LDS_TEXT = 12288;                              // bytes of text a trip stages in LDS; a longer span is read from memory
+constexpr int GZ_SEG_EMIT_LANES = 8;                                // lanes that copy one token
+struct GzSegSlot { unsigned long long key; uint32_t cost, len, off, pad; };      // key 0: empty; the entry's bytes at ebytes[off .. off + len)
+GZ_HD unsigned long long gz_seg_mix64(unsigned long long x)
+{
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+constexpr unsigned long long GZ_SEG_HASH_SEED = 0xCBF29CE484222325ull;
+// the key's hash, byte by byte (FNV-1a), finished over its length; the host hashes the entries with the same two functions
+GZ_HD unsigned long long gz_seg_hash_byte(unsigned long long h, uint32_t b) { return (h ^ b) * 0x100000001B3ull; }
+GZ_HD unsigned long long gz_seg_hash_fin(unsigned long long h, uint32_t n) { return gz_seg_mix64(h ^ (unsigned long long)n); }
+GZ_HD unsigned long long gz_seg_slot(unsigned long long hk) { return gz_seg_mix64(hk + 0x9E3779B97F4A7C15ull) >> 20; }
+// The Vietnamese alphabet's lower-case map on UTF-8 bytes: byte b of a key whose two bytes before it are p2, p1 (0 before the key's
+// start).  Only a character's last byte changes, so the lengths stay: A-Z; U+00C0..U+00DE but U+00D7 (C3 80..9E -> + 0x20); U+0102,
+// U+0110, U+0128, U+0168, U+01A0, U+01AF (+ 1); the even code points of U+1EA0..U+1EF8 (E1 BA A0 .. E1 BB B8, + 1).
+GZ_HD uint32_t gz_seg_fold(uint32_t p2, uint32_t p1, uint32_t b)
+{
+    if (b - 0x41u < 26u) return b + 32u;
+    if (b < 0x80u) return b;
+    if (p1 == 0xC3u) return b <= 0x9Eu && b != 0x97u ? b + 0x20u : b;
+    if ((p1 == 0xC4u && (b == 0x82u || b == 0x90u || b == 0xA8u)) || (p1 == 0xC5u && b == 0xA8u) || (p1 == 0xC6u && (b == 0xA0u || b == 0xAFu))) return b + 1u;
+    if (p2 == 0xE1u && !(b & 1u) && ((p1 == 0xBAu && b >= 0xA0u && b <= 0xBEu) || (p1 == 0xBBu && b <= 0xB8u))) return b + 1u;
+    return b;
+}
+// ASCII string.punctuation without '_'
+GZ_HD bool gz_seg_punct(uint32_t b) { return b != 0x5Fu && ((b >= 0x21u && b <= 0x2Fu) || (b >= 0x3Au && b <= 0x40u) || (b >= 0x5Bu && b <= 0x60u) || (b >= 0x7Bu && b <= 0x7Eu)); }
+enum { GZ_SEG_CTL_STRETCHES, GZ_SEG_CTL_LEN1, GZ_SEG_CTL_LEN8, GZ_SEG_CTL_LONGER, GZ_SEG_CTL_LONGEST, GZ_SEG_CTL_WORDS = 16 };
+struct GzSegArgs {
+    // the text and the word front's pieces (GzBm25Args: tb + off[d] = document d's first byte, offsets inside [lo, hi])
+    const uint8_t* tb; const int64_t* off; int64_t n_docs, lo, hi;
+    const int64_t* wstart; const int64_t* wend; const uint32_t* wdoc; const uint32_t* woff; int64_t n_pieces;
+    int32_t split_punct, fold_case, K;                              // K = the lexicon's max_syllables, 1 .. GZ_SEG_MAX_SYLLABLES
+    uint32_t unk_cost;
+    // tokens: ptc[p] the tokens of piece p, ptoff its exclusive scan (document d = tokens ptoff[woff[d]] .. ptoff[woff[d + 1]]);
+    // a token's first byte relative to lo, its bytes, its document; tlsum the exclusive scan of tlen
+    uint32_t* ptc; const uint32_t* ptoff; int64_t n_tokens;
+    uint32_t* tstart; uint32_t* tlen; uint32_t* tdoc; const uint32_t* tlsum;
+    int64_t* doclen;                                                // [n_docs] bytes of the document's output
+    const int64_t* out_off;                                         // [n_docs + 1] their exclusive scan
+    unsigned long long* stats;                                      // [n_docs][4] n_tokens, n_words, n_known, cost (may be null in DOCS: no stats wanted)
+    // the lexicon
+    const GzSegSlot* tab; unsigned long long tmask, hmask; const uint8_t* ebytes; const uint32_t* filter; uint32_t max_len;
+    uint32_t* cand;                                                 // [n_tokens][K] cost of the candidate of k tokens that STARTS at the token
+    uint8_t* reach;                                                 // [n_tokens] the largest k >= 2 with a candidate from the token, else 1
+    uint8_t* closed;                                                // [n_tokens] 1: no multi-token candidate covers the boundary before the token
+    uint32_t* starts;                                               // [n_tokens] the closed tokens = stretch starts, in no particular order
+    uint32_t* ctl;                                                  // GZ_SEG_CTL_*: stretches, those of 1 / 2..8 / more tokens, the longest (cleared by the caller)
+    uint8_t* choice;                                                // [n_tokens] k of the best word that ENDS at the token | 0x80 when it is an entry
+    uint8_t* join;                                                  // [n_tokens] 1: the token is glued to the next one
+    uint8_t* out; int64_t* tok_off;                                 // the output text; [n_tokens] the tokens' absolute first bytes (may be null)
+};
+enum { GZ_SEG_COUNT, GZ_SEG_TOKENS, GZ_SEG_DOCS, GZ_SEG_CAND, GZ_SEG_MARK, GZ_SEG_WALK, GZ_SEG_EMIT };
+// lds (GZ_SEG_CAND): the bit filter is staged in LDS on a persistent grid; otherwise every key probes the table
+void gz_launch_segment(int step, const GzSegArgs& A, bool lds, hipStream_t s);

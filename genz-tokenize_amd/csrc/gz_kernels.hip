@@ -726,6 +726,7 @@ void gz_launch_pick(const int64_t* off, const int64_t* off2, int64_t n_docs, int
 #include "gz_substr.inc"
 #include "gz_preproc.inc"
 #include "gz_bm25.inc"
+#include "gz_segment.inc"
 #include "gz_quality.inc"
 #include "gz_topk.inc"
 #include "gz_vocab.inc"
@@ -1100,6 +1101,37 @@ void gz_launch_clf_fit(GzClfArgs A, const int64_t* cls_pieces, unsigned long lon
     const dim3 grid((unsigned)wgs), block(WAVE * CLF_WAVES);
     if (lds) hipLaunchKernelGGL(gz_clf_fit_kernel<true>, grid, block, (size_t)4 << A.bits, s, A);
     else hipLaunchKernelGGL(gz_clf_fit_kernel<false>, grid, block, 0, s, A);
+}
+
+void gz_launch_segment(int step, const GzSegArgs& A, bool lds, hipStream_t s)
+{
+    const auto grid = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
+    switch (step) {
+    case GZ_SEG_COUNT: if (A.n_pieces > 0) hipLaunchKernelGGL(gz_seg_piece_kernel<false>, grid(A.n_pieces), dim3(256), 0, s, A); break;
+    case GZ_SEG_TOKENS: if (A.n_pieces > 0) hipLaunchKernelGGL(gz_seg_piece_kernel<true>, grid(A.n_pieces), dim3(256), 0, s, A); break;
+    case GZ_SEG_DOCS: if (A.n_docs > 0) hipLaunchKernelGGL(gz_seg_docs_kernel, grid(A.n_docs), dim3(256), 0, s, A); break;
+    case GZ_SEG_CAND: {
+        if (A.n_tokens <= 0) break;
+        static const bool attr = [] {                              // (more than 64 KB of dynamic LDS needs the attribute)
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&gz_seg_cand_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(SEG_LDS_BYTES + (size_t)SEG_FILTER_WORDS * 4));
+            return true;
+        }();
+        (void)attr;
+        // LDS: a workgroup a compute unit takes trips blockIdx, + gridDim, ..., so the filter is copied once a workgroup; otherwise a trip each
+        const int64_t trips = (A.n_tokens + GZ_SEG_TILE - 1) / GZ_SEG_TILE;
+        const size_t recs = SEG_LDS_BYTES;
+        if (lds) hipLaunchKernelGGL(gz_seg_cand_kernel<true>, dim3((unsigned)(trips < clf_cus() ? trips : clf_cus())), dim3(SEG_THREADS),
+                                    recs + (size_t)SEG_FILTER_WORDS * 4, s, A, trips);
+        else hipLaunchKernelGGL(gz_seg_cand_kernel<false>, dim3((unsigned)(trips < (1 << 20) ? trips : (1 << 20))), dim3(SEG_THREADS), recs, s, A, trips);
+        break;
+    }
+    case GZ_SEG_MARK: if (A.n_tokens > 0) hipLaunchKernelGGL(gz_seg_mark_kernel, grid(A.n_tokens), dim3(256), 0, s, A); break;
+    // (a stretch has a token at least: a lane a token is a lane a stretch and more; the lanes behind the count leave at once)
+    case GZ_SEG_WALK: if (A.n_tokens > 0) hipLaunchKernelGGL(gz_seg_walk_kernel, grid(A.n_tokens), dim3(256), 0, s, A); break;
+    case GZ_SEG_EMIT: if (A.n_tokens > 0) hipLaunchKernelGGL(gz_seg_emit_kernel, grid(A.n_tokens * GZ_SEG_EMIT_LANES), dim3(256), 0, s, A); break;
+    default: break;
+    }
 }
 
 void gz_launch_clf_derive(const GzClfArgs& A, hipStream_t s)

@@ -25,6 +25,10 @@ GZ_PADDING, GZ_TRUNCATION, GZ_MAX_LEN_NONE, GZ_TIMING, GZ_NO_WORD_TABLE, GZ_KEEP
 GZ_NONE = -1
 GZ_PP_HTML, GZ_PP_UNICODE, GZ_PP_PUNCT, GZ_PP_EMOJI, GZ_PP_URL = 1, 2, 3, 4, 5
 # the rows of gz_text_signals' signals (GZ_Q_*), in order; the walk's bytes a trip and documents a workgroup (what the tests place edges by)
+GZ_LEX_FOLD_CASE, GZ_SEG_SPLIT_PUNCT, GZ_SEG_MAX_SYLLABLES, GZ_SEG_COST_LIMIT = 1, 1, 8, 1 << 24
+LEX_INFO = ("n_entries", "max_syllables", "flags", "entry_bytes", "table_slots", "device_bytes", "max_entry_bytes", "seg_lds", "tile", "wave", None, None,
+            "docs", "tokens", "stretches", "stretches_1", "stretches_2_8", "stretches_longer", "longest_stretch", "front_ns", "candidates_ns", "walk_ns",
+            "emit_ns", None)
 GZ_Q_NAMES = ("n_chars", "n_words", "word_chars", "n_alpha_words", "n_hash", "n_ellipsis", "n_lines", "n_bullet_lines", "n_ellipsis_lines",
               "dup_lines", "dup_line_chars", "n_paragraphs", "dup_paragraphs", "dup_paragraph_chars")
 GZ_QUALITY_TRIP, GZ_QUALITY_WPB, GZ_QUALITY_LONG = 256, 4, 512
@@ -71,6 +75,7 @@ SYMBOLS = [
     "gz_ngram_clf_create", "gz_ngram_clf_destroy", "gz_ngram_clf_fit", "gz_ngram_clf_fit_device", "gz_ngram_clf_info", "gz_ngram_clf_totals",
     "gz_ngram_clf_counts", "gz_ngram_clf_weights", "gz_ngram_clf_set_counts", "gz_ngram_clf_set_weights", "gz_ngram_clf_score",
     "gz_ngram_clf_score_device",
+    "gz_lexicon_create", "gz_lexicon_destroy", "gz_lexicon_info", "gz_segment_batch", "gz_segment_batch_device",
 ]
 
 _lib = None
@@ -312,13 +317,19 @@ def load_library():
         cs = [vp, vp, vp, vp, i64, i32, i32, vp, vp, vp]
         L.gz_ngram_clf_score.argtypes = cs
         L.gz_ngram_clf_score_device.argtypes = cs
+    if hasattr(L, "gz_lexicon_create"):
+        L.gz_lexicon_create.argtypes = [vp, vp, vp, vp, i64, i32, u32, P(vp)]
+        L.gz_lexicon_destroy.argtypes = [vp]; L.gz_lexicon_destroy.restype = None
+        L.gz_lexicon_info.argtypes = [vp, vp, vp]
+        L.gz_segment_batch.argtypes = [vp, vp, vp, vp, i64, u32, i64, vp, i64, vp, vp, vp, vp]
+        L.gz_segment_batch_device.argtypes = [vp, vp, vp, vp, i64, u32, i64, vp, i64, vp, vp, vp, vp, P(i64)]
     for name in SYMBOLS:
         if os.environ.get("GZ_LIBRARY") and not hasattr(L, name):
             continue                                     # (an older build loaded for an A/B run: entry points it lacks stay unbound)
         fn = getattr(L, name)
         if name not in ("gz_destroy", "gz_last_error", "gz_bpe_word", "gz_bpe_word_dropout", "gz_host_tables_destroy", "gz_block_release", "gz_block_dlpack",
                         "gz_dlpack_capsule_destructor", "gz_limit", "gz_bm25_destroy", "gz_wordset_destroy", "gz_ngram_index_destroy",
-                        "gz_ngram_lm_destroy", "gz_ngram_clf_destroy"):
+                        "gz_ngram_lm_destroy", "gz_ngram_clf_destroy", "gz_lexicon_destroy"):
             fn.restype = C.c_int
     if hasattr(L, "gz_limit"):
         L.gz_limit.argtypes = [C.c_int]
@@ -1282,6 +1293,58 @@ class Context:
         """gz_span_labels_device: every pointer a device address (0: NULL)."""
         self._check(self.lib.gz_span_labels_device(self.handle, *_dptrs(d_span), C.c_void_p(d_word_off), n_docs, n_words, *_dptrs(d_marks),
                                                    C.c_void_p(d_mark_off), n_marks, scheme, outside, *_dptrs(d_word_labels, d_mark_words)))
+
+    # ---- word segmentation by lexicon ---------------------------------------------------------------------
+    def lexicon_create(self, words: np.ndarray, word_off: np.ndarray, costs: np.ndarray, max_syllables: int, flags: int) -> int:
+        """gz_lexicon_create: packed entries (uint8 bytes, int64 offsets [n + 1]) and their int32 costs -> handle"""
+        words = np.ascontiguousarray(words, dtype=np.uint8)
+        word_off = np.ascontiguousarray(word_off, dtype=np.int64)
+        costs = np.ascontiguousarray(costs, dtype=np.int32)
+        n = len(word_off) - 1
+        h = C.c_void_p()
+        self._check(self.lib.gz_lexicon_create(self.handle, _ptr(words) if len(words) else None, _ptr(word_off), _ptr(costs) if n else None, n,
+                                               int(max_syllables), int(flags), C.byref(h)))
+        return h.value
+
+    def lexicon_destroy(self, lex: int):
+        if lex and getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.gz_lexicon_destroy(C.c_void_p(lex))
+
+    def lexicon_info(self, lex: int) -> dict:
+        """dict of LEX_INFO (gz_lexicon_info)"""
+        info = np.zeros(24, dtype=np.int64)
+        self._check(self.lib.gz_lexicon_info(self.handle, C.c_void_p(lex), _ptr(info)))
+        return {k: int(v) for k, v in zip(LEX_INFO, info) if k}
+
+    def segment(self, lex: int, text: np.ndarray, text_off: np.ndarray, flags: int, unk_cost: int, want_tokens: bool = False, capacity=None):
+        """gz_segment_batch: packed UTF-8 + int64 offsets -> (text uint8, offsets int64 [n + 1], stats int64 [n, 4], join uint8 [tokens] | None,
+        tok_off int64 [tokens] | None).  `capacity` (default: what always fits) is the room the call is told of; the GzError of a
+        GZ_E_CAPACITY carries the valid `.out_off`."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        n = len(text_off) - 1
+        nbytes = int(text_off[n] - text_off[0])
+        cap = (2 * nbytes if flags & GZ_SEG_SPLIT_PUNCT else nbytes) if capacity is None else int(capacity)
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        stats = np.zeros((n, 4), dtype=np.int64)
+        join = np.zeros(max(nbytes, 1), dtype=np.uint8) if want_tokens else None      # (a token has a byte at least)
+        tok_off = np.zeros(max(nbytes, 1), dtype=np.int64) if want_tokens else None
+        try:
+            self._check(self.lib.gz_segment_batch(self.handle, C.c_void_p(lex), _ptr(text) if len(text) else None, _ptr(text_off), n, int(flags), int(unk_cost),
+                                                  _ptr(out), cap, _ptr(out_off), _ptr(stats), _ptr(join), _ptr(tok_off)))
+        except GzError as e:
+            e.out_off = out_off
+            raise
+        if want_tokens:
+            t = int(stats[:, 0].sum())
+            join, tok_off = join[:t], tok_off[:t]
+        return out[:int(out_off[n])], out_off, stats, join, tok_off
+
+    def segment_device(self, lex: int, d_text, d_off, n_docs, flags, unk_cost, d_out, capacity, d_out_off, d_stats=0, d_join=0, d_tok_off=0) -> int:
+        """gz_segment_batch_device: every pointer a device address (0: NULL); returns the output's bytes (GzError.total on GZ_E_CAPACITY)"""
+        return self._call_total(self.lib.gz_segment_batch_device, self.handle, C.c_void_p(lex), *_dptrs(d_text), C.c_void_p(d_off), n_docs, int(flags),
+                                int(unk_cost), *_dptrs(d_out), capacity, C.c_void_p(d_out_off), *_dptrs(d_stats, d_join, d_tok_off))
 
     # ---- text pre-pass ----------------------------------------------------------------------------------
     def preprocess(self, ops, text: np.ndarray, text_off: np.ndarray):

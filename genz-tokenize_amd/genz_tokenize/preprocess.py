@@ -3,7 +3,8 @@
 Same function names and results as the reference (remove_html, convert_unicode, remove_punctuations, remove_emoji,
 remove_URL); each call runs a batch of one document through the HIP pre-pass (csrc/gz_preproc.inc).  `preprocess_batch`
 is the form meant for real work: many documents, several filters chained, one trip to the device.  There is no CPU
-fallback.  `vncore_tokenize` (preprocess.py:83-89) only forwards to an external VnCoreNLP server and is not mirrored.
+fallback.  `vncore_tokenize` (preprocess.py:83-89) forwards to an external VnCoreNLP server in the reference; here its second
+argument is a `segment.Lexicon` and the words are cut on the GPU by minimum-cost segmentation against it (genz_tokenize/segment.py).
 """
 from typing import List, Optional, Sequence
 
@@ -63,3 +64,15 @@ def remove_emoji(txt: str):
 def remove_URL(txt: str):
     '''remove url (preprocess.py:75-80)'''
     return preprocess_batch([txt], ["url"])[0]
+
+
+def vncore_tokenize(text: str, vncore):
+    '''Word-segment `text` (preprocess.py:83-89): `vncore` is a `genz_tokenize.segment.Lexicon`, the result is
+    `segment_batch([text], vncore)[0]`.  A VnCoreNLP client (anything with a `.tokenize` method) is refused: no server is called.'''
+    from .segment import Lexicon, segment_batch
+    if not isinstance(vncore, Lexicon):
+        if hasattr(vncore, "tokenize"):
+            raise TypeError("vncore_tokenize takes a genz_tokenize.segment.Lexicon (Lexicon.from_tokenizer(), .from_corpus(...), "
+                            ".from_words(...)), not a VnCoreNLP client: the words are cut on the GPU and no server is called")
+        raise TypeError("vncore_tokenize takes a genz_tokenize.segment.Lexicon, not %s" % type(vncore).__name__)
+    return segment_batch([text], vncore)[0]

@@ -308,6 +308,11 @@ int64_t gz_limit(int which);
  *                              one by one (0); the counts are the same either way
  *   clf_lds (0..1; 1)  gz_ngram_clf_fit* and gz_ngram_clf_score* keep the fit's histogram and the score's weight table in LDS where they
  *                              fit (1) or take the global-memory path of both (0); every output is the same either way
+ *   seg_hash_bits (0..62; 0)  gz_lexicon_create keeps only the low k bits of every key's hash (0: all of it), and so do the segment calls
+ *                              on that lexicon: distinct keys share hashes, filter bits and probe chains, the byte comparison decides;
+ *                              results must not change
+ *   seg_lds (0..1; 1)  gz_segment_batch* keep the lexicon's bit filter in LDS and answer most keys there (1) or send every key to the
+ *                              table in memory (0); every output is the same either way
  *   diagnostic build only: diag_poison (0..1), rows_dpw, rows_dbg, ablate, diag_guard (0..2: every device buffer its own mapping
  *                              between unmapped granules, no slack -- 1 the buffer ends at its mapping's last byte, 2 it starts at the first),
  *                              diag_exact (0..1: hipMalloc of exactly the bytes asked for), diag_fresh (0..256: v > 0 fills every fresh
@@ -1305,6 +1310,66 @@ int  gz_ngram_clf_score(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids, cons
                         int32_t skip_back, int32_t *n_features, int64_t *bits_fx, int32_t *best);
 int  gz_ngram_clf_score_device(gz_ctx *ctx, gz_ngram_clf *clf, const int32_t *ids_dev, const int64_t *row_off_dev, int64_t n_rows,
                                int32_t skip_front, int32_t skip_back, int32_t *n_features_dev, int64_t *bits_fx_dev, int32_t *best_dev);
+
+/* ---- segment: Vietnamese word segmentation by lexicon ---------------------------------------------------------------------------------
+ * The tokenizer's input is word-segmented text ("sinh_viên công_nghệ"); raw text is syllables between spaces.  The reference forwards
+ * to an external VnCoreNLP server (preprocess.py:83-89) whose learnt rules cannot be reproduced, so the rule is this library's own:
+ * MINIMUM-COST SEGMENTATION AGAINST A LEXICON, the unigram-model form of the dictionary segmenters.  With equal costs it is "fewest
+ * words"; with costs from counts, cost = -log2 p scaled, it is the most probable segmentation.
+ *   tokens      a document is split at Unicode whitespace exactly as the encoder and gz_bm25_build split it.  With GZ_SEG_SPLIT_PUNCT
+ *               every ASCII string.punctuation character except '_' in the leading run and in the trailing run of such a piece is
+ *               a token of its own; inner punctuation stays; a piece of punctuation only is one token a character.  "(Hà" gives
+ *               "(", "Hà";  "Nội)," gives "Nội", ")", ",";  "3.5" stays.  Non-ASCII punctuation is left alone.  A token that holds
+ *               '_' is one token
+ *   lexicon     n entries of UTF-8 bytes, each with an integer cost in [1, 2^24).  An entry has 1 + (its '_' bytes) syllables;
+ *               max_syllables K is 1..8.  An empty entry, one with more than K syllables, one that holds whitespace (or is not
+ *               UTF-8), a cost out of range and an entry given twice are GZ_E_INVALID with a message that names the entry
+ *   candidates  the key of a candidate is k consecutive tokens of ONE document, 1 <= k <= K, joined by single '_' bytes.  With
+ *               GZ_LEX_FOLD_CASE the key -- and every entry when the lexicon is created -- is lower-cased by the Vietnamese alphabet's
+ *               map only: A-Z; U+00C0..U+00DE except U+00D7 (+ 32); U+0102, U+0110, U+0128, U+0168, U+01A0, U+01AF (+ 1); the even code
+ *               points of U+1EA0..U+1EF8 (+ 1).  Every pair has equal UTF-8 length; on bytes that are not UTF-8 the map is the byte
+ *               rule gz_seg_fold states.  The candidate exists when its key equals an entry byte for byte -- a hash decides where to
+ *               look, never whether they are equal -- and costs what the entry costs.  A single token that is no entry costs
+ *               unk_cost, in [1, 2^24); a span of two or more tokens that is no entry is not allowed
+ *   choice      per document with tokens 0..T:  best[0] = 0;  best[i] = min over the allowed k of best[i - k] + cost(i - k, i), exact
+ *               in 64-bit integers;  among equal minima the LARGEST k wins;  the segmentation is the back-trace from T
+ *   output      the tokens of a chosen word joined by '_', words separated by one space, nothing at either end -- as
+ *               ' '.join(text.split()) at preprocess.py:88.  Every token keeps its bytes and case.  Without GZ_SEG_SPLIT_PUNCT the
+ *               output is never longer than the input, with it at most twice as long.
+ *               stats int64 [n_docs][4]: n_tokens, n_words, n_known (the words that are entries), cost.
+ *               join uint8 [tokens]: 1 when the token is glued to the next one;  tok_off int64 [tokens]: the token's first byte,
+ *               absolute as text_off; the tokens of all documents in order, document d's from the sum of the n_tokens before it
+ *   capacity    as gz_preprocess_batch[_device]: out == NULL sizes the output (out_off and every n_tokens are valid, nothing else is
+ *               written and no lexicon work is done); an output larger than `capacity` is GZ_E_CAPACITY with valid out_off
+ *   The outputs are a pure function of (entries, costs, K, flags, unk_cost, text): not of launch geometry, of hash collisions
+ *   (switch seg_hash_bits) or of whether the bit filter sat in LDS (switch seg_lds).
+ *   memory      the lexicon: 48 bytes an entry (a table at load <= 1/2) + its bytes + 128 KB of filter.  Workspace of a call: 20 bytes
+ *               a whitespace piece, 21 + 4 K bytes a token, 48 bytes a document, and the host forms' staged text and output
+ *   GZ_E_LIMIT  a call of 2^31 bytes + documents or more (split the batch); entries of 2^32 bytes or more
+ * gz_lexicon_create: host pointers; entry i = words[word_off[i] .. word_off[i+1]).  The host builds the table and the filter and uploads
+ *   them.  gz_lexicon_destroy frees it (NULL is fine); gz_destroy frees what is left.
+ * gz_lexicon_info: info[24] = entries, K, flags, bytes of the entries, table slots, device bytes, bytes of the longest entry, the switch
+ *   seg_lds, the token starts of a trip of the candidate kernel, the lanes of a wave of the stretch compaction (what tests place edges
+ *   by), 0, 0; then of the last segment call on the lexicon: documents, tokens, stretches, stretches of 1 / of 2..8 / of more tokens,
+ *   the longest stretch, and the nanoseconds of its front, candidate, walk and emit phases on the device; 0.
+ * gz_segment_batch: host pointers; stats, join and tok_off may be NULL; join and tok_off need room for the sum of n_tokens, which is
+ *   never more than the bytes of the text.  gz_segment_batch_device: every pointer but total_host a DEVICE pointer, offsets ABSOLUTE
+ *   from text_dev and text_off_dev[0] need not be 0; out_off_dev starts at 0, so (out_dev, out_off_dev) is valid input to
+ *   gz_encode_batch_device; *total_host = the output's bytes; the call returns when its outputs are complete.
+ * Not here: learnt or rule-based disambiguation (RDRsegmenter), recognisers of names and dates, non-ASCII punctuation, lexicons of
+ *   more than 8 syllables a word, multi-GPU segmentation (shard the documents: they are independent). */
+#define GZ_LEX_FOLD_CASE    0x1u
+#define GZ_SEG_SPLIT_PUNCT  0x1u
+typedef struct gz_lexicon gz_lexicon;
+int  gz_lexicon_create(gz_ctx *ctx, const uint8_t *words, const int64_t *word_off, const int32_t *costs, int64_t n, int32_t max_syllables,
+                       uint32_t flags, gz_lexicon **out);
+void gz_lexicon_destroy(gz_lexicon *lex);
+int  gz_lexicon_info(gz_ctx *ctx, gz_lexicon *lex, int64_t info[24]);
+int  gz_segment_batch(gz_ctx *ctx, gz_lexicon *lex, const uint8_t *text, const int64_t *text_off, int64_t n_docs, uint32_t flags,
+                      int64_t unk_cost, uint8_t *out, int64_t capacity, int64_t *out_off, int64_t *stats, uint8_t *join, int64_t *tok_off);
+int  gz_segment_batch_device(gz_ctx *ctx, gz_lexicon *lex, const uint8_t *text_dev, const int64_t *text_off_dev, int64_t n_docs,
+                             uint32_t flags, int64_t unk_cost, uint8_t *out_dev, int64_t capacity, int64_t *out_off_dev,
+                             int64_t *stats_dev, uint8_t *join_dev, int64_t *tok_off_dev, int64_t *total_host);
 
 /* ---- text pre-pass: the string filters of genz_tokenize/preprocess.py on packed documents ----
  *   GZ_PP_HTML     remove_html          preprocess.py:5-9     re.sub(r'<[^>]*>', '', txt)
